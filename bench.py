@@ -6,7 +6,14 @@ receive set of the same batch (the first k packets that arrived, r data blocks l
 group, recovered out of place), all inputs resident in HBM before timing starts.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload A|B|C|D] [--groups G]
+                  [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...      (N > 1: one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step computed (below).
+--full adds everything else the line can carry: the check of the timed steps' outputs
+(`verified`), the per-phase roofline pass, the CPU baseline, the reference loopback line and
+the host-inclusive (PCIe) leg.
 
 Workloads (BASELINE.json configs):
   A  65,536 groups of (10 data + 1 XOR parity) x 1350 B, 1-loss decode   [default, N = 1]
@@ -23,6 +30,12 @@ strong scaling) with no collective on the data path; a barrier brackets the time
 region and the max time over ranks is reported.
 
 value  = goodput = total groups * k * payload_bytes / step time, GiB/s
+--dump-outputs DIR: a fixed, seeded sample of groups (all of them when they fit in 48 MB of
+float32) of the arrays the last timed step wrote, as DIR/<name>.npy (<name>_rank<i>.npy for
+N > 1): groups (float64 indices into this rank's groups), parity [n][m][bb], recovered
+[n][min(k,m)][bb] (or [n][k][bb] with --decode-layout slots), recovered_rows, status
+(float32).  The inputs are seeded, so two runs with the same arguments write the same files.
+The remaining figures need --full.
 roofline: the dominant kernel's algorithmic HBM bytes per launch / its mean launch time
 (HIP events on the launch stream), against the 8.0 TB/s HBM3E peak.
 cpu_baseline: the reference codec (oracle/_ref, compiled from the reference's own
@@ -456,6 +469,30 @@ def host_inclusive(eng, k, m, bb, payload, data, blocks, rows, steps, recovered)
     }
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # float32 bytes per --dump-outputs directory
+
+
+def dump_outputs(path, seed, rank, world, parity, out, rows_out, status):
+    """Write a seeded sample of groups of the step's outputs as float32 .npy files."""
+    import torch
+    G = parity.shape[0]
+    per_group = parity[0].numel() + out[0].numel() + rows_out[0].numel() + 1
+    n = max(1, min(G, DUMP_BUDGET_BYTES // (4 * per_group)))
+    if n < G:
+        pick = np.sort(np.random.default_rng(seed).choice(G, size=n, replace=False))
+    else:
+        pick = np.arange(G)
+    idx = torch.from_numpy(pick).to(parity.device)
+    os.makedirs(path, exist_ok=True)
+    tail = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"groups{tail}.npy"), pick.astype(np.float64))
+    for name, t in (("parity", parity), ("recovered", out), ("recovered_rows", rows_out),
+                    ("status", status)):
+        np.save(os.path.join(path, f"{name}{tail}.npy"),
+                t[idx].cpu().numpy().astype(np.float32))
+    return n
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -473,15 +510,24 @@ def main():
                     help="a QuicR FEC preset instead of the BASELINE codes (quic_fec_group.cc:"
                          "22-82: 5,5 10,10 10,15 10,20 15,15 250,5): 65,536 groups of (K + M) x "
                          "1350 B, min(K, M) // 2 losses unless --losses")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the timed steps' outputs (`verified`) and run the "
+                         "per-phase roofline pass, the CPU baseline, the reference loopback "
+                         "line and the host-inclusive leg; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write a seeded sample of groups of what the "
+                         "last step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-groups", type=int, default=None,
                     help="groups per thread in the CPU sample (default: about 8 MB of data "
                          "blocks, so the reference's working set stays cache-resident as on "
                          "the QUIC thread)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline and the reference loopback line")
     ap.add_argument("--verify", action="store_true",
-                    help="accepted for compatibility: every line verifies the timed steps")
-    ap.add_argument("--no-host", action="store_true", help="skip the host-inclusive (PCIe) leg")
+                    help="accepted for compatibility: every --full line verifies the timed steps")
+    ap.add_argument("--no-host", action="store_true",
+                    help="with --full: skip the host-inclusive (PCIe) leg")
     ap.add_argument("--loss-mode", choices=("random", "fixed"), default="random",
                     help="lost data rows: a fresh random set per group, or rows 0..r-1 in every "
                          "group")
@@ -637,10 +683,11 @@ def main():
     torch.cuda.synchronize(dev)
 
     # The timed launches must prove they did the work: keep the parity the untimed encode
-    # wrote, then poison every output the step writes (parity, recovered blocks, their rows,
-    # status) so that what is checked after the timed region can only come from the timed
-    # replays themselves.
-    parity_ref = parity.clone()
+    # wrote (--full checks against it), then poison every output the step writes (parity,
+    # recovered blocks, their rows, status) so that what is dumped or checked after the timed
+    # region can only come from the timed replays themselves.
+    full = args.full
+    parity_ref = parity.clone() if full else None
     parity.zero_()
     out.zero_()
     rows_out.zero_()
@@ -659,90 +706,103 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
 
-    # ---- what the timed steps wrote, checked before anything else touches the outputs:
-    # the parity equals the untimed encode's, every group recovered exactly its r lost blocks
-    # and each equals the data row it names, every status is 0
-    verified = torch.equal(parity, parity_ref) and int(status.abs().max()) == 0
-    del parity_ref
-    if recovered:
-        got = rows_out != 255
-        g_idx = torch.arange(G, device=dev)[:, None].expand(G, rmax)[got]
-        verified = verified and bool((got.sum(dim=1) == r).all()) and bool(
-            torch.equal(out[got], data[g_idx, rows_out.long()[got]]))
-    else:
-        slot = rows.long() >= k
-        g_idx = torch.arange(G, device=dev)[:, None].expand(G, k)[slot]
-        verified = verified and bool(torch.equal(out[slot], data[g_idx, rows_out.long()[slot]]))
-    del g_idx
-    if pg:
-        flags = [None] * world
-        dist.all_gather_object(flags, verified)
-        verified = all(flags)
+    # ---- what the last timed step wrote, sampled to DIR before anything else launches
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, seed, rank, world, parity, out, rows_out,
+                              status)
 
-    # ---- roofline pass (after the timed region, same K steps): per-phase kernel timing
-    # with HIP events on the launch stream.  The library records a start event at its first
-    # kernel's start and a stop event at its last kernel's end (qfec_set_timing_events ->
-    # hipExtLaunchKernel), so a phase is timed from its kernels alone, as rocprofv3 times
-    # them.  Fallback: event pairs recorded between the calls (these also count the
-    # dispatch gaps, ~5-10 us per launch).
-    from quic_amd import _lib
-    lib = _lib.load()
-    try:
-        dev_ev = DeviceEvents(4 * args.steps)
-        event_kind = "hipExtLaunchKernel start/stop events"
+    verified = None
+    if full:
+        # ---- what the timed steps wrote, checked before anything else writes the outputs:
+        # the parity equals the untimed encode's, every group recovered exactly its r lost
+        # blocks and each equals the data row it names, every status is 0
+        verified = torch.equal(parity, parity_ref) and int(status.abs().max()) == 0
+        del parity_ref
+        if recovered:
+            got = rows_out != 255
+            g_idx = torch.arange(G, device=dev)[:, None].expand(G, rmax)[got]
+            verified = verified and bool((got.sum(dim=1) == r).all()) and bool(
+                torch.equal(out[got], data[g_idx, rows_out.long()[got]]))
+        else:
+            slot = rows.long() >= k
+            g_idx = torch.arange(G, device=dev)[:, None].expand(G, k)[slot]
+            verified = verified and bool(
+                torch.equal(out[slot], data[g_idx, rows_out.long()[slot]]))
+        del g_idx
+        if pg:
+            flags = [None] * world
+            dist.all_gather_object(flags, verified)
+            verified = all(flags)
 
-        def rec(a, b):
-            ea = dev_ev.ev[a] if a is not None else None
-            eb = dev_ev.ev[b] if b is not None else None
-            if lib.qfec_set_timing_events(ea, eb) != 0:
-                raise RuntimeError("qfec_set_timing_events failed")
-        elapsed_ev = dev_ev.elapsed_ms
-        # probe once outside the timed region: both events must have been recorded
-        rec(0, 1)
-        eng.encode(k, m, bb, data, parity)
-        rec(None, None)
+    enc_ms = dec_ms = None
+    if full:
+        # ---- roofline pass (after the timed region, same K steps): per-phase kernel timing
+        # with HIP events on the launch stream.  The library records a start event at its
+        # first kernel's start and a stop event at its last kernel's end
+        # (qfec_set_timing_events -> hipExtLaunchKernel), so a phase is timed from its kernels
+        # alone, as rocprofv3 times them.  Fallback: event pairs recorded between the calls
+        # (these also count the dispatch gaps, ~5-10 us per launch).
+        from quic_amd import _lib
+        lib = _lib.load()
+        try:
+            dev_ev = DeviceEvents(4 * args.steps)
+            event_kind = "hipExtLaunchKernel start/stop events"
+
+            def rec(a, b):
+                ea = dev_ev.ev[a] if a is not None else None
+                eb = dev_ev.ev[b] if b is not None else None
+                if lib.qfec_set_timing_events(ea, eb) != 0:
+                    raise RuntimeError("qfec_set_timing_events failed")
+            elapsed_ev = dev_ev.elapsed_ms
+            # probe once outside the timed region: both events must have been recorded
+            rec(0, 1)
+            eng.encode(k, m, bb, data, parity)
+            rec(None, None)
+            torch.cuda.synchronize(dev)
+            if not elapsed_ev(0, 1) > 0:
+                raise RuntimeError("kernel events not recorded")
+        except Exception:
+            if lib.qfec_set_timing_events(None, None) != 0:
+                raise
+            dev_ev = None
+            event_kind = "torch.cuda.Event pairs between calls"
+            tev = [torch.cuda.Event(enable_timing=True) for _ in range(4 * args.steps)]
+            pending = [None]   # stop event of the phase in progress
+
+            def rec(a, b):
+                if pending[0] is not None:
+                    tev[pending[0]].record(stream)
+                if a is not None:
+                    tev[a].record(stream)
+                pending[0] = b
+            elapsed_ev = lambda a, b: tev[a].elapsed_time(tev[b])
         torch.cuda.synchronize(dev)
-        if not elapsed_ev(0, 1) > 0:
-            raise RuntimeError("kernel events not recorded")
-    except Exception:
-        if lib.qfec_set_timing_events(None, None) != 0:
-            raise
-        dev_ev = None
-        event_kind = "torch.cuda.Event pairs between calls"
-        tev = [torch.cuda.Event(enable_timing=True) for _ in range(4 * args.steps)]
-        pending = [None]   # stop event of the phase in progress
-
-        def rec(a, b):
-            if pending[0] is not None:
-                tev[pending[0]].record(stream)
-            if a is not None:
-                tev[a].record(stream)
-            pending[0] = b
-        elapsed_ev = lambda a, b: tev[a].elapsed_time(tev[b])
-    torch.cuda.synchronize(dev)
-    t0 = time.perf_counter()
-    for i in range(args.steps):
-        step(i)
-    torch.cuda.synchronize(dev)
-    elapsed_events = time.perf_counter() - t0
-    enc_ms = float(np.mean([elapsed_ev(4 * i, 4 * i + 1) for i in range(args.steps)]))
-    dec_ms = float(np.mean([elapsed_ev(4 * i + 2, 4 * i + 3) for i in range(args.steps)]))
-    if dev_ev is not None:
-        dev_ev.close()
+        t0 = time.perf_counter()
+        for i in range(args.steps):
+            step(i)
+        torch.cuda.synchronize(dev)
+        elapsed_events = time.perf_counter() - t0
+        enc_ms = float(np.mean([elapsed_ev(4 * i, 4 * i + 1) for i in range(args.steps)]))
+        dec_ms = float(np.mean([elapsed_ev(4 * i + 2, 4 * i + 3) for i in range(args.steps)]))
+        if dev_ev is not None:
+            dev_ev.close()
 
     # algorithmic HBM bytes per launch: encode reads k, writes m blocks;
     # decode reads the k received blocks and writes the r recovered ones
     enc_bytes = G * (k + m) * bb
     dec_bytes = G * (k + r) * bb
-    enc_gbs = enc_bytes / (enc_ms * 1e-3) / 1e9
-    dec_gbs = dec_bytes / (dec_ms * 1e-3) / 1e9
-    step_gbs = (enc_bytes + dec_bytes) / (enc_ms + dec_ms) / 1e6
     mine = {"rank": rank, "device": local, "groups": G, "first_group": g0,
             "wall_ms_per_step": round(elapsed * 1e3 / args.steps, 5),
+            "GiBps": round(G * k * payload / 2**30 / (elapsed / args.steps), 3)}
+    if full:
+        enc_gbs = enc_bytes / (enc_ms * 1e-3) / 1e9
+        dec_gbs = dec_bytes / (dec_ms * 1e-3) / 1e9
+        step_gbs = (enc_bytes + dec_bytes) / (enc_ms + dec_ms) / 1e6
+        mine.update({
             "wall_ms_per_step_with_events": round(elapsed_events * 1e3 / args.steps, 5),
-            "GiBps": round(G * k * payload / 2**30 / (elapsed / args.steps), 3),
             "encode_ms": round(enc_ms, 5), "decode_ms": round(dec_ms, 5),
-            "step_hbm_frac": round(step_gbs / HBM_PEAK_GBS, 4)}
+            "step_hbm_frac": round(step_gbs / HBM_PEAK_GBS, 4)})
     if pg:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
@@ -753,27 +813,52 @@ def main():
     ms_per_step = elapsed * 1e3 / args.steps
     goodput = total_groups * k * payload / 2**30 / (elapsed / args.steps)
 
-    phase = "encode" if enc_ms >= dec_ms else "decode"
-    # PMC summaries: profiles/r*/pmc_<A|B|D>.json, pmc_P<k>_<m>.json for the presets (C: B's)
-    traffic, traffic_src = pmc_traffic(f"P{k}_{m}" if wname == "P" else "B" if wname == "C" else wname,
-                                       phase, G)
-    if phase == "encode":
-        dom = (kernels["encode"], enc_gbs, enc_bytes, enc_ms)
-    else:
-        dom = (kernels["decode"], dec_gbs, dec_bytes, dec_ms)
+    roofline = None
+    kern = {"encode": kernels["encode"], "decode": kernels["decode"]}
+    if full:
+        phase = "encode" if enc_ms >= dec_ms else "decode"
+        # PMC summaries: profiles/r*/pmc_<A|B|D>.json, pmc_P<k>_<m>.json for the presets
+        # (C: B's)
+        traffic, traffic_src = pmc_traffic(
+            f"P{k}_{m}" if wname == "P" else "B" if wname == "C" else wname, phase, G)
+        if phase == "encode":
+            dom = (kernels["encode"], enc_gbs, enc_bytes, enc_ms)
+        else:
+            dom = (kernels["decode"], dec_gbs, dec_bytes, dec_ms)
+        roofline = {
+            "bound": "hbm",
+            "kernel": dom[0],
+            "phase": phase,
+            "achieved": round(dom[1], 1),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(dom[1] / HBM_PEAK_GBS, 4),
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "algorithmic_bytes_per_launch": dom[2],
+            "launch_ms": round(dom[3], 5),
+            "timing": event_kind + " on the launch stream, per phase, over a second pass "
+                      "of the same K steps after the timed region",
+        }
+        kern.update({
+            "encode_ms": round(enc_ms, 5), "encode_GBps": round(enc_gbs, 1),
+            "decode_ms": round(dec_ms, 5), "decode_GBps": round(dec_gbs, 1),
+            "step_GBps": round(step_gbs, 1),
+            "step_hbm_frac": round(step_gbs / HBM_PEAK_GBS, 4),
+        })
 
     cpu = None
     cfg0 = None
     # the CPU baseline runs on rank 0 only, after the timed region (the other ranks wait at
     # the final barrier)
-    if rank == 0 and not args.no_cpu_baseline:
+    if full and rank == 0 and not args.no_cpu_baseline:
         n = min((args.cpu_groups or max(16, (8 << 20) // (k * bb))) * cpu_share(), G)
         cpu = cpu_baseline(k, m, bb, payload, r, data[:n].cpu().numpy(),
                            blocks[:n].cpu().numpy(), rows_np[:n], args.cpu_seconds)
         cfg0 = loopback_config0()
 
     host = None
-    if rank == 0 and world == 1 and not args.no_host:
+    if full and rank == 0 and world == 1 and not args.no_host:
         hg = args.host_groups or max(1, min(G, (4 << 30) // (2 * k * bb)))
         host = host_inclusive(eng, k, m, bb, payload, data[:hg], blocks[:hg], rows[:hg],
                               args.host_steps, recovered)
@@ -810,28 +895,9 @@ def main():
                 "options": args.opt,
                 "launch": launch_mode,
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": dom[0],
-                "phase": phase,
-                "achieved": round(dom[1], 1),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(dom[1] / HBM_PEAK_GBS, 4),
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": dom[2],
-                "launch_ms": round(dom[3], 5),
-                "timing": event_kind + " on the launch stream, per phase, over a second pass "
-                          "of the same K steps after the timed region",
-            },
-            "kernels": {
-                "encode": kernels["encode"], "decode": kernels["decode"],
-                "encode_ms": round(enc_ms, 5), "encode_GBps": round(enc_gbs, 1),
-                "decode_ms": round(dec_ms, 5), "decode_GBps": round(dec_gbs, 1),
-                "step_GBps": round(step_gbs, 1),
-                "step_hbm_frac": round(step_gbs / HBM_PEAK_GBS, 4),
-            },
+            "full": full,
+            "roofline": roofline,
+            "kernels": kern,
             "per_gpu": per_rank,
             "cpu_baseline": cpu,
             "cpu_reference_config0": cfg0,
@@ -842,6 +908,11 @@ def main():
                           "poisoned before the timed replays; parity equal to the untimed "
                           "encode's, every lost block recovered and equal to its data row, "
                           "status 0 (all groups, on the device)")
+        if not full:
+            line["verify"] = "not checked: a plain run only times the steps (--full checks)"
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "groups": dumped,
+                                    "of": G, "dtype": "float32"}
         if pp is not None:
             line["packet_protection"] = pp
         print(json.dumps(line), flush=True)

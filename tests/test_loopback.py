@@ -2,8 +2,9 @@
 
 Models the reference's end-to-end check (Script/tests.py:104-108 — send a file through the
 lossy loopback, compare digests) on UDP 127.0.0.1 with a seeded dropper.  CPU: the tool run
-with the oracle codec (and with the reference codec built in oracle/_ref when present) —
-exercising the group framing, the wire format and reassembly.  GPU: --gpu-fec, per-group
+with the oracle codec, held against the reference codec's recorded results
+(tests/golden/ref_recorded.json) and against the reference codec built in oracle/_ref when
+present, exercising the group framing, the wire format and reassembly.  GPU: --gpu-fec, per-group
 and batched, must reproduce the CPU run exactly (same drops -> same revived set and digest)."""
 import json
 import os
@@ -57,13 +58,16 @@ def test_loopback_oracle_codec(tool, args):
 
 
 def test_loopback_reference_codec_agrees(tool):
-    if not os.path.exists(REF_LIB):
-        pytest.skip("reference codec not built (oracle/_ref)")
+    with open(os.path.join(ROOT, "tests", "golden", "ref_recorded.json")) as f:
+        recorded = json.load(f)["loopback"]
     for args in CASES:
         a, _ = run(tool, *args, codec=ORACLE_LIB)
-        b, _ = run(tool, *args, codec=REF_LIB)
-        for key in ("dropped", "revived", "unrecovered", "sha256_out"):
-            assert a[key] == b[key], (args, key)
+        refs = [recorded[" ".join(args)]]
+        if os.path.exists(REF_LIB):
+            refs.append(run(tool, *args, codec=REF_LIB)[0])
+        for b in refs:
+            for key in ("dropped", "revived", "unrecovered", "sha256_out"):
+                assert a[key] == b[key], (args, key)
 
 
 def test_loopback_zero_loss(tool):

@@ -1,7 +1,10 @@
 """CPU: the oracle (plain-C restatement, oracle/fec_oracle.c) against the golden
 vectors produced by the reference codec itself (tests/golden/gen_golden.py), and
-against the compiled reference directly when oracle/_ref is built."""
+against the compiled reference: directly when oracle/_ref is built, and always against what
+it returned when tests/golden/gen_ref_recorded.py recorded it (tests/golden/ref_recorded.json)."""
 import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
@@ -78,20 +81,37 @@ def test_gf_field_is_0x187(oracle):
             assert oracle.gf_div(oracle.gf_mul(a, b), b) == a
 
 
-@pytest.mark.skipif("not __import__('oracle.oracle', fromlist=['x']).ref_available()")
-@pytest.mark.parametrize("k,m,bb,r", [(10, 1, 1352, 1), (32, 4, 1352, 2), (29, 11, 72, 9),
-                                      (7, 30, 16, 7), (100, 100, 8, 60), (3, 2, 1352, 2)])
-def test_oracle_equals_compiled_reference(oracle, k, m, bb, r):
-    G = 3
+REF_CASES = [(10, 1, 1352, 1), (32, 4, 1352, 2), (29, 11, 72, 9),
+             (7, 30, 16, 7), (100, 100, 8, 60), (3, 2, 1352, 2)]
+REF_GROUPS = 3
+
+
+@pytest.fixture(scope="module")
+def ref_recorded():
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "golden", "ref_recorded.json")) as f:
+        return json.load(f)["direct"]
+
+
+@pytest.mark.parametrize("k,m,bb,r", REF_CASES)
+def test_oracle_equals_compiled_reference(oracle, ref_recorded, k, m, bb, r):
+    G = REF_GROUPS
+    rec = ref_recorded[f"{k}_{m}_{bb}_{r}"]
     data = synth.group_data(99 + k, k, bb, G)
-    p_ref, rc_ref = oracle.encode_batch(k, m, bb, data, use_ref=True)
     p_or, rc_or = oracle.encode_batch(k, m, bb, data)
-    assert rc_ref == rc_or
-    np.testing.assert_array_equal(p_ref, p_or)
+    assert rc_or == rec["encode_rc"]
+    assert sha(p_or) == rec["parity_sha256"]
     rows, src = synth.loss_patterns(k, m, r, G, 5, shuffle=True)
-    recv = synth.assemble_received(data, p_ref, src)
-    b1, r1, s1 = oracle.decode_batch(k, m, bb, recv, rows, use_ref=True)
+    recv = synth.assemble_received(data, p_or, src)
     b2, r2, s2 = oracle.decode_batch(k, m, bb, recv, rows)
-    np.testing.assert_array_equal(b1, b2)
-    np.testing.assert_array_equal(r1, r2)
-    np.testing.assert_array_equal(s1, s2)
+    assert sha(b2) == rec["blocks_sha256"]
+    assert sha(r2) == rec["rows_sha256"]
+    assert s2.tolist() == rec["status"]
+    if oracle.ref_available():     # the compiled reference itself, array against array
+        p_ref, rc_ref = oracle.encode_batch(k, m, bb, data, use_ref=True)
+        assert rc_ref == rc_or
+        np.testing.assert_array_equal(p_ref, p_or)
+        b1, r1, s1 = oracle.decode_batch(k, m, bb, recv, rows, use_ref=True)
+        np.testing.assert_array_equal(b1, b2)
+        np.testing.assert_array_equal(r1, r2)
+        np.testing.assert_array_equal(s1, s2)

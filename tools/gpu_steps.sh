@@ -10,9 +10,10 @@
 #   pg1:<W>[:<args>]      bench.py under torchrun with one rank and the RCCL process group kept
 #                         (QFEC_BENCH_PG=1): the N > 1 control flow on one GPU
 #   smoke                 __graft_entry__.smoke()
-#   default               python bench.py (the driver's round-end line)
-#   bench:<W>[:<args>]    bench.py --workload W --verify (W = A B C D), extra args after ':'
-#   quick:<W>[:<args>]    bench.py --workload W, no CPU baseline, no host leg, 10 steps
+#   default               python bench.py --full (every leg of the result line)
+#   bench:<W>[:<args>]    bench.py --full --workload W (W = A B C D), extra args after ':'
+#   quick:<W>[:<args>]    bench.py --full --workload W (verified, roofline pass), no CPU
+#                         baseline, no host leg, 10 steps
 #   preset:<k>,<m>        quick bench of a QuicR preset
 #   prof:<W>[:<args>]     rocprofv3 --kernel-trace --stats of a quick bench
 #   proflib:<name>,<W>[:<args>]  the same against quic_amd/libquic_fec_<name>.so
@@ -36,7 +37,7 @@ for step in "$@"; do
   # a repeated step gets its own log: <tag>_2, <tag>_3, ...
   n=1; base="$tag"; while [[ " ${tags[*]} " == *" $tag "* ]]; do n=$((n + 1)); tag="${base}_$n"; done
   tags+=("$tag")
-  quick="python bench.py --no-cpu-baseline --no-host --steps 10 --warmup 3"
+  quick="python bench.py --full --no-cpu-baseline --no-host --steps 10 --warmup 3"
   case "$kind" in
     tests)
       if [ -z "$rest" ]; then sel="tests"
@@ -46,10 +47,10 @@ for step in "$@"; do
     testlib) L="${W%%,*}"; F="${W#*,}"
             specs+=("$tag::900::QFEC_LIB_PATH=quic_amd/libquic_fec_$L.so python -u -m pytest $F -m gpu -x -q --timeout 120 --timeout-method thread") ;;
     mb)     specs+=("$tag::120::tools/microbench/$W") ;;
-    pg1)    specs+=("$tag::300::QFEC_BENCH_PG=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --workload $W --no-host --steps 10 --warmup 3 $extra") ;;
-    default) specs+=("default::600::python bench.py") ;;
+    pg1)    specs+=("$tag::300::QFEC_BENCH_PG=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --full --workload $W --no-host --steps 10 --warmup 3 $extra") ;;
+    default) specs+=("default::600::python bench.py --full") ;;
     smoke)  specs+=("smoke::300::python -c 'import __graft_entry__ as g; g.smoke()'") ;;
-    bench)  specs+=("$tag::600::python bench.py --workload $W --verify $extra") ;;
+    bench)  specs+=("$tag::600::python bench.py --full --workload $W $extra") ;;
     quick)  specs+=("$tag::300::$quick --workload $W $extra") ;;
     preset) specs+=("$tag::300::$quick --preset $W $extra") ;;
     aboldp) specs+=("$tag::300::QFEC_LIB_PATH=quic_amd/libquic_fec_abold.so $quick --preset $W $extra") ;;
