@@ -101,7 +101,6 @@ int pow2_at_least(int v) {
     return p;
 }
 int encode_rc(int m, const qfec::Tune& t) { return std::min(pow2_at_least(m), t.enc_rc); }
-int decode_rc(int rmax) { return std::min(pow2_at_least(rmax), 8); }
 // Encode table rows: gf_apply's chunk (<= 8), or 16 where gf_stream takes 9..16 outputs in
 // one unit (m <= 8: one unit of m outputs; more than 16: chunks of 8; compiled codes read no
 // table)
@@ -113,7 +112,7 @@ int stream_encode_rc(int k, int m, int bb, bool aligned, const qfec::Tune& t) {
 // at most 8 losses leaves its second unit empty, and empty units read nothing, while one unit
 // of 16 accumulators halves the occupancy for every group ((10, 10) at 5 losses: 0.615 ms
 // with 16 against 0.544 ms).
-int stream_decode_rc(int rmax) { return decode_rc(rmax); }
+int decode_rc(int rmax) { return std::min(pow2_at_least(rmax), 8); }
 
 struct DevBuf {
     void* p = nullptr;
@@ -232,6 +231,18 @@ int ws_end(qfec_ctx* c, hipStream_t st) {
     return 0;
 }
 
+// The bracket of one C entry point whose kernels on `st` use the decode workspace: applied
+// once per call, around everything the call enqueues.  ws_end runs whenever ws_begin
+// succeeded, also when the body fails after it has enqueued work.
+template <class F>
+int with_workspace(qfec_ctx* c, hipStream_t st, F&& body) {
+    int r = ws_begin(c, st);
+    if (r) return r;
+    r = body();
+    const int r2 = ws_end(c, st);
+    return r ? r : r2;
+}
+
 // The workspace of a call on `st`: the graph workspace while `st` is capturing.
 Workspace& ws_for(qfec_ctx* c, hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -283,27 +294,42 @@ int get_cenc(qfec_ctx* c, int k, int m, const uint8_t** out) {
     return 0;
 }
 
-int decode_workspace(Workspace& W, int k, int rmax, int rc, long long groups) {
-    const int rcp = std::max(rc, 4);
-    const int nchunk = (rmax + rc - 1) / rc;
-    // per group: the apply coefficients, or a syndrome table (bsyn:: / syn::)
-    const size_t per = std::max<size_t>({(size_t)nchunk * k * rcp, (size_t)qfec::bsyn::kBytes,
-                                         (size_t)qfec::psyn::kBytes});
-    QF_HIP(W.ensure(W.dcoef, (size_t)groups * per));
-    QF_HIP(W.ensure(W.dslots, (size_t)groups * rmax));
-    QF_HIP(W.ensure(W.dnout, (size_t)groups * sizeof(int32_t)));
-    return 0;
+// What a decode of one shape needs, stated once: the dispatch below sizes its workspace from
+// it, and qfec_reserve pre-sizes from the same answer.
+struct DecodePlan {
+    int rmax = 0;                // recovered blocks per group, at most
+    int rc = 0, nchunk = 0;      // output chunk of the run-time paths and the chunks of rmax
+    long long tab_gstride = 0;   // apply coefficients per group: [nchunk][k][max(rc, 4)]
+    // workspace bytes per group
+    size_t coef = 0;             // the apply coefficients, or a syndrome table (bsyn:: / psyn::)
+    size_t slots = 0;            // output slots (m == 1: the erased slot)
+    size_t nout = 0;             // recovered-block count
+    size_t scratch = 0;          // slot layout in place with several chunks: [rmax][bb]
+    bool cenc = false;           // reads the (k, m) encode matrix
+};
+
+DecodePlan decode_plan(int k, int m, int bb) {
+    DecodePlan p;
+    p.rmax = std::min(k, m);
+    if (k <= 1) return p;        // cauchy_256.cpp:1257-1261: no tables at all
+    p.slots = p.rmax;
+    if (m == 1) return p;        // :1264-1267
+    p.rc = decode_rc(p.rmax);
+    p.nchunk = (p.rmax + p.rc - 1) / p.rc;
+    p.tab_gstride = (long long)p.nchunk * k * std::max(p.rc, 4);
+    p.coef = std::max<size_t>({(size_t)p.tab_gstride, (size_t)qfec::bsyn::kBytes,
+                               (size_t)qfec::psyn::kBytes});
+    p.nout = sizeof(int32_t);
+    if (p.nchunk > 1) p.scratch = (size_t)p.rmax * bb;
+    p.cenc = true;
+    return p;
 }
 
-// The (32, 4) x 1352 B syndrome decode (configs B / C): prep, then gf_bsyn.
-int bsyn_decode(qfec_ctx* c, const uint8_t* d_blocks, const uint8_t* d_rows_in,
-                uint8_t* d_rows_out, uint8_t* d_out, uint8_t* d_rec_rows, int32_t* d_status,
-                const uint8_t* cenc, qfec::DecodeWork w, int k, int m, int bb, int rmax,
-                long long G, long long out_gstride, const uint8_t* slots, hipStream_t st) {
-    QF_HIP(qfec::launch_decode_prep_bsyn(d_rows_in, d_rows_out, d_status, cenc, w.coef, w.slots,
-                                         w.nout, d_rec_rows, k, m, bb, rmax, G, st));
-    QF_HIP(qfec::launch_gf_bsyn(d_blocks, d_out, w.coef, cenc, slots, w.nout, k, m, bb, G, rmax,
-                                out_gstride, st, c->tune));
+int reserve_workspace(Workspace& W, const DecodePlan& p, long long groups, bool scratch) {
+    QF_HIP(W.ensure(W.dcoef, (size_t)groups * p.coef));
+    QF_HIP(W.ensure(W.dslots, (size_t)groups * p.slots));
+    QF_HIP(W.ensure(W.dnout, (size_t)groups * p.nout));
+    if (scratch) QF_HIP(W.ensure(W.dscratch, (size_t)groups * p.scratch));
     return 0;
 }
 
@@ -349,180 +375,119 @@ int encode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d
     return 0;
 }
 
-int decode_body(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d_blocks,
-                const uint8_t* d_rows_in, uint8_t* d_out, uint8_t* d_rows_out, int32_t* d_status,
-                hipStream_t st) {
+// Where a decode writes.  Slot layout (qfec_decode_batch): recovered blocks go back into their
+// slots of out [G][k][bb] (which may be the blocks themselves) and rows [G][k] gets every
+// slot's row tag.  Compact layout (qfec_decode_batch_recovered): recovered block j of group g
+// goes to out + (g * rmax + j) * bb and its data row to rows[g * rmax + j] (ascending, 255
+// past the erasure count); blocks and row tags are left as they are.  This is what the
+// receiver consumes (getRevivedPackets, quic_fec_group.cc:280-293, only extracts the missing
+// packets), and the writes are dense.
+struct DecodeOut {
+    uint8_t* out;
+    uint8_t* rows;
+    bool compact;
+};
+
+// The one decode dispatch: which kernels a (k, m, bb) decode runs, for either layout.  The
+// caller holds the workspace bracket (with_workspace).
+int decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d_blocks,
+                const uint8_t* d_rows_in, DecodeOut o, int32_t* d_status, hipStream_t st) {
+    if (G == 0) return 0;
+    const DecodePlan p = decode_plan(k, m, bb);
+    const int rmax = p.rmax, rc = p.rc;
     if (k <= 1) {   // cauchy_256.cpp:1257-1261
-        QF_HIP(qfec::launch_rows_k1(d_rows_in, d_rows_out, d_status, G, st));
+        if (o.compact)
+            QF_HIP(qfec::launch_rec_k1(d_blocks, d_rows_in, o.out, o.rows, d_status, bb, rmax, G,
+                                       st));
+        else
+            QF_HIP(qfec::launch_rows_k1(d_rows_in, o.rows, d_status, G, st));
         return 0;
     }
     Workspace& W = ws_for(c, st);
+    int r = reserve_workspace(W, p, G, false);
+    if (r) return r;
     if (m == 1) {   // :1264-1267
-        QF_HIP(W.ensure(W.dslots, (size_t)G));
-        QF_HIP(qfec::launch_xor_decode(d_blocks, d_out, d_rows_in, d_rows_out, d_status,
-                                       (uint8_t*)W.dslots.p, k, bb, G, st, c->tune));
+        QF_HIP(qfec::launch_xor_decode(d_blocks, o.out, d_rows_in, o.rows, d_status,
+                                       (uint8_t*)W.dslots.p, k, bb, G, st, c->tune, o.compact));
         return 0;
     }
-    const int rmax = std::min(k, m);
-    const int rc = stream_decode_rc(rmax);
-    const int nchunk = (rmax + rc - 1) / rc;
     const uint8_t* cenc = nullptr;
-    int r = get_cenc(c, k, m, &cenc);
-    if (r) return r;
-    if ((r = decode_workspace(W, k, rmax, rc, G))) return r;
+    if ((r = get_cenc(c, k, m, &cenc))) return r;
     qfec::DecodeWork w{(uint8_t*)W.dcoef.p, (uint8_t*)W.dslots.p, (int32_t*)W.dnout.p};
-    const long long tab_gstride = (long long)nchunk * k * std::max(rc, 4);
-    const bool dcol = qfec::gf_dcol_supported(k, m, bb, c->tune) && rmax <= 16;
-    if (dcol && ((uintptr_t)d_blocks & 15) == 0) {
-        // compiled (128, 16) code: syndromes, then the r x r solve (reads precede stores
-        // within a group, so in place needs no scratch)
-        QF_HIP(qfec::launch_decode_prep(d_rows_in, d_rows_out, d_status, cenc, w, k, m, bb, rc,
-                                        rmax, G, st, c->tune, nullptr, true));
-        QF_HIP(qfec::launch_gf_dcol_syndrome(d_blocks, d_out, w.coef, w.slots, w.nout, cenc, k,
-                                             m, bb, G, rmax, tab_gstride, (long long)k * bb, st,
+    // what the layout decides: which row output the prep writes, whether the kernels scatter
+    // through the slot table, and the stride between the groups of `out`
+    uint8_t* const rows_out = o.compact ? nullptr : o.rows;
+    uint8_t* const rec_rows = o.compact ? o.rows : nullptr;
+    const uint8_t* const slots = o.compact ? nullptr : w.slots;
+    const long long out_gstride = (long long)(o.compact ? rmax : k) * bb;
+    const bool aligned = ((uintptr_t)d_blocks & 15) == 0;
+    // The compiled codes.  In each, a group's stores follow all of its reads, so the slot
+    // layout in place needs no scratch.
+    if (qfec::gf_dcol_supported(k, m, bb, c->tune) && rmax <= 16 && aligned) {
+        // compiled (128, 16) code: syndromes, then the r x r solve
+        QF_HIP(qfec::launch_decode_prep(d_rows_in, rows_out, d_status, cenc, w, k, m, bb, rc,
+                                        rmax, G, st, c->tune, rec_rows, true));
+        QF_HIP(qfec::launch_gf_dcol_syndrome(d_blocks, o.out, w.coef, slots, w.nout, cenc, k, m,
+                                             bb, G, rmax, p.tab_gstride, out_gstride, st,
                                              c->tune));
         return 0;
     }
-    if (qfec::gf_psyn_supported(k, m, bb, rmax, c->tune) && ((uintptr_t)d_blocks & 15) == 0) {
-        // compiled QuicR preset code: syndromes of every parity row, then Gauss-Jordan in
-        // place (a group's stores follow all of its reads: in place needs no scratch)
-        QF_HIP(qfec::launch_decode_prep_psyn(d_rows_in, d_rows_out, d_status, cenc, w.coef,
-                                             w.slots, w.nout, nullptr, k, m, bb, rmax, G, st));
-        QF_HIP(qfec::launch_gf_psyn(d_blocks, d_out, w.coef, cenc, w.slots, w.nout, k, m, bb, G,
-                                    rmax, (long long)k * bb, st, c->tune));
+    if (qfec::gf_psyn_supported(k, m, bb, rmax, c->tune) && aligned) {
+        // compiled QuicR preset code: syndromes of every parity row, then Gauss-Jordan in place
+        QF_HIP(qfec::launch_decode_prep_psyn(d_rows_in, rows_out, d_status, cenc, w.coef,
+                                             w.slots, w.nout, rec_rows, k, m, bb, rmax, G, st));
+        QF_HIP(qfec::launch_gf_psyn(d_blocks, o.out, w.coef, cenc, slots, w.nout, k, m, bb, G,
+                                    rmax, out_gstride, st, c->tune));
         return 0;
     }
-    if (qfec::gf_bsyn_supported(k, m, bb, rmax, c->tune) && ((uintptr_t)d_blocks & 15) == 0) {
-        // compiled (32, 4) code: syndromes of every parity row, then the r x r solve (a
-        // group's stores follow all of its reads: in place needs no scratch)
-        return bsyn_decode(c, d_blocks, d_rows_in, d_rows_out, d_out, nullptr, d_status, cenc,
-                           w, k, m, bb, rmax, G, (long long)k * bb, w.slots, st);
+    if (qfec::gf_bsyn_supported(k, m, bb, rmax, c->tune) && aligned) {
+        // compiled (32, 4) x 1352 B code (configs B / C): syndromes of every parity row, then
+        // the r x r solve
+        QF_HIP(qfec::launch_decode_prep_bsyn(d_rows_in, rows_out, d_status, cenc, w.coef,
+                                             w.slots, w.nout, rec_rows, k, m, bb, rmax, G, st));
+        QF_HIP(qfec::launch_gf_bsyn(d_blocks, o.out, w.coef, cenc, slots, w.nout, k, m, bb, G,
+                                    rmax, out_gstride, st, c->tune));
+        return 0;
     }
-    QF_HIP(qfec::launch_decode_prep(d_rows_in, d_rows_out, d_status, cenc, w, k, m, bb, rc, rmax,
-                                    G, st, c->tune));
+    // The run-time codes: the prep's coefficients, applied in chunks of rc recovered blocks.
+    QF_HIP(qfec::launch_decode_prep(d_rows_in, rows_out, d_status, cenc, w, k, m, bb, rc, rmax,
+                                    G, st, c->tune, rec_rows));
     if (bb % 8 != 0 || k + m > 256) return 0;   // every group is a no-op or status -1
-    if (qfec::gf_stream_supported(k, m, bb, rc, true, c->tune) &&
-        ((uintptr_t)d_blocks & 15) == 0) {
-        const int rcp = std::max(rc, 4);
-        if (nchunk == 1 || d_out != d_blocks) {
-            // one chunk: a group's stores follow all of its reads, so in place needs no
-            // scratch; several chunks (units on different waves) write out of place only
-            QF_HIP(qfec::launch_gf_stream(d_blocks, d_out, w.coef, w.slots, w.nout, k, m, bb, G,
-                                          rc, rmax, (long long)nchunk * k * rcp,
-                                          (long long)k * bb, true, st, c->tune));
-            return 0;
-        }
-        // in place with several chunks: the recovered blocks go to scratch first, then to
-        // their slots (a later chunk reads slots an earlier one would have overwritten)
-        QF_HIP(W.ensure(W.dscratch, (size_t)G * rmax * bb));
-        QF_HIP(qfec::launch_gf_stream(d_blocks, (uint8_t*)W.dscratch.p, w.coef, nullptr, w.nout,
-                                      k, m, bb, G, rc, rmax, (long long)nchunk * k * rcp,
-                                      (long long)rmax * bb, true, st, c->tune));
-        QF_HIP(qfec::launch_scatter_recovered((const uint8_t*)W.dscratch.p, d_out, w, k, bb,
-                                              rmax, G, st));
-        return 0;
+    // One primitive, the dense decode into a [G][rmax][bb] destination: the compact layout's
+    // `out` is one.  The slot layout writes straight into its slots instead (`direct`) where a
+    // group's stores follow all of its reads: one chunk, or out of place.  In place with
+    // several chunks (units on different waves) a later chunk would read slots an earlier one
+    // already overwrote, so it is the dense decode into scratch, then the scatter.
+    const bool direct = !o.compact && (p.nchunk == 1 || o.out != d_blocks);
+    uint8_t* dst = o.out;
+    if (!o.compact && !direct) {
+        QF_HIP(W.ensure(W.dscratch, (size_t)G * p.scratch));
+        dst = (uint8_t*)W.dscratch.p;
     }
-    if (nchunk > 1 && d_out == d_blocks) {
-        // in place with several output chunks: a later chunk would read slots an earlier
-        // chunk already overwrote, so stage the recovered blocks first
-        QF_HIP(W.ensure(W.dscratch, (size_t)G * rmax * bb));
-        QF_HIP(qfec::launch_gf_decode_scratch(d_blocks, (uint8_t*)W.dscratch.p, w, k, m, bb, G,
-                                              rc, rmax, st, c->tune));
-        QF_HIP(qfec::launch_scatter_recovered((const uint8_t*)W.dscratch.p, d_out, w, k, bb,
-                                              rmax, G, st));
-        return 0;
-    }
-    QF_HIP(qfec::launch_gf_decode(d_blocks, d_out, w, k, m, bb, G, rc, rmax, st, c->tune));
+    if (qfec::gf_stream_supported(k, m, bb, rc, true, c->tune) && aligned)
+        QF_HIP(qfec::launch_gf_stream(d_blocks, dst, w.coef, direct ? w.slots : nullptr, w.nout,
+                                      k, m, bb, G, rc, rmax, p.tab_gstride,
+                                      (long long)(direct ? k : rmax) * bb, true, st, c->tune));
+    else if (direct)
+        QF_HIP(qfec::launch_gf_decode(d_blocks, dst, w, k, m, bb, G, rc, rmax, st, c->tune));
+    else
+        QF_HIP(qfec::launch_gf_decode_scratch(d_blocks, dst, w, k, m, bb, G, rc, rmax, st,
+                                              c->tune));
+    if (dst != o.out)
+        QF_HIP(qfec::launch_scatter_recovered(dst, o.out, w, k, bb, rmax, G, st));
     return 0;
 }
 
-int decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d_blocks,
-                const uint8_t* d_rows_in, uint8_t* d_out, uint8_t* d_rows_out, int32_t* d_status,
-                hipStream_t st) {
-    if (G == 0) return 0;
-    int r = ws_begin(c, st);
-    if (r) return r;
-    r = decode_body(c, k, m, bb, G, d_blocks, d_rows_in, d_out, d_rows_out, d_status, st);
-    const int r2 = ws_end(c, st);
-    return r ? r : r2;
-}
-
-// Recovered-blocks layout (qfec_decode_batch_recovered): the same decode, but recovered
-// block j of group g goes to d_rec + (g * rmax + j) * bb and its data row to
-// d_rec_rows[g * rmax + j] (ascending, 255 past the erasure count); blocks and row tags
-// are left as they are.  This is what the receiver consumes (getRevivedPackets,
-// quic_fec_group.cc:280-293, only extracts the missing packets), and the writes are dense.
-int decode_recovered_body(qfec_ctx* c, int k, int m, int bb, long long G,
-                          const uint8_t* d_blocks, const uint8_t* d_rows_in, uint8_t* d_rec,
-                          uint8_t* d_rec_rows, int32_t* d_status, hipStream_t st) {
-    const int rmax = std::min(k, m);
-    if (k <= 1) {
-        QF_HIP(qfec::launch_rec_k1(d_blocks, d_rows_in, d_rec, d_rec_rows, d_status, bb, rmax, G,
-                                   st));
-        return 0;
+// Carves consecutive 256-byte aligned sub-buffers out of one staging buffer.
+struct Carve {
+    uint8_t* p;
+    uint8_t* take(size_t bytes) {
+        uint8_t* r = p;
+        p += (bytes + 255) & ~(size_t)255;
+        return r;
     }
-    Workspace& W = ws_for(c, st);
-    if (m == 1) {
-        QF_HIP(W.ensure(W.dslots, (size_t)G));
-        QF_HIP(qfec::launch_xor_decode(d_blocks, d_rec, d_rows_in, d_rec_rows, d_status,
-                                       (uint8_t*)W.dslots.p, k, bb, G, st, c->tune, true));
-        return 0;
-    }
-    const int rc = stream_decode_rc(rmax);
-    const uint8_t* cenc = nullptr;
-    int r = get_cenc(c, k, m, &cenc);
-    if (r) return r;
-    if ((r = decode_workspace(W, k, rmax, rc, G))) return r;
-    qfec::DecodeWork w{(uint8_t*)W.dcoef.p, (uint8_t*)W.dslots.p, (int32_t*)W.dnout.p};
-    const bool dcol = qfec::gf_dcol_supported(k, m, bb, c->tune) && rmax <= 16;
-    if (dcol && ((uintptr_t)d_blocks & 15) == 0) {
-        const int nchunk = (rmax + rc - 1) / rc;
-        QF_HIP(qfec::launch_decode_prep(d_rows_in, nullptr, d_status, cenc, w, k, m, bb, rc, rmax,
-                                        G, st, c->tune, d_rec_rows, true));
-        QF_HIP(qfec::launch_gf_dcol_syndrome(d_blocks, d_rec, w.coef, nullptr, w.nout, cenc, k, m,
-                                             bb, G, rmax, (long long)nchunk * k * std::max(rc, 4),
-                                             (long long)rmax * bb, st, c->tune));
-        return 0;
-    }
-    if (qfec::gf_psyn_supported(k, m, bb, rmax, c->tune) && ((uintptr_t)d_blocks & 15) == 0) {
-        QF_HIP(qfec::launch_decode_prep_psyn(d_rows_in, nullptr, d_status, cenc, w.coef, w.slots,
-                                             w.nout, d_rec_rows, k, m, bb, rmax, G, st));
-        QF_HIP(qfec::launch_gf_psyn(d_blocks, d_rec, w.coef, cenc, nullptr, w.nout, k, m, bb, G,
-                                    rmax, (long long)rmax * bb, st, c->tune));
-        return 0;
-    }
-    if (qfec::gf_bsyn_supported(k, m, bb, rmax, c->tune) && ((uintptr_t)d_blocks & 15) == 0) {
-        return bsyn_decode(c, d_blocks, d_rows_in, nullptr, d_rec, d_rec_rows, d_status, cenc,
-                           w, k, m, bb, rmax, G, (long long)rmax * bb, nullptr, st);
-    }
-    QF_HIP(qfec::launch_decode_prep(d_rows_in, nullptr, d_status, cenc, w, k, m, bb, rc, rmax, G,
-                                    st, c->tune, d_rec_rows));
-    if (bb % 8 != 0 || k + m > 256) return 0;   // every group is a no-op or status -1
-    if (qfec::gf_stream_supported(k, m, bb, rc, true, c->tune) &&
-        ((uintptr_t)d_blocks & 15) == 0) {
-        const int rcp = std::max(rc, 4);
-        const int nchunk = (rmax + rc - 1) / rc;
-        QF_HIP(qfec::launch_gf_stream(d_blocks, d_rec, w.coef, nullptr, w.nout, k, m, bb, G, rc,
-                                      rmax, (long long)nchunk * k * rcp, (long long)rmax * bb,
-                                      true, st, c->tune));
-        return 0;
-    }
-    QF_HIP(qfec::launch_gf_decode_scratch(d_blocks, d_rec, w, k, m, bb, G, rc, rmax, st,
-                                          c->tune));
-    return 0;
-}
-
-int decode_recovered_impl(qfec_ctx* c, int k, int m, int bb, long long G,
-                          const uint8_t* d_blocks, const uint8_t* d_rows_in, uint8_t* d_rec,
-                          uint8_t* d_rec_rows, int32_t* d_status, hipStream_t st) {
-    if (G == 0) return 0;
-    int r = ws_begin(c, st);
-    if (r) return r;
-    r = decode_recovered_body(c, k, m, bb, G, d_blocks, d_rows_in, d_rec, d_rec_rows, d_status,
-                              st);
-    const int r2 = ws_end(c, st);
-    return r ? r : r2;
-}
+};
+constexpr size_t kCarveSlack = 16 * 256;   // alignment padding of up to 16 sub-buffers
 
 // Host-pointer batches, chunked and pipelined: chunk i's H2D (s_in), kernels (stream)
 // and D2H (s_out) are ordered by events, and NB staging buffers rotate, so the copy-in of
@@ -532,7 +497,7 @@ int decode_recovered_impl(qfec_ctx* c, int k, int m, int bb, long long G,
 // at least the host_min_groups option's groups (512).
 // fn(g0, n, buf, phase): phase 0 enqueues the H2D, 1 the kernels, 2 the D2H.
 template <class F>
-int host_pipeline_body(qfec_ctx* c, long long groups, size_t per_group, size_t slack, F&& fn) {
+int host_pipeline_body(qfec_ctx* c, long long groups, size_t per_group, F&& fn) {
     if (!c->s_in) {
         QF_HIP(hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
         QF_HIP(hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
@@ -552,7 +517,7 @@ int host_pipeline_body(qfec_ctx* c, long long groups, size_t per_group, size_t s
                                                   (long long)((2ull << 30) / per_group));
     const long long chunk =
         std::max<long long>(1, std::min<long long>(groups, std::max(by_bytes, floor_g)));
-    const size_t bytes = (size_t)chunk * per_group + slack;
+    const size_t bytes = (size_t)chunk * per_group + kCarveSlack;
     for (int b = 0; b < qfec_ctx::NB; ++b) QF_HIP(c->pbuf[b].ensure(bytes));
     int i = 0;
     for (long long g0 = 0; g0 < groups; g0 += chunk, ++i) {
@@ -577,12 +542,11 @@ int host_pipeline_body(qfec_ctx* c, long long groups, size_t per_group, size_t s
 // On any error, drain all three streams before returning, so no copy of an earlier chunk
 // still writes into the caller's host buffers after the call has returned.
 template <class F>
-int host_pipeline(qfec_ctx* c, long long groups, size_t per_group, F&& fn, size_t slack = 16) {
+int host_pipeline(qfec_ctx* c, long long groups, size_t per_group, F&& fn) {
     // the kernels of every chunk run on the context stream: order them after the last eager
     // use of the decode workspace, and the next use after them
-    int r = ws_begin(c, c->stream);
-    if (!r) r = host_pipeline_body(c, groups, per_group, slack, fn);
-    if (!r) r = ws_end(c, c->stream);
+    const int r = with_workspace(c, c->stream,
+                                 [&] { return host_pipeline_body(c, groups, per_group, fn); });
     if (r)
         for (hipStream_t s : {c->s_in, c->stream, c->s_out})
             if (s) (void)hipStreamSynchronize(s);
@@ -661,24 +625,51 @@ int open_decode_impl(qfec_ctx* c, int k, int m, int bb, long long groups, const 
     QF_HIP(qfec::launch_open_groups(k, m, bb, groups, d_pkt, pkt_stride,
                                     (const int32_t*)d_pkt_len, (const int32_t*)d_ad_len,
                                     ad_len_all, d_blocks, d_rows, (int32_t*)d_open_len, st));
-    int rc = decode_recovered_impl(c, k, m, bb, groups, d_blocks, d_rows, d_rec, d_rec_rows,
-                                   (int32_t*)d_status, st);
+    int rc = decode_impl(c, k, m, bb, groups, d_blocks, d_rows, {d_rec, d_rec_rows, true},
+                         (int32_t*)d_status, st);
     if (rc) return rc;
     QF_HIP(qfec::launch_open_status(k, std::min(k, m), groups, d_rows, d_rec_rows,
                                     (int32_t*)d_status, st));
     return 0;
 }
 
-// Carves consecutive 256-byte aligned sub-buffers out of one staging buffer.
-struct Carve {
-    uint8_t* p;
-    uint8_t* take(size_t bytes) {
-        uint8_t* r = p;
-        p += (bytes + 255) & ~(size_t)255;
-        return r;
-    }
+// The options of qfec_ctx_set_option / qfec_ctx_get_option: a member of the context's Tune, the
+// values it accepts (lo > hi: read only, set does not know the name) and any further rule.
+struct Opt {
+    const char* name;
+    int qfec::Tune::*member;
+    int lo, hi;
+    bool (*ok)(int) = nullptr;
 };
-constexpr size_t kCarveSlack = 16 * 256;   // alignment padding of up to 16 sub-buffers
+using Tu = qfec::Tune;
+const Opt kOptions[] = {
+    {"cus", &Tu::cus, 1, 0},
+    {"xor_slots", &Tu::xor_slots, 2, 4},       {"xor_waves", &Tu::xor_waves, 1, 4},
+    {"dma", &Tu::dma, 0, 1},                   {"stream", &Tu::stream, 0, 1},
+    {"stream_ring", &Tu::stream_ring, 4, 36},  {"stream_grid", &Tu::stream_grid, 0, 1 << 20},
+    {"const_enc", &Tu::const_enc, 0, 1},       {"stream_static", &Tu::stream_static, 0, 1},
+    {"ring_wide", &Tu::ring_wide, 0, 1},       {"psyn_wide", &Tu::psyn_wide, 0, 2},
+    {"ring_split", &Tu::ring_split, 0, 1},
+    {"dcol", &Tu::dcol, 0, 1},                 {"dcol_grid", &Tu::dcol_grid, 0, 1 << 20},
+    {"dcol_depth", &Tu::dcol_depth, 6, 8, [](int v) { return v != 7; }},
+    {"bsyn", &Tu::bsyn, 0, 1},
+    {"bsyn_depth", &Tu::bsyn_depth, 3, 7, [](int v) { return (v & 1) != 0; }},
+    {"psyn", &Tu::psyn, 0, 1},
+    {"pd", &Tu::pd, 1, 3},                     {"flat", &Tu::flat, 0, 1},
+    {"enc_rc", &Tu::enc_rc, 2, 8, [](int v) { return (v & (v - 1)) == 0; }},
+    {"prep_lane", &Tu::prep_lane, 0, 1},
+    {"host_chunk_mb", &Tu::host_chunk_mb, 1, 4096},
+    {"host_min_groups", &Tu::host_min_groups, 1, 1 << 20},
+    {"ring_wg", &Tu::ring_wg, -1, 1 << 20},    {"bsyn_wg", &Tu::bsyn_wg, -1, 1 << 20},
+    {"psyn_wg", &Tu::psyn_wg, 0, 1 << 20},     {"dcol_wg", &Tu::dcol_wg, 0, 1 << 20},
+    {"stream_wg", &Tu::stream_wg, -1, 1 << 20}, {"xor_wg", &Tu::xor_wg, 0, 1 << 20},
+};
+
+const Opt* find_option(const char* name) {
+    for (const Opt& o : kOptions)
+        if (strcmp(o.name, name) == 0) return &o;
+    return nullptr;
+}
 
 }  // namespace
 
@@ -705,58 +696,21 @@ int qfec_set_timing_events(void* start_event, void* stop_event) {
 int qfec_ctx_set_option(qfec_ctx* c, const char* name, int value) {
     if (!c || !name) return fail(-2, "null context or option name");
     std::lock_guard<std::mutex> lk(c->mu);
-    struct Opt { const char* n; int* p; int lo, hi; };
-    qfec::Tune& t = c->tune;
-    const Opt opts[] = {
-        {"xor_slots", &t.xor_slots, 2, 4},     {"xor_waves", &t.xor_waves, 1, 4},
-        {"dma", &t.dma, 0, 1},                 {"stream", &t.stream, 0, 1},
-        {"stream_ring", &t.stream_ring, 4, 36}, {"stream_grid", &t.stream_grid, 0, 1 << 20},
-        {"const_enc", &t.const_enc, 0, 1},     {"stream_static", &t.stream_static, 0, 1},
-        {"ring_wide", &t.ring_wide, 0, 1}, {"psyn_wide", &t.psyn_wide, 0, 2},
-        {"ring_split", &t.ring_split, 0, 1},
-        {"dcol", &t.dcol, 0, 1},               {"dcol_grid", &t.dcol_grid, 0, 1 << 20},
-        {"dcol_depth", &t.dcol_depth, 6, 8},
-        {"bsyn", &t.bsyn, 0, 1},               {"bsyn_depth", &t.bsyn_depth, 3, 7},
-        {"psyn", &t.psyn, 0, 1},
-        {"pd", &t.pd, 1, 3},                   {"flat", &t.flat, 0, 1},
-        {"enc_rc", &t.enc_rc, 2, 8},           {"prep_lane", &t.prep_lane, 0, 1},
-        {"host_chunk_mb", &t.host_chunk_mb, 1, 4096},
-        {"host_min_groups", &t.host_min_groups, 1, 1 << 20},
-        {"ring_wg", &t.ring_wg, -1, 1 << 20}, {"bsyn_wg", &t.bsyn_wg, -1, 1 << 20},
-        {"psyn_wg", &t.psyn_wg, 0, 1 << 20},  {"dcol_wg", &t.dcol_wg, 0, 1 << 20},
-        {"stream_wg", &t.stream_wg, -1, 1 << 20},
-        {"xor_wg", &t.xor_wg, 0, 1 << 20},
-    };
-    for (const Opt& o : opts) {
-        if (strcmp(o.n, name) != 0) continue;
-        if (value < o.lo || value > o.hi || (o.p == &t.enc_rc && (value & (value - 1))) ||
-            (o.p == &t.dcol_depth && value == 7) || (o.p == &t.bsyn_depth && !(value & 1)))
-            return fail(-2, std::string("option value out of range: ") + name);
-        *o.p = value;
-        return 0;
-    }
-    return fail(-2, std::string("unknown option: ") + name);
+    const Opt* o = find_option(name);
+    if (!o || o->lo > o->hi) return fail(-2, std::string("unknown option: ") + name);
+    if (value < o->lo || value > o->hi || (o->ok && !o->ok(value)))
+        return fail(-2, std::string("option value out of range: ") + name);
+    c->tune.*o->member = value;
+    return 0;
 }
 
 int qfec_ctx_get_option(qfec_ctx* c, const char* name, int* value) {
     if (!c || !name || !value) return fail(-2, "null argument");
     std::lock_guard<std::mutex> lk(c->mu);
-    const qfec::Tune& t = c->tune;
-    const std::pair<const char*, int> opts[] = {
-        {"cus", t.cus}, {"xor_slots", t.xor_slots}, {"xor_waves", t.xor_waves}, {"dma", t.dma},
-        {"stream", t.stream}, {"stream_ring", t.stream_ring}, {"stream_grid", t.stream_grid},
-        {"const_enc", t.const_enc}, {"stream_static", t.stream_static}, {"ring_wide", t.ring_wide}, {"psyn_wide", t.psyn_wide}, {"ring_split", t.ring_split},
-        {"dcol", t.dcol},
-        {"dcol_grid", t.dcol_grid}, {"dcol_depth", t.dcol_depth},
-        {"bsyn", t.bsyn}, {"bsyn_depth", t.bsyn_depth}, {"psyn", t.psyn},
-        {"pd", t.pd}, {"flat", t.flat}, {"enc_rc", t.enc_rc}, {"prep_lane", t.prep_lane},
-        {"host_chunk_mb", t.host_chunk_mb}, {"host_min_groups", t.host_min_groups},
-        {"ring_wg", t.ring_wg}, {"bsyn_wg", t.bsyn_wg}, {"psyn_wg", t.psyn_wg}, {"stream_wg", t.stream_wg},
-        {"dcol_wg", t.dcol_wg}, {"xor_wg", t.xor_wg},
-    };
-    for (const auto& o : opts)
-        if (strcmp(o.first, name) == 0) { *value = o.second; return 0; }
-    return fail(-2, std::string("unknown option: ") + name);
+    const Opt* o = find_option(name);
+    if (!o) return fail(-2, std::string("unknown option: ") + name);
+    *value = c->tune.*o->member;
+    return 0;
 }
 
 int qfec_cauchy_matrix(int k, int m, unsigned char* out) {
@@ -813,32 +767,36 @@ int qfec_encode_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
     return encode_impl(c, k, m, bb, groups, d_data, d_parity, pick(c, stream));
 }
 
+// The two device decodes differ only in where they write (DecodeOut).
+static int decode_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
+                        const unsigned char* d_blocks, const unsigned char* d_rows_in,
+                        DecodeOut o, int* d_status, void* stream) {
+    int rc = check_common(c, k, m, bb, groups);
+    if (rc) return rc;
+    if (groups && (!d_blocks || !d_rows_in || !o.out || !o.rows)) return fail(-2, "null buffer");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    if (groups == 0) return 0;
+    const hipStream_t st = pick(c, stream);
+    return with_workspace(c, st, [&] {
+        return decode_impl(c, k, m, bb, groups, d_blocks, d_rows_in, o, (int32_t*)d_status, st);
+    });
+}
+
 int qfec_decode_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
                       const unsigned char* d_blocks, const unsigned char* d_rows_in,
                       unsigned char* d_out, unsigned char* d_rows_out, int* d_status,
                       void* stream) {
-    int rc = check_common(c, k, m, bb, groups);
-    if (rc) return rc;
-    if (groups && (!d_blocks || !d_rows_in || !d_out || !d_rows_out))
-        return fail(-2, "null buffer");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    return decode_impl(c, k, m, bb, groups, d_blocks, d_rows_in, d_out, d_rows_out,
-                       (int32_t*)d_status, pick(c, stream));
+    return decode_batch(c, k, m, bb, groups, d_blocks, d_rows_in, {d_out, d_rows_out, false},
+                        d_status, stream);
 }
 
 int qfec_decode_batch_recovered(qfec_ctx* c, int k, int m, int bb, long long groups,
                                 const unsigned char* d_blocks, const unsigned char* d_rows_in,
                                 unsigned char* d_rec, unsigned char* d_rec_rows, int* d_status,
                                 void* stream) {
-    int rc = check_common(c, k, m, bb, groups);
-    if (rc) return rc;
-    if (groups && (!d_blocks || !d_rows_in || !d_rec || !d_rec_rows))
-        return fail(-2, "null buffer");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    return decode_recovered_impl(c, k, m, bb, groups, d_blocks, d_rows_in, d_rec, d_rec_rows,
-                                 (int32_t*)d_status, pick(c, stream));
+    return decode_batch(c, k, m, bb, groups, d_blocks, d_rows_in, {d_rec, d_rec_rows, true},
+                        d_status, stream);
 }
 
 // ---- packet protection (pp_null.hip; null_encrypter.cc:23-43, null_decrypter.cc)
@@ -973,12 +931,11 @@ int qfec_open_decode_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     const hipStream_t st = pick(c, stream);
-    if ((rc = ws_begin(c, st))) return rc;
-    if ((rc = open_decode_impl(c, k, m, bb, groups, d_pkt, pkt_stride, d_pkt_len, d_ad_len,
-                               ad_len_all, d_blocks, d_rows, d_open_len, d_rec, d_rec_rows,
-                               d_status, st)))
-        return rc;
-    return ws_end(c, st);
+    return with_workspace(c, st, [&] {
+        return open_decode_impl(c, k, m, bb, groups, d_pkt, pkt_stride, d_pkt_len, d_ad_len,
+                                ad_len_all, d_blocks, d_rows, d_open_len, d_rec, d_rec_rows,
+                                d_status, st);
+    });
 }
 
 int qfec_decode_batch_recovered_host(qfec_ctx* c, int k, int m, int bb, long long groups,
@@ -993,23 +950,23 @@ int qfec_decode_batch_recovered_host(qfec_ctx* c, int k, int m, int bb, long lon
     if ((rc = set_device(c))) return rc;
     const int rmax = std::min(k, m);
     const size_t blk_g = (size_t)k * bb, rec_g = (size_t)rmax * bb;
-    // per group: blocks, recovered blocks, row tags, recovered rows, status (aligned)
+    // per group: blocks, recovered blocks, row tags, recovered rows, status
     const size_t per = blk_g + rec_g + k + rmax + sizeof(int32_t);
     return host_pipeline(c, groups, per, [&](long long g0, long long n, uint8_t* buf,
                                              int phase) -> int {
-        uint8_t* db = buf;
-        uint8_t* dre = db + (size_t)n * blk_g;
-        uint8_t* dr = dre + (size_t)n * rec_g;
-        uint8_t* drr = dr + (size_t)n * k;
-        int32_t* ds = (int32_t*)(((uintptr_t)(drr + (size_t)n * rmax) + 3) & ~(uintptr_t)3);
+        Carve cv{buf};
+        uint8_t* db = cv.take((size_t)n * blk_g);
+        uint8_t* dre = cv.take((size_t)n * rec_g);
+        uint8_t* dr = cv.take((size_t)n * k);
+        uint8_t* drr = cv.take((size_t)n * rmax);
+        int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
         if (phase == 0) {
             QF_HIP(hipMemcpyAsync(db, h_blocks + (size_t)g0 * blk_g, (size_t)n * blk_g,
                                   hipMemcpyHostToDevice, c->s_in));
             QF_HIP(hipMemcpyAsync(dr, h_rows + (size_t)g0 * k, (size_t)n * k,
                                   hipMemcpyHostToDevice, c->s_in));
         } else if (phase == 1) {
-            const int r = decode_recovered_impl(c, k, m, bb, n, db, dr, dre, drr, ds, c->stream);
-            if (r) return r;
+            return decode_impl(c, k, m, bb, n, db, dr, {dre, drr, true}, ds, c->stream);
         } else {
             QF_HIP(hipMemcpyAsync(h_rec + (size_t)g0 * rec_g, dre, (size_t)n * rec_g,
                                   hipMemcpyDeviceToHost, c->s_out));
@@ -1092,7 +1049,7 @@ int qfec_encode_seal_groups_batch_host(qfec_ctx* c, int k, int m, int bb, long l
                                   hipMemcpyDeviceToHost, c->s_out));
         }
         return 0;
-    }, kCarveSlack);
+    });
     return rc;
 }
 
@@ -1155,7 +1112,7 @@ int qfec_open_decode_batch_host(qfec_ctx* c, int k, int m, int bb, long long gro
                                       hipMemcpyDeviceToHost, c->s_out));
         }
         return 0;
-    }, kCarveSlack);
+    });
 }
 
 int qfec_encode_batch_host(qfec_ctx* c, int k, int m, int bb, long long groups,
@@ -1173,8 +1130,9 @@ int qfec_encode_batch_host(qfec_ctx* c, int k, int m, int bb, long long groups,
     int result = 0;
     rc = host_pipeline(c, groups, in_g + out_g, [&](long long g0, long long n, uint8_t* buf,
                                                      int phase) -> int {
-        uint8_t* dd = buf;
-        uint8_t* dp = buf + (size_t)n * in_g;
+        Carve cv{buf};
+        uint8_t* dd = cv.take((size_t)n * in_g);
+        uint8_t* dp = cv.take((size_t)n * out_g);
         if (phase == 0) {
             QF_HIP(hipMemcpyAsync(dd, h_data + (size_t)g0 * in_g, (size_t)n * in_g,
                                   hipMemcpyHostToDevice, c->s_in));
@@ -1203,21 +1161,21 @@ int qfec_decode_batch_host(qfec_ctx* c, int k, int m, int bb, long long groups,
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     const size_t blk_g = (size_t)k * bb;
-    // per group: blocks, row tags, status (4-byte aligned inside the chunk buffer)
+    // per group: blocks, row tags, status
     const size_t per = blk_g + k + sizeof(int32_t);
     return host_pipeline(c, groups, per, [&](long long g0, long long n, uint8_t* buf,
                                              int phase) -> int {
-        uint8_t* db = buf;
-        uint8_t* dr = db + (size_t)n * blk_g;
-        int32_t* ds = (int32_t*)(((uintptr_t)(dr + (size_t)n * k) + 3) & ~(uintptr_t)3);
+        Carve cv{buf};
+        uint8_t* db = cv.take((size_t)n * blk_g);
+        uint8_t* dr = cv.take((size_t)n * k);
+        int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
         if (phase == 0) {
             QF_HIP(hipMemcpyAsync(db, h_blocks + (size_t)g0 * blk_g, (size_t)n * blk_g,
                                   hipMemcpyHostToDevice, c->s_in));
             QF_HIP(hipMemcpyAsync(dr, h_rows + (size_t)g0 * k, (size_t)n * k,
                                   hipMemcpyHostToDevice, c->s_in));
         } else if (phase == 1) {
-            const int r = decode_impl(c, k, m, bb, n, db, dr, db, dr, ds, c->stream);
-            if (r) return r;
+            return decode_impl(c, k, m, bb, n, db, dr, {db, dr, false}, ds, c->stream);
         } else {
             QF_HIP(hipMemcpyAsync(h_blocks + (size_t)g0 * blk_g, db, (size_t)n * blk_g,
                                   hipMemcpyDeviceToHost, c->s_out));
@@ -1309,7 +1267,9 @@ int cauchy_256_decode(int k, int m, Block* blocks, int block_bytes) {
     uint8_t* dr = dd + data_bytes;
     int32_t* dst = (int32_t*)(((uintptr_t)(dr + 256) + 3) & ~(uintptr_t)3);
     QF_HIP(hipMemcpyAsync(dd, hs, data_bytes + 256, hipMemcpyHostToDevice, c->stream));
-    rc = decode_impl(c, k, m, block_bytes, 1, dd, dr, dd, dr, dst, c->stream);
+    rc = with_workspace(c, c->stream, [&] {
+        return decode_impl(c, k, m, block_bytes, 1, dd, dr, {dd, dr, false}, dst, c->stream);
+    });
     if (rc) return rc;
     QF_HIP(hipMemcpyAsync(hs, dd, data_bytes + k, hipMemcpyDeviceToHost, c->stream));
     QF_HIP(hipMemcpyAsync(hst, dst, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1328,19 +1288,14 @@ int qfec_reserve(qfec_ctx* c, int k, int m, int bb, long long groups) {
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     // both workspaces: the eager one and the one calls captured into a graph use
-    for (Workspace* W : {&c->ws, &c->ws_graph}) {
-        QF_HIP(W->ensure(W->dslots, (size_t)groups));   // m == 1 decode: erased slot per group
-        if (m > 1 && k > 1) {
-            const int rmax = std::min(k, m);
-            if ((rc = decode_workspace(*W, k, rmax, decode_rc(rmax), groups))) return rc;
-            if (rmax > decode_rc(rmax)) QF_HIP(W->ensure(W->dscratch, (size_t)groups * rmax * bb));
-        }
-    }
+    const DecodePlan p = decode_plan(k, m, bb);
+    for (Workspace* W : {&c->ws, &c->ws_graph})
+        if ((rc = reserve_workspace(*W, p, groups, true))) return rc;
     if (m > 1 && k > 1 && k + m <= 256) {
         const uint8_t* t;
         if ((rc = get_enc_table(c, k, m, stream_encode_rc(k, m, bb, true, c->tune), &t))) return rc;
     }
-    if (m > 1 && k > 1) {
+    if (p.cenc) {
         const uint8_t* t;
         if ((rc = get_cenc(c, k, m, &t))) return rc;
     }

@@ -1170,3 +1170,174 @@ def test_syndrome_decode_patterns(tuned_engine, oracle, grid, opts):
     assert st.tolist() == [-3, -3]
     np.testing.assert_array_equal(rr, rows[bad])
     np.testing.assert_array_equal(b, recv[bad])
+
+
+# ------------------------------------------------- which kernels each decode path runs
+# (k, m, bb, groups): one shape per rung of the host layer's decode dispatch
+PATH_SHAPES = [
+    (1, 3, 64, 64),          # k <= 1
+    (4, 1, 1352, 64),        # m == 1
+    (4, 1, 100, 64),         # m == 1, bb not a multiple of 8
+    (4, 2, 100, 64),         # bb not a multiple of 8: prep only, every status -1
+    (32, 4, 1352, 64),       # gf_bsyn
+    (10, 10, 1352, 64),      # gf_psyn
+    (5, 5, 1352, 64),        # gf_psyn
+    (128, 16, 9008, 2),      # gf_dcol
+    (250, 5, 1352, 64),      # gf_stream, one chunk
+    (12, 10, 1352, 64),      # gf_stream, rmax 10 > 8: two chunks, in place through scratch
+    (6, 3, 4096, 64),        # gf_apply
+    (20, 12, 4096, 64),      # gf_apply, two chunks, in place through scratch
+]
+# the first shape of each compiled path again with each compiled path switched off
+PATH_COMPILED = [(32, 4, 1352, 64), (10, 10, 1352, 64), (128, 16, 9008, 2), (250, 5, 1352, 64)]
+PATH_CASES = (
+    [(s, {}, 0) for s in PATH_SHAPES] +
+    [(s, {o: 0}, 0) for s in PATH_COMPILED for o in ("bsyn", "psyn", "dcol", "stream")] +
+    # blocks 8 bytes past a 16-byte boundary: the fall-through past the compiled paths
+    [((32, 4, 1352, 64), {}, 8), ((10, 10, 1352, 64), {}, 8)])
+
+
+def path_case_id(case):
+    (k, m, bb, G), opts, offset = case
+    return "-".join([f"k{k}m{m}bb{bb}"] + [f"{o}={v}" for o, v in opts.items()] +
+                    ([f"off{offset}"] if offset else []))
+
+
+# (encode, decode in place, decode out of place, decode_recovered): fec.last_kernels() after
+# each call.  Recorded strings, not derived from the dispatch: a change of the host layer that
+# is meant to keep the path selection must pass without editing them
+_BSYN = "decode_prep_bsyn_kernel + gf_bsyn_kernel<decode,k32m4>"
+_PSYN = "decode_prep_psyn_kernel + gf_psyn_kernel<decode,preset>"
+_DCOL = "decode_prep_kernel<syndrome> + gf_dcol_kernel<decode,k128m16>"
+_STREAM = "decode_prep_kernel + gf_stream_kernel<decode>"
+_STREAM_LANE = "decode_prep_lane_kernel + gf_stream_kernel<decode>"
+_STREAM_WIDE = "decode_prep_wide_kernel + gf_stream_kernel<decode>"
+_APPLY = "decode_prep_kernel + gf_apply_kernel<decode>"
+_APPLY_LANE = "decode_prep_lane_kernel + gf_apply_kernel<decode>"
+_APPLY_WIDE = "decode_prep_wide_kernel + gf_apply_kernel<decode>"
+_SCATTER = " + scatter_recovered_kernel"
+_M1_FLAT = "m1_prep_kernel + xor_flat_kernel<decode>"
+PATH_KERNELS = {
+    "k1m3bb64": ("replicate_kernel", "rows_k1_kernel", "rows_k1_kernel", "rec_k1_kernel"),
+    "k4m1bb1352": ("xor_dma_kernel<encode>", "xor_dma_kernel<decode>", "xor_dma_kernel<decode>",
+                   "xor_dma_kernel<decode,recovered>"),
+    "k4m1bb100": ("xor_flat_kernel<encode>", _M1_FLAT, _M1_FLAT, _M1_FLAT),
+    "k4m2bb100": ("xor_flat_kernel<encode>", "decode_prep_lane_kernel", "decode_prep_lane_kernel",
+                  "decode_prep_lane_kernel"),
+    "k32m4bb1352": ("gf_ring_kernel<encode,k32m4>", _BSYN, _BSYN, _BSYN),
+    "k10m10bb1352": ("gf_ring_kernel<encode,k10m10>", _PSYN, _PSYN, _PSYN),
+    "k5m5bb1352": ("gf_ring_kernel<encode,k5m5>", _PSYN, _PSYN, _PSYN),
+    "k128m16bb9008": ("gf_dcol_kernel<encode,k128m16>", _DCOL, _DCOL, _DCOL),
+    "k250m5bb1352": ("gf_ring_kernel<encode,k250m5>", _STREAM, _STREAM, _STREAM),
+    "k12m10bb1352": ("gf_stream_kernel<encode>", _STREAM_WIDE + _SCATTER, _STREAM_WIDE,
+                     _STREAM_WIDE),
+    "k6m3bb4096": ("gf_apply_kernel<encode>", _APPLY_WIDE, _APPLY_WIDE, _APPLY_WIDE),
+    "k20m12bb4096": ("gf_apply_kernel<encode>", _APPLY_WIDE + _SCATTER, _APPLY_WIDE, _APPLY_WIDE),
+    "k32m4bb1352-bsyn=0": ("gf_ring_kernel<encode,k32m4>", _STREAM_LANE, _STREAM_LANE,
+                           _STREAM_LANE),
+    "k32m4bb1352-psyn=0": ("gf_ring_kernel<encode,k32m4>", _BSYN, _BSYN, _BSYN),
+    "k32m4bb1352-dcol=0": ("gf_ring_kernel<encode,k32m4>", _BSYN, _BSYN, _BSYN),
+    "k32m4bb1352-stream=0": ("gf_apply_kernel<encode,flat>", _BSYN, _BSYN, _BSYN),
+    "k10m10bb1352-bsyn=0": ("gf_ring_kernel<encode,k10m10>", _PSYN, _PSYN, _PSYN),
+    "k10m10bb1352-psyn=0": ("gf_ring_kernel<encode,k10m10>", _STREAM_WIDE + _SCATTER,
+                            _STREAM_WIDE, _STREAM_WIDE),
+    "k10m10bb1352-dcol=0": ("gf_ring_kernel<encode,k10m10>", _PSYN, _PSYN, _PSYN),
+    "k10m10bb1352-stream=0": ("gf_apply_kernel<encode,flat>", _PSYN, _PSYN, _PSYN),
+    "k128m16bb9008-bsyn=0": ("gf_dcol_kernel<encode,k128m16>", _DCOL, _DCOL, _DCOL),
+    "k128m16bb9008-psyn=0": ("gf_dcol_kernel<encode,k128m16>", _DCOL, _DCOL, _DCOL),
+    "k128m16bb9008-dcol=0": ("gf_apply_kernel<encode,flat>", _APPLY + _SCATTER, _APPLY, _APPLY),
+    "k128m16bb9008-stream=0": ("gf_dcol_kernel<encode,k128m16>", _DCOL, _DCOL, _DCOL),
+    "k250m5bb1352-bsyn=0": ("gf_ring_kernel<encode,k250m5>", _STREAM, _STREAM, _STREAM),
+    "k250m5bb1352-psyn=0": ("gf_ring_kernel<encode,k250m5>", _STREAM, _STREAM, _STREAM),
+    "k250m5bb1352-dcol=0": ("gf_ring_kernel<encode,k250m5>", _STREAM, _STREAM, _STREAM),
+    "k250m5bb1352-stream=0": ("gf_apply_kernel<encode,flat>", _APPLY, _APPLY, _APPLY),
+    "k32m4bb1352-off8": ("gf_ring_kernel<encode,k32m4>", _APPLY_LANE, _APPLY_LANE, _APPLY_LANE),
+    "k10m10bb1352-off8": ("gf_ring_kernel<encode,k10m10>", _APPLY_WIDE + _SCATTER, _APPLY_WIDE,
+                          _APPLY_WIDE),
+}
+
+
+_path_refs = {}
+
+
+def path_reference(oracle, k, m, bb, G):
+    """Inputs and the oracle's results for one shape, computed once (read-only)."""
+    key = (k, m, bb, G)
+    if key not in _path_refs:
+        data = synth.group_data(8100 + 3 * k + m, k, bb, G)
+        p_or, rc_or = oracle.encode_batch(k, m, bb, data)
+        rows, src = synth.loss_patterns(k, m, min(k, m), G, 61 + k + bb, shuffle=True)
+        recv = synth.assemble_received(data, p_or, src)
+        b_or, r_or, s_or = oracle.decode_batch(k, m, bb, recv, rows)
+        exp, exp_rows = expected_recovered(k, m, bb, rows, b_or, r_or, s_or)
+        _path_refs[key] = (data, p_or, rc_or, rows, recv, b_or, r_or, s_or, exp, exp_rows)
+    return _path_refs[key]
+
+
+def dev_at(a, offset):
+    """A device copy of `a` that starts `offset` bytes past a 16-byte boundary."""
+    import torch
+    buf = torch.empty(a.size + 16, dtype=torch.uint8, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    v = buf[offset:offset + a.size].view(a.shape)
+    v.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+    assert v.data_ptr() % 16 == offset
+    return v
+
+
+def run_decode_paths(engine, oracle, k, m, bb, G, offset):
+    """Encode, decode (slot layout in place and out of place) and decode_recovered, each
+    bit-exact with the oracle; returns the kernels each of the four calls launched."""
+    import torch
+    data, p_or, rc_or, rows, recv, b_or, r_or, s_or, exp, exp_rows = \
+        path_reference(oracle, k, m, bb, G)
+    kernels = []
+    p_gpu, rc = gpu_encode(engine, k, m, bb, data)
+    kernels.append(fec.last_kernels())
+    assert rc == rc_or
+    np.testing.assert_array_equal(p_gpu, p_or)
+    # slot layout, in place
+    b, r = dev_at(recv, offset), dev(rows)
+    st = torch.full((G,), 7, dtype=torch.int32, device="cuda")
+    engine.decode(k, m, bb, b, r, status=st)
+    kernels.append(fec.last_kernels())
+    np.testing.assert_array_equal(host(st), s_or)
+    np.testing.assert_array_equal(host(r), r_or)
+    np.testing.assert_array_equal(host(b), b_or)
+    # slot layout, out of place: only the recovered slots are written
+    b, r = dev_at(recv, offset), dev(rows)
+    out, ro = torch.zeros((G, k, bb), dtype=torch.uint8, device="cuda"), torch.zeros_like(r)
+    st = torch.full((G,), 7, dtype=torch.int32, device="cuda")
+    engine.decode(k, m, bb, b, r, out=out, rows_out=ro, status=st)
+    kernels.append(fec.last_kernels())
+    np.testing.assert_array_equal(host(st), s_or)
+    np.testing.assert_array_equal(host(ro), r_or)
+    written = (r_or != rows) & (k > 1)      # k <= 1 only retags the block it was given
+    np.testing.assert_array_equal(host(out)[written], b_or[written])
+    assert not host(out)[~written].any()
+    np.testing.assert_array_equal(host(b), recv)
+    # recovered-blocks layout
+    rmax = min(k, m)
+    rec = torch.zeros((G, rmax, bb), dtype=torch.uint8, device="cuda")
+    rec_rows = torch.zeros((G, rmax), dtype=torch.uint8, device="cuda")
+    st = torch.full((G,), 7, dtype=torch.int32, device="cuda")
+    engine.decode_recovered(k, m, bb, b, r, rec, rec_rows, status=st)
+    kernels.append(fec.last_kernels())
+    np.testing.assert_array_equal(host(st), s_or)
+    np.testing.assert_array_equal(host(rec_rows), exp_rows)
+    mask = exp_rows != 255
+    np.testing.assert_array_equal(host(rec)[mask], exp[mask])
+    np.testing.assert_array_equal(host(b), recv)
+    return tuple(kernels)
+
+
+@pytest.mark.parametrize("case", PATH_CASES, ids=path_case_id)
+def test_decode_path_selection(tuned_engine, oracle, case):
+    """Every rung of the decode dispatch, in both output layouts: the kernels launched are
+    exactly the recorded ones and every output, row tag and status is the oracle's."""
+    (k, m, bb, G), opts, offset = case
+    for name, v in opts.items():
+        tuned_engine.set_option(name, v)
+    got = run_decode_paths(tuned_engine, oracle, k, m, bb, G, offset)
+    print(path_case_id(case), got)
+    assert got == PATH_KERNELS[path_case_id(case)]
