@@ -20,11 +20,11 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden \
 DCOLK := e63 e83 d62 d82
 # preset syndrome-decode instantiations, one object per code (gf_psyn.h)
 PSYNK := 1010 1015 1020 1515 55
-SRCS := $(CSRC)/fec_kernels.hip $(CSRC)/xor_dma.hip $(CSRC)/gf_stream.hip $(CSRC)/gf_bsyn.hip $(CSRC)/gf_psyn.hip $(PSYNK:%=$(CSRC)/gf_psyn_%.hip) $(CSRC)/gf_dcol.hip $(DCOLK:%=$(CSRC)/gf_dcol_%.hip) $(CSRC)/pp_null.hip $(CSRC)/fec_api.cpp $(CSRC)/fec_group.cpp $(CSRC)/fec_wire.cpp
+SRCS := $(CSRC)/fec_kernels.hip $(CSRC)/xor_dma.hip $(CSRC)/gf_stream.hip $(CSRC)/gf_bsyn.hip $(CSRC)/gf_psyn.hip $(PSYNK:%=$(CSRC)/gf_psyn_%.hip) $(CSRC)/gf_dcol.hip $(DCOLK:%=$(CSRC)/gf_dcol_%.hip) $(CSRC)/gf_ragged.hip $(CSRC)/pp_null.hip $(CSRC)/fec_api.cpp $(CSRC)/fec_ragged_host.cpp $(CSRC)/fec_group.cpp $(CSRC)/fec_wire.cpp
 # the headers every object depends on; the rest (include/*.h, pp_null.h, ...) are tracked per
 # object by -MMD below, so a public-header edit rebuilds only the host files that include it
 HDRS := $(CSRC)/fec_kernels.h $(CSRC)/gf256.h $(CSRC)/gf_bitslice.h
-OBJS := $(ROOT)build/fec_kernels.o $(ROOT)build/xor_dma.o $(ROOT)build/gf_stream.o $(ROOT)build/gf_bsyn.o $(ROOT)build/gf_psyn.o $(PSYNK:%=$(ROOT)build/gf_psyn_%.o) $(ROOT)build/gf_dcol.o $(DCOLK:%=$(ROOT)build/gf_dcol_%.o) $(ROOT)build/pp_null.o $(ROOT)build/fec_api.o $(ROOT)build/fec_group.o $(ROOT)build/fec_wire.o
+OBJS := $(ROOT)build/fec_kernels.o $(ROOT)build/xor_dma.o $(ROOT)build/gf_stream.o $(ROOT)build/gf_bsyn.o $(ROOT)build/gf_psyn.o $(PSYNK:%=$(ROOT)build/gf_psyn_%.o) $(ROOT)build/gf_dcol.o $(DCOLK:%=$(ROOT)build/gf_dcol_%.o) $(ROOT)build/gf_ragged.o $(ROOT)build/pp_null.o $(ROOT)build/fec_api.o $(ROOT)build/fec_ragged_host.o $(ROOT)build/fec_group.o $(ROOT)build/fec_wire.o
 
 # Build guard (tools/check_stubs.py): every kernel stub a host pass registers has device code
 # in the same object.  Run after each HIP compile (the object is deleted on a mismatch) and on
@@ -57,9 +57,21 @@ $(TOOL): $(ROOT)tools/loopback/fec_loopback.cpp $(LIB) $(ROOT)include/quic_fec_g
 	g++ -O2 -std=c++17 -Wall -I$(ROOT)include -o $@ $< -L$(ROOT)quic_amd -lquic_fec \
 	    -Wl,-rpath,'$$ORIGIN/..' -ldl -lpthread
 
+# Host-code sanitizer check of the ragged layout and packing: a stand-alone program (its own
+# main, no HIP, not loaded into Python) built with ASan + UBSan; `make ragged-check` runs it.
+RPCK := $(ROOT)quic_amd/bin/ragged_pack_check
+$(RPCK): $(ROOT)tools/ragged_pack_check.cpp $(CSRC)/fec_ragged_host.cpp $(CSRC)/fec_ragged_host.h $(ROOT)include/quic_fec.h
+	@mkdir -p $(ROOT)quic_amd/bin
+	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all \
+	    -I$(ROOT)include -I$(CSRC) -o $@ $(ROOT)tools/ragged_pack_check.cpp $(CSRC)/fec_ragged_host.cpp
+
+.PHONY: ragged-check
+ragged-check: $(RPCK)
+	$(RPCK)
+
 lib: $(LIB)
 
-$(ROOT)build/fec_kernels.o: $(CSRC)/fec_kernels.hip $(HDRS)
+$(ROOT)build/fec_kernels.o: $(CSRC)/fec_kernels.hip $(CSRC)/gf_colword.h $(HDRS)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
@@ -118,6 +130,12 @@ $(ROOT)build/gf_dcol_%.o: $(CSRC)/gf_dcol_%.hip $(CSRC)/gf_dcol.h $(CSRC)/gf_win
 	$(HIPCC) $(HIPFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
 
+# run-time-shape kernels of the ragged batches (per-group block_bytes)
+$(ROOT)build/gf_ragged.o: $(CSRC)/gf_ragged.hip $(CSRC)/gf_colword.h $(HDRS)
+	@mkdir -p $(ROOT)build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
+
 $(ROOT)build/pp_null.o: $(CSRC)/pp_null.hip $(HDRS)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -132,6 +150,12 @@ $(ROOT)build/fec_group.o: $(CSRC)/fec_group.cpp $(HDRS)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
+
+# host-only (no HIP): the ragged layout and the queue's packing; also linked alone by the
+# sanitizer check below
+$(ROOT)build/fec_ragged_host.o: $(CSRC)/fec_ragged_host.cpp $(CSRC)/fec_ragged_host.h $(ROOT)include/quic_fec.h
+	@mkdir -p $(ROOT)build
+	g++ -O2 -std=c++17 -fPIC -fvisibility=hidden -DQFEC_BUILD -Wall -MMD -MP -c $< -o $@
 
 $(ROOT)build/fec_wire.o: $(CSRC)/fec_wire.cpp $(HDRS)
 	@mkdir -p $(ROOT)build
@@ -150,5 +174,5 @@ oracle:
 -include $(OBJS:.o=.d)
 
 clean:
-	rm -rf $(ROOT)build $(LIB) $(TOOL) $(LAT)
+	rm -rf $(ROOT)build $(LIB) $(TOOL) $(LAT) $(RPCK)
 	$(MAKE) -s -C $(ROOT)oracle clean

@@ -144,6 +144,84 @@ QFEC_API int qfec_decode_batch_recovered_host(qfec_ctx *ctx, int k, int m, int b
                                      unsigned char *h_rec_rows, int *h_status);
 
 /* ---------------------------------------------------------------------------------
+ * Ragged batches: one launch over groups that share (k, m) but each carry their own
+ * block_bytes (the group layer fixes block_bytes per group, quic_fec_group.cc:344-352; a
+ * short group cannot be zero-padded to a common size, because the sub-row split bb/8 is part
+ * of the code and parity is wire-visible).
+ *
+ * Packed layout: group g's k blocks are [k][bb[g]], contiguous, at base + off[g]; its outputs
+ * are [m][bb[g]] (parity) or [min(k,m)][bb[g]] (recovered blocks) at their own base + off[g].
+ * Offsets are byte offsets, multiples of 16, in explicit arrays; sizes are the int array
+ * bb [G].  The base pointers must be 16-byte aligned.  Gaps between groups are allowed and
+ * are never written.  rows [G][k], rec_rows [G][min(k,m)] and status [G] are dense as in the
+ * uniform calls.
+ *
+ * Per-group semantics are exactly those of the uniform call with block_bytes = bb[g], i.e.
+ * of cauchy_256_encode / cauchy_256_decode on that group: k <= 1 copies; m == 1 is XOR with
+ * any bb >= 1; for m > 1 and bb[g] % 8 != 0 the group's status is -1 (on encode its first
+ * parity block still receives the XOR parity, cauchy_256.cpp:1519-1534, and nothing else of
+ * that group is written; on decode a group without a recovery block has status 0, :1287-1289);
+ * a malformed receive set has status -3 and is left as it was.  rec_rows is 255 past a
+ * group's erasure count and the rec bytes of such entries are not written.  Call-level
+ * errors follow the uniform calls: with m > 1 and k + m > 256 the encode writes every
+ * group's XOR parity and returns -1; a null pointer or groups < 0 returns -2.
+ *
+ * Workspace, streams, graphs: the device entry points only enqueue on `stream`; they never
+ * read d_bb or the offsets back to the host, so a group with bb[g] < 1 is skipped by the
+ * kernels rather than reported.  The ragged decode uses the same decode workspace, in the
+ * same bracket, as the uniform decodes: everything the paragraph above says about streams,
+ * contexts and captured graphs holds for it unchanged.  Its workspace does not depend on
+ * the block sizes: qfec_reserve(ctx, k, m, any block_bytes, groups) covers a capture of up
+ * to `groups` groups (pass the largest bb; the reserve also loads the encode table of the
+ * ragged encode).  In-place and slot-layout ragged decodes do not exist; the recovered layout
+ * is what the group layer consumes.
+ * ------------------------------------------------------------------------------- */
+/* Host helper, no GPU: fills data_off / par_off / rec_off [G] (any may be NULL) with each
+ * group's offset in a buffer that packs the groups in order, every group rounded up to 16
+ * bytes: k, m and min(k, m) blocks of bb[g] bytes per group.  totals (may be NULL) receives
+ * the three buffer sizes (multiples of 16).  -2 on bb[g] < 1, a bad k / m / groups or
+ * overflow. */
+QFEC_API int qfec_ragged_layout(int k, int m, long long groups, const int *bb,
+                                long long *data_off, long long *par_off, long long *rec_off,
+                                long long totals[3]);
+
+/* d_parity + d_par_off[g] receives [m][bb[g]].  d_status [G] may be NULL. */
+QFEC_API int qfec_encode_batch_ragged(qfec_ctx *ctx, int k, int m, long long groups,
+                                      const int *d_bb, const unsigned char *d_data,
+                                      const long long *d_data_off, unsigned char *d_parity,
+                                      const long long *d_par_off, int *d_status, void *stream);
+
+/* As qfec_decode_batch_recovered: d_blocks and d_rows_in [G][k] are left untouched; recovered
+ * block j of group g goes to d_rec + d_rec_off[g] + j * bb[g] and its data row to
+ * d_rec_rows[g * min(k,m) + j] (ascending; 255 past the count).  d_status may be NULL. */
+QFEC_API int qfec_decode_batch_ragged_recovered(qfec_ctx *ctx, int k, int m, long long groups,
+                                                const int *d_bb, const unsigned char *d_blocks,
+                                                const long long *d_blocks_off,
+                                                const unsigned char *d_rows_in,
+                                                unsigned char *d_rec, const long long *d_rec_off,
+                                                unsigned char *d_rec_rows, int *d_status,
+                                                void *stream);
+
+/* Host-pointer variants: the same arguments in host memory; synchronous; chunked and
+ * pipelined like the other host batches.  Chunks are cut on group boundaries by bytes (the
+ * "host_chunk_mb" option; "host_min_groups" does not apply, a chunk holds at least one group).
+ * The offsets must be ascending and the groups must not overlap (-2 otherwise, and for
+ * bb[g] < 1 or an offset that is not a multiple of 16); qfec_ragged_layout produces such
+ * offsets.  Bytes of the output buffer the call does not write keep the caller's values. */
+QFEC_API int qfec_encode_batch_ragged_host(qfec_ctx *ctx, int k, int m, long long groups,
+                                           const int *h_bb, const unsigned char *h_data,
+                                           const long long *h_data_off, unsigned char *h_parity,
+                                           const long long *h_par_off, int *h_status);
+QFEC_API int qfec_decode_batch_ragged_recovered_host(qfec_ctx *ctx, int k, int m,
+                                                     long long groups, const int *h_bb,
+                                                     const unsigned char *h_blocks,
+                                                     const long long *h_blocks_off,
+                                                     const unsigned char *h_rows,
+                                                     unsigned char *h_rec,
+                                                     const long long *h_rec_off,
+                                                     unsigned char *h_rec_rows, int *h_status);
+
+/* ---------------------------------------------------------------------------------
  * Packet protection next to the FEC path (SURVEY.md §8 f, rank 4).
  *
  * The reference encrypts every packet after serialisation -- the FEC packets right after
@@ -281,7 +359,9 @@ QFEC_API int qfec_synth_gather(const unsigned char *d_data, const unsigned char 
 
 QFEC_API const char *qfec_last_error(void);
 /* Names of the kernels this thread's last engine call launched, " + "-separated, e.g.
- * "decode_prep_lane_kernel + gf_stream_kernel<decode>" (bench.py reports it). */
+ * "decode_prep_lane_kernel + gf_stream_kernel<decode>" (bench.py reports it).  The ragged
+ * calls name "gf_ragged_kernel<encode>", "gf_ragged_kernel<decode>", "xor_ragged_kernel" and
+ * "copy_ragged_kernel". */
 QFEC_API const char *qfec_last_kernels(void);
 /* Grids of the persistent kernels the last call on this thread launched, as space-separated
  * "kernel=workgroups" entries (e.g. "gf_psyn_kernel=1024"); diagnostics and tests. */

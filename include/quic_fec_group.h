@@ -95,6 +95,13 @@ QFEC_API void qfec_packets_free(qfec_packets *l);
 typedef struct qfec_batch qfec_batch;
 QFEC_API qfec_batch *qfec_batch_new(qfec_ctx *ctx, size_t max_groups, unsigned max_delay_us);
 QFEC_API void qfec_batch_free(qfec_batch *b);
+/* Ragged buckets (off by default).  on != 0: buckets are keyed by (k, m) only, every queued
+ * group keeps its own block_bytes, and a flush packs the bucket (qfec_ragged_layout) and runs
+ * ONE ragged host call (qfec_*_batch_ragged*_host) per (k, m); max_groups counts per (k, m)
+ * bucket.  Worth it when the groups of a flush spread over many block sizes (short last
+ * writes, small packets), where the uniform buckets turn into many launches of a few groups
+ * each.  Returns -2 while groups are queued (flush first). */
+QFEC_API int qfec_batch_set_ragged(qfec_batch *b, int on);
 QFEC_API int qfec_batch_add_encode(qfec_batch *b, qfec_group *g);   /* group must stay alive */
 QFEC_API int qfec_batch_add_decode(qfec_batch *b, qfec_group *g);
 QFEC_API int qfec_batch_poll(qfec_batch *b);    /* flushes if the timeout expired; >= 0 = groups done */

@@ -54,6 +54,31 @@ SIGNATURES = {
                                                         ctypes.c_longlong, ctypes.c_void_p,
                                                         ctypes.c_void_p, ctypes.c_void_p,
                                                         ctypes.c_void_p, ctypes.c_void_p]),
+    "qfec_ragged_layout": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "qfec_encode_batch_ragged": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_longlong, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "qfec_decode_batch_ragged_recovered": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
+                                                          ctypes.c_int, ctypes.c_longlong,
+                                                          ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_void_p,
+                                                          ctypes.c_void_p]),
+    "qfec_encode_batch_ragged_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_longlong, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p]),
+    "qfec_decode_batch_ragged_recovered_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
+                                                               ctypes.c_int, ctypes.c_longlong,
+                                                               ctypes.c_void_p, ctypes.c_void_p,
+                                                               ctypes.c_void_p, ctypes.c_void_p,
+                                                               ctypes.c_void_p, ctypes.c_void_p,
+                                                               ctypes.c_void_p, ctypes.c_void_p]),
     "qfec_null_seal_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
                                             ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                             ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]),

@@ -496,8 +496,10 @@ constexpr size_t kCarveSlack = 16 * 256;   // alignment padding of up to 16 sub-
 // never shared by two chunks in flight.  Chunk size: the host_chunk_mb option (64 MiB), and
 // at least the host_min_groups option's groups (512).
 // fn(g0, n, buf, phase): phase 0 enqueues the H2D, 1 the kernels, 2 the D2H.
-template <class F>
-int host_pipeline_body(qfec_ctx* c, long long groups, size_t per_group, F&& fn) {
+// next(g0): groups in the chunk that starts at group g0 (0: no group left); `bytes`: the
+// staging one chunk needs at most.
+template <class N, class F>
+int host_pipeline_chunks(qfec_ctx* c, size_t bytes, N&& next, F&& fn) {
     if (!c->s_in) {
         QF_HIP(hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
         QF_HIP(hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
@@ -507,21 +509,10 @@ int host_pipeline_body(qfec_ctx* c, long long groups, size_t per_group, F&& fn) 
             QF_HIP(hipEventCreateWithFlags(&c->ev_out[b], hipEventDisableTiming));
         }
     }
-    // at least host_min_groups groups per chunk (up to 2 GiB of staging per buffer): a
-    // 64 MiB chunk of D's 1.2 MB groups is 54 groups, too few to fill the device (D at
-    // 16,384 groups: 16.1 GiB/s with 64 MiB chunks, 22.9 with 256 MiB, 23.3 with 1 GiB).
-    // Both are options, so a caller (and the tests) can still force small chunks.
-    const size_t target = (size_t)std::max(1, c->tune.host_chunk_mb) << 20;
-    const long long by_bytes = (long long)(target / per_group);
-    const long long floor_g = std::min<long long>(std::max(1, c->tune.host_min_groups),
-                                                  (long long)((2ull << 30) / per_group));
-    const long long chunk =
-        std::max<long long>(1, std::min<long long>(groups, std::max(by_bytes, floor_g)));
-    const size_t bytes = (size_t)chunk * per_group + kCarveSlack;
     for (int b = 0; b < qfec_ctx::NB; ++b) QF_HIP(c->pbuf[b].ensure(bytes));
     int i = 0;
-    for (long long g0 = 0; g0 < groups; g0 += chunk, ++i) {
-        const long long n = std::min(chunk, groups - g0);
+    long long n = 0;
+    for (long long g0 = 0; (n = next(g0)) > 0; g0 += n, ++i) {
         const int b = i % qfec_ctx::NB;
         uint8_t* buf = (uint8_t*)c->pbuf[b].p;
         if (i >= qfec_ctx::NB) QF_HIP(hipStreamWaitEvent(c->s_in, c->ev_out[b], 0));
@@ -539,18 +530,39 @@ int host_pipeline_body(qfec_ctx* c, long long groups, size_t per_group, F&& fn) 
     return 0;
 }
 
+template <class F>
+int host_pipeline_body(qfec_ctx* c, long long groups, size_t per_group, F&& fn) {
+    // at least host_min_groups groups per chunk (up to 2 GiB of staging per buffer): a
+    // 64 MiB chunk of D's 1.2 MB groups is 54 groups, too few to fill the device (D at
+    // 16,384 groups: 16.1 GiB/s with 64 MiB chunks, 22.9 with 256 MiB, 23.3 with 1 GiB).
+    // Both are options, so a caller (and the tests) can still force small chunks.
+    const size_t target = (size_t)std::max(1, c->tune.host_chunk_mb) << 20;
+    const long long by_bytes = (long long)(target / per_group);
+    const long long floor_g = std::min<long long>(std::max(1, c->tune.host_min_groups),
+                                                  (long long)((2ull << 30) / per_group));
+    const long long chunk =
+        std::max<long long>(1, std::min<long long>(groups, std::max(by_bytes, floor_g)));
+    return host_pipeline_chunks(
+        c, (size_t)chunk * per_group + kCarveSlack,
+        [&](long long g0) { return std::min(chunk, groups - g0); }, fn);
+}
+
 // On any error, drain all three streams before returning, so no copy of an earlier chunk
 // still writes into the caller's host buffers after the call has returned.
-template <class F>
-int host_pipeline(qfec_ctx* c, long long groups, size_t per_group, F&& fn) {
+template <class B>
+int host_pipeline_guard(qfec_ctx* c, B&& body) {
     // the kernels of every chunk run on the context stream: order them after the last eager
     // use of the decode workspace, and the next use after them
-    const int r = with_workspace(c, c->stream,
-                                 [&] { return host_pipeline_body(c, groups, per_group, fn); });
+    const int r = with_workspace(c, c->stream, body);
     if (r)
         for (hipStream_t s : {c->s_in, c->stream, c->s_out})
             if (s) (void)hipStreamSynchronize(s);
     return r;
+}
+
+template <class F>
+int host_pipeline(qfec_ctx* c, long long groups, size_t per_group, F&& fn) {
+    return host_pipeline_guard(c, [&] { return host_pipeline_body(c, groups, per_group, fn); });
 }
 
 // Default context for the single-group drop-ins (created on the caller's current device;
@@ -1189,6 +1201,278 @@ int qfec_decode_batch_host(qfec_ctx* c, int k, int m, int bb, long long groups,
     });
 }
 
+// ---- ragged batches: the groups share (k, m), each has its own block_bytes (gf_ragged.hip).
+// Nothing here reads d_bb or the offsets back: every per-group decision is the kernels'.
+// Output chunk of the ragged kernels: at most 4.  Their loops around the unit leave no room
+// for 8 x 8 accumulators (256 VGPRs and scratch at two waves per SIMD: (10, 10) encode 2.57 ms
+// against the (32, 4) encode's 0.86 ms for less data); more chunks re-read the group from L2.
+static int ragged_rc(int rc) { return std::min(rc, 4); }
+
+static int encode_ragged_impl(qfec_ctx* c, int k, int m, long long G, qfec::RaggedView v,
+                              const uint8_t* d_data, uint8_t* d_par, int32_t* d_status,
+                              hipStream_t st) {
+    if (G == 0) return 0;
+    if (k <= 1) {   // cauchy_256.cpp:1508-1516
+        QF_HIP(qfec::launch_copy_ragged(d_data, d_par, v, nullptr, nullptr, d_status, m, G, false,
+                                        st, c->tune));
+        return 0;
+    }
+    if (m == 1 || k + m > 256) {   // :1519-1534, as encode_impl: P0 only
+        QF_HIP(qfec::launch_xor_ragged(d_data, d_par, v, nullptr, d_status, k, G, false,
+                                       m == 1 ? 0 : 1, st, c->tune));
+        return m == 1 ? 0 : fail(-1, "unsupported (k + m > 256)");
+    }
+    const int rc = ragged_rc(encode_rc(m, c->tune));
+    const uint8_t* tab = nullptr;
+    int r = get_enc_table(c, k, m, rc, &tab);
+    if (r) return r;
+    // the groups with bb % 8 != 0: P0 and status -1; every other group: the GF encode
+    QF_HIP(qfec::launch_xor_ragged(d_data, d_par, v, nullptr, d_status, k, G, false, 2, st,
+                                   c->tune));
+    QF_HIP(qfec::launch_gf_ragged(d_data, d_par, v, tab, nullptr, k, m, G, rc, (m + rc - 1) / rc,
+                                  0, false, st, c->tune));
+    return 0;
+}
+
+// The caller holds the workspace bracket (with_workspace).
+static int decode_ragged_impl(qfec_ctx* c, int k, int m, long long G, qfec::RaggedView v,
+                              const uint8_t* d_blocks, const uint8_t* d_rows_in, uint8_t* d_rec,
+                              uint8_t* d_rec_rows, int32_t* d_status, hipStream_t st) {
+    if (G == 0) return 0;
+    // the prep's tables do not depend on the block size: plan and prep with the smallest valid
+    // one, the per-group size only enters the apply and the status fix-up
+    DecodePlan p = decode_plan(k, m, 8);
+    if (p.rc > ragged_rc(p.rc)) {   // smaller chunks never need more table bytes per group
+        p.rc = ragged_rc(p.rc);
+        p.nchunk = (p.rmax + p.rc - 1) / p.rc;
+        p.tab_gstride = (long long)p.nchunk * k * std::max(p.rc, 4);
+    }
+    if (k <= 1) {   // cauchy_256.cpp:1257-1261
+        QF_HIP(qfec::launch_copy_ragged(d_blocks, d_rec, v, d_rows_in, d_rec_rows, d_status, m, G,
+                                        true, st, c->tune));
+        return 0;
+    }
+    Workspace& W = ws_for(c, st);
+    int r = reserve_workspace(W, p, G, false);
+    if (r) return r;
+    if (m == 1) {   // :1264-1267
+        QF_HIP(qfec::launch_m1_prep(d_rows_in, d_rec_rows, d_status, (uint8_t*)W.dslots.p, k, G,
+                                    true, st));
+        QF_HIP(qfec::launch_xor_ragged(d_blocks, d_rec, v, (const uint8_t*)W.dslots.p, nullptr, k,
+                                       G, true, 0, st, c->tune));
+        return 0;
+    }
+    const uint8_t* cenc = nullptr;
+    if ((r = get_cenc(c, k, m, &cenc))) return r;
+    qfec::DecodeWork w{(uint8_t*)W.dcoef.p, (uint8_t*)W.dslots.p, (int32_t*)W.dnout.p};
+    QF_HIP(qfec::launch_decode_prep(d_rows_in, nullptr, d_status, cenc, w, k, m, 8, p.rc, p.rmax,
+                                    G, st, c->tune, d_rec_rows));
+    if (k + m > 256) return 0;   // every group is a no-op or status -1
+    QF_HIP(qfec::launch_ragged_decode_status(v.bb, d_rows_in, d_rec_rows, d_status, w.nout, k,
+                                             p.rmax, G, st));
+    QF_HIP(qfec::launch_gf_ragged(d_blocks, d_rec, v, w.coef, w.nout, k, m, G, p.rc, p.nchunk,
+                                  p.tab_gstride, true, st, c->tune));
+    return 0;
+}
+
+static int ragged_check(qfec_ctx* c, int k, int m, long long groups, const void* bb,
+                        const void* a, const void* a_off, const void* b, const void* b_off) {
+    int rc = check_common(c, k, m, 1, groups < 0 ? 0 : groups);
+    if (rc) return rc;
+    if (groups < 0) return fail(-2, "groups < 0");
+    if (!bb || !a || !a_off || !b || !b_off) return fail(-2, "null buffer");
+    if ((((uintptr_t)a) | (uintptr_t)b) & 15) return fail(-2, "ragged base pointers must be 16-byte aligned");
+    return 0;
+}
+
+int qfec_encode_batch_ragged(qfec_ctx* c, int k, int m, long long groups, const int* d_bb,
+                             const unsigned char* d_data, const long long* d_data_off,
+                             unsigned char* d_parity, const long long* d_par_off, int* d_status,
+                             void* stream) {
+    int rc = ragged_check(c, k, m, groups, d_bb, d_data, d_data_off, d_parity, d_par_off);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    return encode_ragged_impl(c, k, m, groups, {(const int32_t*)d_bb, d_data_off, d_par_off},
+                              d_data, d_parity, (int32_t*)d_status, pick(c, stream));
+}
+
+int qfec_decode_batch_ragged_recovered(qfec_ctx* c, int k, int m, long long groups,
+                                       const int* d_bb, const unsigned char* d_blocks,
+                                       const long long* d_blocks_off,
+                                       const unsigned char* d_rows_in, unsigned char* d_rec,
+                                       const long long* d_rec_off, unsigned char* d_rec_rows,
+                                       int* d_status, void* stream) {
+    int rc = ragged_check(c, k, m, groups, d_bb, d_blocks, d_blocks_off, d_rec, d_rec_off);
+    if (rc) return rc;
+    if (!d_rows_in || !d_rec_rows) return fail(-2, "null buffer");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    if (groups == 0) return 0;
+    const hipStream_t st = pick(c, stream);
+    return with_workspace(c, st, [&] {
+        return decode_ragged_impl(c, k, m, groups, {(const int32_t*)d_bb, d_blocks_off, d_rec_off},
+                                  d_blocks, d_rows_in, d_rec, d_rec_rows, (int32_t*)d_status, st);
+    });
+}
+
+// Host-pointer ragged batches.  The chunks of the pipeline are cut on group boundaries by
+// bytes (the host_chunk_mb option; a chunk holds at least one group): chunk c stages the span
+// of its groups' inputs and the span of their outputs, and the offsets it hands the kernels
+// are relative to its first group.  The output span is first filled with the caller's bytes,
+// so the copy back returns every byte the kernels did not write (gaps, groups with a negative
+// status, entries past a group's erasure count) as it was.
+struct RaggedChunks {
+    std::vector<long long> first;          // chunk c = groups [first[c], first[c + 1])
+    std::vector<long long> in_rel, out_rel;  // [G] offsets relative to the chunk's first group
+    size_t max_in = 0, max_out = 0, max_groups = 0;
+    long long in_span(const long long* off, const int* bb, long long g0, long long g1, int n) const {
+        return off[g1 - 1] + (long long)n * bb[g1 - 1] - off[g0];
+    }
+};
+
+static int ragged_chunks(qfec_ctx* c, int n_in, int n_out, long long G, const int* bb,
+                         const long long* in_off, const long long* out_off, size_t small_per_group,
+                         RaggedChunks* rc) {
+    for (long long g = 0; g < G; ++g) {
+        if (bb[g] < 1) return fail(-2, "bb[g] < 1");
+        if (in_off[g] < 0 || out_off[g] < 0 || ((in_off[g] | out_off[g]) & 15))
+            return fail(-2, "ragged offsets must be non-negative multiples of 16");
+        if (g && (in_off[g] < in_off[g - 1] + (long long)n_in * bb[g - 1] ||
+                  out_off[g] < out_off[g - 1] + (long long)n_out * bb[g - 1]))
+            return fail(-2, "host ragged batches need ascending, non-overlapping offsets");
+    }
+    const long long target = (long long)std::max(1, c->tune.host_chunk_mb) << 20;
+    rc->in_rel.resize((size_t)G);
+    rc->out_rel.resize((size_t)G);
+    long long g0 = 0;
+    rc->first.push_back(0);
+    auto close = [&](long long g1) {
+        rc->max_in = std::max(rc->max_in, (size_t)rc->in_span(in_off, bb, g0, g1, n_in));
+        rc->max_out = std::max(rc->max_out, (size_t)rc->in_span(out_off, bb, g0, g1, n_out));
+        rc->max_groups = std::max(rc->max_groups, (size_t)(g1 - g0));
+    };
+    for (long long g = 0; g < G; ++g) {
+        const long long bytes = rc->in_span(in_off, bb, g0, g + 1, n_in) +
+                                rc->in_span(out_off, bb, g0, g + 1, n_out) +
+                                (g + 1 - g0) * (long long)small_per_group;
+        if (g > g0 && bytes > target) {
+            close(g);
+            g0 = g;
+            rc->first.push_back(g);
+        }
+        rc->in_rel[(size_t)g] = in_off[g] - in_off[g0];
+        rc->out_rel[(size_t)g] = out_off[g] - out_off[g0];
+    }
+    close(G);
+    rc->first.push_back(G);
+    return 0;
+}
+
+// Shared by the two host entry points: decode adds the row tags in and the recovered rows out.
+static int ragged_host(qfec_ctx* c, int k, int m, long long G, const int* h_bb,
+                       const unsigned char* h_in, const long long* h_in_off,
+                       const unsigned char* h_rows, unsigned char* h_out,
+                       const long long* h_out_off, unsigned char* h_rec_rows, int* h_status,
+                       bool decode) {
+    const int n_out = decode ? std::min(k, m) : m;
+    const size_t small = sizeof(int32_t) * 2 + 2 * sizeof(long long) +
+                         (decode ? (size_t)k + (size_t)n_out : 0);
+    RaggedChunks ch;
+    int rc = ragged_chunks(c, k, n_out, G, h_bb, h_in_off, h_out_off, small, &ch);
+    if (rc) return rc;
+    const size_t bytes = ch.max_in + ch.max_out + ch.max_groups * small + kCarveSlack;
+    int result = 0;
+    size_t ci = 0;
+    rc = host_pipeline_guard(c, [&] {
+        return host_pipeline_chunks(
+            c, bytes,
+            [&](long long g0) -> long long {
+                if (g0 >= G) return 0;
+                while (ch.first[ci] != g0) ++ci;
+                return ch.first[ci + 1] - g0;
+            },
+            [&](long long g0, long long n, uint8_t* buf, int phase) -> int {
+                const size_t in_b = (size_t)ch.in_span(h_in_off, h_bb, g0, g0 + n, k);
+                const size_t out_b = (size_t)ch.in_span(h_out_off, h_bb, g0, g0 + n, n_out);
+                Carve cv{buf};
+                uint8_t* di = cv.take(in_b);
+                uint8_t* dout = cv.take(out_b);
+                int32_t* dbb = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
+                long long* dio = (long long*)cv.take((size_t)n * sizeof(long long));
+                long long* doo = (long long*)cv.take((size_t)n * sizeof(long long));
+                int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
+                uint8_t* dr = decode ? cv.take((size_t)n * k) : nullptr;
+                uint8_t* drr = decode ? cv.take((size_t)n * n_out) : nullptr;
+                const unsigned char* src = h_in + h_in_off[g0];
+                unsigned char* dst = h_out + h_out_off[g0];
+                if (phase == 0) {
+                    QF_HIP(hipMemcpyAsync(di, src, in_b, hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(dout, dst, out_b, hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(dbb, h_bb + g0, (size_t)n * sizeof(int32_t),
+                                          hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(dio, ch.in_rel.data() + g0, (size_t)n * sizeof(long long),
+                                          hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(doo, ch.out_rel.data() + g0, (size_t)n * sizeof(long long),
+                                          hipMemcpyHostToDevice, c->s_in));
+                    if (decode)
+                        QF_HIP(hipMemcpyAsync(dr, h_rows + (size_t)g0 * k, (size_t)n * k,
+                                              hipMemcpyHostToDevice, c->s_in));
+                } else if (phase == 1) {
+                    const qfec::RaggedView v{dbb, dio, doo};
+                    if (decode)
+                        return decode_ragged_impl(c, k, m, n, v, di, dr, dout, drr, ds, c->stream);
+                    const int r = encode_ragged_impl(c, k, m, n, v, di, dout, ds, c->stream);
+                    if (r < -1) return r;
+                    if (r) result = r;
+                } else {
+                    QF_HIP(hipMemcpyAsync(dst, dout, out_b, hipMemcpyDeviceToHost, c->s_out));
+                    if (decode)
+                        QF_HIP(hipMemcpyAsync(h_rec_rows + (size_t)g0 * n_out, drr,
+                                              (size_t)n * n_out, hipMemcpyDeviceToHost, c->s_out));
+                    if (h_status)
+                        QF_HIP(hipMemcpyAsync(h_status + g0, ds, (size_t)n * sizeof(int32_t),
+                                              hipMemcpyDeviceToHost, c->s_out));
+                }
+                return 0;
+            });
+    });
+    return rc ? rc : result;
+}
+
+int qfec_encode_batch_ragged_host(qfec_ctx* c, int k, int m, long long groups, const int* h_bb,
+                                  const unsigned char* h_data, const long long* h_data_off,
+                                  unsigned char* h_parity, const long long* h_par_off,
+                                  int* h_status) {
+    int rc = check_common(c, k, m, 1, groups < 0 ? 0 : groups);
+    if (rc) return rc;
+    if (groups < 0) return fail(-2, "groups < 0");
+    if (!h_bb || !h_data || !h_data_off || !h_parity || !h_par_off) return fail(-2, "null buffer");
+    if (groups == 0) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    return ragged_host(c, k, m, groups, h_bb, h_data, h_data_off, nullptr, h_parity, h_par_off,
+                       nullptr, h_status, false);
+}
+
+int qfec_decode_batch_ragged_recovered_host(qfec_ctx* c, int k, int m, long long groups,
+                                            const int* h_bb, const unsigned char* h_blocks,
+                                            const long long* h_blocks_off,
+                                            const unsigned char* h_rows, unsigned char* h_rec,
+                                            const long long* h_rec_off,
+                                            unsigned char* h_rec_rows, int* h_status) {
+    int rc = check_common(c, k, m, 1, groups < 0 ? 0 : groups);
+    if (rc) return rc;
+    if (groups < 0) return fail(-2, "groups < 0");
+    if (!h_bb || !h_blocks || !h_blocks_off || !h_rows || !h_rec || !h_rec_off || !h_rec_rows)
+        return fail(-2, "null buffer");
+    if (groups == 0) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    return ragged_host(c, k, m, groups, h_bb, h_blocks, h_blocks_off, h_rows, h_rec, h_rec_off,
+                       h_rec_rows, h_status, true);
+}
+
 int qfec_synth_fill(void* d_dst, unsigned long long bytes, unsigned long long seed,
                     unsigned long long byte_offset, void* stream) {
     qfec::TimingMute mute;
@@ -1294,6 +1578,8 @@ int qfec_reserve(qfec_ctx* c, int k, int m, int bb, long long groups) {
     if (m > 1 && k > 1 && k + m <= 256) {
         const uint8_t* t;
         if ((rc = get_enc_table(c, k, m, stream_encode_rc(k, m, bb, true, c->tune), &t))) return rc;
+        // the ragged encode's table (chunks of at most 4 outputs)
+        if ((rc = get_enc_table(c, k, m, std::min(encode_rc(m, c->tune), 4), &t))) return rc;
     }
     if (p.cenc) {
         const uint8_t* t;

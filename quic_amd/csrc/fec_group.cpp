@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/quic_fec_group.h"
+#include "fec_ragged_host.h"
 
 namespace qfec {
 
@@ -280,13 +281,16 @@ struct qfec_batch {
     qfec_ctx* ctx;
     size_t max_groups;
     unsigned max_delay_us;
+    bool ragged = false;   // buckets keyed by (k, m) only (key bb = 0), one ragged call each
     struct Enc {
         qfec_group* g;
+        int bb;
         std::vector<unsigned char> blocks;
         std::chrono::steady_clock::time_point t;
     };
     struct Dec {
         qfec_group* g;
+        int bb;
         std::vector<uint64_t> missing;
         std::vector<unsigned char> blocks, rows;
         std::chrono::steady_clock::time_point t;
@@ -295,14 +299,66 @@ struct qfec_batch {
     std::map<std::tuple<int, int, int>, std::vector<Dec>> dec;
     std::vector<unsigned char> hbuf, hrows;
     std::vector<int> hstatus;
+    qfec::RaggedPack pack;
 };
 
 namespace {
+
+// A ragged bucket (key bb = 0): the groups keep their own block sizes; pack them
+// (qfec::ragged_pack) and make one ragged host call.
+int flush_enc_ragged(qfec_batch* b, std::vector<qfec_batch::Enc>& v, int k, int m) {
+    const size_t G = v.size();
+    std::vector<const unsigned char*> blocks(G);
+    std::vector<int> bb(G);
+    for (size_t i = 0; i < G; ++i) {
+        blocks[i] = v[i].blocks.data();
+        bb[i] = v[i].bb;
+    }
+    qfec::RaggedPack& p = b->pack;
+    int rc = qfec::ragged_pack(k, m, false, blocks, bb, &p);
+    if (rc) return rc;
+    b->hstatus.assign(G, 0);
+    rc = qfec_encode_batch_ragged_host(b->ctx, k, m, (long long)G, p.bb.data(), p.in.data(),
+                                       p.in_off.data(), p.out.data(), p.out_off.data(),
+                                       b->hstatus.data());
+    for (size_t i = 0; i < G; ++i)
+        v[i].g->g.SetRedundancy(p.out.data() + p.out_off[i], p.bb[i], rc ? rc : b->hstatus[i]);
+    v.clear();
+    return rc < -1 ? rc : (int)G;
+}
+
+int flush_dec_ragged(qfec_batch* b, std::vector<qfec_batch::Dec>& v, int k, int m) {
+    const size_t G = v.size();
+    const size_t rmax = (size_t)std::min(k, m);
+    std::vector<const unsigned char*> blocks(G);
+    std::vector<int> bb(G);
+    b->hrows.resize(G * ((size_t)k + rmax));
+    unsigned char* rows = b->hrows.data();
+    unsigned char* rec_rows = rows + G * (size_t)k;
+    for (size_t i = 0; i < G; ++i) {
+        blocks[i] = v[i].blocks.data();
+        bb[i] = v[i].bb;
+        memcpy(rows + i * (size_t)k, v[i].rows.data(), (size_t)k);
+    }
+    qfec::RaggedPack& p = b->pack;
+    int rc = qfec::ragged_pack(k, m, true, blocks, bb, &p);
+    if (rc) return rc;
+    b->hstatus.assign(G, 0);
+    rc = qfec_decode_batch_ragged_recovered_host(b->ctx, k, m, (long long)G, p.bb.data(),
+                                                 p.in.data(), p.in_off.data(), rows, p.out.data(),
+                                                 p.out_off.data(), rec_rows, b->hstatus.data());
+    for (size_t i = 0; i < G; ++i)
+        v[i].g->g.SetRevived(v[i].missing, p.out.data() + p.out_off[i], rec_rows + i * rmax,
+                             p.bb[i], rc ? rc : b->hstatus[i], rmax);
+    v.clear();
+    return rc ? rc : (int)G;
+}
 
 int flush_enc(qfec_batch* b, const std::tuple<int, int, int>& key) {
     auto& v = b->enc[key];
     if (v.empty()) return 0;
     const int k = std::get<0>(key), m = std::get<1>(key), bb = std::get<2>(key);
+    if (bb == 0) return flush_enc_ragged(b, v, k, m);
     const size_t G = v.size();
     b->hbuf.resize(G * (size_t)(k + m) * bb);
     unsigned char* data = b->hbuf.data();
@@ -319,6 +375,7 @@ int flush_dec(qfec_batch* b, const std::tuple<int, int, int>& key) {
     auto& v = b->dec[key];
     if (v.empty()) return 0;
     const int k = std::get<0>(key), m = std::get<1>(key), bb = std::get<2>(key);
+    if (bb == 0) return flush_dec_ragged(b, v, k, m);
     const size_t G = v.size();
     const size_t rmax = (size_t)std::min(k, m);
     // inputs [G][k][bb] + [G][k]; outputs: only the recovered blocks (rmax per group)
@@ -427,13 +484,21 @@ qfec_batch* qfec_batch_new(qfec_ctx* ctx, size_t max_groups, unsigned max_delay_
 }
 void qfec_batch_free(qfec_batch* b) { delete b; }
 
+int qfec_batch_set_ragged(qfec_batch* b, int on) {
+    if (!b) return -2;
+    if (qfec_batch_pending(b)) return -2;   // queued groups sit in buckets of the other kind
+    b->ragged = on != 0;
+    return 0;
+}
+
 int qfec_batch_add_encode(qfec_batch* b, qfec_group* g) {
     qfec_batch::Enc e;
     int bb = 0;
     if (!g->g.EncodeInput(&bb, &e.blocks)) return -2;
     e.g = g;
+    e.bb = bb;
     e.t = std::chrono::steady_clock::now();
-    auto key = std::make_tuple((int)g->g.k(), (int)g->g.m(), bb);
+    auto key = std::make_tuple((int)g->g.k(), (int)g->g.m(), b->ragged ? 0 : bb);
     auto& v = b->enc[key];
     v.push_back(std::move(e));
     return v.size() >= b->max_groups ? flush_enc(b, key) : 0;
@@ -444,8 +509,9 @@ int qfec_batch_add_decode(qfec_batch* b, qfec_group* g) {
     int bb = 0;
     if (!g->g.DecodeInput(&d.missing, &bb, &d.blocks, &d.rows)) return -2;
     d.g = g;
+    d.bb = bb;
     d.t = std::chrono::steady_clock::now();
-    auto key = std::make_tuple((int)g->g.k(), (int)g->g.m(), bb);
+    auto key = std::make_tuple((int)g->g.k(), (int)g->g.m(), b->ragged ? 0 : bb);
     auto& v = b->dec[key];
     v.push_back(std::move(d));
     return v.size() >= b->max_groups ? flush_dec(b, key) : 0;

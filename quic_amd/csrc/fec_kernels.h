@@ -163,6 +163,11 @@ hipError_t launch_xor_decode(const uint8_t* blocks, uint8_t* out, const uint8_t*
                              long long groups, hipStream_t st, const Tune& t,
                              bool compact = false);
 
+// The m == 1 decode bookkeeping alone (the ragged decode runs its own XOR after it): eidx [G]
+// gets the erased slot (255: nothing erased); compact: rows_out [G] the recovered data row.
+hipError_t launch_m1_prep(const uint8_t* rows_in, uint8_t* rows_out, int32_t* status,
+                          uint8_t* eidx, int k, long long groups, bool compact, hipStream_t st);
+
 // k <= 1 encode: copy data[0] into each of the m outputs (cauchy_256.cpp:1508-1516).
 hipError_t launch_replicate(const uint8_t* data, uint8_t* parity, int m, int bb,
                             long long groups, hipStream_t st);
@@ -262,6 +267,38 @@ hipError_t launch_gf_psyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
                           const uint8_t* cenc, const uint8_t* slots, const int32_t* nout, int k,
                           int m, int bb, long long groups, int rmax, long long out_gstride,
                           hipStream_t st, const Tune& t);
+
+// Ragged batches (gf_ragged.hip): the groups share (k, m), each has its own block size.
+// Group g's input blocks are [k][bb[g]] at in + in_off[g] and its outputs [n][bb[g]] at
+// out + out_off[g] (byte offsets, multiples of 16; all three arrays in device memory).
+struct RaggedView {
+    const int32_t* bb;
+    const long long* in_off;
+    const long long* out_off;
+};
+// m > 1, the groups with bb % 8 == 0 (the others are skipped).  Encode: coef is the shared
+// [nchunk][k][max(rc, 4)] table; decode: the prep's per-group tables, outputs o < nout[g] in
+// the recovered-blocks layout.  rc 2 or 4.
+hipError_t launch_gf_ragged(const uint8_t* in, uint8_t* out, RaggedView v, const uint8_t* coef,
+                            const int32_t* nout, int k, int m, long long groups, int rc,
+                            int nchunk, long long coef_gstride, bool decode, hipStream_t st,
+                            const Tune& t);
+// XOR of each group's k blocks.  Encode modes: 0 every group, status 0; 1 every group, status
+// -1; 2 only the groups with bb % 8 != 0 (status -1, the rest 0).  Decode: the recovered block
+// of the groups with eidx[g] != 255 (m1_prep_kernel's erased slot).
+hipError_t launch_xor_ragged(const uint8_t* in, uint8_t* out, RaggedView v, const uint8_t* eidx,
+                             int32_t* status, int k, long long groups, bool decode, int mode,
+                             hipStream_t st, const Tune& t);
+// k <= 1: encode copies the group's block into its m outputs; decode (rmax = 1) copies a block
+// not tagged row 0 into rec and writes rec_rows [G].
+hipError_t launch_copy_ragged(const uint8_t* in, uint8_t* out, RaggedView v,
+                              const uint8_t* rows_in, uint8_t* rec_rows, int32_t* status, int m,
+                              long long groups, bool decode, hipStream_t st, const Tune& t);
+// After launch_decode_prep with a block size of 8: status -1 and nothing recovered for the
+// groups whose own bb % 8 != 0 and that hold a recovery block.
+hipError_t launch_ragged_decode_status(const int32_t* bb, const uint8_t* rows_in,
+                                       uint8_t* rec_rows, int32_t* status, int32_t* nout, int k,
+                                       int rmax, long long groups, hipStream_t st);
 
 // Synthetic workload helpers (bench / tests): splitmix64 stream and receive-set gather.
 hipError_t launch_synth_fill(uint8_t* dst, unsigned long long bytes, unsigned long long seed,

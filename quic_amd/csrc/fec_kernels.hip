@@ -25,10 +25,10 @@
 #include "fec_kernels.h"
 #include "gf256.h"
 #include "gf_bitslice.h"
+#include "gf_colword.h"
 
 namespace qfec {
 
-typedef uint32_t u32ua __attribute__((aligned(1)));   // unaligned dword (gfx950 unaligned mode)
 typedef uint64_t u64a __attribute__((aligned(8)));
 
 __constant__ GfTables c_gf = make_gf_tables();
@@ -224,49 +224,8 @@ __global__ void rows_k1_kernel(const uint8_t* __restrict__ rows_in, uint8_t* row
     if (status) status[g] = 0;
 }
 
-// Column-word access.  Word c of sub-row t covers bytes [t*s + 4c, +4); the last word of a
-// sub-row may be partial (s % 4 != 0).  Loads of the last word are shifted back inside the
-// sub-row (never past the block) and realigned; stores write only the valid bytes.
-struct ColAccess {
-    int lo;        // byte offset of the dword actually loaded within the sub-row
-    int shift;     // right shift (bits) that realigns it
-    int nvalid;    // valid bytes of this lane's word (0 = lane idle)
-};
-
-template <bool TINY>
-__device__ __forceinline__ ColAccess col_access(int c, int nw, int s) {
-    ColAccess a;
-    const int cc = c < nw ? c : nw - 1;
-    const int off = 4 * cc;
-    a.nvalid = c < nw ? min(4, s - off) : 0;
-    if (!TINY) {
-        a.lo = min(off, s - 4);
-        a.shift = 8 * (off - a.lo);
-    } else {
-        a.lo = 0;
-        a.shift = 0;
-    }
-    return a;
-}
-
-// TINY = blocks under 32 bytes (s < 4): bytewise, never past the sub-row.  Otherwise the
-// raw (unshifted) dword; the caller applies `>> shift`.
-template <bool TINY>
-__device__ __forceinline__ uint32_t load_raw(const uint8_t* sub, const ColAccess& a, int s) {
-    if (!TINY) return *(const u32ua*)(sub + a.lo);
-    uint32_t v = 0;
-    for (int b = 0; b < 3; ++b)
-        if (b < s) v |= (uint32_t)sub[b] << (8 * b);
-    return v;
-}
-
-__device__ __forceinline__ void store_word(uint8_t* sub, int c, const ColAccess& a, uint32_t v) {
-    if (a.nvalid == 4) {
-        *(u32ua*)(sub + 4 * c) = v;
-    } else if (a.nvalid > 0) {
-        for (int b = 0; b < a.nvalid; ++b) sub[4 * c + b] = (uint8_t)(v >> (8 * b));
-    }
-}
+// Column-word access (col_access / load_raw / store_word): gf_colword.h, shared with the
+// ragged kernels.
 
 // Workgroup-size bound per output-chunk width: it caps VGPRs at 512 / ceil(waves / 4), so
 // the RC x 8 accumulators never spill (RC 4: 128 VGPR, RC 8: 170, RC 16: 256).
@@ -1164,6 +1123,15 @@ hipError_t launch_xor_decode(const uint8_t* blocks, uint8_t* out, const uint8_t*
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return xor_any<true>(blocks, out, eidx, k, bb, groups, gb, ogs, st, t, compact ? 0 : bb);
+}
+
+hipError_t launch_m1_prep(const uint8_t* rows_in, uint8_t* rows_out, int32_t* status,
+                          uint8_t* eidx, int k, long long groups, bool compact, hipStream_t st) {
+    if (groups <= 0) return hipSuccess;
+    note_kernel("m1_prep_kernel");
+    qlaunch((m1_prep_kernel), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, rows_in,
+            rows_out, status, eidx, k, groups, compact ? 1 : 0);
+    return hipGetLastError();
 }
 
 hipError_t launch_replicate(const uint8_t* data, uint8_t* parity, int m, int bb,

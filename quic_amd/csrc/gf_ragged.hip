@@ -1,0 +1,349 @@
+// gf_ragged.hip — run-time-shape kernels for batches whose groups share (k, m) but carry their
+// own block_bytes (qfec_*_batch_ragged*, include/quic_fec.h).
+//
+// Packed layout: group g's blocks are [n][bb[g]] contiguous at base + off[g] (off a multiple
+// of 16, gaps never written).  Per-group semantics are those of the uniform call with
+// block_bytes = bb[g]; the bit-sliced code splits a block into 8 sub-rows of bb/8 bytes, so
+// the sub-row stride differs per group and a short group cannot be padded to a common size.
+//
+// Work mapping: persistent, oversubscribed grids.  Wave w walks the
+// units w, w + W, ... and loops over the unit's 64-word column tiles, so no unit-start table
+// has to be scanned first and nothing depends on the sizes on the host.
+//   gf_ragged_kernel   unit = (group, output chunk), chunk fastest; m > 1
+//   xor_ragged_kernel  unit = group; m == 1, and the XOR parity of the groups the reference
+//                      rejects (cauchy_256.cpp:1519-1534)
+//   copy_ragged_kernel unit = group; k <= 1
+// All of a unit's shape (bb, offsets, counts) is wave-uniform.  No MFMA: byte XORs only.
+#include <algorithm>
+
+#include "fec_kernels.h"
+#include "gf256.h"
+#include "gf_bitslice.h"
+#include "gf_colword.h"
+
+namespace qfec {
+
+// Logical workgroup of hardware block b: consecutive logical workgroups run on one XCD (the
+// bijection of gf_apply_kernel), so the chunks of one group share an L2.
+__device__ __forceinline__ unsigned xcd_logical_block() {
+    const unsigned nbk = gridDim.x, b = blockIdx.x, xcd = b & 7u, q8 = nbk >> 3, r8 = nbk & 7u;
+    return xcd * q8 + (xcd < r8 ? xcd : r8) + (b >> 3);
+}
+
+// A wave-uniform 64-bit value the compiler may not see as uniform (loaded per group): keep
+// it in scalar registers.
+__device__ __forceinline__ long long uniform64(long long v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// One (group, chunk) unit: n <= RC outputs over every column tile of the group.
+//   cw: the unit's coefficient words, [k][RCP] bytes (RCP = max(4, RC))
+//   outputs j < n go to gout + j * bb
+template <int RC, bool TINY>
+__device__ __forceinline__ void ragged_unit(const uint8_t* gin, uint8_t* gout,
+                                            const uint32_t* cw, int k, int bb, int n,
+                                            int lane) {
+    constexpr int RCP = RC < 4 ? 4 : RC;
+    constexpr int NCW = RCP / 4;
+    constexpr int PD = 2;
+    const int s = bb >> 3;
+    const int nw = (s + 3) >> 2;
+    const int ntiles = (nw + 63) >> 6;
+#pragma unroll 1
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int c = tile * 64 + lane;
+        const ColAccess ca = col_access<TINY>(c, nw, s);
+        uint32_t acc[RC][8];
+#pragma unroll
+        for (int j = 0; j < RC; ++j)
+#pragma unroll
+            for (int r = 0; r < 8; ++r) acc[j][r] = 0;
+        // two blocks in flight while one is combined, as gf_apply_kernel (PD = 2)
+        uint32_t raw[PD][8];
+#pragma unroll
+        for (int u = 0; u < PD; ++u) {
+            const uint8_t* p = gin + (long long)min(u, k - 1) * bb;
+#pragma unroll
+            for (int t = 0; t < 8; ++t) raw[u][t] = load_raw<TINY>(p + t * s, ca, s);
+        }
+#pragma unroll 1
+        for (int pos0 = 0; pos0 < k; pos0 += PD) {
+#pragma unroll
+            for (int u = 0; u < PD; ++u) {
+                const int pos = pos0 + u;
+                if (pos < k) {
+                    WZ v;
+#pragma unroll
+                    for (int t = 0; t < 8; ++t)
+                        v.W[t] = TINY ? raw[u][t] : (raw[u][t] >> ca.shift);
+                    const uint8_t* p = gin + (long long)min(pos + PD, k - 1) * bb;
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) raw[u][t] = load_raw<TINY>(p + t * s, ca, s);
+                    uint32_t cwv[NCW];
+#pragma unroll
+                    for (int q = 0; q < NCW; ++q) cwv[q] = cw[pos * NCW + q];
+                    expand_wz(v);
+#pragma unroll
+                    for (int j = 0; j < RC; ++j) {
+                        if (j < n) {
+                            const uint32_t a = (cwv[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+                            apply_nibble<0>(acc[j], a & 15u, v);
+                            apply_nibble<4>(acc[j], a >> 4, v);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < RC; ++j) {
+            if (j < n) {
+                uint8_t* dst = gout + (long long)j * bb;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) store_word(dst + r * s, c, ca, acc[j][r]);
+            }
+        }
+    }
+}
+
+// Register bound (the kernel is launched with 256 threads; the bound only caps VGPRs at
+// 512 / ceil(waves / 4) = 168, three waves per SIMD).  The loops around the unit cost registers
+// that gf_apply_kernel's straight-line body does not need: at gf_apply's bound for RC 4
+// (128 VGPRs) the kernel spilled 232 bytes per lane; at 168 it needs no scratch.  Measured on
+// one box, alternating: (32, 4) encode 1.10 -> 0.87 ms, decode 1.01 -> 0.75 ms.  RC 8 does
+// not fit under any bound (256 VGPRs and 404 bytes of scratch at two waves), so the ragged
+// paths use chunks of at most 4 outputs.
+constexpr int kRaggedBound = 640;
+
+//   coef:   encode: the shared [nchunk][k][RCP] table; decode: + g * coef_gstride
+//   encode: outputs o = chunk*RC + j < m go to out + out_off[g] + o*bb[g]
+//   decode: outputs o < nout[g], same place (the recovered-blocks layout)
+// A group with bb % 8 != 0 (or bb < 8) is skipped: its status and XOR parity are the other
+// kernels' business.
+template <int RC, bool DECODE>
+__global__ __launch_bounds__(kRaggedBound) void gf_ragged_kernel(
+    const uint8_t* __restrict__ in, const long long* __restrict__ in_off, uint8_t* out,
+    const long long* __restrict__ out_off, const int32_t* __restrict__ bbs,
+    const uint8_t* __restrict__ coef, const int32_t* __restrict__ nout, int k, int m,
+    int nchunk, long long coef_gstride, long long total_units) {
+    constexpr int RCP = RC < 4 ? 4 : RC;
+    const int lane = threadIdx.x & 63;
+    // 32-bit unit numbers (the launcher caps them at 2^31): a 64-bit division has no scalar
+    // form and would drag the unit's addresses into vector registers
+    const unsigned stride = gridDim.x * 4u, total = (unsigned)total_units;
+#pragma unroll 1
+    for (unsigned unit = xcd_logical_block() * 4u + (unsigned)wave_id(); unit < total;
+         unit += stride) {
+        unsigned gq = unit, chunk = 0;
+        if (nchunk > 1) {
+            gq = __builtin_amdgcn_readfirstlane(unit / (unsigned)nchunk);
+            chunk = unit - gq * (unsigned)nchunk;
+        }
+        const long long g = gq;
+        const int bb = __builtin_amdgcn_readfirstlane(bbs[g]);
+        if (bb < 8 || (bb & 7)) continue;
+        int n = DECODE ? __builtin_amdgcn_readfirstlane(nout[g]) : m;
+        n = min(n - (int)chunk * RC, RC);
+        if (n <= 0) continue;
+        const uint8_t* gin = in + uniform64(in_off[g]);
+        uint8_t* gout = out + uniform64(out_off[g]) + (long long)chunk * RC * bb;
+        const uint32_t* cw = (const uint32_t*)(coef + (DECODE ? g * coef_gstride : 0) +
+                                               (long long)chunk * k * RCP);
+        if (bb >= 32) ragged_unit<RC, false>(gin, gout, cw, k, bb, n, lane);
+        else ragged_unit<RC, true>(gin, gout, cw, k, bb, n, lane);
+    }
+}
+
+// ------------------------------------------------------------------ XOR (m == 1)
+typedef uint32_t rg_u32x4a8 __attribute__((ext_vector_type(4), aligned(8)));
+
+// out block of group g = XOR of its k blocks.  16-byte units where bb % 8 == 0 (every block
+// then starts 8-byte aligned), unaligned 4-byte units otherwise, and a byte tail.  Every byte
+// is touched once: non-temporal, as xor_flat_kernel.
+//   encode modes: 0 every group, status 0 (m == 1); 1 every group, status -1 (m > 1 and
+//   k + m > 256); 2 only the groups with bb % 8 != 0, status -1 for those and 0 for the rest
+//   decode: the group's recovered block, unless eidx[g] == 255 (nothing erased); the XOR
+//   runs over all k slots, the recovery block included (cauchy_256.cpp:505-531)
+template <bool DECODE>
+__global__ __launch_bounds__(256) void xor_ragged_kernel(
+    const uint8_t* __restrict__ in, const long long* __restrict__ in_off, uint8_t* out,
+    const long long* __restrict__ out_off, const int32_t* __restrict__ bbs,
+    const uint8_t* __restrict__ eidx, int32_t* __restrict__ status, int k, long long groups,
+    int mode) {
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * 4;
+#pragma unroll 1
+    for (long long g = (long long)xcd_logical_block() * 4 + wave_id(); g < groups; g += stride) {
+        const int bb = __builtin_amdgcn_readfirstlane(bbs[g]);
+        if (DECODE) {
+            if (eidx[g] == 255) continue;
+        } else {
+            const bool bad = mode == 1 || (mode == 2 && (bb & 7) != 0);
+            if (status && lane == 0) status[g] = bad ? -1 : 0;
+            if (mode == 2 && !bad) continue;
+        }
+        if (bb < 1) continue;
+        const uint8_t* p = in + uniform64(in_off[g]);
+        uint8_t* dst = out + uniform64(out_off[g]);
+        int done;
+        if ((bb & 7) == 0) {
+            const int nu = bb >> 4;
+            for (int q = lane; q < nu; q += 64) {
+                const uint8_t* pq = p + 16 * q;
+                rg_u32x4a8 acc = __builtin_nontemporal_load((const rg_u32x4a8*)pq);
+#pragma unroll 4
+                for (int x = 1; x < k; ++x)
+                    acc ^= __builtin_nontemporal_load((const rg_u32x4a8*)(pq + (long long)x * bb));
+                __builtin_nontemporal_store(acc, (rg_u32x4a8*)(dst + 16 * q));
+            }
+            done = nu << 4;
+        } else {
+            const int nu = bb >> 2;
+            for (int q = lane; q < nu; q += 64) {
+                const uint8_t* pq = p + 4 * q;
+                uint32_t acc = __builtin_nontemporal_load((const u32ua*)pq);
+#pragma unroll 4
+                for (int x = 1; x < k; ++x)
+                    acc ^= __builtin_nontemporal_load((const u32ua*)(pq + (long long)x * bb));
+                __builtin_nontemporal_store(acc, (u32ua*)(dst + 4 * q));
+            }
+            done = nu << 2;
+        }
+        for (int i = done + lane; i < bb; i += 64) {   // at most 8 bytes
+            uint8_t acc = 0;
+            for (int x = 0; x < k; ++x) acc ^= p[(long long)x * bb + i];
+            dst[i] = acc;
+        }
+    }
+}
+
+// ------------------------------------------------------------------ k <= 1
+// encode: the group's one block into each of its m outputs (cauchy_256.cpp:1508-1516).
+// decode: a block tagged anything but row 0 is a copy of data row 0, so it is the recovered
+// block (rec_k1_kernel); rmax = 1.
+template <bool DECODE>
+__global__ __launch_bounds__(256) void copy_ragged_kernel(
+    const uint8_t* __restrict__ in, const long long* __restrict__ in_off, uint8_t* out,
+    const long long* __restrict__ out_off, const int32_t* __restrict__ bbs,
+    const uint8_t* __restrict__ rows_in, uint8_t* __restrict__ rec_rows,
+    int32_t* __restrict__ status, int m, long long groups) {
+    const int lane = threadIdx.x & 63;
+    const long long stride = (long long)gridDim.x * 4;
+#pragma unroll 1
+    for (long long g = (long long)blockIdx.x * 4 + wave_id(); g < groups; g += stride) {
+        const int bb = __builtin_amdgcn_readfirstlane(bbs[g]);
+        int copies = m;
+        if (DECODE) {
+            const bool lost = rows_in[g] != 0;
+            if (lane == 0) rec_rows[g] = lost ? 0 : 255;
+            copies = lost ? 1 : 0;
+        }
+        if (status && lane == 0) status[g] = 0;
+        const uint8_t* p = in + uniform64(in_off[g]);
+        uint8_t* dst = out + uniform64(out_off[g]);
+        for (int y = 0; y < copies; ++y)
+            for (int i = lane; i < bb; i += 64) dst[(long long)y * bb + i] = p[i];
+    }
+}
+
+// After the run-time decode prep (run with a block size of 8: its tables do not depend on
+// it): a group whose own bb is not a multiple of 8 has status -1 unless it holds no recovery
+// block (cauchy_256.cpp:1287-1294), and recovers nothing.
+__global__ __launch_bounds__(256) void ragged_decode_status_kernel(
+    const int32_t* __restrict__ bbs, const uint8_t* __restrict__ rows_in,
+    uint8_t* __restrict__ rec_rows, int32_t* __restrict__ status, int32_t* __restrict__ nout,
+    int k, int rmax, long long groups) {
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= groups) return;
+    if ((bbs[g] & 7) == 0) return;
+    bool anyrec = false;
+    for (int i = 0; i < k; ++i) anyrec |= rows_in[g * k + i] >= k;
+    if (!anyrec) return;
+    nout[g] = 0;
+    for (int j = 0; j < rmax; ++j) rec_rows[g * rmax + j] = 255;
+    if (status) status[g] = -1;
+}
+
+// ---------------------------------------------------------------------- launchers
+// Oversubscribed persistent grid: about two units per wave once the device is full, never
+// fewer workgroups than the device holds while there are units for them.
+static unsigned ragged_grid(const void* kern, int threads, long long units, const Tune& t) {
+    const long long per_wg = 4;
+    const long long all = (units + per_wg - 1) / per_wg;
+    const long long resident = (long long)t.cus * resident_blocks(kern, threads, 0);
+    const long long two = (units + 2 * per_wg - 1) / (2 * per_wg);
+    const long long nb = std::max<long long>(1, std::min(all, std::max(resident, two)));
+    return (unsigned)std::min<long long>(nb, 0x7fffffffLL);
+}
+
+hipError_t launch_gf_ragged(const uint8_t* in, uint8_t* out, RaggedView v, const uint8_t* coef,
+                            const int32_t* nout, int k, int m, long long groups, int rc,
+                            int nchunk, long long coef_gstride, bool decode, hipStream_t st,
+                            const Tune& t) {
+    const long long units = groups * nchunk;
+    if (units <= 0) return hipSuccess;
+    if (units > 0x7fffffffLL) return hipErrorInvalidValue;
+    note_kernel(decode ? "gf_ragged_kernel<decode>" : "gf_ragged_kernel<encode>");
+#define QF_RAGGED(RCV, DEC)                                                                    \
+    do {                                                                                       \
+        const unsigned nb = ragged_grid((const void*)gf_ragged_kernel<RCV, DEC>, 256, units, t); \
+        note_grid("gf_ragged_kernel", nb);                                                     \
+        qlaunch((gf_ragged_kernel<RCV, DEC>), dim3(nb), dim3(256), 0, st, in, v.in_off, out,    \
+                v.out_off, v.bb, coef, nout, k, m, nchunk, coef_gstride, units);               \
+    } while (0)
+    switch (rc) {
+        case 2: if (decode) QF_RAGGED(2, true); else QF_RAGGED(2, false); break;
+        case 4: if (decode) QF_RAGGED(4, true); else QF_RAGGED(4, false); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef QF_RAGGED
+    return hipGetLastError();
+}
+
+hipError_t launch_xor_ragged(const uint8_t* in, uint8_t* out, RaggedView v, const uint8_t* eidx,
+                             int32_t* status, int k, long long groups, bool decode, int mode,
+                             hipStream_t st, const Tune& t) {
+    if (groups <= 0) return hipSuccess;
+    note_kernel("xor_ragged_kernel");
+    if (decode) {
+        const unsigned nb = ragged_grid((const void*)xor_ragged_kernel<true>, 256, groups, t);
+        note_grid("xor_ragged_kernel", nb);
+        qlaunch((xor_ragged_kernel<true>), dim3(nb), dim3(256), 0, st, in, v.in_off, out,
+                v.out_off, v.bb, eidx, status, k, groups, mode);
+    } else {
+        const unsigned nb = ragged_grid((const void*)xor_ragged_kernel<false>, 256, groups, t);
+        note_grid("xor_ragged_kernel", nb);
+        qlaunch((xor_ragged_kernel<false>), dim3(nb), dim3(256), 0, st, in, v.in_off, out,
+                v.out_off, v.bb, eidx, status, k, groups, mode);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_copy_ragged(const uint8_t* in, uint8_t* out, RaggedView v,
+                              const uint8_t* rows_in, uint8_t* rec_rows, int32_t* status, int m,
+                              long long groups, bool decode, hipStream_t st, const Tune& t) {
+    if (groups <= 0) return hipSuccess;
+    note_kernel("copy_ragged_kernel");
+    const unsigned nb =
+        (unsigned)std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)t.cus * 16));
+    if (decode)
+        qlaunch((copy_ragged_kernel<true>), dim3(nb), dim3(256), 0, st, in, v.in_off, out,
+                v.out_off, v.bb, rows_in, rec_rows, status, m, groups);
+    else
+        qlaunch((copy_ragged_kernel<false>), dim3(nb), dim3(256), 0, st, in, v.in_off, out,
+                v.out_off, v.bb, rows_in, rec_rows, status, m, groups);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_decode_status(const int32_t* bb, const uint8_t* rows_in,
+                                       uint8_t* rec_rows, int32_t* status, int32_t* nout, int k,
+                                       int rmax, long long groups, hipStream_t st) {
+    if (groups <= 0) return hipSuccess;
+    note_kernel("ragged_decode_status_kernel");
+    qlaunch((ragged_decode_status_kernel), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0,
+            st, bb, rows_in, rec_rows, status, nout, k, rmax, groups);
+    return hipGetLastError();
+}
+
+}  // namespace qfec

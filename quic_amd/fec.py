@@ -81,7 +81,8 @@ def _dptr(t):
     import torch
     if not isinstance(t, torch.Tensor):
         raise TypeError("device buffers must be torch tensors")
-    if not t.is_cuda or t.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32):
+    if not t.is_cuda or t.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32,
+                                       torch.int64):
         raise TypeError("device buffers must be integer tensors on a ROCm device")
     if not t.is_contiguous():
         raise ValueError("device buffers must be contiguous")
@@ -172,6 +173,43 @@ class FecEngine:
                                                   _dptr(status), _stream(stream, blocks))
         if rc:
             raise FecError(rc, "qfec_decode_batch_recovered")
+        return rc
+
+    # ragged batches: one (k, m), a block size per group (packed layout, include/quic_fec.h)
+    @staticmethod
+    def _ragged_args(bb, *offs):
+        import torch
+        if bb.dtype != torch.int32 or bb.dim() != 1:
+            raise TypeError("bb must be an int32 [G] device tensor")
+        for o in offs:
+            if o.dtype != torch.int64 or o.shape != bb.shape:
+                raise TypeError("offsets must be int64 [G] device tensors")
+        return bb.shape[0]
+
+    def encode_ragged(self, k, m, bb, data, data_off, parity, par_off, status=None, stream=None):
+        """Group g: data + data_off[g] holds [k][bb[g]], parity + par_off[g] receives
+        [m][bb[g]].  bb int32 [G], offsets int64 [G] (bytes, multiples of 16), data / parity
+        flat uint8, all on the device; status: optional int32 [G] (per-group 0 / -1).  Returns
+        0 or -1 (k + m > 256 with m > 1)."""
+        G = self._ragged_args(bb, data_off, par_off)
+        rc = self.lib.qfec_encode_batch_ragged(self._h, k, m, G, _dptr(bb), _dptr(data),
+                                               _dptr(data_off), _dptr(parity), _dptr(par_off),
+                                               _dptr(status), _stream(stream, data))
+        if rc < -1:
+            raise FecError(rc, "qfec_encode_batch_ragged")
+        return rc
+
+    def decode_ragged_recovered(self, k, m, bb, blocks, blocks_off, rows_in, rec, rec_off,
+                                rec_rows, status=None, stream=None):
+        """Recovered-blocks layout per group: rec + rec_off[g] receives up to
+        [min(k,m)][bb[g]], rec_rows [G][min(k,m)] the restored data rows (255 = unused).
+        blocks / rows_in [G][k] are not modified."""
+        G = self._ragged_args(bb, blocks_off, rec_off)
+        rc = self.lib.qfec_decode_batch_ragged_recovered(
+            self._h, k, m, G, _dptr(bb), _dptr(blocks), _dptr(blocks_off), _dptr(rows_in),
+            _dptr(rec), _dptr(rec_off), _dptr(rec_rows), _dptr(status), _stream(stream, blocks))
+        if rc:
+            raise FecError(rc, "qfec_decode_batch_ragged_recovered")
         return rc
 
     # packet protection next to the codec (NullEncrypter / NullDecrypter, pp_null.hip)
@@ -437,6 +475,82 @@ def decode_recovered_host_into(engine, k, m, block_bytes, blocks_h, rows_h, rec_
         _hptr(rec_h), _hptr(rec_rows_h), None if status_h is None else _hptr(status_h))
     if rc:
         raise FecError(rc, "qfec_decode_batch_recovered_host")
+    return rc
+
+
+def ragged_layout(k, m, bb):
+    """The packed layout of groups with block sizes `bb` (qfec_ragged_layout; host only):
+    (data_off, par_off, rec_off, totals), int64 arrays [G] of byte offsets (multiples of 16)
+    and the three buffer sizes.  ValueError for a size < 1 or an overflow."""
+    bb = np.ascontiguousarray(bb, dtype=np.int32)
+    if bb.ndim != 1:
+        raise ValueError("bb must be one-dimensional")
+    G = bb.shape[0]
+    offs = [np.zeros(G, np.int64) for _ in range(3)]
+    totals = np.zeros(3, np.int64)
+    rc = load().qfec_ragged_layout(k, m, G, bb.ctypes.data_as(ctypes.c_void_p),
+                                   *[o.ctypes.data_as(ctypes.c_void_p) for o in offs],
+                                   totals.ctypes.data_as(ctypes.c_void_p))
+    if rc:
+        raise ValueError(f"qfec_ragged_layout: rc={rc} (k={k} m={m}, a size < 1 or overflow)")
+    return offs[0], offs[1], offs[2], tuple(int(t) for t in totals)
+
+
+def _hcheck_ragged(k, nout, bb_h, in_h, in_off_h, out_h, out_off_h):
+    """Host arguments of a ragged call: bb int32 [G], offsets int64 [G], flat uint8 buffers that
+    hold every group the offsets name."""
+    import torch
+    G = bb_h.shape[0] if isinstance(bb_h, torch.Tensor) and bb_h.dim() == 1 else None
+    _hcheck(bb_h, "bb", torch.int32, (G,))
+    _hcheck(in_off_h, "in_off", torch.int64, (G,))
+    _hcheck(out_off_h, "out_off", torch.int64, (G,))
+    _hcheck(in_h, "in", torch.uint8, (None,))
+    _hcheck(out_h, "out", torch.uint8, (None,))
+    if int(bb_h.min()) < 1:
+        raise ValueError("bb: every block size must be >= 1")
+    bb64 = bb_h.to(torch.int64)
+    for name, buf, off, n in (("in", in_h, in_off_h, k), ("out", out_h, out_off_h, nout)):
+        if int(off.min()) < 0 or int((off % 16).max()) != 0:
+            raise ValueError(f"{name}_off: offsets must be non-negative multiples of 16")
+        if int((off + n * bb64).max()) > buf.numel():
+            raise ValueError(f"{name}: buffer of {buf.numel()} bytes is too short for its groups")
+    return G
+
+
+def encode_ragged_host_into(engine, k, m, bb_h, data_h, data_off_h, parity_h, par_off_h,
+                            status_h=None):
+    """Host-pointer ragged encode on caller-owned CPU tensors (qfec_encode_batch_ragged_host):
+    bb int32 [G], offsets int64 [G] (ascending, as ragged_layout gives them), data / parity flat
+    uint8.  Returns 0 / -1."""
+    import torch
+    G = _hcheck_ragged(k, m, bb_h, data_h, data_off_h, parity_h, par_off_h)
+    if status_h is not None:
+        _hcheck(status_h, "status", torch.int32, (G,))
+    rc = engine.lib.qfec_encode_batch_ragged_host(
+        engine._h, k, m, G, _hptr(bb_h), _hptr(data_h), _hptr(data_off_h), _hptr(parity_h),
+        _hptr(par_off_h), None if status_h is None else _hptr(status_h))
+    if rc < -1:
+        raise FecError(rc, "qfec_encode_batch_ragged_host")
+    return rc
+
+
+def decode_ragged_recovered_host_into(engine, k, m, bb_h, blocks_h, blocks_off_h, rows_h, rec_h,
+                                      rec_off_h, rec_rows_h, status_h=None):
+    """Host-pointer ragged decode returning only the recovered blocks
+    (qfec_decode_batch_ragged_recovered_host); rows [G][k], rec_rows [G][min(k,m)]."""
+    import torch
+    rmax = min(k, m)
+    G = _hcheck_ragged(k, rmax, bb_h, blocks_h, blocks_off_h, rec_h, rec_off_h)
+    _hcheck(rows_h, "rows", torch.uint8, (G, k))
+    _hcheck(rec_rows_h, "rec_rows", torch.uint8, (G, rmax))
+    if status_h is not None:
+        _hcheck(status_h, "status", torch.int32, (G,))
+    rc = engine.lib.qfec_decode_batch_ragged_recovered_host(
+        engine._h, k, m, G, _hptr(bb_h), _hptr(blocks_h), _hptr(blocks_off_h), _hptr(rows_h),
+        _hptr(rec_h), _hptr(rec_off_h), _hptr(rec_rows_h),
+        None if status_h is None else _hptr(status_h))
+    if rc:
+        raise FecError(rc, "qfec_decode_batch_ragged_recovered_host")
     return rc
 
 

@@ -48,6 +48,7 @@ _SIG = {
     "qfec_packets_free": (None, [_c.c_void_p]),
     "qfec_batch_new": (_c.c_void_p, [_c.c_void_p, _c.c_size_t, _c.c_uint]),
     "qfec_batch_free": (None, [_c.c_void_p]),
+    "qfec_batch_set_ragged": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "qfec_batch_add_encode": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
     "qfec_batch_add_decode": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
     "qfec_batch_poll": (_c.c_int, [_c.c_void_p]),
@@ -194,6 +195,13 @@ class FecBatch:
         h, self._h = getattr(self, "_h", None), None
         if h:
             self._L.qfec_batch_free(h)
+
+    def set_ragged(self, on):
+        """Key the buckets by (k, m) only and run one ragged launch per bucket, each group
+        with its own block_bytes (qfec_batch_set_ragged; off by default).  Only while nothing
+        is queued."""
+        if self._L.qfec_batch_set_ragged(self._h, 1 if on else 0):
+            raise ValueError("set_ragged: flush the queued groups first")
 
     def add_encode(self, group):
         self._keep.append(group)

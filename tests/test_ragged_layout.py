@@ -1,0 +1,137 @@
+"""Ragged batches, host side (no GPU): the packed layout of qfec_ragged_layout and the argument
+checks of the Python host wrappers."""
+import numpy as np
+import pytest
+
+from quic_amd import fec
+
+
+def up16(v):
+    return (v + 15) & ~15
+
+
+def test_layout_hand_written():
+    k, m = 10, 4                      # min(k, m) = 4 = m: use (3, 5) below for rec != par
+    bb = [8, 1352, 1, 24, 2064, 17]
+    d, p, r, tot = fec.ragged_layout(k, m, bb)
+    # data: 80 -> 80; 13520 -> 13600; 10 -> 13616; 240 -> 13856; 20640 -> 34496; 170 -> 34672
+    assert d.tolist() == [0, 80, 13600, 13616, 13856, 34496]
+    # parity: 32; 5408 -> 5440; 4 -> 5456; 96 -> 5552; 8256 -> 13808; 68 -> 13888
+    assert p.tolist() == [0, 32, 5440, 5456, 5552, 13808]
+    assert r.tolist() == p.tolist()
+    assert tot == (34672, 13888, 13888)
+    assert d.dtype == p.dtype == r.dtype == np.int64
+
+
+def test_layout_rec_uses_min_k_m():
+    k, m = 3, 5
+    bb = [40, 7, 104]
+    d, p, r, tot = fec.ragged_layout(k, m, bb)
+    assert d.tolist() == [0, up16(120), up16(120) + up16(21)]
+    assert p.tolist() == [0, up16(200), up16(200) + up16(35)]
+    assert r.tolist() == d.tolist()               # min(k, m) = k
+    assert tot == (128 + 32 + 312 + 8, 208 + 48 + 520 + 8, 128 + 32 + 312 + 8)
+    for off in (d, p, r):
+        assert all(int(o) % 16 == 0 for o in off)
+    assert all(t % 16 == 0 for t in tot)
+
+
+def test_layout_random_matches_running_sum():
+    rng = np.random.default_rng(5)
+    for k, m in ((10, 1), (5, 5), (32, 4), (10, 20), (1, 3), (250, 5)):
+        bb = rng.integers(1, 2100, size=57).astype(np.int32)
+        d, p, r, tot = fec.ragged_layout(k, m, bb)
+        for off, n, t in ((d, k, tot[0]), (p, m, tot[1]), (r, min(k, m), tot[2])):
+            run = 0
+            for g, b in enumerate(bb):
+                assert off[g] == run
+                run = up16(run + n * int(b))
+            assert t == run
+    assert fec.ragged_layout(4, 2, [])[3] == (0, 0, 0)
+
+
+def test_layout_rejects_bad_sizes():
+    L = fec.load()
+    bb = np.array([8, 0, 8], np.int32)
+    tot = np.zeros(3, np.int64)
+    assert L.qfec_ragged_layout(4, 2, 3, bb.ctypes.data, None, None, None, tot.ctypes.data) == -2
+    neg = np.array([-8], np.int32)
+    assert L.qfec_ragged_layout(4, 2, 1, neg.ctypes.data, None, None, None, tot.ctypes.data) == -2
+    assert L.qfec_ragged_layout(4, 2, -1, bb.ctypes.data, None, None, None, tot.ctypes.data) == -2
+    assert L.qfec_ragged_layout(4, 2, 1, None, None, None, None, tot.ctypes.data) == -2
+    with pytest.raises(ValueError):
+        fec.ragged_layout(4, 2, [8, 0, 8])
+    # offsets may be omitted one by one
+    good = np.array([8, 24], np.int32)
+    only = np.zeros(2, np.int64)
+    assert L.qfec_ragged_layout(4, 2, 2, good.ctypes.data, None, only.ctypes.data, None, None) == 0
+    assert only.tolist() == [0, 16]
+
+
+def test_device_entry_points_reject_null_and_negative_groups():
+    """Argument errors are -2 before anything touches a GPU."""
+    L = fec.load()
+    assert L.qfec_encode_batch_ragged(None, 4, 2, 1, 16, 16, 16, 16, 16, None, None) == -2
+    assert L.qfec_decode_batch_ragged_recovered(None, 4, 2, 1, 16, 16, 16, 16, 16, 16, 16, None,
+                                                None) == -2
+    assert L.qfec_encode_batch_ragged_host(None, 4, 2, 1, 16, 16, 16, 16, 16, None) == -2
+    assert L.qfec_decode_batch_ragged_recovered_host(None, 4, 2, 1, 16, 16, 16, 16, 16, 16, 16,
+                                                     None) == -2
+
+
+def _host_args(k, m, bb):
+    import torch
+    d, p, r, tot = fec.ragged_layout(k, m, bb)
+    G = len(bb)
+    return dict(
+        bb=torch.tensor(bb, dtype=torch.int32),
+        data=torch.zeros(tot[0], dtype=torch.uint8), data_off=torch.from_numpy(d),
+        par=torch.zeros(tot[1], dtype=torch.uint8), par_off=torch.from_numpy(p),
+        rec=torch.zeros(tot[2], dtype=torch.uint8), rec_off=torch.from_numpy(r),
+        rows=torch.zeros((G, k), dtype=torch.uint8),
+        rec_rows=torch.zeros((G, min(k, m)), dtype=torch.uint8),
+        status=torch.zeros(G, dtype=torch.int32))
+
+
+def _enc(a, **kw):
+    a = dict(a, **kw)
+    return fec.encode_ragged_host_into(None, 4, 2, a["bb"], a["data"], a["data_off"], a["par"],
+                                       a["par_off"], a["status"])
+
+
+def _dec(a, **kw):
+    a = dict(a, **kw)
+    return fec.decode_ragged_recovered_host_into(None, 4, 2, a["bb"], a["data"], a["data_off"],
+                                                 a["rows"], a["rec"], a["rec_off"],
+                                                 a["rec_rows"], a["status"])
+
+
+def test_host_wrappers_reject_bad_buffers():
+    """Non-contiguous, mis-typed or short host arrays are refused before the library is called
+    (engine None: a call that got through would fail differently)."""
+    import torch
+    a = _host_args(4, 2, [8, 24, 1352])
+    bad = [
+        dict(bb=a["bb"].to(torch.int64)),                       # sizes must be int32
+        dict(bb=torch.tensor([8, 0, 1352], dtype=torch.int32)),  # a size < 1
+        dict(data_off=a["data_off"].to(torch.int32)),           # offsets must be int64
+        dict(data_off=a["data_off"] + 8),                       # not a multiple of 16
+        dict(data_off=a["data_off"][:2]),                       # one offset per group
+        dict(data=a["data"][:-16]),                             # too short for the last group
+        dict(data=torch.zeros(2 * a["data"].numel(), dtype=torch.uint8)[::2]),  # non-contiguous
+        dict(data=a["data"].to(torch.int8)),                    # wrong dtype
+        dict(data=a["data"].numpy()),                           # not a tensor
+        dict(status=a["status"].to(torch.int64)),
+    ]
+    for kw in bad:
+        with pytest.raises((TypeError, ValueError)):
+            _enc(a, **kw)
+        with pytest.raises((TypeError, ValueError)):
+            _dec(a, **kw)
+    for kw in (dict(par=a["par"][:-1]), dict(par_off=a["par_off"].flip(0)[::1] * 0 - 16)):
+        with pytest.raises((TypeError, ValueError)):
+            _enc(a, **kw)
+    for kw in (dict(rec=a["rec"][:-1]), dict(rows=a["rows"][:, :3]),
+               dict(rows=a["rows"].t().contiguous().t()), dict(rec_rows=a["rec_rows"][:2])):
+        with pytest.raises((TypeError, ValueError)):
+            _dec(a, **kw)

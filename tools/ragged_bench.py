@@ -1,0 +1,216 @@
+#!/usr/bin/env python3
+"""Ragged batches against what the uniform entry points can do with the same groups.
+
+Device-resident.  Every call is bracketed by the library's kernel timing events
+(qfec_set_timing_events: first kernel start to last kernel end, as bench.py's roofline pass), so
+a figure is kernel time, not enqueue time; the wall clock of the whole sequence (enqueue to
+synchronise) is reported next to it, because the launch count is what the ragged path removes.
+Warm-up, then the median of --reps repetitions, the variants alternating inside one repetition.
+
+Workload (seeded): --groups groups of (32, 4) and of (10, 1); per group bb = 1352 with
+probability 0.7, otherwise uniform over the multiples of 8 in [48, 1352].
+  ragged    one qfec_encode_batch_ragged / qfec_decode_batch_ragged_recovered call
+  buckets   the groups pre-sorted into per-bb uniform buffers (not timed) and one
+            qfec_encode_batch / qfec_decode_batch_recovered per bucket: sum of the event times
+Reference point: the ragged path with every bb = 1352 against the uniform compiled path.
+Outputs of the two paths are compared byte for byte at the timed size before anything is timed.
+
+  python tools/ragged_bench.py --out profiles/ragged/ragged_bench.json
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_BYTES_PER_S = 8.0e12
+
+
+def draw_sizes(G, seed):
+    rng = np.random.default_rng(seed)
+    bb = np.full(G, 1352, np.int32)
+    short = rng.random(G) >= 0.7
+    bb[short] = 8 * rng.integers(6, 170, size=int(short.sum()))     # 48 .. 1352
+    return bb
+
+
+def views(flat, offs, sizes):
+    return [flat[int(o):int(o) + int(n)] for o, n in zip(offs, sizes)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--groups", type=int, default=65536)
+    ap.add_argument("--reps", type=int, default=21)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--seed", type=int, default=2025)
+    ap.add_argument("--codes", default="32,4,2 10,1,1",
+                    help="space-separated k,m,losses triples (default: the two measured codes)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.reps < 20:
+        ap.error("--reps must be at least 20")
+
+    import torch
+    from bench import DeviceEvents
+    from quic_amd import _lib, fec
+    if not torch.cuda.is_available():
+        sys.exit("ragged_bench needs a GPU")
+    lib = _lib.load()
+    eng = fec.FecEngine(0)
+    results = []
+
+    def timed(ev, i, fn):
+        lib.qfec_set_timing_events(ev.ev[2 * i], ev.ev[2 * i + 1])
+        fn()
+        lib.qfec_set_timing_events(None, None)
+
+    def run_config(k, m, r, bb, label):
+        G = len(bb)
+        rmax = min(k, m)
+        d_off, p_off, r_off, tot = fec.ragged_layout(k, m, bb)
+        data = torch.empty(tot[0], dtype=torch.uint8, device="cuda")
+        fec.synth_fill(data, seed=args.seed)
+        par = torch.zeros(tot[1], dtype=torch.uint8, device="cuda")
+        rec = torch.zeros(tot[2], dtype=torch.uint8, device="cuda")
+        bb_d = torch.from_numpy(bb).cuda()
+        d_off_d, p_off_d, r_off_d = (torch.from_numpy(o).cuda() for o in (d_off, p_off, r_off))
+        # receive set: slot i < r holds parity row i (data rows 0 .. r-1 lost)
+        rows_np = np.tile(np.arange(k, dtype=np.uint8), (G, 1))
+        rows_np[:, :r] = k + np.arange(r, dtype=np.uint8)
+        rows = torch.from_numpy(rows_np).cuda()
+        rr = torch.zeros((G, rmax), dtype=torch.uint8, device="cuda")
+        st = torch.zeros(G, dtype=torch.int32, device="cuda")
+
+        assert eng.encode_ragged(k, m, bb_d, data, d_off_d, par, p_off_d) == 0
+        blocks = data.clone()
+        torch._foreach_copy_(views(blocks, d_off, r * bb.astype(np.int64)),
+                             views(par, p_off, r * bb.astype(np.int64)))
+        eng.decode_ragged_recovered(k, m, bb_d, blocks, d_off_d, rows, rec, r_off_d, rr, status=st)
+        torch.cuda.synchronize()
+        assert int(st.abs().max()) == 0
+        kern = {"ragged_encode": None, "ragged_decode": fec.last_kernels()}
+
+        # the parent's route: per-bb buckets, gathered once (not timed)
+        buckets = []
+        for b in np.unique(bb):
+            idx = np.nonzero(bb == b)[0]
+            b = int(b)
+            Gb = len(idx)
+            bd = torch.stack(views(data, d_off[idx], [k * b] * Gb)).view(Gb, k, b)
+            bbk = torch.stack(views(blocks, d_off[idx], [k * b] * Gb)).view(Gb, k, b)
+            buckets.append(dict(
+                bb=b, G=Gb, idx=idx, data=bd, blocks=bbk, rows=rows[torch.from_numpy(idx).cuda()],
+                par=torch.zeros((Gb, m, b), dtype=torch.uint8, device="cuda"),
+                rec=torch.zeros((Gb, rmax, b), dtype=torch.uint8, device="cuda"),
+                rr=torch.zeros((Gb, rmax), dtype=torch.uint8, device="cuda"),
+                st=torch.zeros(Gb, dtype=torch.int32, device="cuda")))
+        nb = len(buckets)
+
+        def bucket_encode(ev=None, base=0):
+            for i, B in enumerate(buckets):
+                f = lambda: eng.encode(k, m, B["bb"], B["data"], B["par"])
+                timed(ev, base + i, f) if ev else f()
+
+        def bucket_decode(ev=None, base=0):
+            for i, B in enumerate(buckets):
+                f = lambda: eng.decode_recovered(k, m, B["bb"], B["blocks"], B["rows"], B["rec"],
+                                                 B["rr"], status=B["st"])
+                timed(ev, base + i, f) if ev else f()
+
+        def ragged_encode():
+            eng.encode_ragged(k, m, bb_d, data, d_off_d, par, p_off_d)
+
+        def ragged_decode():
+            eng.decode_ragged_recovered(k, m, bb_d, blocks, d_off_d, rows, rec, r_off_d, rr,
+                                        status=st)
+
+        # same bytes from both paths, at the timed size
+        bucket_encode()
+        bucket_decode()
+        torch.cuda.synchronize()
+        for B in buckets:
+            idx, b, Gb = B["idx"], B["bb"], B["G"]
+            assert torch.equal(torch.stack(views(par, p_off[idx], [m * b] * Gb)).view(Gb, m, b),
+                               B["par"]), "parity differs between the paths"
+            assert torch.equal(torch.stack(views(rec, r_off[idx], [r * b] * Gb)).view(Gb, r, b),
+                               B["rec"][:, :r]), "recovered blocks differ between the paths"
+            assert torch.equal(torch.stack(views(rec, r_off[idx], [r * b] * Gb)).view(Gb, r, b),
+                               B["data"][:, :r]), "recovered blocks are not the lost data"
+        ragged_encode()
+        kern["ragged_encode"] = fec.last_kernels()
+
+        # events: [0] ragged enc, [1] ragged dec, [2 .. 2+nb) bucket enc, then bucket dec
+        ev = DeviceEvents(2 * (2 + 2 * nb))
+        t = {x: [] for x in ("ragged_encode", "ragged_decode", "bucket_encode", "bucket_decode")}
+        wall = {x: [] for x in t}
+
+        def walled(name, fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            wall[name].append((time.perf_counter() - t0) * 1e3)
+
+        for rep in range(args.warmup + args.reps):
+            order = [("ragged_encode", lambda: timed(ev, 0, ragged_encode)),
+                     ("bucket_encode", lambda: bucket_encode(ev, 2)),
+                     ("ragged_decode", lambda: timed(ev, 1, ragged_decode)),
+                     ("bucket_decode", lambda: bucket_decode(ev, 2 + nb))]
+            if rep % 2:
+                order = [order[1], order[0], order[3], order[2]]
+            for name, fn in order:
+                walled(name, fn)
+            if rep < args.warmup:
+                for x in wall:
+                    wall[x].clear()
+                continue
+            t["ragged_encode"].append(ev.elapsed_ms(0, 1))
+            t["ragged_decode"].append(ev.elapsed_ms(2, 3))
+            t["bucket_encode"].append(sum(ev.elapsed_ms(2 * (2 + i), 2 * (2 + i) + 1)
+                                          for i in range(nb)))
+            t["bucket_decode"].append(sum(ev.elapsed_ms(2 * (2 + nb + i), 2 * (2 + nb + i) + 1)
+                                          for i in range(nb)))
+        ev.close()
+        total = int(bb.astype(np.int64).sum())
+        nbytes = {"encode": (k + m) * total, "decode": (k + r) * total}
+        line = dict(config=label, k=k, m=m, losses=r, groups=G, distinct_bb=nb,
+                    uniform_launches_per_phase=nb, reps=args.reps, kernels=kern,
+                    bytes_moved=nbytes)
+        for name, v in t.items():
+            med = statistics.median(v)
+            by = nbytes["encode" if name.endswith("encode") else "decode"]
+            line[name] = dict(kernel_ms_median=round(med, 4), kernel_ms_min=round(min(v), 4),
+                              kernel_ms_max=round(max(v), 4),
+                              wall_ms_median=round(statistics.median(wall[name]), 4),
+                              GBps=round(by / (med * 1e-3) / 1e9, 1),
+                              hbm_fraction=round(by / (med * 1e-3) / HBM_BYTES_PER_S, 4))
+        results.append(line)
+        print(json.dumps(line), flush=True)
+
+    G = args.groups
+    mixed = draw_sizes(G, args.seed)
+    flat = np.full(G, 1352, np.int32)
+    for k, m, r in (tuple(int(v) for v in c.split(",")) for c in args.codes.split()):
+        run_config(k, m, r, mixed, f"mixed ({k},{m})")
+        # the price of run-time shapes: every bb = 1352, one bucket = the compiled path (A / B)
+        run_config(k, m, r, flat, f"all-1352 ({k},{m})")
+    eng.close()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(dict(tool="tools/ragged_bench.py", seed=args.seed, hbm_peak_Bps=HBM_BYTES_PER_S,
+                           timing="qfec_set_timing_events (first kernel start to last kernel end); "
+                                  "wall = enqueue to synchronise",
+                           results=results), f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
