@@ -67,6 +67,11 @@ QFEC_API int cauchy_256_decode(int k, int m, Block *blocks, int block_bytes);
  *                       defined (a row tag >= k + m, the same recovery row twice, fewer
  *                       missing data rows than recovery blocks); such a group is left as
  *                       it was
+ * The byte buffers of the uniform calls (data, parity, blocks, out, rec and the row-tag arrays)
+ * may start at any address, like the reference codec's: the library picks its kernels from the
+ * pointers' alignment (16-byte aligned data / blocks and 8-byte aligned outputs take the fastest
+ * ones) and the result is the same bytes.  status is an int array, aligned as its type requires.
+ * A call writes the bytes this header names and no others.
  * `stream` is a hipStream_t (NULL = HIP's null stream, as everywhere in HIP).  Device
  * entry points only enqueue work on that stream; they do not synchronise.
  *

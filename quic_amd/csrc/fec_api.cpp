@@ -440,9 +440,11 @@ int decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d
                                     rmax, out_gstride, st, c->tune));
         return 0;
     }
-    if (qfec::gf_bsyn_supported(k, m, bb, rmax, c->tune) && aligned) {
+    if (qfec::gf_bsyn_supported(k, m, bb, rmax, c->tune) && aligned &&
+        ((uintptr_t)d_rows_in & 3) == 0) {
         // compiled (32, 4) x 1352 B code (configs B / C): syndromes of every parity row, then
-        // the r x r solve
+        // the r x r solve.  Its prep reads the row tags as dwords; tags at any other address
+        // take the run-time path below (decode_prep_wide_kernel reads them bytewise)
         QF_HIP(qfec::launch_decode_prep_bsyn(d_rows_in, rows_out, d_status, cenc, w.coef,
                                              w.slots, w.nout, rec_rows, k, m, bb, rmax, G, st));
         QF_HIP(qfec::launch_gf_bsyn(d_blocks, o.out, w.coef, cenc, slots, w.nout, k, m, bb, G,

@@ -347,10 +347,16 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
                                                               512u * h + 8u * (uint32_t)ln, 0, 2);
                 }
             });
-            // pad to exactly NSTW stores (empty range)
+            // pad to exactly NSTW stores (empty range).  Distinct offsets and a compiler barrier
+            // per store: identical stores in this loop were merged into ONE instruction, so a
+            // group with fewer than RC recovered blocks issued 3 n + 1 stores and the next
+            // group's vmcnt(WAIT0) could pass before its block had landed in LDS
             const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0u, 0x00020000);
 #pragma unroll 1
-            for (int q = 3 * n; q < NSTW; ++q) __builtin_amdgcn_raw_buffer_store_b32(0u, none, 0u, 0, 0);
+            for (int q = 3 * n; q < NSTW; ++q) {
+                __builtin_amdgcn_raw_buffer_store_b32(0u, none, 0u, 4 * q, 0);
+                asm volatile("" ::: "memory");
+            }
             asm volatile("" ::: "memory");
             continue;
         }

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from quic_amd import fec, synth
+from tests.guarded import FILL, guarded, guarded_from
 
 pytestmark = pytest.mark.gpu
 
@@ -25,30 +26,58 @@ def host(t):
     return t.cpu().numpy()
 
 
-def gpu_encode(engine, k, m, bb, data):
+def status_buf(G):
+    """A guarded int32 [G] status array holding 7 (no status code)."""
     import torch
+    st, h = guarded((G,), dtype=torch.int32)
+    st.fill_(7)
+    return st, h
+
+
+def parity_written(p_or, rc_or):
+    """The parity buffer after an encode that started as the fill byte: an encode that returns
+    -1 writes the XOR parity into block 0 and nothing else (cauchy_256.cpp:1519-1534)."""
+    if rc_or == 0:
+        return p_or
+    exp = np.full_like(p_or, FILL)
+    exp[:, 0] = p_or[:, 0]
+    return exp
+
+
+def gpu_encode(engine, k, m, bb, data):
+    """The parity buffer starts as the fill byte, between guards (tests/guarded.py)."""
     d = dev(data)
-    p = torch.zeros((data.shape[0], m, bb), dtype=torch.uint8, device="cuda")
+    p, hp = guarded((data.shape[0], m, bb))
     rc = engine.encode(k, m, bb, d, p)
+    hp.check_guards()
     return host(p), rc
 
 
 def gpu_decode(engine, k, m, bb, blocks, rows, inplace=True):
-    import torch
+    """Every output between guards; out of place, `out` starts as the fill byte and only
+    slots tagged as recovery blocks may change."""
+    G = blocks.shape[0]
+    st, hst = status_buf(G)
+    if inplace:
+        b, hb = guarded_from(blocks)
+        r, hr = guarded_from(rows)
+        engine.decode(k, m, bb, b, r, status=st)
+        for h in (hb, hr, hst):
+            h.check_guards()
+        return host(b), host(r), host(st)
     b = dev(blocks)
     r = dev(rows)
-    st = torch.full((blocks.shape[0],), 7, dtype=torch.int32, device="cuda")
-    if inplace:
-        engine.decode(k, m, bb, b, r, status=st)
-        return host(b), host(r), host(st)
-    out = torch.zeros_like(b)
-    ro = torch.zeros_like(r)
+    out, ho = guarded(blocks.shape)
+    ro, hro = guarded(rows.shape)
     engine.decode(k, m, bb, b, r, out=out, rows_out=ro, status=st)
+    for h in (ho, hro, hst):
+        h.check_guards()
     # out-of-place: only recovered slots are written; merge for comparison
     o = host(out)
     rin = rows.astype(np.int64)
     merged = blocks.copy()
     mask = rin >= k
+    assert (o[~mask] == FILL).all()
     merged[mask] = o[mask]
     return merged, host(ro), host(st)
 
@@ -156,7 +185,8 @@ def test_unsupported_params_status(engine, oracle):
     p_gpu, rc = gpu_encode(engine, k, m, bb, data)
     p_or, rc_or = oracle.encode_batch(k, m, bb, data)
     assert rc == rc_or == -1
-    np.testing.assert_array_equal(p_gpu, p_or)
+    assert not p_or[:, 1:].any()
+    np.testing.assert_array_equal(p_gpu, parity_written(p_or, rc_or))
     rows = np.tile(np.array(list(range(1, 250)) + [250], np.uint8), (3, 1))
     b, rr, s = gpu_decode(engine, k, m, bb, data, rows)
     b2, rr2, s2 = oracle.decode_batch(k, m, bb, data, rows)
@@ -169,7 +199,8 @@ def test_unsupported_params_status(engine, oracle):
     p_gpu, rc = gpu_encode(engine, k, m, bb, data)
     p_or, rc_or = oracle.encode_batch(k, m, bb, data)
     assert rc == rc_or == -1
-    np.testing.assert_array_equal(p_gpu, p_or)
+    assert not p_or[:, 1:].any()
+    np.testing.assert_array_equal(p_gpu, parity_written(p_or, rc_or))
 
 
 def test_host_pointer_batch(engine, oracle):
@@ -1088,7 +1119,6 @@ def test_tile_many_groups_per_workgroup(tuned_engine, oracle, grid, k, m, r, opt
 
 def check_decodes(engine, oracle, k, m, bb, recv, rows, dec_kernel):
     """Both in-place layouts and the recovered-blocks layout against the oracle."""
-    import torch
     G = recv.shape[0]
     b_or, r_or, s_or = oracle.decode_batch(k, m, bb, recv, rows)
     for inplace in (True, False):
@@ -1099,15 +1129,18 @@ def check_decodes(engine, oracle, k, m, bb, recv, rows, dec_kernel):
         np.testing.assert_array_equal(b, b_or)
     exp, exp_rows = expected_recovered(k, m, bb, rows, b_or, r_or, s_or)
     rmax = min(k, m)
-    rec = torch.zeros((G, rmax, bb), dtype=torch.uint8, device="cuda")
-    rec_rows = torch.zeros((G, rmax), dtype=torch.uint8, device="cuda")
-    st = torch.full((G,), 7, dtype=torch.int32, device="cuda")
+    rec, hrec = guarded((G, rmax, bb))
+    rec_rows, hrr = guarded((G, rmax))
+    st, hst = status_buf(G)
     engine.decode_recovered(k, m, bb, dev(recv), dev(rows), rec, rec_rows, status=st)
     assert dec_kernel in fec.last_kernels()
+    for h in (hrec, hrr, hst):
+        h.check_guards()
     np.testing.assert_array_equal(host(st), s_or)
     np.testing.assert_array_equal(host(rec_rows), exp_rows)
     mask = exp_rows != 255
     np.testing.assert_array_equal(host(rec)[mask], exp[mask])
+    assert (host(rec)[s_or != 0] == FILL).all()      # a group that failed recovers nothing
     return s_or
 
 
@@ -1288,45 +1321,51 @@ def dev_at(a, offset):
 def run_decode_paths(engine, oracle, k, m, bb, G, offset):
     """Encode, decode (slot layout in place and out of place) and decode_recovered, each
     bit-exact with the oracle; returns the kernels each of the four calls launched."""
-    import torch
     data, p_or, rc_or, rows, recv, b_or, r_or, s_or, exp, exp_rows = \
         path_reference(oracle, k, m, bb, G)
     kernels = []
     p_gpu, rc = gpu_encode(engine, k, m, bb, data)
     kernels.append(fec.last_kernels())
     assert rc == rc_or
-    np.testing.assert_array_equal(p_gpu, p_or)
+    np.testing.assert_array_equal(p_gpu, parity_written(p_or, rc_or))
     # slot layout, in place
     b, r = dev_at(recv, offset), dev(rows)
-    st = torch.full((G,), 7, dtype=torch.int32, device="cuda")
+    st, hst = status_buf(G)
     engine.decode(k, m, bb, b, r, status=st)
     kernels.append(fec.last_kernels())
+    hst.check_guards()
     np.testing.assert_array_equal(host(st), s_or)
     np.testing.assert_array_equal(host(r), r_or)
     np.testing.assert_array_equal(host(b), b_or)
     # slot layout, out of place: only the recovered slots are written
     b, r = dev_at(recv, offset), dev(rows)
-    out, ro = torch.zeros((G, k, bb), dtype=torch.uint8, device="cuda"), torch.zeros_like(r)
-    st = torch.full((G,), 7, dtype=torch.int32, device="cuda")
+    out, ho = guarded((G, k, bb))
+    ro, hro = guarded((G, k))
+    st, hst = status_buf(G)
     engine.decode(k, m, bb, b, r, out=out, rows_out=ro, status=st)
     kernels.append(fec.last_kernels())
+    for h in (ho, hro, hst):
+        h.check_guards()
     np.testing.assert_array_equal(host(st), s_or)
     np.testing.assert_array_equal(host(ro), r_or)
     written = (r_or != rows) & (k > 1)      # k <= 1 only retags the block it was given
     np.testing.assert_array_equal(host(out)[written], b_or[written])
-    assert not host(out)[~written].any()
+    assert (host(out)[~written] == FILL).all()
     np.testing.assert_array_equal(host(b), recv)
     # recovered-blocks layout
     rmax = min(k, m)
-    rec = torch.zeros((G, rmax, bb), dtype=torch.uint8, device="cuda")
-    rec_rows = torch.zeros((G, rmax), dtype=torch.uint8, device="cuda")
-    st = torch.full((G,), 7, dtype=torch.int32, device="cuda")
+    rec, hrec = guarded((G, rmax, bb))
+    rec_rows, hrr = guarded((G, rmax))
+    st, hst = status_buf(G)
     engine.decode_recovered(k, m, bb, b, r, rec, rec_rows, status=st)
     kernels.append(fec.last_kernels())
+    for h in (hrec, hrr, hst):
+        h.check_guards()
     np.testing.assert_array_equal(host(st), s_or)
     np.testing.assert_array_equal(host(rec_rows), exp_rows)
     mask = exp_rows != 255
     np.testing.assert_array_equal(host(rec)[mask], exp[mask])
+    assert (host(rec)[s_or != 0] == FILL).all()      # a group that failed recovers nothing
     np.testing.assert_array_equal(host(b), recv)
     return tuple(kernels)
 
