@@ -416,8 +416,8 @@ int decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d
     qfec::DecodeWork w{(uint8_t*)W.dcoef.p, (uint8_t*)W.dslots.p, (int32_t*)W.dnout.p};
     // what the layout decides: which row output the prep writes, whether the kernels scatter
     // through the slot table, and the stride between the groups of `out`
-    uint8_t* const rows_out = o.compact ? nullptr : o.rows;
-    uint8_t* const rec_rows = o.compact ? o.rows : nullptr;
+    const qfec::PrepIO io{d_rows_in, o.compact ? nullptr : o.rows, o.compact ? o.rows : nullptr,
+                          d_status, w};
     const uint8_t* const slots = o.compact ? nullptr : w.slots;
     const long long out_gstride = (long long)(o.compact ? rmax : k) * bb;
     const bool aligned = ((uintptr_t)d_blocks & 15) == 0;
@@ -425,8 +425,7 @@ int decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d
     // layout in place needs no scratch.
     if (qfec::gf_dcol_supported(k, m, bb, c->tune) && rmax <= 16 && aligned) {
         // compiled (128, 16) code: syndromes, then the r x r solve
-        QF_HIP(qfec::launch_decode_prep(d_rows_in, rows_out, d_status, cenc, w, k, m, bb, rc,
-                                        rmax, G, st, c->tune, rec_rows, true));
+        QF_HIP(qfec::launch_decode_prep(io, cenc, k, m, bb, rc, rmax, G, st, c->tune, true));
         QF_HIP(qfec::launch_gf_dcol_syndrome(d_blocks, o.out, w.coef, slots, w.nout, cenc, k, m,
                                              bb, G, rmax, p.tab_gstride, out_gstride, st,
                                              c->tune));
@@ -434,8 +433,7 @@ int decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d
     }
     if (qfec::gf_psyn_supported(k, m, bb, rmax, c->tune) && aligned) {
         // compiled QuicR preset code: syndromes of every parity row, then Gauss-Jordan in place
-        QF_HIP(qfec::launch_decode_prep_psyn(d_rows_in, rows_out, d_status, cenc, w.coef,
-                                             w.slots, w.nout, rec_rows, k, m, bb, rmax, G, st));
+        QF_HIP(qfec::launch_decode_prep_psyn(io, cenc, k, m, bb, rmax, G, st));
         QF_HIP(qfec::launch_gf_psyn(d_blocks, o.out, w.coef, cenc, slots, w.nout, k, m, bb, G,
                                     rmax, out_gstride, st, c->tune));
         return 0;
@@ -445,15 +443,13 @@ int decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d
         // compiled (32, 4) x 1352 B code (configs B / C): syndromes of every parity row, then
         // the r x r solve.  Its prep reads the row tags as dwords; tags at any other address
         // take the run-time path below (decode_prep_wide_kernel reads them bytewise)
-        QF_HIP(qfec::launch_decode_prep_bsyn(d_rows_in, rows_out, d_status, cenc, w.coef,
-                                             w.slots, w.nout, rec_rows, k, m, bb, rmax, G, st));
+        QF_HIP(qfec::launch_decode_prep_bsyn(io, cenc, k, m, bb, rmax, G, st));
         QF_HIP(qfec::launch_gf_bsyn(d_blocks, o.out, w.coef, cenc, slots, w.nout, k, m, bb, G,
                                     rmax, out_gstride, st, c->tune));
         return 0;
     }
     // The run-time codes: the prep's coefficients, applied in chunks of rc recovered blocks.
-    QF_HIP(qfec::launch_decode_prep(d_rows_in, rows_out, d_status, cenc, w, k, m, bb, rc, rmax,
-                                    G, st, c->tune, rec_rows));
+    QF_HIP(qfec::launch_decode_prep(io, cenc, k, m, bb, rc, rmax, G, st, c->tune));
     if (bb % 8 != 0 || k + m > 256) return 0;   // every group is a no-op or status -1
     // One primitive, the dense decode into a [G][rmax][bb] destination: the compact layout's
     // `out` is one.  The slot layout writes straight into its slots instead (`direct`) where a
@@ -1267,8 +1263,8 @@ static int decode_ragged_impl(qfec_ctx* c, int k, int m, long long G, qfec::Ragg
     const uint8_t* cenc = nullptr;
     if ((r = get_cenc(c, k, m, &cenc))) return r;
     qfec::DecodeWork w{(uint8_t*)W.dcoef.p, (uint8_t*)W.dslots.p, (int32_t*)W.dnout.p};
-    QF_HIP(qfec::launch_decode_prep(d_rows_in, nullptr, d_status, cenc, w, k, m, 8, p.rc, p.rmax,
-                                    G, st, c->tune, d_rec_rows));
+    const qfec::PrepIO io{d_rows_in, nullptr, d_rec_rows, d_status, w};
+    QF_HIP(qfec::launch_decode_prep(io, cenc, k, m, 8, p.rc, p.rmax, G, st, c->tune));
     if (k + m > 256) return 0;   // every group is a no-op or status -1
     QF_HIP(qfec::launch_ragged_decode_status(v.bb, d_rows_in, d_rec_rows, d_status, w.nout, k,
                                              p.rmax, G, st));

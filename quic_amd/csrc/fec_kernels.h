@@ -107,6 +107,17 @@ struct DecodeWork {
     int32_t* nout;     // [G]                  number of recovered blocks in this group
 };
 
+// What every decode prep reads and writes (decode_prep.hip).  w.coef is the table its apply
+// kernel reads: the coefficients, or the syn:: / bsyn:: / psyn:: table.
+struct PrepIO {
+    const uint8_t* rows_in;   // [G][k]
+    uint8_t* rows_out;        // [G][k], may alias rows_in; null: recovered-blocks layout, then
+    uint8_t* rec_rows;        // [G][rmax] gets the data row of recovered block j (ascending),
+                              //   255 past the group's erasure count; null in the slot layout
+    int32_t* status;          // [G] or null
+    DecodeWork w;
+};
+
 // Syndrome table (decode prep in syndrome mode, read by gf_dcol's syndrome decode), one per
 // group at coef + g * coef_gstride, k <= 128 and at most 16 parity rows:
 namespace syn {
@@ -189,14 +200,10 @@ hipError_t launch_gf_encode(const uint8_t* data, uint8_t* parity, const uint8_t*
 
 // Decode prep: per group, sort blocks, invert the erasure submatrix in GF(256) and
 // emit the r x k recovery coefficients (syndrome: the syn:: table instead).  cenc is the
-// [m][k] encode matrix (row 0 = ones).
-// rows_out == nullptr: recovered-blocks layout, rec_rows [G][rmax] gets the data row of
-// recovered block j (ascending), 255 past the group's erasure count.
-hipError_t launch_decode_prep(const uint8_t* rows_in, uint8_t* rows_out, int32_t* status,
-                              const uint8_t* cenc, DecodeWork w, int k, int m, int bb,
+// [m][k] encode matrix (row 0 = ones).  All preps live in decode_prep.hip.
+hipError_t launch_decode_prep(const PrepIO& io, const uint8_t* cenc, int k, int m, int bb,
                               int rc, int rmax, long long groups, hipStream_t st,
-                              const Tune& t, uint8_t* rec_rows = nullptr,
-                              bool syndrome = false);
+                              const Tune& t, bool syndrome = false);
 
 // Decode apply: recovered block j of group g = sum_pos coef[g][..][pos][j] (x) blocks[g][pos],
 // written to out[g][slots[g][j]].
@@ -243,25 +250,21 @@ hipError_t launch_gf_dcol_syndrome(const uint8_t* in, uint8_t* out, const uint8_
                                    int rmax, long long tab_gstride, long long out_gstride,
                                    hipStream_t st, const Tune& t);
 
-// Syndrome decode of the compiled (32, 4) x 1352-byte code (gf_bsyn.hip): prep (bsyn::
-// table, one lane per group) and the block pass + r x r solve.
+// Syndrome decode of the compiled (32, 4) x 1352-byte code: prep (bsyn:: table, one lane per
+// group; reads the row tags as dwords) and the block pass + r x r solve (gf_bsyn.hip).
 bool gf_bsyn_supported(int k, int m, int bb, int rmax, const Tune& t);
-hipError_t launch_decode_prep_bsyn(const uint8_t* rows_in, uint8_t* rows_out, int32_t* status,
-                                   const uint8_t* cenc, uint8_t* tab, uint8_t* slots,
-                                   int32_t* nout, uint8_t* rec_rows, int k, int m, int bb,
+hipError_t launch_decode_prep_bsyn(const PrepIO& io, const uint8_t* cenc, int k, int m, int bb,
                                    int rmax, long long groups, hipStream_t st);
 hipError_t launch_gf_bsyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
                           const uint8_t* cenc, const uint8_t* slots, const int32_t* nout, int k,
                           int m, int bb, long long groups, int rmax, long long out_gstride,
                           hipStream_t st, const Tune& t);
 
-// Syndrome decode of the compiled QuicR preset codes with m >= 7 and (5, 5) at 1352-byte blocks
-// (gf_psyn.hip): prep (psyn:: table, 16 lanes per group) and the block pass + in-place
-// Gauss-Jordan replay.
+// Syndrome decode of the compiled QuicR preset codes with m >= 7 and (5, 5) at 1352-byte
+// blocks: prep (psyn:: table, 16 lanes per group) and the block pass + in-place Gauss-Jordan
+// replay (gf_psyn.hip).
 bool gf_psyn_supported(int k, int m, int bb, int rmax, const Tune& t);
-hipError_t launch_decode_prep_psyn(const uint8_t* rows_in, uint8_t* rows_out, int32_t* status,
-                                   const uint8_t* cenc, uint8_t* tab, uint8_t* slots,
-                                   int32_t* nout, uint8_t* rec_rows, int k, int m, int bb,
+hipError_t launch_decode_prep_psyn(const PrepIO& io, const uint8_t* cenc, int k, int m, int bb,
                                    int rmax, long long groups, hipStream_t st);
 hipError_t launch_gf_psyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
                           const uint8_t* cenc, const uint8_t* slots, const int32_t* nout, int k,

@@ -14,9 +14,8 @@
 //   gf_apply<RC>              bit-sliced GF(256) matrix x blocks, RC outputs per wave;
 //                             used for encode (Cauchy rows, :1502-1601) and for decode
 //                             (per-group recovery rows from the prep kernel)
-//   decode_prep               per-group GF(256) inverse of the erasure submatrix
-//                             (replaces sort_blocks/eliminate_original/bitmatrix GE,
-//                             :543-1252: same unique solution, one pass over the data)
+// The decode preps (per-group GF(256) inverse of the erasure submatrix, replacing
+// sort_blocks/eliminate_original/bitmatrix GE, :543-1252) are in decode_prep.hip.
 //
 // The coefficient of a (output, input) pair is wave-uniform, so it lives in SGPRs and the
 // 8x8 expansion is a scalar branch over its two nibbles; the data lane only ever runs
@@ -30,8 +29,6 @@
 namespace qfec {
 
 typedef uint64_t u64a __attribute__((aligned(8)));
-
-__constant__ GfTables c_gf = make_gf_tables();
 
 // ------------------------------------------------------------------ m = 1 XOR paths
 // Flat mapping: every lane owns one VS-byte unit (g, q) of one group and issues all k of
@@ -343,659 +340,6 @@ __global__ __launch_bounds__(ApplyBound<RC>::T) void gf_apply_kernel(
     }
 }
 
-// ------------------------------------------------------------------- decode prep
-// One wave per group (persistent: each wave walks groups w, w + W, ...; the GF log/exp
-// tables are staged in LDS once per workgroup).  Restates the reference's decode
-// bookkeeping (sort_blocks :543-575, erasure list, recovery row rewrite :791) and replaces
-// its GF(2) bitmatrix elimination by a GF(256) Gauss-Jordan inverse of the r x r erasure
-// submatrix S[i][j] = C[y_i][e_j]: since c -> (8x8 expansion) is a ring homomorphism, the
-// inverse bitmatrix is the expansion of S^-1, and the recovered data is unique.  Output:
-//   recovered e_j = sum_i Sinv[j][i] * R_i + sum_{x present} (sum_i Sinv[j][i] C[y_i][x]) * D_x
-// so one coefficient per (j, input slot) and a single pass over the received blocks.
-// Lanes of one wave exchange data through LDS without barriers: a wave's LDS operations
-// execute in order, so wave_sync() only has to stop the compiler from reordering them.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-}
-
-struct PrepScratch {
-    uint8_t* rowl;      // 256
-    uint8_t* present;   // 256
-    uint8_t* recpos;    // 256: slot of recovery i
-    uint8_t* era;       // 256: erased row j
-    uint8_t* recidx;    // 256: recovery index of slot (255 = original)
-    uint8_t* mat;       // rmax x (2 rmax)
-};
-
-__device__ __forceinline__ void prep_group(
-    long long g, int lane, const uint8_t* gexp, const uint8_t* glog, const PrepScratch& sc,
-    const uint8_t* __restrict__ rows_in, uint8_t* rows_out, int32_t* __restrict__ status,
-    const uint8_t* cenc, uint8_t* __restrict__ coef, uint8_t* __restrict__ slots,
-    int32_t* __restrict__ nout, uint8_t* __restrict__ rec_rows, int k, int m, int bb, int rc,
-    int rmax, int nchunk, bool syndrome) {
-    uint8_t* rowl = sc.rowl;
-    uint8_t* present = sc.present;
-    uint8_t* recpos = sc.recpos;
-    uint8_t* era = sc.era;
-    uint8_t* recidx = sc.recidx;
-    uint8_t* mat = sc.mat;
-    const int rcp = rc < 4 ? 4 : rc;
-    for (int i = lane; i < 256; i += 64) {
-        present[i] = 0;
-        recidx[i] = 255;
-    }
-    const uint8_t* rg = rows_in + g * k;
-    uint8_t* ro = rows_out ? rows_out + g * k : nullptr;   // null: recovered-blocks layout
-    uint8_t* rec = rec_rows ? rec_rows + g * rmax : nullptr;
-    for (int i = lane; i < k; i += 64) rowl[i] = rg[i];
-    wave_sync();
-    // present[x] != 0: data row x received; syndrome mode keeps one of its slots + 1
-    for (int i = lane; i < k; i += 64)
-        if (rowl[i] < k) present[rowl[i]] = syndrome ? (uint8_t)(i + 1) : 1;
-    wave_sync();
-    // recovery blocks in array order (sort_blocks)
-    int nrec = 0;
-    for (int base = 0; base < k; base += 64) {
-        const int i = base + lane;
-        const bool isrec = i < k && rowl[i] >= k;
-        const unsigned long long msk = __ballot(isrec);
-        const int pre = __popcll(msk & ((1ull << lane) - 1));
-        if (isrec) {
-            recpos[nrec + pre] = (uint8_t)i;
-            recidx[i] = (uint8_t)(nrec + pre);
-        }
-        nrec += __popcll(msk);
-    }
-    // erasures: the first nrec data rows not present, ascending
-    int nera = 0;
-    for (int base = 0; base < k && nera < nrec; base += 64) {
-        const int x = base + lane;
-        const bool miss = x < k && !present[x];
-        const unsigned long long msk = __ballot(miss);
-        const int pre = __popcll(msk & ((1ull << lane) - 1));
-        if (miss && nera + pre < nrec) era[nera + pre] = (uint8_t)x;
-        nera += __popcll(msk);
-    }
-    wave_sync();
-
-    uint8_t* tb = coef + g * (long long)nchunk * k * rcp;   // syndrome table (syn::)
-    auto finish_unchanged = [&](int st) {
-        if (syndrome) {
-            // a stream of k extras in slot order that feeds no syndrome row: the apply
-            // kernel still reads every group's k blocks
-            for (int i = lane; i < k; i += 64) tb[syn::kPerm + i] = (uint8_t)i;
-            if (lane < 5) ((uint32_t*)(tb + syn::kMask))[lane] = 0;   // mask and need
-            // gf_dcol: every row position a zero block, no extras
-            for (int x = lane; x < 128; x += 64) tb[syn::kRowSlot + x] = 255;
-            if (lane == 0) *(uint32_t*)(tb + syn::kNExt) = 0;
-        }
-        if (ro && ro != rg)
-            for (int i = lane; i < k; i += 64) ro[i] = rowl[i];
-        if (rec)
-            for (int j = lane; j < rmax; j += 64) rec[j] = 255;
-        if (lane == 0) {
-            nout[g] = 0;
-            if (status) status[g] = st;
-        }
-    };
-    if (nrec == 0) { finish_unchanged(0); return; }                       // :1287-1289
-    if (k + m > 256 || (bb & 7)) { finish_unchanged(-1); return; }        // :1292-1294
-    if (nrec > rmax || nera < nrec) { finish_unchanged(-3); return; }     // malformed rows
-    const int n = nrec;
-    const int n2 = 2 * n;
-    bool bad = false;
-    for (int i = 0; i < n; ++i)
-        if (rowl[recpos[i]] - k >= m) bad = true;                          // row >= k + m
-    if (bad) { finish_unchanged(-3); return; }
-
-    // [S | I]
-    for (int idx = lane; idx < n * n2; idx += 64) {
-        const int i = idx / n2, j = idx % n2;
-        uint8_t v;
-        if (j < n) v = cenc[(rowl[recpos[i]] - k) * k + era[j]];
-        else v = (j - n == i) ? 1 : 0;
-        mat[i * n2 + j] = v;
-    }
-    wave_sync();
-    auto mul = [&](uint8_t a, uint8_t b) -> uint8_t {
-        return (a && b) ? gexp[glog[a] + glog[b]] : 0;
-    };
-    for (int p = 0; p < n; ++p) {
-        int piv = -1;
-        for (int base = p; base < n && piv < 0; base += 64) {
-            const int i = base + lane;
-            const unsigned long long msk = __ballot(i < n && mat[i * n2 + p] != 0);
-            if (msk) piv = base + __ffsll((long long)msk) - 1;
-        }
-        if (piv < 0) { finish_unchanged(-3); return; }                     // singular
-        if (piv != p) {
-            for (int j = lane; j < n2; j += 64) {
-                const uint8_t t = mat[p * n2 + j];
-                mat[p * n2 + j] = mat[piv * n2 + j];
-                mat[piv * n2 + j] = t;
-            }
-            wave_sync();
-        }
-        const uint8_t inv = gexp[255 - glog[mat[p * n2 + p]]];
-        wave_sync();
-        for (int j = lane; j < n2; j += 64) mat[p * n2 + j] = mul(mat[p * n2 + j], inv);
-        wave_sync();
-        for (int i = 0; i < n; ++i) {
-            if (i == p) continue;
-            const uint8_t f = mat[i * n2 + p];
-            wave_sync();
-            if (f)
-                for (int j = lane; j < n2; j += 64) mat[i * n2 + j] ^= mul(f, mat[p * n2 + j]);
-            wave_sync();
-        }
-    }
-
-    if (syndrome) {
-        // recovered e_j = sum_i Sinv[j][i] T_i with the syndromes
-        // T_i = R_i ^ sum_{data slots} C[y_i][row] D_slot (cauchy_256.cpp:1269-1420: the
-        // originals are eliminated from the recovery rows, then the r x r system is solved)
-        int np = 0;
-        for (int base = 0; base < 128; base += 64) {   // present rows ascending, k <= 128
-            const int x = base + lane;
-            const bool pres = x < k && present[x] != 0;
-            const unsigned long long msk = __ballot(pres);
-            const int pre = __popcll(msk & ((1ull << lane) - 1));
-            if (pres) tb[syn::kPerm + np + pre] = (uint8_t)(present[x] - 1);
-            if (lane < 2)
-                ((uint32_t*)(tb + syn::kMask))[base / 32 + lane] = (uint32_t)(msk >> (32 * lane));
-            np += __popcll(msk);
-        }
-        int ne = 0;
-        for (int base = 0; base < k; base += 64) {    // extras in slot order
-            const int i = base + lane;
-            const bool ext = i < k && (rowl[i] >= k || present[rowl[i]] != i + 1);
-            const unsigned long long msk = __ballot(ext);
-            const int pre = __popcll(msk & ((1ull << lane) - 1));
-            if (ext) {
-                tb[syn::kPerm + np + ne + pre] = (uint8_t)i;
-                tb[syn::kERow + ne + pre] = rowl[i];
-            }
-            ne += __popcll(msk);
-        }
-        // gf_dcol: the slot of each data row (255: erased), the parity row of each syndrome,
-        // the count of extras
-        for (int x = lane; x < 128; x += 64)
-            tb[syn::kRowSlot + x] = x < k && present[x] ? (uint8_t)(present[x] - 1) : (uint8_t)255;
-        if (lane < n) tb[syn::kYmap + lane] = (uint8_t)(rowl[recpos[lane]] - k);
-        if (lane == 0) *(uint32_t*)(tb + syn::kNExt) = (uint32_t)ne;
-        uint32_t need = 0;
-        for (int i = 0; i < n; ++i) need |= 1u << (rowl[recpos[i]] - k);
-        if (lane < n) tb[syn::kISlot + rowl[recpos[lane]] - k] = (uint8_t)lane;
-        if (lane == 0) *(uint32_t*)(tb + syn::kNeed) = need;
-        for (int idx = lane; idx < n * n; idx += 64) {
-            const int j = idx / n, i = idx % n;
-            tb[syn::kSinv + j * 16 + i] = mat[j * n2 + n + i];
-        }
-    }
-    // recovery coefficients per (output j, input slot pos)
-    for (int pos = lane; pos < k && !syndrome; pos += 64) {
-        const int ri = recidx[pos];
-        for (int j = 0; j < n; ++j) {
-            const uint8_t* inv_row = mat + j * n2 + n;   // Sinv[j][*]
-            uint8_t cval;
-            if (ri != 255) {
-                cval = inv_row[ri];
-            } else {
-                const int x = rowl[pos];
-                cval = 0;
-                for (int i = 0; i < n; ++i)
-                    cval ^= mul(inv_row[i], cenc[(rowl[recpos[i]] - k) * k + x]);
-            }
-            const int ch = j / rc, jj = j % rc;
-            coef[g * (long long)nchunk * k * rcp + ((long long)ch * k + pos) * rcp + jj] = cval;
-        }
-    }
-    if (ro && ro != rg)
-        for (int i = lane; i < k; i += 64) ro[i] = rowl[i];
-    wave_sync();
-    for (int j = lane; j < n; j += 64) {
-        slots[g * rmax + j] = recpos[j];
-        if (ro) ro[recpos[j]] = era[j];                                    // :791
-    }
-    if (rec)
-        for (int j = lane; j < rmax; j += 64) rec[j] = j < n ? era[j] : 255;
-    if (lane == 0) {
-        nout[g] = n;
-        if (status) status[g] = 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void decode_prep_kernel(
-    const uint8_t* __restrict__ rows_in, uint8_t* rows_out, int32_t* __restrict__ status,
-    const uint8_t* __restrict__ cenc, uint8_t* __restrict__ coef, uint8_t* __restrict__ slots,
-    int32_t* __restrict__ nout, uint8_t* __restrict__ rec_rows, long long groups, int k, int m,
-    int bb, int rc, int rmax, int nchunk, int scratch_bytes, int syndrome) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t* gexp = smem;              // 512
-    uint8_t* glog = gexp + 512;        // 256
-    uint8_t* lcenc = glog + 256;       // m x k encode matrix (the inner loops read it at random)
-    const int cbytes = (m * k + 15) & ~15;
-    for (int i = threadIdx.x; i < 512; i += blockDim.x) gexp[i] = c_gf.exp[i];
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) glog[i] = c_gf.log[i];
-    for (int i = threadIdx.x; i < m * k; i += blockDim.x) lcenc[i] = cenc[i];
-    __syncthreads();
-    const int nwv = blockDim.x >> 6;
-    const int w = wave_id(), lane = threadIdx.x & 63;
-    uint8_t* base = lcenc + cbytes + (size_t)w * scratch_bytes;
-    PrepScratch sc{base, base + 256, base + 512, base + 768, base + 1024, base + 1280};
-    for (long long g = (long long)blockIdx.x * nwv + w; g < groups;
-         g += (long long)gridDim.x * nwv)
-        prep_group(g, lane, gexp, glog, sc, rows_in, rows_out, status, lcenc, coef, slots, nout,
-                   rec_rows, k, m, bb, rc, rmax, nchunk, syndrome != 0);
-}
-
-// Decode prep with SIXTEEN lanes per group for small groups with up to 16 erasures (k <= 64:
-// the QuicR presets (5, 5) .. (15, 15) at 1350-byte payloads).  Same bookkeeping, status
-// codes and outputs as prep_group (cauchy_256.cpp:543-575, :791, :1287-1294).  The 16 lanes
-// split the slots (bookkeeping by ballots), then the columns of [S | I] (lane l owns columns
-// l and l + 16 of the group's n x 2n matrix in LDS) for the Gauss-Jordan inverse, then the
-// slots again for the per-slot coefficients.  A wave holds four groups and the lanes of a
-// group exchange data through LDS in program order (one wave: no barrier).  prep_group runs
-// one group per wave through a chain of wave-wide LDS round trips: 270 us for 65,536
-// (10, 10) groups with 5 losses.
-constexpr int kWideLanes = 16;
-__global__ __launch_bounds__(256) void decode_prep_wide_kernel(
-    const uint8_t* __restrict__ rows_in, uint8_t* rows_out, int32_t* __restrict__ status,
-    const uint8_t* __restrict__ cenc, uint8_t* __restrict__ coef, uint8_t* __restrict__ slots,
-    int32_t* __restrict__ nout, uint8_t* __restrict__ rec_rows, long long groups, int k, int m,
-    int bb, int rc, int rmax, int nchunk) {
-    __shared__ uint8_t gexp[512];
-    __shared__ uint8_t glog[256];
-    constexpr int GPB = 256 / kWideLanes;                       // groups per block
-    __shared__ uint8_t lrows[GPB][64];
-    __shared__ uint8_t lmat[GPB][16][32];                       // [S | I], row-major
-    __shared__ uint8_t llist[GPB][3][16];                       // recpos, y, era
-    extern __shared__ __attribute__((aligned(16))) uint8_t lcenc[];   // m x k
-    for (int i = threadIdx.x; i < 512; i += blockDim.x) gexp[i] = c_gf.exp[i];
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) glog[i] = c_gf.log[i];
-    for (int i = threadIdx.x; i < m * k; i += blockDim.x) lcenc[i] = cenc[i];
-    const long long gfirst = (long long)blockIdx.x * GPB;
-    const int ng = (int)min((long long)GPB, groups - gfirst);
-    for (int i = threadIdx.x; i < ng * k; i += blockDim.x)
-        lrows[i / k][i % k] = rows_in[gfirst * k + i];
-    __syncthreads();
-    const int gl = threadIdx.x / kWideLanes, l = threadIdx.x % kWideLanes;
-    const int seg = (threadIdx.x & 63) / kWideLanes;            // the group's 16 lanes in the wave
-    if (gl >= ng) return;                                       // whole groups: no barrier below
-    const long long g = gfirst + gl;
-    const uint8_t* rg = lrows[gl];
-    uint8_t (*M)[32] = lmat[gl];
-    uint8_t* lrec = llist[gl][0];
-    uint8_t* ly = llist[gl][1];
-    uint8_t* lera = llist[gl][2];
-    auto mul = [&](int a, int b) -> int { return (a && b) ? gexp[glog[a] + glog[b]] : 0; };
-
-    // ---- bookkeeping: slot i = 16 q + l.  isrec: bit i = slot i holds a recovery block;
-    // present: bit r = data row r was received (OR over the group's lanes)
-    uint64_t isrec = 0, present = 0;
-    bool badrow = false;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int i = kWideLanes * q + l;
-        const int r = i < k ? rg[i] : 0;
-        const bool rec = i < k && r >= k;
-        if (i < k && r < k) present |= 1ull << r;
-        const uint64_t b = __ballot(rec);
-        isrec |= ((b >> (kWideLanes * seg)) & 0xFFFFull) << (kWideLanes * q);
-    }
-#pragma unroll
-    for (int o = 1; o < kWideLanes; o <<= 1) present |= __shfl_xor(present, o, kWideLanes);
-    const int nrec = __popcll(isrec);
-    const uint64_t kmask = k == 64 ? ~0ull : ((1ull << k) - 1);
-    const uint64_t missing = ~present & kmask;
-    const int nera = __popcll(missing);
-    // entry l of the lists: the l-th recovery slot, its parity row, the l-th erased row
-    int myrec = -1, myera = -1;
-    {
-        uint64_t a = isrec, e = missing;
-        for (int j = 0; j < l && a; ++j) a &= a - 1;
-        for (int j = 0; j < l && e; ++j) e &= e - 1;
-        if (a) myrec = __ffsll((long long)a) - 1;
-        if (e) myera = __ffsll((long long)e) - 1;
-    }
-    const int myy = myrec >= 0 ? rg[myrec] - k : 0;
-    if (l < nrec && l < 16) badrow = myy >= m;
-    const bool anybad = (__ballot(badrow) >> (kWideLanes * seg)) & 0xFFFFull;
-    uint8_t* ro = rows_out ? rows_out + g * k : nullptr;        // null: recovered-blocks layout
-    const uint8_t* rgg = rows_in + g * k;
-    uint8_t* rec = rec_rows ? rec_rows + g * rmax : nullptr;
-    auto finish_unchanged = [&](int st) {
-        if (ro && ro != rgg)
-            for (int i = l; i < k; i += kWideLanes) ro[i] = rg[i];
-        if (rec)
-            for (int j = l; j < rmax; j += kWideLanes) rec[j] = 255;
-        if (l == 0) {
-            nout[g] = 0;
-            if (status) status[g] = st;
-        }
-    };
-    if (nrec == 0) { finish_unchanged(0); return; }                       // :1287-1289
-    if (k + m > 256 || (bb & 7)) { finish_unchanged(-1); return; }        // :1292-1294
-    if (nrec > rmax || nera < nrec || anybad) { finish_unchanged(-3); return; }   // malformed
-    const int n = nrec;                                                   // <= rmax <= 16
-    if (l < n) {
-        lrec[l] = (uint8_t)myrec;
-        ly[l] = (uint8_t)myy;
-        lera[l] = (uint8_t)myera;
-    }
-    wave_sync();
-    // ---- [S | I], S[i][j] = C[y_i][e_j]: lane l fills columns l and l + 16
-    for (int i = 0; i < n; ++i) {
-        const int yi = ly[i];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int c = l + kWideLanes * h;
-            if (c < 2 * n) M[i][c] = c < n ? lcenc[yi * k + lera[c]] : (uint8_t)(c - n == i);
-        }
-    }
-    wave_sync();
-    // ---- Gauss-Jordan (the lanes own columns; rows through LDS)
-    for (int p = 0; p < n; ++p) {
-        int piv = -1;
-        for (int i = p; i < n && piv < 0; ++i)
-            if (M[i][p]) piv = i;                                 // the same for every lane
-        if (piv < 0) { finish_unchanged(-3); return; }             // singular
-        if (piv != p) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int c = l + kWideLanes * h;
-                if (c < 2 * n) {
-                    const uint8_t t = M[p][c];
-                    M[p][c] = M[piv][c];
-                    M[piv][c] = t;
-                }
-            }
-            wave_sync();
-        }
-        const int inv = gexp[255 - glog[M[p][p]]];
-        wave_sync();                                              // every lane read M[p][p]
-        int rowp[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int c = l + kWideLanes * h;
-            rowp[h] = c < 2 * n ? mul(M[p][c], inv) : 0;
-            if (c < 2 * n) M[p][c] = (uint8_t)rowp[h];
-        }
-        for (int i = 0; i < n; ++i) {
-            if (i == p) continue;
-            const int f = M[i][p];                               // before column p changes
-            wave_sync();
-            if (f) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int c = l + kWideLanes * h;
-                    if (c < 2 * n) M[i][c] ^= (uint8_t)mul(f, rowp[h]);
-                }
-            }
-            wave_sync();
-        }
-    }
-    // ---- coefficients per (output j, input slot pos): recovery slot ri: Sinv[j][ri]; data
-    // row x: sum_i Sinv[j][i] C[y_i][x]
-    for (int pos = l; pos < k; pos += kWideLanes) {
-        const bool isr = (isrec >> pos) & 1;
-        const int ri = isr ? __popcll(isrec & ((1ull << pos) - 1)) : -1;
-        const int x = rg[pos];
-        for (int j = 0; j < n; ++j) {
-            int cval;
-            if (isr) {
-                cval = M[j][n + ri];
-            } else {
-                cval = 0;
-                for (int i = 0; i < n; ++i) cval ^= mul(M[j][n + i], lcenc[ly[i] * k + x]);
-            }
-            const int ch = j / rc, jj = j % rc;
-            coef[g * (long long)nchunk * k * (rc < 4 ? 4 : rc) + ((long long)ch * k + pos) *
-                 (rc < 4 ? 4 : rc) + jj] = (uint8_t)cval;
-        }
-    }
-    if (ro && ro != rgg)
-        for (int i = l; i < k; i += kWideLanes) ro[i] = rg[i];
-    wave_sync();
-    if (l < n) {
-        slots[g * rmax + l] = lrec[l];
-        if (ro) ro[lrec[l]] = lera[l];                                     // :791
-    }
-    if (rec)
-        for (int j = l; j < rmax; j += kWideLanes) rec[j] = j < n ? lera[j] : 255;
-    if (l == 0) {
-        nout[g] = n;
-        if (status) status[g] = 0;
-    }
-}
-
-// Decode prep with four LANES per group, for small erasure counts (rmax <= 4, k <= 64: the
-// 1350-byte configs).  Same bookkeeping, status codes and outputs as prep_group above
-// (cauchy_256.cpp:543-575, :791, :1287-1294); the r x r inverse and the per-slot
-// coefficients are computed in registers with the GF(256) log/exp tables in LDS, so a
-// group costs a few hundred independent LDS reads instead of a chain of wave-wide LDS
-// round trips (prep_group: ~90 us for 65,536 (32, 4) groups, most of it latency).
-// Packed small lists: byte j of recpos/recrow/era = entry j (j < 4).
-__global__ __launch_bounds__(256) void decode_prep_lane_kernel(
-    const uint8_t* __restrict__ rows_in, uint8_t* rows_out, int32_t* __restrict__ status,
-    const uint8_t* __restrict__ cenc, uint8_t* __restrict__ coef, uint8_t* __restrict__ slots,
-    int32_t* __restrict__ nout, uint8_t* __restrict__ rec_rows, long long groups, int k, int m,
-    int bb, int rmax) {
-    // LDS: exp/log tables, the m x k encode matrix, the block's row tags [256][k] (loaded
-    // coalesced) and its coefficient dwords [256][k + 1] (stored coalesced at the end)
-    __shared__ uint8_t gexp[512];
-    __shared__ uint8_t glog[256];
-    extern __shared__ __attribute__((aligned(16))) uint8_t lsm[];
-    uint8_t* lcenc = lsm;                                       // m x k (padded to 16)
-    constexpr int LPG = 4;                                      // lanes per group
-    constexpr int GPB = 256 / LPG;                              // groups per block
-    uint8_t* lrows = lsm + ((m * k + 15) & ~15);                // GPB x k
-    uint32_t* lcoef = (uint32_t*)(lrows + GPB * k);             // GPB x (k + 1), k % 4 == 0
-    for (int i = threadIdx.x; i < 512; i += blockDim.x) gexp[i] = c_gf.exp[i];
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) glog[i] = c_gf.log[i];
-    for (int i = threadIdx.x; i < m * k; i += blockDim.x) lcenc[i] = cenc[i];
-    const long long gfirst = (long long)blockIdx.x * GPB;
-    const int ng = (int)min((long long)GPB, groups - gfirst);
-    {
-        const uint32_t* src = (const uint32_t*)(rows_in + gfirst * k);   // 4-byte aligned
-        const int nd = ng * k / 4;
-#pragma unroll 4
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) ((uint32_t*)lrows)[i] = src[i];
-    }
-    __syncthreads();
-    // LPG lanes per group: each runs the bookkeeping and the r x r inverse (cheap) and
-    // computes the coefficients of every LPG-th input slot; lane q == 0 writes the rest
-    const int gl = threadIdx.x / LPG, q = threadIdx.x % LPG;
-    const long long g = gfirst + gl;
-    const bool live = gl < ng;
-    const bool lead = live && q == 0;
-    const uint8_t* rg = lrows + gl * k;                         // this group's tags (LDS)
-    const uint8_t* rgg = rows_in + g * k;
-    uint8_t* ro = rows_out ? rows_out + g * k : nullptr;
-    uint8_t* rec = rec_rows ? rec_rows + g * rmax : nullptr;
-    uint32_t* mycoef = lcoef + gl * (k + 1);
-    // every lane runs the body (dead lanes on a copy of lane 0's tags, no global writes)
-    // so that the block reaches the coalesced coefficient store together
-    if (!live) rg = lrows;
-
-    // tags four at a time (k % 4 == 0, rows 4-byte aligned in LDS)
-    const uint32_t* rg4 = (const uint32_t*)rg;
-    uint64_t present = 0;
-    int nrec = 0;
-    uint32_t recpos = 0, recrow = 0;
-    for (int i4 = 0; i4 < k; i4 += 4) {
-        const uint32_t t4 = rg4[i4 >> 2];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = i4 + u;
-            const int r = (int)((t4 >> (8 * u)) & 0xFF);
-            if (r < k) {
-                present |= 1ull << r;
-            } else {
-                if (nrec < 4) {
-                    recpos |= (uint32_t)i << (8 * nrec);
-                    recrow |= (uint32_t)(r - k < 255 ? r - k : 255) << (8 * nrec);
-                }
-                ++nrec;
-            }
-        }
-    }
-    const uint64_t kmask = k == 64 ? ~0ull : ((1ull << k) - 1);
-    uint64_t missing = ~present & kmask;
-    const int nera = __popcll(missing);
-
-    // a group left unchanged writes no coefficients (nout = 0: the apply skips it)
-    auto finish_unchanged = [&](int st) {
-        if (!lead) return;
-        if (ro && ro != rgg)
-            for (int i = 0; i < k; ++i) ro[i] = rg[i];
-        if (rec)
-            for (int j = 0; j < rmax; ++j) rec[j] = 255;
-        nout[g] = 0;
-        if (status) status[g] = st;
-    };
-    int early = 1;   // status of a group that needs no coefficients; 1 = go on
-    if (nrec == 0) early = 0;                                               // :1287-1289
-    else if (k + m > 256 || (bb & 7)) early = -1;                           // :1292-1294
-    else if (nrec > rmax || nera < nrec) early = -3;                        // malformed rows
-    else
-        for (int i = 0; i < nrec; ++i)
-            if ((int)((recrow >> (8 * i)) & 0xFF) >= m) early = -3;         // row >= k + m
-    const int n = early == 1 ? nrec : 0;
-    uint32_t era = 0;
-    for (int j = 0; j < n; ++j) {
-        const int e = __ffsll((long long)missing) - 1;
-        missing &= missing - 1;
-        era |= (uint32_t)e << (8 * j);
-    }
-    auto B = [](uint32_t v, int j) -> int { return (int)((v >> (8 * j)) & 0xFF); };
-    auto mul = [&](int a, int b) -> int { return (a && b) ? gexp[glog[a] + glog[b]] : 0; };
-
-    // [S | I], S[i][j] = C[y_i][e_j]; Gauss-Jordan fully unrolled over the 4 x 8 maximum
-    uint8_t M[4][8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            uint8_t v = 0;
-            if (i < n && j < n) v = lcenc[B(recrow, i) * k + B(era, j)];
-            else if (i < n && j >= 4) v = (j - 4 == i) ? 1 : 0;
-            M[i][j] = v;
-        }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        if (p < n) {
-            int piv = -1;
-#pragma unroll
-            for (int i = 3; i >= p; --i)
-                if (i < n && M[i][p] != 0) piv = i;
-            if (piv < 0) {                                                  // singular
-                early = -3;
-                piv = p;
-            }
-#pragma unroll
-            for (int i = p + 1; i < 4; ++i) {
-                if (i == piv) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const uint8_t t = M[p][j];
-                        M[p][j] = M[i][j];
-                        M[i][j] = t;
-                    }
-                }
-            }
-            const int inv = M[p][p] ? gexp[255 - glog[M[p][p]]] : 0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) M[p][j] = (uint8_t)mul(M[p][j], inv);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (i != p && i < n) {
-                    const int f = M[i][p];
-                    if (f) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) M[i][j] ^= (uint8_t)mul(f, M[p][j]);
-                    }
-                }
-            }
-        }
-    }
-    // log of S^-1 (256 = zero)
-    int lsi[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int v = (j < n && i < n) ? M[j][4 + i] : 0;
-            lsi[j][i] = v ? glog[v] : 256;
-        }
-    // coefficient dword per input slot: byte j = recovered row j's coefficient
-    for (int pos4 = 4 * q; pos4 < k; pos4 += 4 * LPG) {
-      const uint32_t t4 = rg4[pos4 >> 2];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {   // four independent lookup chains
-        const int pos = pos4 + u;
-        int ri = -1;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            if (i < n && B(recpos, i) == pos) ri = i;
-        uint32_t cw = 0;
-        if (ri >= 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (j < n) {
-                    int v = 0;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (i == ri) v = M[j][4 + i];
-                    cw |= (uint32_t)v << (8 * j);
-                }
-        } else if (n > 0) {
-            const int x = (int)((t4 >> (8 * u)) & 0xFF);
-            int acc[4] = {0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (i < n) {
-                    const int cv = lcenc[B(recrow, i) * k + x];
-                    if (cv) {
-                        const int lc = glog[cv];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            if (j < n && lsi[j][i] != 256) acc[j] ^= gexp[lsi[j][i] + lc];
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) cw |= (uint32_t)acc[j] << (8 * j);
-        }
-        mycoef[pos] = cw;
-      }
-    }
-    if (early != 1) {
-        finish_unchanged(early);
-    } else if (lead) {
-        if (ro && ro != rgg)
-            for (int i = 0; i < k; ++i) ro[i] = rg[i];
-        for (int j = 0; j < n; ++j) {
-            slots[g * rmax + j] = (uint8_t)B(recpos, j);
-            if (ro) ro[B(recpos, j)] = (uint8_t)B(era, j);                // :791
-        }
-        if (rec)
-            for (int j = 0; j < rmax; ++j) rec[j] = j < n ? (uint8_t)B(era, j) : 255;
-        nout[g] = n;
-        if (status) status[g] = 0;
-    }
-    __syncthreads();
-    // coalesced store of the block's coefficient rows [ng][k] dwords
-    uint32_t* cdst = (uint32_t*)(coef + gfirst * (long long)k * 4);
-    const int nd = ng * k;
-#pragma unroll 4
-    for (int d = threadIdx.x; d < nd; d += blockDim.x) {
-        const int gg = d / k;
-        cdst[d] = lcoef[gg * (k + 1) + (d - gg * k)];
-    }
-}
-
 // In-place decode with more recovered blocks than one wave holds: the chunks write to a
 // [G][rmax][bb] scratch, then this copies each recovered block into its slot.
 __global__ __launch_bounds__(256) void scatter_recovered_kernel(
@@ -1220,47 +564,6 @@ hipError_t launch_gf_encode(const uint8_t* data, uint8_t* parity, const uint8_t*
     const int nchunk = (m + rc - 1) / rc;
     return gf_apply_dispatch<false>(data, parity, coef, nullptr, nullptr, k, m, bb, groups, rc,
                                     nchunk, 0, 0, (long long)m * bb, st, t);
-}
-
-hipError_t launch_decode_prep(const uint8_t* rows_in, uint8_t* rows_out, int32_t* status,
-                              const uint8_t* cenc, DecodeWork w, int k, int m, int bb, int rc,
-                              int rmax, long long groups, hipStream_t st, const Tune& t,
-                              uint8_t* rec_rows, bool syndrome) {
-    if (groups <= 0) return hipSuccess;
-    if (syndrome && (k > 128 || m > 16 || (long long)((rmax + rc - 1) / rc) * k * std::max(rc, 4) <
-                                                 syn::kBytes))
-        return hipErrorInvalidValue;
-    if (!syndrome && t.prep_lane && rmax <= 4 && k <= 64 && k % 4 == 0 && (long long)m * k <= 4096 && rc <= 4 &&
-        ((((uintptr_t)w.coef) | (uintptr_t)rows_in) & 3) == 0) {
-        const unsigned nb = (unsigned)((groups + 63) / 64);     // 64 groups x 4 lanes
-        const size_t lds = (((size_t)m * k + 15) & ~(size_t)15) + 64 * (size_t)k +
-                           64 * (size_t)(k + 1) * 4;
-        note_kernel("decode_prep_lane_kernel");
-        qlaunch((decode_prep_lane_kernel), dim3(nb), dim3(256), lds, st, 
-            rows_in, rows_out, status, cenc, w.coef, w.slots, w.nout, rec_rows, groups, k, m, bb,
-            rmax);
-        return hipGetLastError();
-    }
-    const int nchunk = (rmax + rc - 1) / rc;
-    if (!syndrome && t.prep_lane && k <= 64 && rmax <= 16 && (long long)m * k <= 16384) {
-        note_kernel("decode_prep_wide_kernel");
-        qlaunch((decode_prep_wide_kernel), dim3((unsigned)((groups + 15) / 16)), dim3(256),
-                (uint32_t)(((size_t)m * k + 15) & ~(size_t)15), st, rows_in, rows_out, status,
-                cenc, w.coef, w.slots, w.nout, rec_rows, groups, k, m, bb, rc, rmax, nchunk);
-        return hipGetLastError();
-    }
-    const int scratch = (int)((1280 + (size_t)rmax * 2 * rmax + 15) & ~(size_t)15);
-    const size_t fixed = 768 + (((size_t)m * k + 15) & ~(size_t)15);
-    int nwv = 4;
-    while (nwv > 1 && fixed + (size_t)nwv * scratch > 64 * 1024) nwv >>= 1;
-    const size_t lds = fixed + (size_t)nwv * scratch;
-    const long long want = (groups + nwv - 1) / nwv;
-    const unsigned nb = (unsigned)std::min<long long>(want, (long long)t.cus * 16);
-    note_kernel(syndrome ? "decode_prep_kernel<syndrome>" : "decode_prep_kernel");
-    qlaunch((decode_prep_kernel), dim3(nb), dim3(nwv * 64), lds, st, rows_in, rows_out, status, cenc, w.coef,
-                                                   w.slots, w.nout, rec_rows, groups, k, m, bb,
-                                                   rc, rmax, nchunk, scratch, syndrome ? 1 : 0);
-    return hipGetLastError();
 }
 
 hipError_t launch_gf_decode(const uint8_t* blocks, uint8_t* out, DecodeWork w, int k, int m,

@@ -16,8 +16,9 @@
 // that repeats a data row.
 //
 // Stream: every wave owns groups g0, g0 + W, ... (no barriers, no cross-wave traffic) and
-// streams each group's k received blocks in the order the prep's table gives: the present
-// data rows ascending, then the extras (recovery blocks, repeated data rows) in slot order.
+// streams each group's k received blocks in the order the prep's table gives
+// (decode_prep_bsyn_kernel, decode_prep.hip; bsyn:: in fec_kernels.h): the present data
+// rows ascending, then the extras (recovery blocks, repeated data rows) in slot order.
 // A block is read from wherever its slot lies (bb = 1352 is 8 mod 16: the 16-byte aligned
 // envelope of the block is DMA'd, buffer_load_dwordx4 ... lds, and the block is read at the
 // 8-byte skew), into a ring of D + 1 block buffers per wave.  The unrolled loop over the k
@@ -79,8 +80,6 @@ __device__ __forceinline__ void bsyn_wait_stores(int n) {
 }
 
 constexpr unsigned kBDrop = 0x80000000u;   // buffer offset past any range: lane dropped
-
-__constant__ GfTables c_gf_bsyn = make_gf_tables();   // this code object's copy
 
 template <int S>
 struct BsynShape {
@@ -338,181 +337,6 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
     bsyn_wait_vmcnt<0>();
 }
 
-// ------------------------------------------------------------------ prep
-// One lane per group: the bookkeeping of cauchy_256_decode (sort_blocks :543-575, the
-// erased rows ascending, the row rewrite :791, the status codes :1287-1294) and the r x r
-// GF(256) Gauss-Jordan inverse, then the bsyn:: table.  k <= 64, rmax <= 4.
-__global__ __launch_bounds__(256) void decode_prep_bsyn_kernel(
-    const uint8_t* __restrict__ rows_in, uint8_t* rows_out, int32_t* __restrict__ status,
-    const uint8_t* __restrict__ cenc, uint8_t* __restrict__ tab, uint8_t* __restrict__ slots,
-    int32_t* __restrict__ nout, uint8_t* __restrict__ rec_rows, long long groups, int k, int m,
-    int bb, int rmax) {
-    __shared__ uint8_t gexp[512];
-    __shared__ uint8_t glog[256];
-    extern __shared__ __attribute__((aligned(16))) uint8_t lsm[];
-    uint8_t* lcenc = lsm;                                    // m x k (padded to 16)
-    uint8_t* lrows = lsm + ((m * k + 15) & ~15);             // 256 x k (k % 4 == 0)
-    uint8_t* ltab = lrows + 256 * k;                         // 256 x kBytes
-    for (int i = threadIdx.x; i < 512; i += blockDim.x) gexp[i] = c_gf_bsyn.exp[i];
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) glog[i] = c_gf_bsyn.log[i];
-    for (int i = threadIdx.x; i < m * k; i += blockDim.x) lcenc[i] = cenc[i];
-    const long long gfirst = (long long)blockIdx.x * 256;
-    const int ng = (int)min(256LL, groups - gfirst);
-    {
-        const uint32_t* src = (const uint32_t*)(rows_in + gfirst * k);
-        const int nd = ng * k / 4;
-        for (int i = threadIdx.x; i < nd; i += blockDim.x) ((uint32_t*)lrows)[i] = src[i];
-    }
-    __syncthreads();
-    const int gl = threadIdx.x;
-    const long long g = gfirst + gl;
-    const bool live = gl < ng;
-    const uint8_t* rg = lrows + (live ? gl : 0) * k;
-    uint8_t* T = ltab + gl * bsyn::kBytes;
-    auto B = [](uint32_t v, int j) -> int { return (int)((v >> (8 * j)) & 0xFF); };
-    auto mul = [&](int a, int b2) -> int { return (a && b2) ? gexp[glog[a] + glog[b2]] : 0; };
-
-    uint64_t present = 0, first = 0;
-    int nrec = 0;
-    uint32_t recpos = 0, recrow = 0;
-    for (int i = 0; i < k; ++i) {
-        const int r = rg[i];
-        if (r < k) {
-            if (!((present >> r) & 1)) {
-                present |= 1ull << r;
-                first |= 1ull << i;
-            }
-        } else {
-            if (nrec < 4) {
-                recpos |= (uint32_t)i << (8 * nrec);
-                recrow |= (uint32_t)(r - k < 255 ? r - k : 255) << (8 * nrec);
-            }
-            ++nrec;
-        }
-    }
-    const uint64_t kmask = k == 64 ? ~0ull : ((1ull << k) - 1);
-    uint64_t missing = ~present & kmask;
-    const int nera = __popcll(missing);
-    int early = 1;
-    if (nrec == 0) early = 0;                                               // :1287-1289
-    else if (k + m > 256 || (bb & 7)) early = -1;                           // :1292-1294
-    else if (nrec > rmax || nera < nrec) early = -3;                        // malformed rows
-    else
-        for (int i = 0; i < nrec; ++i)
-            if (B(recrow, i) >= m) early = -3;                              // row >= k + m
-    int n = early == 1 ? nrec : 0;
-    uint32_t era = 0;
-    for (int j = 0; j < n; ++j) {
-        const int e = __ffsll((long long)missing) - 1;
-        missing &= missing - 1;
-        era |= (uint32_t)e << (8 * j);
-    }
-    // [S | I], S[i][j] = C[y_i][e_j]; Gauss-Jordan unrolled over the 4 x 8 maximum
-    uint8_t M[4][8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            uint8_t v = 0;
-            if (i < n && j < n) v = lcenc[B(recrow, i) * k + B(era, j)];
-            else if (i < n && j >= 4) v = (j - 4 == i) ? 1 : 0;
-            M[i][j] = v;
-        }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        if (p < n) {
-            int piv = -1;
-#pragma unroll
-            for (int i = 3; i >= p; --i)
-                if (i < n && M[i][p] != 0) piv = i;
-            if (piv < 0) {                                                  // singular
-                early = -3;
-                piv = p;
-            }
-#pragma unroll
-            for (int i = p + 1; i < 4; ++i) {
-                if (i == piv) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const uint8_t t = M[p][j];
-                        M[p][j] = M[i][j];
-                        M[i][j] = t;
-                    }
-                }
-            }
-            const int inv = M[p][p] ? gexp[255 - glog[M[p][p]]] : 0;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) M[p][j] = (uint8_t)mul(M[p][j], inv);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (i != p && i < n) {
-                    const int f = M[i][p];
-                    if (f) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) M[i][j] ^= (uint8_t)mul(f, M[p][j]);
-                    }
-                }
-            }
-        }
-    }
-    if (early != 1) n = 0;
-
-    // the table: a changed group streams its present rows ascending, then the extras in slot
-    // order; an unchanged one streams its slots in order as no-op extras (row tag 255)
-    if (n > 0) {
-        int ne = 0;
-        const int np = __popcll(present);
-        for (int i = 0; i < k; ++i) {
-            const int r = rg[i];
-            if ((first >> i) & 1) {
-                T[bsyn::kPerm + __popcll(present & ((1ull << r) - 1))] = (uint8_t)i;
-            } else {
-                T[bsyn::kPerm + np + ne] = (uint8_t)i;
-                T[bsyn::kERow + ne] = (uint8_t)r;
-                ++ne;
-            }
-        }
-        *(uint32_t*)(T + bsyn::kMask) = (uint32_t)present;
-        *(uint32_t*)(T + bsyn::kMask + 4) = (uint32_t)(present >> 32);
-        *(uint32_t*)(T + bsyn::kY) = recrow;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            uint32_t sw = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (j < n && i < n) sw |= (uint32_t)M[j][4 + i] << (8 * i);
-            *(uint32_t*)(T + bsyn::kSinv + 4 * j) = sw;
-        }
-    } else {
-        for (int i = 0; i < k; ++i) {
-            T[bsyn::kPerm + i] = (uint8_t)i;
-            T[bsyn::kERow + i] = 255;
-        }
-        *(uint32_t*)(T + bsyn::kMask) = 0;
-        *(uint32_t*)(T + bsyn::kMask + 4) = 0;
-    }
-    if (live) {
-        const uint8_t* rgg = rows_in + g * k;
-        uint8_t* ro = rows_out ? rows_out + g * k : nullptr;
-        uint8_t* rec = rec_rows ? rec_rows + g * rmax : nullptr;
-        if (ro && ro != rgg)
-            for (int i = 0; i < k; ++i) ro[i] = rg[i];
-        for (int j = 0; j < n; ++j) {
-            slots[g * rmax + j] = (uint8_t)B(recpos, j);
-            if (ro) ro[B(recpos, j)] = (uint8_t)B(era, j);                  // :791
-        }
-        if (rec)
-            for (int j = 0; j < rmax; ++j) rec[j] = j < n ? (uint8_t)B(era, j) : 255;
-        nout[g] = n;
-        if (status) status[g] = early == 1 ? 0 : early;
-    }
-    __syncthreads();
-    // coalesced copy of the block's tables
-    uint32_t* dst = (uint32_t*)(tab + gfirst * (long long)bsyn::kBytes);
-    const int nd = ng * bsyn::kBytes / 4;
-    for (int d = threadIdx.x; d < nd; d += blockDim.x) dst[d] = ((const uint32_t*)ltab)[d];
-}
-
 // ------------------------------------------------------------------ launchers
 namespace {
 constexpr int kBsynS = 169;   // bb = 1352: 1350-byte payloads (BASELINE configs B, C)
@@ -520,23 +344,6 @@ constexpr int kBsynS = 169;   // bb = 1352: 1350-byte payloads (BASELINE configs
 
 bool gf_bsyn_supported(int k, int m, int bb, int rmax, const Tune& t) {
     return t.bsyn && t.const_enc && k == 32 && m == 4 && bb == 8 * kBsynS && rmax <= kBsynRC;
-}
-
-hipError_t launch_decode_prep_bsyn(const uint8_t* rows_in, uint8_t* rows_out, int32_t* status,
-                                   const uint8_t* cenc, uint8_t* tab, uint8_t* slots,
-                                   int32_t* nout, uint8_t* rec_rows, int k, int m, int bb,
-                                   int rmax, long long groups, hipStream_t st) {
-    if (groups <= 0) return hipSuccess;
-    if (k > 64 || k % 4 != 0 || rmax > 4 || (long long)m * k > 4096 ||
-        ((((uintptr_t)tab) | (uintptr_t)rows_in) & 3))
-        return hipErrorInvalidValue;
-    const unsigned nb = (unsigned)((groups + 255) / 256);
-    const size_t lds = (((size_t)m * k + 15) & ~(size_t)15) + 256 * (size_t)k +
-                       256 * (size_t)bsyn::kBytes;
-    note_kernel("decode_prep_bsyn_kernel");
-    qlaunch((decode_prep_bsyn_kernel), dim3(nb), dim3(256), lds, st, rows_in, rows_out, status,
-            cenc, tab, slots, nout, rec_rows, groups, k, m, bb, rmax);
-    return hipGetLastError();
 }
 
 hipError_t launch_gf_bsyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,

@@ -53,22 +53,23 @@ def gpu_encode(engine, k, m, bb, data):
     return host(p), rc
 
 
-def gpu_decode(engine, k, m, bb, blocks, rows, inplace=True):
+def gpu_decode(engine, k, m, bb, blocks, rows, inplace=True, rows_offset=0):
     """Every output between guards; out of place, `out` starts as the fill byte and only
-    slots tagged as recovery blocks may change."""
+    slots tagged as recovery blocks may change.  rows_offset: the row tags (in and out) start
+    that many bytes past a 16-byte boundary."""
     G = blocks.shape[0]
     st, hst = status_buf(G)
     if inplace:
         b, hb = guarded_from(blocks)
-        r, hr = guarded_from(rows)
+        r, hr = guarded_from(rows, rows_offset)
         engine.decode(k, m, bb, b, r, status=st)
         for h in (hb, hr, hst):
             h.check_guards()
         return host(b), host(r), host(st)
     b = dev(blocks)
-    r = dev(rows)
+    r, _ = guarded_from(rows, rows_offset)
     out, ho = guarded(blocks.shape)
-    ro, hro = guarded(rows.shape)
+    ro, hro = guarded(rows.shape, rows_offset)
     engine.decode(k, m, bb, b, r, out=out, rows_out=ro, status=st)
     for h in (ho, hro, hst):
         h.check_guards()
@@ -1117,12 +1118,13 @@ def test_tile_many_groups_per_workgroup(tuned_engine, oracle, grid, k, m, r, opt
     check_decodes(engine, oracle, k, m, bb, recv, rows, dec_kernel)
 
 
-def check_decodes(engine, oracle, k, m, bb, recv, rows, dec_kernel):
+def check_decodes(engine, oracle, k, m, bb, recv, rows, dec_kernel, rows_offset=0):
     """Both in-place layouts and the recovered-blocks layout against the oracle."""
     G = recv.shape[0]
     b_or, r_or, s_or = oracle.decode_batch(k, m, bb, recv, rows)
     for inplace in (True, False):
-        b, rr, s = gpu_decode(engine, k, m, bb, recv, rows, inplace=inplace)
+        b, rr, s = gpu_decode(engine, k, m, bb, recv, rows, inplace=inplace,
+                              rows_offset=rows_offset)
         assert dec_kernel in fec.last_kernels()
         np.testing.assert_array_equal(s, s_or)
         np.testing.assert_array_equal(rr, r_or)
@@ -1132,7 +1134,8 @@ def check_decodes(engine, oracle, k, m, bb, recv, rows, dec_kernel):
     rec, hrec = guarded((G, rmax, bb))
     rec_rows, hrr = guarded((G, rmax))
     st, hst = status_buf(G)
-    engine.decode_recovered(k, m, bb, dev(recv), dev(rows), rec, rec_rows, status=st)
+    engine.decode_recovered(k, m, bb, dev(recv), guarded_from(rows, rows_offset)[0], rec,
+                            rec_rows, status=st)
     assert dec_kernel in fec.last_kernels()
     for h in (hrec, hrr, hst):
         h.check_guards()
