@@ -1001,6 +1001,7 @@ hipError_t launch_decode_prep(const PrepIO& io, const uint8_t* cenc, int k, int 
     const long long want = (groups + nwv - 1) / nwv;
     const unsigned nb = (unsigned)std::min<long long>(want, (long long)t.cus * 16);
     note_kernel(syndrome ? "decode_prep_kernel<syndrome>" : "decode_prep_kernel");
+    note_grid("decode_prep_kernel", nb);
     qlaunch((decode_prep_kernel), dim3(nb), dim3(nwv * 64), lds, st, io.rows_in, io.rows_out,
             io.status, cenc, w.coef, w.slots, w.nout, io.rec_rows, groups, k, m, bb, rc, rmax,
             nchunk, scratch, syndrome ? 1 : 0);

@@ -77,6 +77,23 @@ def test_cauchy_matrix_matches_oracle(oracle, k, m):
     np.testing.assert_array_equal(fec.cauchy_matrix(k, m), oracle.cauchy_matrix(k, m))
 
 
+def test_cauchy_matrix_matches_oracle_every_m(oracle):
+    """Each m >= 7 has its own X vector in the table blob, so every m = 2..255 is compared at
+    its full row length k = 256 - m and at k = 1 (the column that reads no X entry)."""
+    for m in range(2, 256):
+        for k in (256 - m, 1):
+            np.testing.assert_array_equal(fec.cauchy_matrix(k, m), oracle.cauchy_matrix(k, m),
+                                          err_msg=f"k={k} m={m}")
+
+
+@pytest.mark.parametrize("m", [2, 6, 7, 9, 13, 17, 100, 128, 200])
+def test_cauchy_matrix_smaller_k_is_a_column_prefix(m):
+    full = fec.cauchy_matrix(256 - m, m)
+    assert full.shape == (m - 1, 256 - m)
+    for k in sorted({1, 2, 5, (256 - m) // 2, 255 - m} & set(range(1, 257 - m))):
+        np.testing.assert_array_equal(fec.cauchy_matrix(k, m), full[:, :k], err_msg=f"k={k}")
+
+
 def test_cauchy_matrix_rejects_bad_params():
     with pytest.raises(ValueError):
         fec.cauchy_matrix(250, 7)
