@@ -102,12 +102,12 @@ WJGEN := $(ROOT)build/gen/win_jump.h
 $(WJGEN): $(ROOT)tools/gen_win_jump.py
 	python3 $(ROOT)tools/gen_win_jump.py && touch $@
 
-$(ROOT)build/gf_stream.o: $(CSRC)/gf_stream.hip $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
+$(ROOT)build/gf_stream.o: $(CSRC)/gf_stream.hip $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
 
-$(ROOT)build/gf_bsyn.o: $(CSRC)/gf_bsyn.hip $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
+$(ROOT)build/gf_bsyn.o: $(CSRC)/gf_bsyn.hip $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
@@ -116,22 +116,22 @@ $(ROOT)build/gf_bsyn.o: $(CSRC)/gf_bsyn.hip $(CSRC)/gf_winjump.h $(HDRS) $(GEN) 
 # the branches' identical loads into one load with a computed index, which leaves the
 # arrays in scratch memory (VMEM outside the counted waits)
 PSYNFLAGS := -mllvm -simplifycfg-sink-common=false
-$(ROOT)build/gf_psyn.o: $(CSRC)/gf_psyn.hip $(CSRC)/gf_psyn.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
+$(ROOT)build/gf_psyn.o: $(CSRC)/gf_psyn.hip $(CSRC)/gf_psyn.h $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) $(PSYNFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
 
-$(ROOT)build/gf_psyn_%.o: $(CSRC)/gf_psyn_%.hip $(CSRC)/gf_psyn.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
+$(ROOT)build/gf_psyn_%.o: $(CSRC)/gf_psyn_%.hip $(CSRC)/gf_psyn.h $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) $(PSYNFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
 
-$(ROOT)build/gf_dcol.o: $(CSRC)/gf_dcol.hip $(CSRC)/gf_dcol.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
+$(ROOT)build/gf_dcol.o: $(CSRC)/gf_dcol.hip $(CSRC)/gf_dcol.h $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
 
-$(ROOT)build/gf_dcol_%.o: $(CSRC)/gf_dcol_%.hip $(CSRC)/gf_dcol.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
+$(ROOT)build/gf_dcol_%.o: $(CSRC)/gf_dcol_%.hip $(CSRC)/gf_dcol.h $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }

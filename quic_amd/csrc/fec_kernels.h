@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 namespace qfec {
 
 // Per-context launch configuration.  The defaults are the measured best shapes
@@ -68,6 +70,23 @@ void note_grid(const char* name, unsigned grid);
 // Workgroups of `kern` one CU holds at once (the runtime's occupancy answer), cached per
 // (kernel, threads, LDS bytes); thread-safe.
 int resident_blocks(const void* kern, int threads, size_t lds);
+
+// Grid of a persistent kernel whose waves each walk units u0, u0 + W, ... (W = waves in the
+// grid): enough workgroups of `waves` waves for one unit per wave, capped at `resident` (the
+// workgroups the device holds at once), or, oversubscribed (wg > 0), at about wg units per wave;
+// grid_cap > 0 (stream_grid / dcol_grid: tests) overrides both caps.  0 = invalid: a wave's
+// units times per_unit (what its 32-bit counters count per unit) must stay below 2^31.
+inline unsigned persistent_grid(long long units, int waves, long long resident, int wg,
+                                int grid_cap, long long per_unit = 1) {
+    const long long want = (units + waves - 1) / waves;
+    long long cap = resident;
+    if (wg > 0) cap = (units + (long long)waves * wg - 1) / ((long long)waves * wg);
+    if (grid_cap > 0) cap = grid_cap;
+    const unsigned grid = (unsigned)std::min<long long>(want, cap);
+    const long long total = (long long)grid * waves;
+    if (grid == 0 || (units + total - 1) / total * per_unit >= (1LL << 31)) return 0;
+    return grid;
+}
 
 // Kernel timing hook (qfec_set_timing_events, per thread).  While a stop event is set, each
 // engine call records `start` at the start of its first kernel and `stop` at the end of

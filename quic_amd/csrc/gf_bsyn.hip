@@ -25,7 +25,7 @@
 // data rows consumes the next streamed block only where row x is present (a uniform branch
 // per row), so every coefficient stays a compile-time constant.
 //
-// vmcnt bookkeeping as in gf_tile.hip: a block is NPC DMA instructions; a group's stores
+// vmcnt bookkeeping (primitives in gf_counted.h): a block is NPC DMA instructions; a group's stores
 // (8 * SPR per recovered block) sit in the count before the waits for the next group's
 // blocks 1 .. D - 1.  tests/test_isa.py checks the compiler adds no VMEM instruction or
 // vmcnt wait of its own.
@@ -33,32 +33,10 @@
 #include "fec_kernels.h"
 #include "gf256.h"
 #include "gf_bitslice.h"
+#include "gf_counted.h"
 #include "gf_winjump.h"
 
 namespace qfec {
-
-#define QB_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int N>
-__device__ __forceinline__ void bsyn_wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt is 6 bits on gfx9");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// 16 bytes per lane from buffer rs at voff + soff into LDS at lds + 16 * lane (nt).  The
-// builtin is device-only: in a lambda the host pass would drop the kernel's host stub.
-__device__ __forceinline__ void bsyn_dma16(__amdgpu_buffer_rsrc_t rs, uint8_t* lds,
-                                           uint32_t voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, QB_LPTR(lds), 16, voff, soff, 0, 2);
-#else
-    (void)rs, (void)lds, (void)voff, (void)soff;
-#endif
-}
-
-__device__ __forceinline__ uint32_t bsyn_cload_u32(const uint8_t* base, int byte_off) {
-    return ((const __attribute__((address_space(4))) uint32_t*)(base))[byte_off >> 2];
-}
 
 // s_waitcnt vmcnt(BASE + 8 * SPR * n) for a wave-uniform n in [0, 4] (the stores of a group
 // with n recovered blocks), capped at 63
@@ -69,27 +47,15 @@ __device__ __forceinline__ void bsyn_wait_stores(int n) {
     constexpr int W3 = BASE + 3 * PER > 63 ? 63 : BASE + 3 * PER;
     constexpr int W4 = BASE + 4 * PER > 63 ? 63 : BASE + 4 * PER;
     if (n <= 1) {
-        if (n <= 0) bsyn_wait_vmcnt<W0>();
-        else bsyn_wait_vmcnt<W1>();
+        if (n <= 0) wait_vmcnt<W0>();
+        else wait_vmcnt<W1>();
     } else if (n <= 2) {
-        bsyn_wait_vmcnt<W2>();
+        wait_vmcnt<W2>();
     } else {
-        if (n == 3) bsyn_wait_vmcnt<W3>();
-        else bsyn_wait_vmcnt<W4>();
+        if (n == 3) wait_vmcnt<W3>();
+        else wait_vmcnt<W4>();
     }
 }
-
-constexpr unsigned kBDrop = 0x80000000u;   // buffer offset past any range: lane dropped
-
-template <int S>
-struct BsynShape {
-    static constexpr int BB = 8 * S;
-    static constexpr int NW = (S + 3) / 4, NWF = S / 4;
-    static constexpr int SPR = 1 + ((S >> 1) & 1) + (S & 1);   // stores per sub-row
-    static constexpr int BUFB = (BB + 8 + 15) / 16 * 16;        // the 16-byte envelope
-    static constexpr int NPC = BUFB > 1024 ? 2 : 1;              // DMA instructions per block
-    static constexpr int P1L = BUFB > 1024 ? (BUFB - 1024) / 16 : 0;   // lanes of the 2nd
-};
 
 constexpr int kBsynWaves = 4;   // waves per workgroup (independent)
 constexpr int kBsynRC = 4;      // recovered blocks per group (rmax <= 4)
@@ -101,8 +67,8 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
     const uint8_t* in, uint8_t* out, const uint8_t* __restrict__ tab,
     const uint8_t* __restrict__ cenc, const uint8_t* __restrict__ slots,
     const int32_t* __restrict__ nout, long long groups, int rmax, long long out_gstride) {
-    using SH = BsynShape<S>;
-    constexpr int BB = SH::BB, NW = SH::NW, NWF = SH::NWF, SPR = SH::SPR;
+    using SH = SubrowShape<S>;
+    constexpr int BB = SH::BB, NW = SH::NW, SPR = SH::SPR;
     constexpr int BUFB = SH::BUFB, NPC = SH::NPC, P1L = SH::P1L;
     constexpr int NB = D + 1;                 // the block being read + D in flight
     constexpr int RC = kBsynRC;
@@ -133,15 +99,15 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
     const long long tstride = W * (long long)bsyn::kBytes;
     uint32_t perm_w = 0, skew = 0;
     auto issue_next = [&]() __attribute__((always_inline)) {
-        if ((iss_x & 3) == 0) perm_w = bsyn_cload_u32(iss_t, bsyn::kPerm + iss_x);
+        if ((iss_x & 3) == 0) perm_w = cload_u32(iss_t, bsyn::kPerm + iss_x);
         const int slot = min((int)((perm_w >> (8 * (iss_x & 3))) & 0xFFu), KC - 1);
         const int off = slot * BB;
         const __amdgpu_buffer_rsrc_t rs =
             __builtin_amdgcn_make_buffer_rsrc((void*)iss_g, 0, 0x7FFFFFFF, 0x00020000);
         uint8_t* dst = ring + iss_buf * BUFB;
-        bsyn_dma16(rs, dst, 16u * (uint32_t)lane, off & ~15);
+        dma16(rs, dst, 16u * (uint32_t)lane, off & ~15);
         if constexpr (NPC == 2)
-            if (lane < P1L) bsyn_dma16(rs, dst + 1024, 1024u + 16u * (uint32_t)lane, off & ~15);
+            if (lane < P1L) dma16(rs, dst + 1024, 1024u + 16u * (uint32_t)lane, off & ~15);
         skew = (off & 15) ? (skew | (1u << iss_buf)) : (skew & ~(1u << iss_buf));
         if (++iss_buf == NB) iss_buf = 0;
         if (--iss_left > 0 && ++iss_x == KC) {
@@ -157,20 +123,13 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
         const int buf = (int)((unsigned)bi % NB);
         uint32_t a = 4u * (uint32_t)c + (uint32_t)(buf * BUFB) + (((skew >> buf) & 1u) << 3);
         asm volatile("" : "+v"(a));   // no hoisting across blocks
-        const uint8_t* L = ring + a;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const int o = t * S;
-            const uint32_t* q = (const uint32_t*)(L + (o & ~3));
-            lo[t] = q[0];
-            hi[t] = (o & 3) ? q[1] : 0u;
-        }
+        read_subrows<S>(ring + a, lo, hi);
     };
 
 #pragma unroll 1
     for (int u = 0; u < D; ++u) issue_next();
     uint32_t lo0[8], hi0[8], lo1[8], hi1[8];
-    bsyn_wait_vmcnt<WAITN>();
+    wait_vmcnt<WAITN>();
     read_block(0, lo0, hi0);
 
     int b = 0;        // stream index of the block in (lo0, hi0) / the current block
@@ -179,8 +138,8 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
     for (int i = 0; i < cnt; ++i) {
         const long long g = g0 + (long long)i * W;
         const uint8_t* tb = tab + g * (long long)bsyn::kBytes;
-        const uint32_t mlo = bsyn_cload_u32(tb, bsyn::kMask), mhi = bsyn_cload_u32(tb, bsyn::kMask + 4);
-        const uint32_t ymap = bsyn_cload_u32(tb, bsyn::kY);
+        const uint32_t mlo = cload_u32(tb, bsyn::kMask), mhi = cload_u32(tb, bsyn::kMask + 4);
+        const uint32_t ymap = cload_u32(tb, bsyn::kY);
         const int n = min(min(nout[g], rmax), RC);
         const int ne = KC - __builtin_popcount(mlo) - __builtin_popcount(mhi);
         int p = 0;    // blocks of this group consumed
@@ -201,15 +160,12 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
             if (prev_n >= 0 && p + 1 <= D - 1)
                 bsyn_wait_stores<WAITN, 8 * SPR>(prev_n);
             else
-                bsyn_wait_vmcnt<WAITN>();
+                wait_vmcnt<WAITN>();
             read_block(b + 1, nlo, nhi);
             ++b;
             ++p;
 #pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int o = t * S;
-                wv[t] = (o & 3) ? __builtin_amdgcn_alignbyte(hi[t], lo[t], o & 3) : lo[t];
-            }
+            for (int t = 0; t < 8; ++t) wv[t] = realign_word<S>(lo, hi, t);
         };
         // data row x (compile time): its block, if present, into every syndrome row
         auto row_step = [&](auto xc, uint32_t (&lo)[8], uint32_t (&hi)[8], uint32_t (&nlo)[8],
@@ -235,7 +191,7 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
             }
         };
         static_for<KC>([&](auto xc) __attribute__((always_inline)) {
-            // accumulators opaque at every block boundary (see gf_tile_kernel)
+            // accumulators opaque at every block boundary (no cross-block XOR reassociation)
 #pragma unroll
             for (int y = 0; y < MC; ++y)
 #pragma unroll
@@ -251,7 +207,7 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
                          uint32_t (&nhi)[8]) __attribute__((always_inline)) {
             WZ v;
             advance(lo, hi, nlo, nhi, v.W8);
-            const int row = (int)((bsyn_cload_u32(tb, bsyn::kERow + (e & ~3)) >> (8 * (e & 3))) & 0xFFu);
+            const int row = cload_u8(tb, bsyn::kERow + e);
             if (row >= KC) {
                 const int y = row - KC;   // >= MC (255: a no-op extra of an unchanged group)
                 static_for<MC>([&](auto yc) __attribute__((always_inline)) {
@@ -265,7 +221,7 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
                 expand_wz(v);
                 static_for<MC>([&](auto yc) __attribute__((always_inline)) {
                     constexpr int yy = decltype(yc)::value;
-                    const uint32_t cf = (bsyn_cload_u32(cenc, yy * KC + (row & ~3)) >> (8 * (row & 3))) & 0xFFu;
+                    const uint32_t cf = (uint32_t)cload_u8(cenc, yy * KC + row);
                     apply_nibble<0>(acc[yy], cf & 15u, v);
                     apply_nibble<4>(acc[yy], cf >> 4, v);
                 });
@@ -293,7 +249,7 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
             uint32_t o[8];
 #pragma unroll
             for (int r = 0; r < 8; ++r) o[r] = 0;
-            const uint32_t sw = bsyn_cload_u32(tb, bsyn::kSinv + 4 * j);   // Sinv[j][0..3]
+            const uint32_t sw = cload_u32(tb, bsyn::kSinv + 4 * j);   // Sinv[j][0..3]
 #pragma unroll 1
             for (int ii = 0; ii < n; ++ii) {
                 const int y = (int)((ymap >> (8 * ii)) & 0xFFu);
@@ -309,32 +265,18 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
                 // the product by two nibble jumps (gf_winjump.h), not two branch trees
                 wz_mul_acc_rt(o, v, (sw >> (8 * ii)) & 0xFFu);
             }
-            const int oslot = slots ? (int)((bsyn_cload_u32(slots, (int)((g * rmax + j) & ~3LL)) >>
-                                             (8 * ((g * rmax + j) & 3))) & 0xFFu)
-                                    : j;
+            const int oslot = slots ? cload_u8(slots, (int)(g * rmax + j)) : j;
             uint8_t* dst = out + g * out_gstride + (long long)oslot * BB;
             const __amdgpu_buffer_rsrc_t rs =
                 __builtin_amdgcn_make_buffer_rsrc(dst, 0, (unsigned)BB, 0x00020000);
             // lane offsets from the lane id (not kept live across the block loop)
             const int ln = (int)__lane_id();
-            uint32_t vo = ln < NWF ? 4u * (uint32_t)ln : kBDrop;
-            uint32_t vt = (ln == NWF && NWF < NW) ? 4u * (uint32_t)ln : kBDrop;
-            asm volatile("" : "+v"(vo), "+v"(vt));
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                constexpr int SA = NTS ? 2 : 0;
-                __builtin_amdgcn_raw_buffer_store_b32(o[r], rs, vo, r * S, SA);
-                if (S & 2)
-                    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)o[r], rs, vt, r * S, SA);
-                if (S & 1)
-                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(o[r] >> (8 * (S & 2))), rs, vt,
-                                                         r * S + (S & 2), SA);
-            }
+            store_subrows<S, NTS ? 2 : 0>(rs, o, subrow_lanes(ln, ln, NW, SH::NWF));
         }
         asm volatile("" ::: "memory");
         prev_n = n;
     }
-    bsyn_wait_vmcnt<0>();
+    wait_vmcnt<0>();
 }
 
 // ------------------------------------------------------------------ launchers
@@ -354,22 +296,17 @@ hipError_t launch_gf_bsyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
     if (!gf_bsyn_supported(k, m, bb, rmax, t)) return hipErrorInvalidValue;
     if ((((uintptr_t)in) & 15) || ((((uintptr_t)tab) | (uintptr_t)cenc | (uintptr_t)slots) & 3))
         return hipErrorInvalidValue;
-    using SH = BsynShape<kBsynS>;
+    using SH = SubrowShape<kBsynS>;
     const int D = t.bsyn_depth;
     if (D != 3 && D != 5 && D != 7) return hipErrorInvalidValue;
     const size_t lds = (size_t)kBsynWaves * (D + 1) * SH::BUFB;
     const int per_cu = std::max(1, std::min((int)((160 * 1024) / lds), 20 / kBsynWaves));
-    const long long want = (groups + kBsynWaves - 1) / kBsynWaves;
-    long long cap = (long long)t.cus * per_cu;
     // oversubscribed: about bwg groups per wave (B decode 0.60-0.61 -> 0.53-0.60 ms, DESIGN.md
     // section 4.5)
     const int bwg = t.bsyn_wg >= 0 ? t.bsyn_wg : 2;
-    if (bwg > 0) cap = (groups + (long long)kBsynWaves * bwg - 1) / ((long long)kBsynWaves * bwg);
-    if (t.stream_grid > 0) cap = t.stream_grid;          // tests: many groups per wave
-    const unsigned grid = (unsigned)std::min<long long>(want, cap);
-    if ((groups + (long long)grid * kBsynWaves - 1) / ((long long)grid * kBsynWaves) * k >=
-        (1LL << 31))
-        return hipErrorInvalidValue;
+    const unsigned grid =
+        persistent_grid(groups, kBsynWaves, (long long)t.cus * per_cu, bwg, t.stream_grid, k);
+    if (!grid) return hipErrorInvalidValue;
     note_kernel("gf_bsyn_kernel<decode,k32m4>");
     // recovered blocks stored non-temporal (B decode 0.655 -> 0.631 ms)
 #define QB_GO(DV)                                                                             \

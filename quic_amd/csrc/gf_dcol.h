@@ -47,60 +47,13 @@
 #include "cauchy_const.h"
 #include "fec_kernels.h"
 #include "gf_bitslice.h"
+#include "gf_counted.h"
 #include "gf_winjump.h"
 
 namespace qfec {
 
 namespace {
 
-#define QD_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int N>
-__device__ __forceinline__ void dc_wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt is 6 bits on gfx9");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// 16 bytes per lane from buffer rs at voff into LDS at lds + 16 * lane (nt).  Lanes whose
-// offset lies past the buffer's range load zeros.  (Device only: in a lambda the builtin
-// would void the kernel's host stub.)
-template <int AUX>
-__device__ __forceinline__ void dc_dma16(__amdgpu_buffer_rsrc_t rs, uint8_t* lds, uint32_t voff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, QD_LPTR(lds), 16, voff, 0, 0, AUX);
-#else
-    (void)rs, (void)lds, (void)voff;
-#endif
-}
-
-// a wave-uniform value made opaque to the optimiser (device only, as above)
-__device__ __forceinline__ void dc_opaque_v(uint32_t& x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("" : "+v"(x));
-#else
-    (void)x;
-#endif
-}
-
-// the lane id, recomputed where it is used (not kept live across the block loop)
-__device__ __forceinline__ int dc_lane_here() {
-    int l = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-#endif
-    return l;
-}
-
-// byte i / dword at byte offset o of a table the kernel never writes, through the scalar
-// cache (constant address space)
-__device__ __forceinline__ uint32_t dc_cload_u32(const uint8_t* base, long long o) {
-    return ((const __attribute__((address_space(4))) uint32_t*)(base))[o >> 2];
-}
-__device__ __forceinline__ int dc_cload_u8(const uint8_t* base, long long i) {
-    return (int)((dc_cload_u32(base, i & ~3LL) >> (8 * (i & 3))) & 0xFFu);
-}
-
-constexpr unsigned kDDrop = 0x80000000u;   // buffer offset past any range: lane dropped
 constexpr int kDcWaves = 4;                // waves per workgroup (independent)
 
 template <int S>
@@ -180,8 +133,8 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
         const int segl = p == NT - 1 ? TAILL : SEGL;
         const int t = lane / SEGL, j = lane - t * SEGL;   // instruction 1: segment t + 4
         const uint32_t base = (uint32_t)(4 * SH::TW * p + 16 * j);
-        v0 = j < segl ? (uint32_t)((t * S) & ~15) + base : kDDrop;
-        v1 = j < segl ? (uint32_t)(((t + 4) * S) & ~15) + base : kDDrop;
+        v0 = j < segl ? (uint32_t)((t * S) & ~15) + base : kLaneDrop;
+        v1 = j < segl ? (uint32_t)(((t + 4) * S) & ~15) + base : kLaneDrop;
     };
     auto make_unit = [&](int i, Unit& un, uint32_t& v0, uint32_t& v1) __attribute__((always_inline)) {
         un.none = i >= cnt;
@@ -193,7 +146,7 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
         un.room = (int)min(in_bytes - g * (long long)KC * BB, (long long)KC * BB + 16);
         un.len = KC;
         if constexpr (DECODE)
-            if (!un.none) un.len = KC + (int)(dc_cload_u32(un.tb, syn::kNExt) & 0xFFu);
+            if (!un.none) un.len = KC + (int)(cload_u32(un.tb, syn::kNExt) & 0xFFu);
         tile_voff(p, v0, v1);
     };
     Unit cu, nu;                                     // the unit combined now, and the next
@@ -209,8 +162,8 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
             __builtin_amdgcn_make_buffer_rsrc((void*)(un.src + boff), 0, nrec, 0x00020000);
         uint8_t* dst = ring + iss_off;
         constexpr int LAUX = (CACHE & 1) ? 0 : 2;
-        dc_dma16<LAUX>(rs, dst, v0);
-        dc_dma16<LAUX>(rs, dst + 1024, v1);
+        dma16<LAUX>(rs, dst, v0);
+        dma16<LAUX>(rs, dst + 1024, v1);
         iss_off += BUFB;
         if (iss_off == NBUF * BUFB) iss_off = 0;
     };
@@ -224,7 +177,7 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
         if constexpr (DECODE) {
             if constexpr (x % 4 == 0) {
                 rw = rn;
-                if constexpr (x + 4 < KC) rn = dc_cload_u32(un.tb, syn::kRowSlot + x + 4);
+                if constexpr (x + 4 < KC) rn = cload_u32(un.tb, syn::kRowSlot + x + 4);
             }
             const int slot = (int)((rw >> (8 * (x % 4))) & 0xFFu);
             dma_block(un, v0, v1, min(slot, KC - 1) * BB, slot >= KC);
@@ -234,13 +187,13 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
     };
     // first word of a unit's row slots (before its row 0 is issued: rn = rows 0..3)
     auto rows_start = [&](const Unit& un, uint32_t& rn) __attribute__((always_inline)) {
-        if constexpr (DECODE) rn = un.none ? 0u : dc_cload_u32(un.tb, syn::kRowSlot);
+        if constexpr (DECODE) rn = un.none ? 0u : cload_u32(un.tb, syn::kRowSlot);
     };
     // extra e of unit un (decode, run time)
     auto issue_extra = [&](int e, const Unit& un, uint32_t v0, uint32_t v1)
                            __attribute__((always_inline)) {
         // extras follow the present rows in the stream order: kPerm[np + e], np = KC - ne
-        const int slot = dc_cload_u8(un.tb, syn::kPerm + e + 2 * KC - un.len);
+        const int slot = cload_u8(un.tb, syn::kPerm + e + 2 * KC - un.len);
         dma_block(un, v0, v1, min(slot, KC - 1) * BB, false);
     };
     // run-time stream position q of the current unit (q >= KC): an extra, or the next unit's
@@ -262,7 +215,7 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
     int rd_off = 0;
     auto read_block = [&](uint32_t (&lo)[8], uint32_t (&hi)[8]) __attribute__((always_inline)) {
         uint32_t c4 = 4u * (uint32_t)lane + (uint32_t)rd_off;
-        dc_opaque_v(c4);   // no hoisting across blocks
+        opaque_v(c4);   // no hoisting across blocks
         const uint8_t* L = ring + c4;
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
@@ -276,16 +229,15 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
                        __attribute__((always_inline)) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
-            const int o = (t * S) & 15;
-            w8[t] = (o & 3) ? __builtin_amdgcn_alignbyte(hi[t], lo[t], o & 3) : lo[t];
+            w8[t] = realign_word<S>(lo, hi, t);   // ((t * S) & 15) & 3 == (t * S) & 3
         }
     };
     // wait for block b + 1 and read it into (nlo, nhi); `early` (compile time): it was issued
     // before the previous unit's stores
     auto next_block = [&](auto early, uint32_t (&nlo)[8], uint32_t (&nhi)[8])
                           __attribute__((always_inline)) {
-        if constexpr (decltype(early)::value) dc_wait_vmcnt<63>();
-        else dc_wait_vmcnt<WAITN>();
+        if constexpr (decltype(early)::value) wait_vmcnt<63>();
+        else wait_vmcnt<WAITN>();
         rd_off += BUFB;
         if (rd_off == NBUF * BUFB) rd_off = 0;
         read_block(nlo, nhi);
@@ -298,14 +250,13 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
     static_for<D>([&](auto xc) __attribute__((always_inline)) { issue_row(xc, cu, vc0, vc1, rw_c, rn_c); });
     asm volatile("" ::: "memory");
     {
-        const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t none = pad_rsrc(out);
 #pragma unroll
-        for (int q = 0; q < NSTMIN; ++q)   // distinct offsets: not merged as duplicate stores
-            __builtin_amdgcn_raw_buffer_store_b32(0u, none, 0u, 4 * q, 0);
+        for (int q = 0; q < NSTMIN; ++q) pad_store(none, q);
     }
     asm volatile("" ::: "memory");
     uint32_t lo0[8], hi0[8], lo1[8], hi1[8];
-    dc_wait_vmcnt<WAITN>();
+    wait_vmcnt<WAITN>();
     read_block(lo0, hi0);
 
 #pragma unroll 1
@@ -321,11 +272,11 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
         // branches (cauchy_256.cpp:712-795: only received recovery rows enter the system)
         uint32_t need = 0xFFFFu, pm0 = ~0u, pm1 = ~0u, pm2 = ~0u, pm3 = ~0u;
         if constexpr (DECODE) {
-            need = dc_cload_u32(tb, syn::kNeed);
-            pm0 = dc_cload_u32(tb, syn::kMask);
-            pm1 = dc_cload_u32(tb, syn::kMask + 4);
-            pm2 = dc_cload_u32(tb, syn::kMask + 8);
-            pm3 = dc_cload_u32(tb, syn::kMask + 12);
+            need = cload_u32(tb, syn::kNeed);
+            pm0 = cload_u32(tb, syn::kMask);
+            pm1 = cload_u32(tb, syn::kMask + 4);
+            pm2 = cload_u32(tb, syn::kMask + 8);
+            pm3 = cload_u32(tb, syn::kMask + 12);
         }
         uint32_t acc[RW][8];
 #pragma unroll
@@ -390,13 +341,13 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
         });
 
         asm volatile("" ::: "memory");   // stores stay in issue order among the DMAs
-        const int lane_e = dc_lane_here();
+        const int lane_e = lane_here();
         const int wcol = SH::TW * p + lane_e;          // this lane's column word
         const bool mine = lane_e < SH::TW;
-        uint32_t vo = mine && wcol < NWF ? 4u * (uint32_t)wcol : kDDrop;
-        uint32_t vt = (mine && wcol == NWF && NWF < NW) ? 4u * (uint32_t)wcol : kDDrop;
-        dc_opaque_v(vo);
-        dc_opaque_v(vt);
+        uint32_t vo = mine && wcol < NWF ? 4u * (uint32_t)wcol : kLaneDrop;
+        uint32_t vt = (mine && wcol == NWF && NWF < NW) ? 4u * (uint32_t)wcol : kLaneDrop;
+        opaque_v(vo);
+        opaque_v(vt);
         // one output block: 8 sub-row dword stores, plus the tail word's 16-bit store in the
         // last tile (S % 4 == 2)
         static_assert(S % 4 == 2, "the tail word of a sub-row holds 2 bytes");
@@ -422,7 +373,7 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
                 store_out(out + g * out_gstride + (long long)y * BB, true, acc[y]);
         } else {
             const int ne = cu.len - KC;
-            const int n = min((int)dc_cload_u32((const uint8_t*)nout, 4 * g), rmax);
+            const int n = min((int)cload_u32((const uint8_t*)nout, 4 * g), rmax);
             // extras: a received parity row y adds its block to T_y; a repeated data row adds
             // C[y][row] times its block to every row (run-time coefficients, cenc = [m][k])
             auto extra = [&](int e, uint32_t (&lo)[8], uint32_t (&hi)[8], uint32_t (&nlo)[8],
@@ -431,7 +382,7 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
                 WZ v;
                 next_block(std::false_type{}, nlo, nhi);
                 realign(lo, hi, v.W8);
-                const int row = dc_cload_u8(tb, syn::kERow + e);
+                const int row = cload_u8(tb, syn::kERow + e);
                 if (row >= KC) {
                     const int y = row - KC;
                     static_for<MC>([&](auto yc) __attribute__((always_inline)) {
@@ -446,7 +397,7 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
                     static_for<MC>([&](auto yc) __attribute__((always_inline)) {
                         constexpr int yy = decltype(yc)::value;
                         if ((need >> yy) & 1u) {
-                            const uint32_t cf = (uint32_t)dc_cload_u8(cenc, yy * KC + row);
+                            const uint32_t cf = (uint32_t)cload_u8(cenc, yy * KC + row);
                             apply_nibble<0>(acc[yy], cf & 15u, v);
                             apply_nibble<4>(acc[yy], cf >> 4, v);
                         }
@@ -480,7 +431,7 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
                     for (int r = 0; r < 8; ++r) o[q][r] = 0;
 #pragma unroll 1
                 for (int ii = 0; ii < n; ++ii) {
-                    const int y = dc_cload_u8(tb, syn::kYmap + ii);
+                    const int y = cload_u8(tb, syn::kYmap + ii);
                     WZ v;
 #pragma unroll
                     for (int r = 0; r < 8; ++r) v.W[r] = 0;
@@ -498,7 +449,7 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
                         if (j < n) {
                             // nibble jumps (gf_winjump.h): one indirect jump per nibble
                             // instead of a 16-way branch tree
-                            const uint32_t cf = (uint32_t)dc_cload_u8(tb, syn::kSinv + j * 16 + ii);
+                            const uint32_t cf = (uint32_t)cload_u8(tb, syn::kSinv + j * 16 + ii);
                             wz_mul_acc_rt(o[q], v, cf);
                         }
                     }
@@ -508,7 +459,7 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
                 for (int q = 0; q < PO; ++q) {
                     const int j = PO * ps + q;
                     const bool on = j < n;
-                    const int oslot = slots ? (on ? dc_cload_u8(slots, g * rmax + j) : 0) : j;
+                    const int oslot = slots ? (on ? cload_u8(slots, g * rmax + j) : 0) : j;
                     store_out(out + g * out_gstride + (long long)oslot * BB, on, o[q]);
                 }
                 asm volatile("" ::: "memory");
@@ -516,11 +467,9 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
             if constexpr (NSTMIN > PO * 8) {
                 if (npass == 1) {
                     // pad: a unit ends with at least NSTMIN stores (empty range)
-                    const __amdgpu_buffer_rsrc_t none =
-                        __builtin_amdgcn_make_buffer_rsrc(out, 0, 0u, 0x00020000);
+                    const __amdgpu_buffer_rsrc_t none = pad_rsrc(out);
 #pragma unroll
-                    for (int q = 0; q < NSTMIN - PO * 8; ++q)
-                        __builtin_amdgcn_raw_buffer_store_b32(0u, none, 0u, 4 * q, 0);
+                    for (int q = 0; q < NSTMIN - PO * 8; ++q) pad_store(none, q);
                 }
             }
         }
@@ -531,7 +480,7 @@ __global__ __launch_bounds__(kDcWaves * 64, 2) void gf_dcol_kernel(
         vc0 = vn0;
         vc1 = vn1;
     }
-    dc_wait_vmcnt<0>();
+    wait_vmcnt<0>();
 }
 
 }  // namespace

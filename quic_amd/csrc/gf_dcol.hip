@@ -9,17 +9,12 @@ bool gf_dcol_supported(int k, int m, int bb, const Tune& t) {
     return t.dcol && t.const_enc && k == 128 && m == 16 && bb == 8 * kDcolS;
 }
 
-// wg_cu: workgroups of 4 waves a CU holds by registers (2 at <= 256 VGPRs), LDS permitting
+// wg_cu: workgroups of 4 waves a CU holds by registers (2 at <= 256 VGPRs), LDS permitting.
+// Units are column tiles; oversubscribed at about dcol_wg units per wave; 0 = invalid.
 static unsigned dcol_grid(long long groups, const Tune& t, size_t lds, int wg_cu) {
-    using SH = DcShape<kDcolS>;
-    const long long units = groups * SH::NT;
-    const long long want = (units + kDcWaves - 1) / kDcWaves;
     const int per_cu = std::max(1, std::min(wg_cu, (int)((160 * 1024) / lds)));
-    long long cap = (long long)t.cus * per_cu;
-    if (t.dcol_wg > 0)   // oversubscribed: about dcol_wg units per wave
-        cap = (units + (long long)kDcWaves * t.dcol_wg - 1) / ((long long)kDcWaves * t.dcol_wg);
-    if (t.dcol_grid > 0) cap = t.dcol_grid;          // tests: many units per wave
-    return (unsigned)std::min<long long>(want, cap);
+    return persistent_grid(groups * DcShape<kDcolS>::NT, kDcWaves, (long long)t.cus * per_cu,
+                           t.dcol_wg, t.dcol_grid);
 }
 
 hipError_t launch_gf_dcol_encode(const uint8_t* in, uint8_t* out, int k, int m, int bb,
@@ -33,8 +28,7 @@ hipError_t launch_gf_dcol_encode(const uint8_t* in, uint8_t* out, int k, int m, 
     if (D != 6 && D != 8) return hipErrorInvalidValue;
     const size_t lds = (size_t)kDcWaves * (D + 1) * SH::BUFB;
     const unsigned grid = dcol_grid(groups, t, lds, 2);
-    const long long waves = (long long)grid * kDcWaves;
-    if ((groups * SH::NT + waves - 1) / waves >= (1LL << 31)) return hipErrorInvalidValue;
+    if (!grid) return hipErrorInvalidValue;
     note_kernel("gf_dcol_kernel<encode,k128m16>");
     note_grid("gf_dcol_kernel<encode>", grid);
     const long long in_bytes = groups * (long long)k * bb;
@@ -65,8 +59,7 @@ hipError_t launch_gf_dcol_syndrome(const uint8_t* in, uint8_t* out, const uint8_
     if (D != 6 && D != 8) return hipErrorInvalidValue;
     const size_t lds = (size_t)kDcWaves * (D + 1) * SH::BUFB;
     const unsigned grid = dcol_grid(groups, t, lds, 2);
-    const long long waves = (long long)grid * kDcWaves;
-    if ((groups * SH::NT + waves - 1) / waves >= (1LL << 31)) return hipErrorInvalidValue;
+    if (!grid) return hipErrorInvalidValue;
     note_kernel("gf_dcol_kernel<decode,k128m16>");
     note_grid("gf_dcol_kernel<decode>", grid);
     // decode: non-temporal loads, plain stores (cached loads: 1.011x instead of 1.167x the

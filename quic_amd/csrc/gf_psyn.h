@@ -6,34 +6,12 @@
 #include "fec_kernels.h"
 #include "gf256.h"
 #include "gf_bitslice.h"
+#include "gf_counted.h"
 #include "gf_winjump.h"
 
 namespace qfec {
 
 namespace {
-
-
-#define QP_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int N>
-__device__ __forceinline__ void psyn_wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt is 6 bits on gfx9");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// 16 bytes per lane from buffer rs at voff into LDS at lds + 16 * lane (nt).  (Device only:
-// in a lambda the builtin would void the kernel's host stub.)
-__device__ __forceinline__ void psyn_dma16(__amdgpu_buffer_rsrc_t rs, uint8_t* lds, uint32_t voff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, QP_LPTR(lds), 16, voff, 0, 0, 2);
-#else
-    (void)rs, (void)lds, (void)voff;
-#endif
-}
-
-__device__ __forceinline__ uint32_t psyn_cload_u32(const uint8_t* base, int byte_off) {
-    return ((const __attribute__((address_space(4))) uint32_t*)(base))[byte_off >> 2];
-}
 
 // f(integral_constant<int, v>) for the run-time v in [LO, HI]: a binary tree of uniform
 // branches, so register arrays can be indexed by a wave-uniform value
@@ -47,19 +25,6 @@ __device__ __forceinline__ void psyn_dispatch(int v, F&& f) {
         else psyn_dispatch<MID + 1, HI>(v, f);
     }
 }
-
-constexpr unsigned kPDrop = 0x80000000u;   // buffer offset past any range: lane dropped
-
-
-template <int S>
-struct PsynShape {
-    static constexpr int BB = 8 * S;
-    static constexpr int NW = (S + 3) / 4, NWF = S / 4;
-    static constexpr int SPR = 1 + ((S >> 1) & 1) + (S & 1);   // stores per sub-row
-    static constexpr int BUFB = (BB + 8 + 15) / 16 * 16;        // the 16-byte envelope
-    static constexpr int NPC = BUFB > 1024 ? 2 : 1;              // DMA instructions per block
-    static constexpr int P1L = BUFB > 1024 ? (BUFB - 1024) / 16 : 0;   // lanes of the 2nd
-};
 
 constexpr int kPsynWaves = 4;   // waves per workgroup (independent)
 
@@ -85,8 +50,8 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
     const uint8_t* in, uint8_t* out, const uint8_t* __restrict__ tab,
     const uint8_t* __restrict__ cenc, const uint8_t* __restrict__ slots,
     const int32_t* __restrict__ nout, long long groups, int rmax, long long out_gstride) {
-    using SH = PsynShape<S>;
-    constexpr int BB = SH::BB, NW = SH::NW, NWF = SH::NWF, SPR = SH::SPR;
+    using SH = SubrowShape<S>;
+    constexpr int BB = SH::BB, NW = SH::NW, SPR = SH::SPR;
     constexpr int BUFB = SH::BUFB, NPC = SH::NPC, P1L = SH::P1L;
     constexpr int NB = D + 1;                 // the block being read + D in flight
     constexpr int WAITN = D * NPC;            // younger than block b when it is awaited
@@ -135,14 +100,14 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
     };
     group_rsrc();
     auto issue_next = [&]() __attribute__((always_inline)) {
-        if ((iss_x & 3) == 0) perm_w = psyn_cload_u32(iss_t, psyn::kPerm + iss_x);
+        if ((iss_x & 3) == 0) perm_w = cload_u32(iss_t, psyn::kPerm + iss_x);
         const int slot = min((int)((perm_w >> (8 * (iss_x & 3))) & 0xFFu), KC - 1);
         const int off = iss_sk + slot * BB;        // the block's offset from the group's 16-B start
         uint32_t vo = v16 + (uint32_t)(off & ~15);
         uint8_t* dst = ring + iss_buf * BUFB;
-        psyn_dma16(iss_rs, dst, vo);
+        dma16(iss_rs, dst, vo);
         if constexpr (NPC == 2)
-            if (__lane_id() < P1L) psyn_dma16(iss_rs, dst + 1024, vo + 1024u);
+            if (__lane_id() < P1L) dma16(iss_rs, dst + 1024, vo + 1024u);
         skew = (off & 8) ? (skew | (1u << iss_buf)) : (skew & ~(1u << iss_buf));
         if (++iss_buf == NB) iss_buf = 0;
         if (--iss_left > 0 && ++iss_x == KC) {
@@ -156,13 +121,12 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
 #pragma unroll 1
     for (int u = 0; u < D; ++u) issue_next();
     asm volatile("" ::: "memory");
+    // the stores a previous group would have issued (empty range): the first group's
+    // blocks 0 .. D - 1 are awaited like every other group's
     {
-        // the stores a previous group would have issued (empty range): the first group's
-        // blocks 0 .. D - 1 are awaited like every other group's
-        const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t none = pad_rsrc(out);
 #pragma unroll
-        for (int q = 0; q < (WIDE ? NSTW : NSTMIN); ++q)
-            __builtin_amdgcn_raw_buffer_store_b32(0u, none, 0u, 4 * q, 0);
+        for (int q = 0; q < (WIDE ? NSTW : NSTMIN); ++q) pad_store(none, q);
     }
     asm volatile("" ::: "memory");
 
@@ -171,10 +135,10 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
     for (int i = 0; i < cnt; ++i) {
         const long long g = g0 + (long long)i * W;
         const uint8_t* tb = tab + g * (long long)psyn::kBytes;
-        const uint32_t mlo = psyn_cload_u32(tb, psyn::kMask), mhi = psyn_cload_u32(tb, psyn::kMask + 4);
+        const uint32_t mlo = cload_u32(tb, psyn::kMask), mhi = cload_u32(tb, psyn::kMask + 4);
         // the syndrome rows the solve uses (the received parity rows); the others are not
         // accumulated (cauchy_256.cpp:712-795: only received recovery rows enter the system)
-        const uint32_t need = psyn_cload_u32(tb, psyn::kNeed);
+        const uint32_t need = cload_u32(tb, psyn::kNeed);
         const int n = min(min(nout[g], rmax), RC);
         const int ne = KC - __builtin_popcount(mlo) - __builtin_popcount(mhi);
         int p = 0;    // blocks of this group consumed
@@ -188,28 +152,18 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
         // were DMA'd before the previous group's >= NSTMIN stores), read and realign it
         auto take = [&](uint32_t (&wv)[8]) __attribute__((always_inline)) {
             issue_next();
-            if (p < D) psyn_wait_vmcnt<WAIT0>();
-            else psyn_wait_vmcnt<WAITN>();
+            if (p < D) wait_vmcnt<WAIT0>();
+            else wait_vmcnt<WAITN>();
             const int buf = (int)((unsigned)b % NB);
             uint32_t a = 4u * (uint32_t)min((int)__lane_id(), NW - 1) + (uint32_t)(buf * BUFB) +
                          (((skew >> buf) & 1u) << 3);
             asm volatile("" : "+v"(a));   // no hoisting across blocks
-            const uint8_t* L = ring + a;
             uint32_t lo[8], hi[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int o = t * S;
-                const uint32_t* q = (const uint32_t*)(L + (o & ~3));
-                lo[t] = q[0];
-                hi[t] = (o & 3) ? q[1] : 0u;
-            }
+            read_subrows<S>(ring + a, lo, hi);
             ++b;
             ++p;
 #pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int o = t * S;
-                wv[t] = (o & 3) ? __builtin_amdgcn_alignbyte(hi[t], lo[t], o & 3) : lo[t];
-            }
+            for (int t = 0; t < 8; ++t) wv[t] = realign_word<S>(lo, hi, t);
         };
         // data row x (compile time): its block, if present, into every syndrome row
         static_for<KC>([&](auto xc) __attribute__((always_inline)) {
@@ -244,7 +198,7 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
         for (int e = 0; e < ne; ++e) {
             WZ v;
             take(v.W8);
-            const int row = (int)((psyn_cload_u32(tb, psyn::kERow + (e & ~3)) >> (8 * (e & 3))) & 0xFFu);
+            const int row = cload_u8(tb, psyn::kERow + e);
             if (row >= KC) {
                 const int y = row - KC;   // >= MC (255: a no-op extra of an unchanged group)
                 if (y < MC)
@@ -257,8 +211,7 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
 #pragma unroll 1
                 for (int yy = 0; yy < MC; ++yy) {
                     if (!((need >> yy) & 1u)) continue;
-                    const int ci = yy * KC + row;
-                    const uint32_t cf = (psyn_cload_u32(cenc, ci & ~3) >> (8 * (ci & 3))) & 0xFFu;
+                    const uint32_t cf = (uint32_t)cload_u8(cenc, yy * KC + row);
                     uint32_t tmp[8];
 #pragma unroll
                     for (int r = 0; r < 8; ++r) {
@@ -278,8 +231,8 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
         }
         if (n > 0) {
             // ---- T_s <- T_{y_s}: ascending, y_s >= s, so no source is overwritten early
-            const uint32_t ys0 = psyn_cload_u32(tb, psyn::kYs), ys1 = psyn_cload_u32(tb, psyn::kYs + 4);
-            const uint32_t ys2 = psyn_cload_u32(tb, psyn::kYs + 8), ys3 = psyn_cload_u32(tb, psyn::kYs + 12);
+            const uint32_t ys0 = cload_u32(tb, psyn::kYs), ys1 = cload_u32(tb, psyn::kYs + 4);
+            const uint32_t ys2 = cload_u32(tb, psyn::kYs + 8), ys3 = cload_u32(tb, psyn::kYs + 12);
             static_for<RC>([&](auto sc) __attribute__((always_inline)) {
                 constexpr int s = decltype(sc)::value;
                 const uint32_t yw = s < 4 ? ys0 : s < 8 ? ys1 : s < 12 ? ys2 : ys3;
@@ -306,7 +259,7 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
                 const int cb = psyn::kCoef + 16 * pv;
                 uint32_t cw[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) cw[q] = psyn_cload_u32(tb, cb + 4 * q);
+                for (int q = 0; q < 4; ++q) cw[q] = cload_u32(tb, cb + 4 * q);
                 expand_wz(v);
                 static_for<RC>([&](auto ic) __attribute__((always_inline)) {
                     constexpr int i = decltype(ic)::value;
@@ -325,36 +278,21 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
             static_for<RC>([&](auto jc) __attribute__((always_inline)) {
                 constexpr int j = decltype(jc)::value;
                 if (j < n) {
-                    const int oslot = slots ? (int)((psyn_cload_u32(slots, (int)((g * rmax + j) & ~3LL)) >>
+                    const int oslot = slots ? (int)((cload_u32(slots, (int)((g * rmax + j) & ~3LL)) >>
                                                      (8 * ((g * rmax + j) & 3))) & 0xFFu)
                                             : j;
                     uint8_t* dst = out + g * out_gstride + (long long)oslot * BB;
                     const __amdgpu_buffer_rsrc_t rs =
                         __builtin_amdgcn_make_buffer_rsrc(dst, 0, (unsigned)BB, 0x00020000);
                     if (ln < NW) stage_block_169(stage, acc[j], ln);
-                    uint64_t v0, v1, v2;
-                    asm volatile("ds_read_b64 %0, %3\n\t"
-                                 "ds_read_b64 %1, %3 offset:512\n\t"
-                                 "ds_read_b64 %2, %3 offset:1024\n\t"
-                                 "s_waitcnt lgkmcnt(0)"
-                                 : "=&v"(v0), "=&v"(v1), "=&v"(v2)
-                                 : "v"(ra)
-                                 : "memory");
-                    const uint64_t vv[3] = {v0, v1, v2};
-#pragma unroll
-                    for (int h = 0; h < 3; ++h)
-                        __builtin_amdgcn_raw_buffer_store_b64(qf_u32x2(vv[h]), rs,
-                                                              512u * h + 8u * (uint32_t)ln, 0, 2);
+                    store_staged_169<2>(rs, ra, ln);
                 }
             });
-            // pad to exactly NSTW stores (empty range).  Distinct offsets and a compiler barrier
-            // per store: identical stores in this loop were merged into ONE instruction, so a
-            // group with fewer than RC recovered blocks issued 3 n + 1 stores and the next
-            // group's vmcnt(WAIT0) could pass before its block had landed in LDS
-            const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0u, 0x00020000);
+            // pad to exactly NSTW stores (a rolled loop: the barrier per store, gf_counted.h)
+            const __amdgpu_buffer_rsrc_t none = pad_rsrc(out);
 #pragma unroll 1
             for (int q = 3 * n; q < NSTW; ++q) {
-                __builtin_amdgcn_raw_buffer_store_b32(0u, none, 0u, 4 * q, 0);
+                pad_store(none, q);
                 asm volatile("" ::: "memory");
             }
             asm volatile("" ::: "memory");
@@ -363,36 +301,25 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
         static_for<RC>([&](auto jc) __attribute__((always_inline)) {
             constexpr int j = decltype(jc)::value;
             if (j < n) {
-                const int oslot = slots ? (int)((psyn_cload_u32(slots, (int)((g * rmax + j) & ~3LL)) >>
+                const int oslot = slots ? (int)((cload_u32(slots, (int)((g * rmax + j) & ~3LL)) >>
                                                  (8 * ((g * rmax + j) & 3))) & 0xFFu)
                                         : j;
                 uint8_t* dst = out + g * out_gstride + (long long)oslot * BB;
                 const __amdgpu_buffer_rsrc_t rs =
                     __builtin_amdgcn_make_buffer_rsrc(dst, 0, (unsigned)BB, 0x00020000);
                 const int ln = (int)__lane_id();
-                uint32_t vo = ln < NWF ? 4u * (uint32_t)ln : kPDrop;
-                uint32_t vt = (ln == NWF && NWF < NW) ? 4u * (uint32_t)ln : kPDrop;
-                asm volatile("" : "+v"(vo), "+v"(vt));
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    __builtin_amdgcn_raw_buffer_store_b32(acc[j][r], rs, vo, r * S, 2);
-                    if (S & 2)
-                        __builtin_amdgcn_raw_buffer_store_b16((uint16_t)acc[j][r], rs, vt, r * S, 2);
-                    if (S & 1)
-                        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(acc[j][r] >> (8 * (S & 2))),
-                                                             rs, vt, r * S + (S & 2), 2);
-                }
+                store_subrows<S, 2>(rs, acc[j], subrow_lanes(ln, ln, NW, SH::NWF));
             }
         });
         static_assert(4 * NSB >= NSTMIN, "four recovered blocks are enough stores");
         if (n < 4) {
-            const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0u, 0x00020000);
+            const __amdgpu_buffer_rsrc_t none = pad_rsrc(out);
 #pragma unroll
-            for (int q = 0; q < NSTMIN; ++q) __builtin_amdgcn_raw_buffer_store_b32(0u, none, 0u, 4 * q, 0);
+            for (int q = 0; q < NSTMIN; ++q) pad_store(none, q);
         }
         asm volatile("" ::: "memory");
     }
-    psyn_wait_vmcnt<0>();
+    wait_vmcnt<0>();
 }
 
 }  // namespace
@@ -421,16 +348,11 @@ hipError_t psyn_go_55(const PsynLaunch& a);
         constexpr int RCV = KV < MV ? KV : MV;                                                 \
         const auto kern = a.wide ? gf_psyn_kernel<KV, MV, RCV, kPsynS, 5, true>               \
                                  : gf_psyn_kernel<KV, MV, RCV, kPsynS, 5, false>;             \
-        const long long want = (a.groups + kPsynWaves - 1) / kPsynWaves;                       \
-        long long cap = (long long)t.cus * resident_blocks((const void*)kern, kPsynWaves * 64, a.lds); \
-        if (t.psyn_wg > 0) /* oversubscribed: about psyn_wg groups per wave */                \
-            cap = (a.groups + (long long)kPsynWaves * t.psyn_wg - 1) /                         \
-                  ((long long)kPsynWaves * t.psyn_wg);                                         \
-        if (t.stream_grid > 0) cap = t.stream_grid; /* tests: many groups per wave */          \
-        const unsigned grid = (unsigned)std::min<long long>(want, cap);                       \
-        if ((a.groups + (long long)grid * kPsynWaves - 1) / ((long long)grid * kPsynWaves) *   \
-                a.k >= (1LL << 31))                                                            \
-            return hipErrorInvalidValue;                                                       \
+        const unsigned grid = persistent_grid(                                                 \
+            a.groups, kPsynWaves,                                                              \
+            (long long)t.cus * resident_blocks((const void*)kern, kPsynWaves * 64, a.lds),     \
+            t.psyn_wg, t.stream_grid, a.k);                                                    \
+        if (!grid) return hipErrorInvalidValue;                                                \
         note_grid("gf_psyn_kernel", grid);                                                     \
         qlaunch(kern, dim3(grid), dim3(kPsynWaves * 64), a.lds, a.st, a.in, a.out, a.tab,      \
                 a.cenc, a.slots, a.nout, a.groups, a.rmax, a.out_gstride);                    \

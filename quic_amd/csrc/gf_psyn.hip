@@ -65,7 +65,7 @@ hipError_t launch_gf_psyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
     if (!gf_psyn_supported(k, m, bb, rmax, t)) return hipErrorInvalidValue;
     if ((((uintptr_t)in) & 15) || ((((uintptr_t)tab) | (uintptr_t)cenc | (uintptr_t)slots) & 3))
         return hipErrorInvalidValue;
-    using SH = PsynShape<kPsynS>;
+    using SH = SubrowShape<kPsynS>;
     PsynLaunch a;
     a.in = in, a.out = out, a.tab = tab, a.cenc = cenc, a.slots = slots, a.nout = nout;
     a.groups = groups, a.rmax = rmax, a.out_gstride = out_gstride, a.st = st, a.t = &t, a.k = k;

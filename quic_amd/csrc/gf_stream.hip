@@ -34,53 +34,13 @@
 #include "cauchy_const.h"
 #include "fec_kernels.h"
 #include "gf_bitslice.h"
+#include "gf_counted.h"
 #include "gf_winjump.h"
 
 namespace qfec {
 
 #define QS_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define QS_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 
-template <int N>
-__device__ __forceinline__ void stream_wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt is 6 bits on gfx9");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform run-time n in [LO, HI]: binary dispatch.
-template <int LO, int HI>
-__device__ __forceinline__ void stream_wait_dyn(int n) {
-    if constexpr (LO == HI) {
-        stream_wait_vmcnt<LO>();
-    } else {
-        constexpr int MID = (LO + HI) / 2;
-        if (n <= MID) stream_wait_dyn<LO, MID>(n);
-        else stream_wait_dyn<MID + 1, HI>(n);
-    }
-}
-
-// 16 bytes per lane from buffer rs at voff into LDS at lds + 16 * lane (nt); offsets past
-// the buffer's range load zeros.  (Device only: in a lambda the builtin would void the
-// kernel's host stub.)
-template <int AUX = 2>
-__device__ __forceinline__ void stream_dma16(__amdgpu_buffer_rsrc_t rs, uint8_t* lds,
-                                             uint32_t voff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, QS_LPTR(lds), 16, voff, 0, 0, AUX);
-#else
-    (void)rs, (void)lds, (void)voff;
-#endif
-}
-
-// Byte i of a 4-byte-aligned kernel-argument array through s_load_dword: a byte load
-// (global_load_ubyte, or flat_load after an integer-to-pointer cast) would be a VMEM
-// instruction outside the vmcnt bookkeeping, and its use would drain the ring.
-__device__ __forceinline__ int sload_u8(const uint8_t* __restrict__ base, long long i) {
-    const uint32_t wv = ((const uint32_t*)base)[i >> 2];
-    return (int)((wv >> (8 * (i & 3))) & 0xFFu);
-}
-
-constexpr unsigned kSDrop = 0x80000000u;   // buffer offset past any range: lane dropped
 constexpr int kStreamWaves = 4;            // waves per workgroup (independent)
 constexpr int kMirror = 2;                 // mirrored slots: a block (<= 2 KiB + 3 B of
                                            // over-read) starting in the ring never wraps
@@ -125,15 +85,8 @@ __global__ __launch_bounds__(kStreamWaves * 64) void gf_stream_kernel(
     constexpr int SPR = S ? 1 + ((S >> 1) & 1) + (S & 1) : 3;
     constexpr int SAUX = DECODE ? 0 : 2;   // encode's dense parity stream: nt stores
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    // the lane id, recomputed where it is used (v_mbcnt): nothing lane-derived stays live
+    // the lane id is recomputed where it is used (lane_here): nothing lane-derived stays live
     // across the block loop (register pressure of the compiled encodes with many outputs)
-    auto lane_here = []() __attribute__((always_inline)) -> int {
-        int l = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-#endif
-        return l;
-    };
     const int w = wave_id();
     const int RB = R * 1024;
     uint8_t* ring = smem + (size_t)w * (R + kMirror) * 1024;
@@ -190,10 +143,10 @@ __global__ __launch_bounds__(kStreamWaves * 64) void gf_stream_kernel(
         const int off = min(iss_p * 1024 + lane * 16, ilast);   // last piece: clamp inside
         const __amdgpu_buffer_rsrc_t rs =
             __builtin_amdgcn_make_buffer_rsrc((void*)isrc, 0, inrec, 0x00020000);
-        stream_dma16(rs, ring + iss_slot * 1024, (uint32_t)off);
+        dma16(rs, ring + iss_slot * 1024, (uint32_t)off);
         ++vm;
         if (iss_slot < kMirror) {
-            stream_dma16(rs, ring + (R + iss_slot) * 1024, (uint32_t)off);
+            dma16(rs, ring + (R + iss_slot) * 1024, (uint32_t)off);
             ++vm;
         }
         vmv = lane == iss_slot ? (uint32_t)(vm - 1) : vmv;
@@ -220,14 +173,14 @@ __global__ __launch_bounds__(kStreamWaves * 64) void gf_stream_kernel(
         // coarse steps (a smaller count only waits longer): 4 scalar branch levels
         if (pending >= 16) {
             if (pending >= 32) {
-                if (pending >= 48) stream_wait_vmcnt<48>();
-                else stream_wait_vmcnt<32>();
+                if (pending >= 48) wait_vmcnt<48>();
+                else wait_vmcnt<32>();
             } else {
-                if (pending >= 24) stream_wait_vmcnt<24>();
-                else stream_wait_vmcnt<16>();
+                if (pending >= 24) wait_vmcnt<24>();
+                else wait_vmcnt<16>();
             }
         } else {
-            stream_wait_dyn<0, 15>(pending < 0 ? 0 : pending);
+            wait_vmcnt_upto<0, 15>(pending < 0 ? 0 : pending);
         }
     };
     // column word c of the 8 sub-rows as aligned dword pairs (block starts are 8-byte
@@ -239,14 +192,7 @@ __global__ __launch_bounds__(kStreamWaves * 64) void gf_stream_kernel(
         // form it would otherwise precompute every block's addresses up front
         uint32_t c4 = 4u * (uint32_t)col_here();
         if constexpr (KC > 0) asm volatile("" : "+v"(c4));
-        const uint8_t* L = ring + bp + c4;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const int o = t * s;
-            const uint32_t* q = (const uint32_t*)(L + (o & ~3));
-            lo[t] = q[0];
-            hi[t] = (S == 0 || (o & 3)) ? q[1] : 0u;
-        }
+        read_subrows<S>(ring + bp + c4, lo, hi, s);
     };
     auto next_pos = [&](uint32_t bp) -> uint32_t {
         bp += BB;
@@ -303,11 +249,7 @@ __global__ __launch_bounds__(kStreamWaves * 64) void gf_stream_kernel(
                 bpos = bn;
                 WZ v;
 #pragma unroll
-                for (int t = 0; t < 8; ++t) {
-                    const int o = t * s;
-                    v.W[t] = (S == 0 || (o & 3)) ? __builtin_amdgcn_alignbyte(hi[t], lo[t], o & 3)
-                                                 : lo[t];
-                }
+                for (int t = 0; t < 8; ++t) v.W[t] = realign_word<S>(lo, hi, t, s);
                 if constexpr (KC > 0) {
                     // windowed form (gf_bitslice.h): one v_bitop3 per (output, sub-row); row 0
                     // is P0, all coefficients 1 (cauchy_256.cpp:1519-1523)
@@ -371,17 +313,14 @@ __global__ __launch_bounds__(kStreamWaves * 64) void gf_stream_kernel(
             asm volatile("" ::: "memory");   // stores stay in issue order among the DMAs
             // ---- outputs: fixed instruction count per output (dropped lanes, no branches).
             // Lane offsets 4c (full words) and the tail lane's, sub-row in the scalar offset:
-            // two address VGPRs, opaque so they are not hoisted as 8 x RC precomputed ones.
+            // two address VGPRs, opaque so they are not hoisted as 8 x RC precomputed ones
+            // (subrow_lanes() spelled out: with run-time s its form compiles to other code).
             const int lane = lane_here(), c = min(lane, NW - 1);
-            uint32_t vo = lane < NWF ? 4u * (uint32_t)c : kSDrop;
-            uint32_t vt = lane == NWF && NWF < NW ? 4u * (uint32_t)c : kSDrop;
+            uint32_t vo = lane < NWF ? 4u * (uint32_t)c : kLaneDrop;
+            uint32_t vt = lane == NWF && NWF < NW ? 4u * (uint32_t)c : kLaneDrop;
             asm volatile("" : "+v"(vo), "+v"(vt));
+            const SubrowLanes sl{vo, vt};
             if constexpr (WIDE) {
-                // 8 ds_write_b32 per lane at the sub-row offsets (the tail word's 3 extra bytes
-                // land on the next sub-row's start, overwritten by its later write; the last
-                // one's inside the staging pad), then 3 x 512 B read back and stored as
-                // contiguous 8-byte lanes (past the block: dropped by the buffer range; the
-                // reads past 1360 B touch the next wave's buffer or read zeros, unused)
                 const uint32_t ra = stage + 8u * (uint32_t)lane;
 #pragma unroll
                 for (int j = 0; j < RC; ++j) {
@@ -390,20 +329,7 @@ __global__ __launch_bounds__(kStreamWaves * 64) void gf_stream_kernel(
                     const __amdgpu_buffer_rsrc_t rs =
                         __builtin_amdgcn_make_buffer_rsrc(dst, 0, (unsigned)BB, 0x00020000);
                     if (lane < NW) stage_block_169(stage, acc[j], lane);
-                    uint64_t v0, v1, v2;
-                    asm volatile("ds_read_b64 %0, %3\n\t"
-                                 "ds_read_b64 %1, %3 offset:512\n\t"
-                                 "ds_read_b64 %2, %3 offset:1024\n\t"
-                                 "s_waitcnt lgkmcnt(0)"
-                                 : "=&v"(v0), "=&v"(v1), "=&v"(v2)
-                                 : "v"(ra)
-                                 : "memory");
-                    const uint64_t vv[3] = {v0, v1, v2};
-#pragma unroll
-                    for (int h = 0; h < 3; ++h)
-                        __builtin_amdgcn_raw_buffer_store_b64(
-                            qf_u32x2(vv[h]),
-                            rs, 512u * h + 8u * (uint32_t)lane, 0, SAUX);
+                    store_staged_169<SAUX>(rs, ra, lane);
                     vm += 3;
                 }
                 asm volatile("" ::: "memory");
@@ -415,22 +341,12 @@ __global__ __launch_bounds__(kStreamWaves * 64) void gf_stream_kernel(
             for (int j = 0; j < RC; ++j) {
                 if (j < n) {
                     const int jo = ch * RC + j;
-                    const int oslot = (DECODE && slots) ? sload_u8(slots, g * rmax + jo) : jo;
+                    const int oslot = (DECODE && slots) ? cload_u8(slots, g * rmax + jo) : jo;
                     uint8_t* dst = out + g * out_gstride + (long long)oslot * BB;
                     const __amdgpu_buffer_rsrc_t rs =
                         __builtin_amdgcn_make_buffer_rsrc(dst, 0, (unsigned)BB, 0x00020000);
 #pragma unroll
-                    for (int r = 0; r < 8; ++r) {
-                        const uint32_t vsum = acc[j][r];
-                        __builtin_amdgcn_raw_buffer_store_b32(vsum, rs, vo, r * s, SAUX);
-                        if (S == 0 || (S & 2))
-                            __builtin_amdgcn_raw_buffer_store_b16(
-                                (uint16_t)vsum, rs, (s & 2) ? vt : kSDrop, r * s, SAUX);
-                        if (S == 0 || (S & 1))
-                            __builtin_amdgcn_raw_buffer_store_b8(
-                                (uint8_t)(vsum >> (8 * (s & 2))), rs, (s & 1) ? vt : kSDrop,
-                                r * s + (s & 2), SAUX);
-                    }
+                    for (int r = 0; r < 8; ++r) store_subrow<S, SAUX>(rs, acc[j][r], r, sl, s);
                     vm += 8 * SPR;
                 }
             }
@@ -439,7 +355,7 @@ __global__ __launch_bounds__(kStreamWaves * 64) void gf_stream_kernel(
             gslot0 = (gslot0 + NP) % R;
         }
     }
-    stream_wait_vmcnt<0>();
+    wait_vmcnt<0>();
 }
 
 // ------------------------------------------------------------------ static ring
@@ -462,44 +378,29 @@ constexpr int kRingWaves = 4;
 // SK: the group's bytes start SK bytes into its stream (odd k at 1352-byte blocks: groups
 // alternate between 0 and 8 bytes past a 16-byte boundary)
 template <int S, int SK = 0>
-struct RingShape {
+struct RingShape : SubrowShape<S> {
     static constexpr int R = 8, RB = R * 1024;
-    static constexpr int BB = 8 * S;
-    static constexpr int NW = (S + 3) / 4, NWF = S / 4;
-    static constexpr int SPR = 1 + ((S >> 1) & 1) + (S & 1);
+    static constexpr int BB = SubrowShape<S>::BB;
     static constexpr int pf(int x) { return (SK + x * BB) >> 10; }             // first piece of block x
     static constexpr int pl(int x) { return (SK + (x + 1) * BB - 1) >> 10; }   // its last piece
-    // smallest count of VMEM instructions younger than a block's last piece when the wave
-    // waits for it (K blocks per group, NST stores per group): one conservative immediate
-    // for the rolled (run-time block index) form
-    static constexpr int min_younger(int K, int NST) {
-        const int NP = (K * BB + 1023) / 1024;
-        const int FM1 = pf(K - 1) + R - 1 - NP;
-        int mn = FM1 - pl(0) + NST;
-        for (int x = 0; x + 1 < K; ++x) {
-            const int y = pf(x) + R - 1 - pl(x + 1) + (pl(x + 1) <= FM1 ? NST : 0);
-            mn = y < mn ? y : mn;
-        }
-        return mn > 63 ? 63 : mn;
-    }
 };
 
-// NT: the encode's parity stores are non-temporal (decode stores plain).  SK: see RingShape.
+// Encode only: the coefficients are cauchy_const.h's at compile time, every group stores its RC
+// parity rows.  (The rolled run-time-coefficient decode this schedule once carried measured
+// slower than gf_stream_kernel's, DESIGN.md section 3.3, and is gone.)
+// NT: the parity stores are non-temporal.  SK: see RingShape.
 // A group whose size is 8 mod 16 is streamed as GBS = GB + 8 bytes from the 16-byte boundary
 // at or below its start; the loads then go through a buffer resource bounded by the end of
 // the input (the last group's stream may end 8 bytes past it: those lanes read zeros).
-// NCH > 1 (encode): a group's MC parity rows are NCH chunks of RC rows, one unit each; unit
+// NCH > 1: a group's MC parity rows are NCH chunks of RC rows, one unit each; unit
 // u = NCH * g + ch, and a wave's units u0, u0 + W, ... (W a multiple of NCH) all have chunk
 // Y0 / RC = u0 % NCH, so the chunk's rows are compile-time; the NCH units of a group run on
 // neighbouring waves, whose reads of the group meet in L2.
-template <int K, int S, int RC, bool DECODE, int MC, bool NT, int SK, bool WIDE, int NCH = 1,
-          int Y0 = 0>
-__device__ __forceinline__ void gf_ring_run(
-    const uint8_t* in, uint8_t* out, const uint8_t* __restrict__ coef,
-    const uint8_t* __restrict__ slots, const int32_t* __restrict__ nout, long long groups,
-    int rmax, long long coef_gstride, long long out_gstride, uint8_t* smem) {
+template <int K, int S, int RC, int MC, bool NT, int SK, bool WIDE, int NCH = 1, int Y0 = 0>
+__device__ __forceinline__ void gf_ring_run(const uint8_t* in, uint8_t* out, long long groups,
+                                            long long out_gstride, uint8_t* smem) {
     using SH = RingShape<S, SK>;
-    constexpr int R = SH::R, RB = SH::RB, BB = SH::BB, NW = SH::NW, NWF = SH::NWF;
+    constexpr int R = SH::R, RB = SH::RB, BB = SH::BB, NW = SH::NW;
     constexpr int GB = K * BB;
     constexpr bool SKEW = GB % 16 != 0;
     constexpr int GBS = (GB + 15) / 16 * 16;              // stream bytes per group
@@ -507,13 +408,11 @@ __device__ __forceinline__ void gf_ring_run(
     static_assert(SKEW ? GB % 16 == 8 : SK == 0, "groups 0 or 8 bytes off 16");
     // stores per group, fixed: 8 sub-rows x SPR per output, or (WIDE) 3 runs of 512 bytes
     constexpr int NST = WIDE ? RC * 3 : RC * 8 * SH::SPR;
-    static_assert(!WIDE || (S == 169 && !DECODE), "wide stores: 1352-byte encode blocks");
-    constexpr int RCP = RC < 4 ? 4 : RC, NCW = RCP / 4;
-    constexpr int SAUX = (DECODE || !NT) ? 0 : 2;         // encode's parity stream: nt
+    static_assert(!WIDE || S == 169, "wide stores: 1352-byte blocks");
+    constexpr int SAUX = NT ? 2 : 0;                      // the parity stream: nt
     constexpr int FM1 = SH::pf(K - 1) + R - 1 - NP;       // next-group pieces issued early
-    static_assert(!DECODE || MC == 0, "decode coefficients are per group");
-    static_assert(DECODE || MC == RC * NCH, "encode: one output per register set");
-    static_assert(NCH == 1 || (!DECODE && Y0 % RC == 0 && Y0 < MC), "chunked encode");
+    static_assert(MC == RC * NCH, "one output per register set");
+    static_assert(NCH == 1 || (Y0 % RC == 0 && Y0 < MC), "chunked encode");
     static_assert(FM1 >= SH::pl(0), "block 0 of the next group is prefetched in full");
     static_assert(SH::pf(K - 1) + R - 1 < 2 * NP, "the frontier stays within the next group");
     const int lane = threadIdx.x & 63;
@@ -549,10 +448,10 @@ __device__ __forceinline__ void gf_ring_run(
             const long long left = in_end - b;
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
                 (void*)b, 0, (unsigned)(left < 1024 ? left : 1024), 0x00020000);
-            stream_dma16<LAUX>(rs, ring + slot * 1024, p == NP - 1 ? vlast : v16);
+            dma16<LAUX>(rs, ring + slot * 1024, p == NP - 1 ? vlast : v16);
         } else {
             const int off = min(p * 1024 + lane * 16, GBS - 16);
-            __builtin_amdgcn_global_load_lds(QS_GPTR(src + off), QS_LPTR(ring + slot * 1024), 16,
+            __builtin_amdgcn_global_load_lds(QS_GPTR(src + off), QF_LPTR(ring + slot * 1024), 16,
                                              0, LAUX);
         }
     };
@@ -568,18 +467,7 @@ __device__ __forceinline__ void gf_ring_run(
             dma(next ? gsrc + gstep : gsrc, next ? n - NP : NP - 1, (phase + n) & (R - 1));
         }
     };
-    // the same for a run-time piece index (rolled decode loop)
-    auto issue_rt = [&](int n) __attribute__((always_inline)) {
-        const uint8_t* src = gsrc;
-        int p = n;
-        if (n >= NP) {
-            const bool next = i + 1 < cnt;
-            src = next ? gsrc + gstep : gsrc;
-            p = next ? n - NP : NP - 1;
-        }
-        dma(src, p, (phase + n) & (R - 1));
-    };
-    // block x (an int or an integral_constant) at ring byte (phase * 1024 + x * BB) mod RB
+    // block x (compile time) at ring byte (phase * 1024 + x * BB) mod RB
     auto read_block = [&](auto xc, uint32_t (&lo)[8], uint32_t (&hi)[8])
                           __attribute__((always_inline)) {
         const int x = xc;
@@ -587,14 +475,7 @@ __device__ __forceinline__ void gf_ring_run(
         asm volatile("" : "+v"(c4));   // opaque: addresses are not hoisted across blocks
         uint32_t bp = ((uint32_t)phase * 1024u + (uint32_t)(SK + x * BB)) & (uint32_t)(RB - 1);
         if (bp + (uint32_t)BB + 4u <= (uint32_t)RB) {
-            const uint8_t* L = ring + bp + c4;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int o = t * S;
-                const uint32_t* q = (const uint32_t*)(L + (o & ~3));
-                lo[t] = q[0];
-                hi[t] = (o & 3) ? q[1] : 0u;
-            }
+            read_subrows<S>(ring + bp + c4, lo, hi);
         } else {
             const uint32_t base = bp + c4;
 #pragma unroll
@@ -619,26 +500,22 @@ __device__ __forceinline__ void gf_ring_run(
     // buffer store across a DMA (it may: they touch different memory).
     asm volatile("" ::: "memory");
     {
-        const __amdgpu_buffer_rsrc_t none = __builtin_amdgcn_make_buffer_rsrc(out, 0, 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t none = pad_rsrc(out);
 #pragma unroll
-        for (int q = 0; q < NST; ++q)   // distinct offsets: not merged as duplicate stores
-            __builtin_amdgcn_raw_buffer_store_b32(0u, none, 0u, 4 * q, 0);
+        for (int q = 0; q < NST; ++q) pad_store(none, q);
     }
 
     uint32_t lo0[8], hi0[8], lo1[8], hi1[8];
 #pragma unroll 1
     for (; i < cnt; ++i) {
         const long long g = g0 + i * W;
-        int n = DECODE ? nout[g] : RC;
-        n = n > RC ? RC : n;
-        const uint32_t* cw = (const uint32_t*)(coef + (DECODE ? g * coef_gstride : 0));
         uint32_t acc[RC][8];
 #pragma unroll
         for (int j = 0; j < RC; ++j)
 #pragma unroll
             for (int r = 0; r < 8; ++r) acc[j][r] = 0;
         // block 0: its pieces were issued before the previous group's stores
-        stream_wait_vmcnt<(FM1 - SH::pl(0) + NST > 63 ? 63 : FM1 - SH::pl(0) + NST)>();
+        wait_vmcnt<(FM1 - SH::pl(0) + NST > 63 ? 63 : FM1 - SH::pl(0) + NST)>();
         read_block(std::integral_constant<int, 0>{}, lo0, hi0);
 
         auto step = [&](auto xc, uint32_t (&lo)[8], uint32_t (&hi)[8], uint32_t (&nlo)[8],
@@ -652,100 +529,32 @@ __device__ __forceinline__ void gf_ring_run(
             if constexpr (x + 1 < K) {
                 constexpr int pl1 = SH::pl(x + 1);
                 constexpr int yng = F1 - pl1 + (pl1 <= FM1 ? NST : 0);
-                stream_wait_vmcnt<(yng > 63 ? 63 : yng)>();
+                wait_vmcnt<(yng > 63 ? 63 : yng)>();
                 read_block(std::integral_constant<int, x + 1>{}, nlo, nhi);
             }
-            if (DECODE && n <= 0) return;   // no loss in this group: nothing to combine
             WZ v;
 #pragma unroll
-            for (int t = 0; t < 8; ++t) {
-                const int o = t * S;
-                v.W[t] = (o & 3) ? __builtin_amdgcn_alignbyte(hi[t], lo[t], o & 3) : lo[t];
-            }
-            if constexpr (!DECODE) {
-                Win win;
-                win_build(v.W8, win);
-                static_for<RC>([&](auto jc) __attribute__((always_inline)) {
-                    constexpr int j = decltype(jc)::value;
-                    win_apply<cauchy_coef(MC, Y0 + j, x)>(acc[j], win);
-                });
-            } else {
-                uint32_t cwv[NCW];
-#pragma unroll
-                for (int q = 0; q < NCW; ++q) cwv[q] = cw[x * NCW + q];
-                expand_wz(v);
-#pragma unroll
-                for (int j = 0; j < RC; ++j) {
-                    if (j < n) {
-                        const uint32_t cf = (cwv[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-                        apply_nibble<0>(acc[j], cf & 15u, v);
-                        apply_nibble<4>(acc[j], cf >> 4, v);
-                    }
-                }
-            }
-        };
-        if constexpr (!DECODE) {
-            static_for<K>([&](auto xc) __attribute__((always_inline)) {
-#pragma unroll
-                for (int j = 0; j < RC; ++j)
-#pragma unroll
-                    for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(acc[j][r]));
-                if constexpr (decltype(xc)::value % 2 == 0) step(xc, lo0, hi0, lo1, hi1);
-                else step(xc, lo1, hi1, lo0, hi0);
+            for (int t = 0; t < 8; ++t) v.W[t] = realign_word<S>(lo, hi, t);
+            Win win;
+            win_build(v.W8, win);
+            static_for<RC>([&](auto jc) __attribute__((always_inline)) {
+                constexpr int j = decltype(jc)::value;
+                win_apply<cauchy_coef(MC, Y0 + j, x)>(acc[j], win);
             });
-        } else {
-            // Decode: run-time coefficients make an unrolled group long (~30K instructions,
-            // past the instruction cache's comfort); the rolled loop issues the same pieces
-            // (frontier pf(x) + R - 1) and waits with the smallest younger count any block
-            // sees, a constant: conservative by at most one piece.
-            constexpr int WMIN = SH::min_younger(K, NST);
-            int fr = FM1;                                  // pieces issued so far (last index)
-            // coefficient rows two blocks ahead (scalar loads have a long latency; the
-            // value for block x is loaded while block x - 2 is combined)
-            static_assert(NCW == 1, "rmax <= 4: one coefficient dword per block");
-            uint32_t cA = cw[0], cB = cw[1];
-            auto rstep = [&](int x, uint32_t (&lo)[8], uint32_t (&hi)[8], uint32_t (&nlo)[8],
-                             uint32_t (&nhi)[8], uint32_t& cc) __attribute__((always_inline)) {
-                const int f1 = ((x * BB) >> 10) + R - 1;
-                for (; fr < f1; ++fr) issue_rt(fr + 1);
-                if (x + 1 < K) {
-                    stream_wait_vmcnt<WMIN>();
-                    read_block(x + 1, nlo, nhi);
-                }
-                if (n <= 0) return;   // no loss in this group: nothing to combine
-                WZ v;
+        };
+        static_for<K>([&](auto xc) __attribute__((always_inline)) {
 #pragma unroll
-                for (int t = 0; t < 8; ++t) {
-                    const int o = t * S;
-                    v.W[t] = (o & 3) ? __builtin_amdgcn_alignbyte(hi[t], lo[t], o & 3) : lo[t];
-                }
-                const uint32_t cwv = cc;
-                cc = cw[min(x + 2, K - 1)];
-                expand_wz(v);
+            for (int j = 0; j < RC; ++j)
 #pragma unroll
-                for (int j = 0; j < RC; ++j) {
-                    if (j < n) {
-                        const uint32_t cf = (cwv >> (8 * (j & 3))) & 0xFFu;
-                        apply_nibble<0>(acc[j], cf & 15u, v);
-                        apply_nibble<4>(acc[j], cf >> 4, v);
-                    }
-                }
-            };
-            static_assert(K % 2 == 0, "register double buffer parity");
-#pragma unroll 1
-            for (int x = 0; x < K; x += 2) {
-                rstep(x, lo0, hi0, lo1, hi1, cA);
-                rstep(x + 1, lo1, hi1, lo0, hi0, cB);
-            }
-        }
+                for (int r = 0; r < 8; ++r) asm volatile("" : "+v"(acc[j][r]));
+            if constexpr (decltype(xc)::value % 2 == 0) step(xc, lo0, hi0, lo1, hi1);
+            else step(xc, lo1, hi1, lo0, hi0);
+        });
 
-        // ---- outputs: NST store instructions whatever n is (unused outputs: empty range),
-        // kept after the last step's DMAs and before the next group's (issue order)
+        // ---- outputs: NST store instructions, kept after the last step's DMAs and before the
+        // next group's (issue order)
         asm volatile("" ::: "memory");
         if constexpr (WIDE) {
-            // each parity block staged in LDS as its contiguous bytes (stage_block_169), read
-            // back as 3 x 512 bytes and stored as 8-byte lanes (past the block: dropped by the
-            // buffer range)
             const uint32_t ra = stage + 8u * (uint32_t)lane;
 #pragma unroll
             for (int j = 0; j < RC; ++j) {
@@ -753,51 +562,24 @@ __device__ __forceinline__ void gf_ring_run(
                 const __amdgpu_buffer_rsrc_t rs =
                     __builtin_amdgcn_make_buffer_rsrc(dst, 0, (unsigned)BB, 0x00020000);
                 if (lane < NW) stage_block_169(stage, acc[j], lane);
-                uint64_t v0, v1, v2;
-                asm volatile("ds_read_b64 %0, %3\n\t"
-                             "ds_read_b64 %1, %3 offset:512\n\t"
-                             "ds_read_b64 %2, %3 offset:1024\n\t"
-                             "s_waitcnt lgkmcnt(0)"
-                             : "=&v"(v0), "=&v"(v1), "=&v"(v2)
-                             : "v"(ra)
-                             : "memory");
-                const uint64_t vv[3] = {v0, v1, v2};
-#pragma unroll
-                for (int h = 0; h < 3; ++h)
-                    __builtin_amdgcn_raw_buffer_store_b64(qf_u32x2(vv[h]), rs,
-                                                          512u * h + 8u * (uint32_t)lane, 0, SAUX);
+                store_staged_169<SAUX>(rs, ra, lane);
             }
-            asm volatile("" ::: "memory");
-            gsrc += gstep;
-            phase = (phase + NP) & (R - 1);
-            continue;
-        }
-        uint32_t vo = lane < NWF ? 4u * (uint32_t)c : kSDrop;
-        uint32_t vt = lane == NWF && NWF < NW ? 4u * (uint32_t)c : kSDrop;
-        asm volatile("" : "+v"(vo), "+v"(vt));
+        } else {
+            const SubrowLanes sl = subrow_lanes(lane, c, NW, SH::NWF);
 #pragma unroll
-        for (int j = 0; j < RC; ++j) {
-            const bool on = j < n;
-            const int oslot = (DECODE && slots) ? (on ? sload_u8(slots, g * rmax + j) : 0) : Y0 + j;
-            uint8_t* dst = out + g * out_gstride + (long long)oslot * BB;
-            const __amdgpu_buffer_rsrc_t rs =
-                __builtin_amdgcn_make_buffer_rsrc(dst, 0, on ? (unsigned)BB : 0u, 0x00020000);
+            for (int j = 0; j < RC; ++j) {
+                uint8_t* dst = out + g * out_gstride + (long long)(Y0 + j) * BB;
+                const __amdgpu_buffer_rsrc_t rs =
+                    __builtin_amdgcn_make_buffer_rsrc(dst, 0, (unsigned)BB, 0x00020000);
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const uint32_t vsum = acc[j][r];
-                __builtin_amdgcn_raw_buffer_store_b32(vsum, rs, vo, r * S, SAUX);
-                if (S & 2)
-                    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)vsum, rs, vt, r * S, SAUX);
-                if (S & 1)
-                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(vsum >> (8 * (S & 2))), rs, vt,
-                                                         r * S + (S & 2), SAUX);
+                for (int r = 0; r < 8; ++r) store_subrow<S, SAUX>(rs, acc[j][r], r, sl);
             }
         }
         asm volatile("" ::: "memory");
         gsrc += gstep;
         phase = (phase + NP) & (R - 1);
     }
-    stream_wait_vmcnt<0>();
+    wait_vmcnt<0>();
 }
 
 #ifndef QF_RING_SKEW_INLINE
@@ -806,50 +588,41 @@ __device__ __forceinline__ void gf_ring_run(
 #ifndef QF_RING_ATTR
 #define QF_RING_ATTR
 #endif
-template <int K, int S, int RC, bool DECODE, int MC, bool NT, bool WIDE, int NCH, int Y0>
-__device__ QF_RING_SKEW_INLINE void gf_ring_skew(
-    const uint8_t* in, uint8_t* out, const uint8_t* __restrict__ coef,
-    const uint8_t* __restrict__ slots, const int32_t* __restrict__ nout, long long groups,
-    int rmax, long long coef_gstride, long long out_gstride, uint8_t* smem) {
+template <int K, int S, int RC, int MC, bool NT, bool WIDE, int NCH, int Y0>
+__device__ QF_RING_SKEW_INLINE void gf_ring_skew(const uint8_t* in, uint8_t* out, long long groups,
+                                                 long long out_gstride, uint8_t* smem) {
     if constexpr ((K * 8 * S) % 16 == 0) {
-        gf_ring_run<K, S, RC, DECODE, MC, NT, 0, WIDE, NCH, Y0>(in, out, coef, slots, nout, groups,
-                                                              rmax, coef_gstride, out_gstride, smem);
+        gf_ring_run<K, S, RC, MC, NT, 0, WIDE, NCH, Y0>(in, out, groups, out_gstride, smem);
     } else {
         // group g starts 8 * (g & 1) bytes past a 16-byte boundary; a wave's groups g0,
         // g0 + W, ... (W = 4 x the grid / NCH, even) all share g0's skew
         const long long g0 = ((long long)blockIdx.x * kRingWaves + wave_id()) / NCH;
         if (g0 & 1)
-            gf_ring_run<K, S, RC, DECODE, MC, NT, 8, WIDE, NCH, Y0>(in, out, coef, slots, nout,
-                                                                  groups, rmax, coef_gstride,
-                                                                  out_gstride, smem);
+            gf_ring_run<K, S, RC, MC, NT, 8, WIDE, NCH, Y0>(in, out, groups, out_gstride, smem);
         else
-            gf_ring_run<K, S, RC, DECODE, MC, NT, 0, WIDE, NCH, Y0>(in, out, coef, slots, nout,
-                                                                  groups, rmax, coef_gstride,
-                                                                  out_gstride, smem);
+            gf_ring_run<K, S, RC, MC, NT, 0, WIDE, NCH, Y0>(in, out, groups, out_gstride, smem);
     }
 }
 
-// NCH: parity-row chunks per group (encode; RC = MC / NCH rows each, chunk = the wave's unit
-// index mod NCH)
+// NCH: parity-row chunks per group (RC = MC / NCH rows each, chunk = the wave's unit index
+// mod NCH).  DECODE is always false: the bench's counter summaries tell encode from decode
+// kernels by this template argument's position, so it stays.  The arguments between `out` and
+// `groups`, and rmax and coef_gstride, are the common launch signature; the encode reads none.
 template <int K, int S, int RC, bool DECODE, int MC, bool NT = true, bool WIDE = false, int NCH = 1>
 __global__ __launch_bounds__(kRingWaves * 64) QF_RING_ATTR void gf_ring_kernel(
     const uint8_t* in, uint8_t* out, const uint8_t* __restrict__ coef,
     const uint8_t* __restrict__ slots, const int32_t* __restrict__ nout, long long groups,
     int rmax, long long coef_gstride, long long out_gstride) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    static_assert(!DECODE, "the static ring schedule is an encode");
     static_assert(NCH == 1 || NCH == 2, "one or two chunks");
     if constexpr (NCH == 1) {
-        gf_ring_skew<K, S, RC, DECODE, MC, NT, WIDE, 1, 0>(in, out, coef, slots, nout, groups,
-                                                         rmax, coef_gstride, out_gstride, smem);
+        gf_ring_skew<K, S, RC, MC, NT, WIDE, 1, 0>(in, out, groups, out_gstride, smem);
     } else {
         if ((blockIdx.x * kRingWaves + wave_id()) & 1)
-            gf_ring_skew<K, S, RC, DECODE, MC, NT, WIDE, 2, RC>(in, out, coef, slots, nout,
-                                                              groups, rmax, coef_gstride,
-                                                              out_gstride, smem);
+            gf_ring_skew<K, S, RC, MC, NT, WIDE, 2, RC>(in, out, groups, out_gstride, smem);
         else
-            gf_ring_skew<K, S, RC, DECODE, MC, NT, WIDE, 2, 0>(in, out, coef, slots, nout,
-                                                             groups, rmax, coef_gstride,
-                                                             out_gstride, smem);
+            gf_ring_skew<K, S, RC, MC, NT, WIDE, 2, 0>(in, out, groups, out_gstride, smem);
     }
 }
 
@@ -912,21 +685,15 @@ hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef
     const int nchunk = decode ? (rmax + rc - 1) / rc
                               : (compiled || m <= 8 || (rc == 16 && m <= 16)) ? 1 : (m + 7) / 8;
     const long long units = groups * nchunk;
-    const long long want = (units + kStreamWaves - 1) / kStreamWaves;
-    long long cap = (long long)t.cus * per_cu;
     // oversubscribed: about swg units per wave ((250, 5) decode 5.02 -> 4.36 ms, DESIGN.md
     // section 4.5); large groups only by default
     const int swg = t.stream_wg >= 0 ? t.stream_wg : ((long long)k * bb >= 65536 ? 1 : 0);
-    if (swg > 0) cap = (units + (long long)kStreamWaves * swg - 1) / ((long long)kStreamWaves * swg);
-    if (t.stream_grid > 0) cap = t.stream_grid;          // tests: many groups per wave
-    const unsigned grid = (unsigned)std::min<long long>(want, cap);
+    // the wave's 32-bit piece counter counts cnt * NP pieces
+    const unsigned grid =
+        persistent_grid(units, kStreamWaves, (long long)t.cus * per_cu, swg, t.stream_grid,
+                        ((long long)k * bb + 8 + 1023) / 1024);
+    if (!grid) return hipErrorInvalidValue;
     const unsigned threads = kStreamWaves * 64;
-    // the wave's 32-bit piece counters: cnt * NP, and (gf_ring) cnt groups
-    {
-        const long long waves = (long long)grid * kStreamWaves;
-        const long long np = ((long long)k * bb + 8 + 1023) / 1024;
-        if ((units + waves - 1) / waves * np >= (1LL << 31)) return hipErrorInvalidValue;
-    }
 #define QS_GO(RCV, SV, DEC, RCPV, KCV)                                                        \
     qlaunch((gf_stream_kernel<RCV, SV, DEC, RCPV, KCV>), dim3(grid), dim3(threads), \
                        lds, st, in, out, coef, slots, nout, groups, k, m, rmax, coef_gstride,   \
@@ -961,8 +728,8 @@ hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef
         case 8: QS_GO(8, SV, false, 8, 0); break;         \
         default: QS_GO(8, SV, false, 8, 0); break;        \
     }
-    // the static ring schedule is used for the encode only: its rolled decode measured
-    // slower than gf_stream's (0.644 vs 0.619 ms on config B)
+    // the static ring schedule is an encode only: a rolled decode on it measured slower than
+    // gf_stream's (0.644 vs 0.619 ms on config B)
     const bool ring_shape = (k == 32 && m == 4) || (k == 10 && (m == 10 || m == 15 || m == 20)) ||
                             (k == 250 && m == 5) || (k == 15 && m == 15) || (k == 5 && m == 5);
     if (t.stream_static && !decode && s == 169 && ring_shape && t.const_enc) {
@@ -978,22 +745,16 @@ hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef
         const bool rwide = t.ring_wide && !(k == 32 && m == 4) && (rsplit || !(k == 10 && m == 20)) &&
                            (((uintptr_t)out | (uintptr_t)out_gstride) & 7) == 0;
         const size_t rlds = (size_t)kRingWaves * (RingShape<169>::RB + (rwide ? kStreamStage : 0));
-        const long long rwant = (groups * (rsplit ? 2 : 1) + kRingWaves - 1) / kRingWaves;
-        long long rcap = (long long)t.cus * (int)((160 * 1024) / rlds);
         // oversubscribed: about rwg units per wave; measured faster for these encodes
         // (B 0.58 -> 0.55 ms, (10,10) 0.361 -> 0.330; (10,20) and (15,15) no better,
         // DESIGN.md section 4.5)
         const int rwg = t.ring_wg >= 0 ? t.ring_wg
                         : ((k == 32 && m == 4) || (k == 10 && m == 10) || (k == 5 && m == 5) ||
                            (k == 250 && m == 5)) ? 1 : 0;
-        if (rwg > 0)
-            rcap = (groups * (rsplit ? 2 : 1) + (long long)kRingWaves * rwg - 1) /
-                   ((long long)kRingWaves * rwg);
-        if (t.stream_grid > 0) rcap = t.stream_grid;
-        const unsigned rgrid = (unsigned)std::min<long long>(rwant, rcap);
-        if ((groups * (rsplit ? 2 : 1) + (long long)rgrid * kRingWaves - 1) / ((long long)rgrid * kRingWaves) >=
-            (1LL << 31))
-            return hipErrorInvalidValue;
+        const unsigned rgrid = persistent_grid(groups * (rsplit ? 2 : 1), kRingWaves,
+                                               (long long)t.cus * (int)((160 * 1024) / rlds), rwg,
+                                               t.stream_grid);
+        if (!rgrid) return hipErrorInvalidValue;
         if (rsplit) {
             note_kernel("gf_ring_kernel<encode,k10m20,split>");
             if (rwide)

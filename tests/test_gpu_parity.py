@@ -742,7 +742,7 @@ def test_config_d_full_size_round_trip(engine, oracle):
 
 
 # ------------------------------------------------- gf_stream at other block sizes
-@pytest.mark.parametrize("bb", [1344, 1000, 520, 136, 2048, 8, 1352])
+@pytest.mark.parametrize("bb", [1344, 1000, 520, 136, 2048, 8, 1352, 48, 56, 1360, 1336])
 @pytest.mark.parametrize("k,m,r", [(32, 4, 2), (10, 3, 3), (6, 8, 5), (5, 5, 4), (15, 12, 11)])
 def test_stream_any_small_block(engine, oracle, bb, k, m, r):
     """Groups whose padded blocks are at most 2 KiB (quic_fec_group.cc:344-352 pads to the

@@ -42,7 +42,8 @@ def stream_isa(tmp_path_factory, request):
         inputs += [f for f in first.split(":", 1)[1].split() if os.path.exists(f)]
     else:
         inputs += [os.path.join(csrc, h) for h in ("fec_kernels.h", "gf_bitslice.h", "gf256.h",
-                                                   "gf_dcol.h", "gf_psyn.h", "gf_winjump.h")]
+                                                   "gf_dcol.h", "gf_psyn.h", "gf_winjump.h",
+                                                   "gf_counted.h")]
     if os.path.exists(built) and all(os.path.getmtime(built) >= os.path.getmtime(f)
                                      for f in inputs):
         out = built
