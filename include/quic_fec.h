@@ -371,7 +371,9 @@ QFEC_API const char *qfec_last_kernels(void);
 /* Grids of the persistent kernels the last call on this thread launched, as space-separated
  * "kernel=workgroups" entries (e.g. "gf_psyn_kernel=1024"); diagnostics and tests.  The general
  * decode prep reports "decode_prep_kernel": its workgroups hold 4, 2 or 1 groups each as the
- * min(k, m)^2 solve scratch fills the LDS. */
+ * min(k, m)^2 solve scratch fills the LDS.  The m = 1 LDS-ring kernel reports "xor_dma_kernel"
+ * for its encode and every decode variant: at most one workgroup per CU, or with the xor_wg
+ * option about xor_wg groups per wave. */
 QFEC_API const char *qfec_last_grids(void);
 /* Measurement hook (bench.py's roofline timing).  While set, every engine call on this
  * thread records start_event (a hipEvent_t) at the start of its first kernel and

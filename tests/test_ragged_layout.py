@@ -50,6 +50,62 @@ def test_layout_random_matches_running_sum():
     assert fec.ragged_layout(4, 2, [])[3] == (0, 0, 0)
 
 
+def test_layout_past_4gib_matches_python_sums():
+    """40,000 groups of (128, 16): every buffer's total and most of its offsets need more than
+    32 bits (data 1.5e10 bytes); they equal running sums kept in Python integers."""
+    k, m, G = 128, 16, 40000
+    bb = np.resize(np.array([1352, 1350, 9000, 1, 1352], np.int32), G)
+    d, p, r, tot = fec.ragged_layout(k, m, bb)
+    assert r.tolist() == p.tolist()
+    for off, n, t in ((d, k, tot[0]), (p, m, tot[1])):
+        run, exp = 0, []
+        for b in bb.tolist():
+            exp.append(run)
+            run = up16(run + n * b)
+        assert off.tolist() == exp
+        assert t == run
+    assert tot[0] > 3 * 2**32 and d[-1] > 3 * 2**32 and int((d >= 2**32).sum()) > G // 2
+    # uniform (128, 16) x 1352: offsets are g * k * bb, past 2^32 from group 24,819 on
+    d, p, r, tot = fec.ragged_layout(k, m, np.full(G, 1352, np.int32))
+    assert d.tolist() == [g * k * 1352 for g in range(G)]
+    assert tot == (G * k * 1352, G * m * 1352, G * m * 1352) and tot[0] == 6_922_240_000
+
+
+def test_layout_overflow_returns_minus_two():
+    """Block sizes near 2^31 - 1 with k = 255: about 1.7e7 of them pass 2^63 bytes of data.  The
+    longest array whose running sum (with its last round-up) still fits is laid out exactly; one
+    more entry returns -2 and writes no total, instead of wrapping."""
+    k, m, top = 255, 1, 2**31 - 1
+    sizes = [top - j for j in range(7)]                  # cycled
+    steps = [up16(k * b) for b in sizes]
+
+    def run_after(n):                                    # the data total of the first n entries
+        return (n // 7) * sum(steps) + sum(steps[:n % 7])
+
+    def entry_fits(n):                                   # entry n (0-based) on top of run_after(n)
+        return run_after(n) + k * sizes[n % 7] + 15 <= 2**63 - 1
+    n_ok = 2**63 // max(steps) - 8
+    while entry_fits(n_ok):
+        n_ok += 1                                        # entries 0 .. n_ok - 1 fit
+    assert 16_800_000 < n_ok < 16_900_000
+    bb = np.resize(np.array(sizes, np.int32), n_ok + 1)
+    L = fec.load()
+    tot = np.full(3, -7, np.int64)
+    assert L.qfec_ragged_layout(k, m, n_ok, bb.ctypes.data, None, None, None, tot.ctypes.data) == 0
+    assert int(tot[0]) == run_after(n_ok) and 2**63 - 2**40 < int(tot[0]) < 2**63
+    assert int(tot[1]) == int(tot[2])
+    assert int(tot[1]) == (n_ok // 7) * sum(up16(b) for b in sizes) + sum(up16(b) for b in sizes[:n_ok % 7])
+    tot[:] = -7
+    assert L.qfec_ragged_layout(k, m, n_ok + 1, bb.ctypes.data, None, None, None,
+                                tot.ctypes.data) == -2
+    assert tot.tolist() == [-7, -7, -7]
+    with pytest.raises(ValueError):
+        fec.ragged_layout(k, m, bb)
+    one = np.array([top], np.int32)
+    assert L.qfec_ragged_layout(k, m, 1, one.ctypes.data, None, None, None, tot.ctypes.data) == 0
+    assert int(tot[0]) == up16(k * top)
+
+
 def test_layout_rejects_bad_sizes():
     L = fec.load()
     bb = np.array([8, 0, 8], np.int32)
