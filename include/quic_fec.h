@@ -347,6 +347,107 @@ QFEC_API int qfec_open_decode_batch_host(qfec_ctx *ctx, int k, int m, int block_
                                          int *h_status, int *h_open_len);
 
 /* ---------------------------------------------------------------------------------
+ * Ragged packet protection: the protected paths above over ragged batches, a block size per
+ * group.  Real groups do not share a block_bytes, so a sender or receiver would otherwise make
+ * one protected call per distinct size, or run the ragged codec and the per-packet seal / open
+ * separately and place the plaintexts by hand.
+ *
+ * Rule: per group, a ragged call does what the uniform call with block_bytes = bb[g] does to
+ * that group.  Only the blocks are packed (the layout of the ragged batches above: group g's
+ * blocks [n][bb[g]] at base + off[g], offsets multiples of 16, base pointers 16-byte aligned,
+ * gaps never written).  Headers, packets and every per-packet array stay dense by packet
+ * index p = g*(k+m) + i with one stride, rows [G][k], rec_rows [G][min(k,m)] and status [G]
+ * stay dense, as in the uniform calls.  What the rule fixes:
+ *   - d_pt_len == NULL: every packet's plaintext is its whole block, bb[g] bytes (there is no
+ *     pt_len_all: no one length fits every group).
+ *   - d_pt_len[p] > bb[g] rejects packet p: d_pkt_len[p] = -1 and nothing is written, as a
+ *     length beyond its row is rejected by the uniform seal.
+ *   - encode + seal, a group whose encode status is -1 (m > 1, k > 1 and bb[g] % 8 != 0; one
+ *     predicate asked by the encode and by the seal): none of its k + m packets is sealed,
+ *     all of its d_pkt_len entries are -1, its d_status is -1, and its first parity block
+ *     holds the XOR parity, exactly as qfec_encode_batch_ragged leaves it.  Every other
+ *     group's d_status is 0.  The call itself returns 0.
+ *   - bb[g] < 1: the device calls never read d_bb back, so the group is skipped by the
+ *     kernels: its packets get d_pkt_len -1 on the seals and d_open_len -1 on the open, and
+ *     on the open its rows are 255, its status is -3 and its rec_rows are 255.  Nothing of it
+ *     is written and its neighbours are unaffected.  (The host forms read h_bb and return -2.)
+ *   - open -> decode: a packet whose plaintext is longer than bb[g] is rejected
+ *     (d_open_len -1); the destination of slot s is d_blocks + d_blocks_off[g] + s*bb[g],
+ *     zero-padded to bb[g].  A slot tagged 255 is not written, unless a packet that passed
+ *     the length checks and then failed its tag had been streamed into it (the open writes
+ *     before the tag is known, as in the uniform call: those bytes are unspecified).  The
+ *     decode is
+ *     qfec_decode_batch_ragged_recovered on what the open placed, and all its per-group
+ *     statuses carry over: -1 for m > 1 with bb[g] % 8 != 0 and a recovery block, -3 for a
+ *     malformed set (an unfilled slot included).
+ *     bb[g] is the caller's.  A receiver takes it from the plaintext length of the group's
+ *     FEC packets (an FEC packet's plaintext is a whole block); the reference sizes a group's
+ *     recovery by the largest packet it stored (quic_fec_group.cc:264-265).
+ *   - call-level limits, -2 before anything is enqueued: k + m > 256 on the seals, k + m > 255
+ *     on the open, groups < 0, a null buffer (d_hdr, d_hdr_len, d_pt_len, d_ad_len and d_status
+ *     may be NULL as in the uniform calls), a base pointer that is not 16-byte aligned, and on
+ *     the seals a d_pkt or pkt_stride that is not 4-byte aligned.
+ *   - workspace, streams, graphs: the seals use no workspace; the open -> decode runs in the
+ *     decode-workspace bracket like every decode, so everything said above about streams,
+ *     contexts and captured graphs holds unchanged, and qfec_reserve(ctx, k, m, largest bb,
+ *     groups) covers a capture as it does for qfec_decode_batch_ragged_recovered.
+ * Launches: qfec_seal_groups_batch_ragged one; qfec_encode_seal_groups_batch_ragged the
+ * ragged encode's and one; qfec_open_decode_batch_ragged two, the ragged decode's, and one.
+ * ------------------------------------------------------------------------------- */
+/* qfec_seal_groups_batch per group: packet p's plaintext is block i of d_data + d_data_off[g]
+ * ([k][bb[g]]) for i < k, block i-k of d_parity + d_par_off[g] ([m][bb[g]]) otherwise. */
+QFEC_API int qfec_seal_groups_batch_ragged(qfec_ctx *ctx, int k, int m, long long groups,
+                                           const int *d_bb, const unsigned char *d_data,
+                                           const long long *d_data_off,
+                                           const unsigned char *d_parity,
+                                           const long long *d_par_off,
+                                           const unsigned char *d_hdr, long long hdr_stride,
+                                           const int *d_hdr_len, int hdr_len_all,
+                                           const int *d_pt_len, unsigned char *d_pkt,
+                                           long long pkt_stride, int *d_pkt_len, void *stream);
+/* qfec_encode_batch_ragged into d_parity (d_status [G], may be NULL), then the seal above. */
+QFEC_API int qfec_encode_seal_groups_batch_ragged(qfec_ctx *ctx, int k, int m, long long groups,
+                                                  const int *d_bb, const unsigned char *d_data,
+                                                  const long long *d_data_off,
+                                                  unsigned char *d_parity,
+                                                  const long long *d_par_off,
+                                                  const unsigned char *d_hdr,
+                                                  long long hdr_stride, const int *d_hdr_len,
+                                                  int hdr_len_all, const int *d_pt_len,
+                                                  unsigned char *d_pkt, long long pkt_stride,
+                                                  int *d_pkt_len, int *d_status, void *stream);
+/* qfec_open_decode_batch per group: d_blocks + d_blocks_off[g] receives [k][bb[g]], d_rec +
+ * d_rec_off[g] up to [min(k,m)][bb[g]]; d_rows, d_open_len, d_rec_rows, d_status as there. */
+QFEC_API int qfec_open_decode_batch_ragged(qfec_ctx *ctx, int k, int m, long long groups,
+                                           const int *d_bb, const unsigned char *d_pkt,
+                                           long long pkt_stride, const int *d_pkt_len,
+                                           const int *d_ad_len, int ad_len_all,
+                                           unsigned char *d_blocks,
+                                           const long long *d_blocks_off, unsigned char *d_rows,
+                                           int *d_open_len, unsigned char *d_rec,
+                                           const long long *d_rec_off, unsigned char *d_rec_rows,
+                                           int *d_status, void *stream);
+/* Host-pointer variants: synchronous; chunked and pipelined like qfec_*_batch_ragged*_host
+ * (chunks cut on group boundaries by bytes, the "host_chunk_mb" option; offsets ascending,
+ * non-overlapping multiples of 16 and bb[g] >= 1, -2 otherwise).  Row strides must be > 0.
+ *   qfec_encode_seal_groups_batch_ragged_host: the parity is laid out on the device and never
+ *     leaves it.  h_pkt rows come back whole, with zeros past h_pkt_len[p] and in rejected
+ *     rows (the uniform host seal's contract); h_status [G] (may be NULL) is the encode's.
+ *   qfec_open_decode_batch_ragged_host: takes h_bb and h_rec_off only and lays the blocks out
+ *     itself.  h_rec bytes the call does not write keep the caller's values (the ragged host
+ *     decode's contract); h_status and h_open_len may be NULL. */
+QFEC_API int qfec_encode_seal_groups_batch_ragged_host(
+    qfec_ctx *ctx, int k, int m, long long groups, const int *h_bb, const unsigned char *h_data,
+    const long long *h_data_off, const unsigned char *h_hdr, long long hdr_stride,
+    const int *h_hdr_len, int hdr_len_all, const int *h_pt_len, unsigned char *h_pkt,
+    long long pkt_stride, int *h_pkt_len, int *h_status);
+QFEC_API int qfec_open_decode_batch_ragged_host(
+    qfec_ctx *ctx, int k, int m, long long groups, const int *h_bb, const unsigned char *h_pkt,
+    long long pkt_stride, const int *h_pkt_len, const int *h_ad_len, int ad_len_all,
+    unsigned char *h_rec, const long long *h_rec_off, unsigned char *h_rec_rows, int *h_status,
+    int *h_open_len);
+
+/* ---------------------------------------------------------------------------------
  * Support: the coefficient tables, a seeded synthetic workload, diagnostics.
  * ------------------------------------------------------------------------------- */
 /* Rows 1..m-1 of the Cauchy matrix the reference selects (cauchy_256.cpp:422-480),
@@ -366,7 +467,9 @@ QFEC_API const char *qfec_last_error(void);
 /* Names of the kernels this thread's last engine call launched, " + "-separated, e.g.
  * "decode_prep_lane_kernel + gf_stream_kernel<decode>" (bench.py reports it).  The ragged
  * calls name "gf_ragged_kernel<encode>", "gf_ragged_kernel<decode>", "xor_ragged_kernel" and
- * "copy_ragged_kernel". */
+ * "copy_ragged_kernel"; the ragged protected calls add "null_seal_kernel<ragged>" and
+ * "open_group_kernel<ragged> + open_assemble_kernel<ragged>" (the uniform grouped calls name
+ * "null_seal_kernel<groups>" and "open_group_kernel + open_assemble_kernel"). */
 QFEC_API const char *qfec_last_kernels(void);
 /* Grids of the persistent kernels the last call on this thread launched, as space-separated
  * "kernel=workgroups" entries (e.g. "gf_psyn_kernel=1024"); diagnostics and tests.  The general

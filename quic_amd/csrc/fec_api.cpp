@@ -1327,6 +1327,13 @@ struct RaggedChunks {
     long long in_span(const long long* off, const int* bb, long long g0, long long g1, int n) const {
         return off[g1 - 1] + (long long)n * bb[g1 - 1] - off[g0];
     }
+    // groups in the chunk that starts at group g0 (0: no group left); asked in ascending order
+    size_t ci = 0;
+    long long next(long long g0) {
+        if (g0 >= first.back()) return 0;
+        while (first[ci] != g0) ++ci;
+        return first[ci + 1] - g0;
+    }
 };
 
 static int ragged_chunks(qfec_ctx* c, int n_in, int n_out, long long G, const int* bb,
@@ -1381,15 +1388,10 @@ static int ragged_host(qfec_ctx* c, int k, int m, long long G, const int* h_bb,
     if (rc) return rc;
     const size_t bytes = ch.max_in + ch.max_out + ch.max_groups * small + kCarveSlack;
     int result = 0;
-    size_t ci = 0;
     rc = host_pipeline_guard(c, [&] {
         return host_pipeline_chunks(
             c, bytes,
-            [&](long long g0) -> long long {
-                if (g0 >= G) return 0;
-                while (ch.first[ci] != g0) ++ci;
-                return ch.first[ci + 1] - g0;
-            },
+            [&](long long g0) { return ch.next(g0); },
             [&](long long g0, long long n, uint8_t* buf, int phase) -> int {
                 const size_t in_b = (size_t)ch.in_span(h_in_off, h_bb, g0, g0 + n, k);
                 const size_t out_b = (size_t)ch.in_span(h_out_off, h_bb, g0, g0 + n, n_out);
@@ -1469,6 +1471,315 @@ int qfec_decode_batch_ragged_recovered_host(qfec_ctx* c, int k, int m, long long
     if ((rc = set_device(c))) return rc;
     return ragged_host(c, k, m, groups, h_bb, h_blocks, h_blocks_off, h_rows, h_rec, h_rec_off,
                        h_rec_rows, h_status, true);
+}
+
+// ---- ragged packet protection: the protected paths over the packed layout (pp_null.hip's
+// ragged kernels around encode_ragged_impl / decode_ragged_impl).  Packets stay dense by
+// packet index; only the blocks are packed.
+static int seal_ragged_args(qfec_ctx* c, int k, int m, long long groups, const int* bb,
+                            const unsigned char* data, const long long* data_off,
+                            const unsigned char* parity, const long long* par_off,
+                            const unsigned char* hdr, long long hdr_stride, const int* hdr_len,
+                            int hdr_len_all, const unsigned char* pkt, long long pkt_stride,
+                            const int* pkt_len) {
+    int rc = ragged_check(c, k, m, groups, bb, data, data_off, parity, par_off);
+    if (rc) return rc;
+    if (k + m > 256) return fail(-2, "k + m > 256");
+    if (!pkt || !pkt_len || (!hdr && (hdr_len || hdr_len_all))) return fail(-2, "null buffer");
+    if (hdr_stride < 0 || pkt_stride < 0) return fail(-2, "bad stride");
+    if ((((uintptr_t)pkt) | (uintptr_t)pkt_stride) & 3) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
+    return 0;
+}
+
+static int seal_groups_ragged(qfec_ctx* c, int k, int m, long long groups, const int* d_bb,
+                              const unsigned char* d_data, const long long* d_data_off,
+                              unsigned char* d_parity, const long long* d_par_off, bool encode,
+                              const unsigned char* d_hdr, long long hdr_stride,
+                              const int* d_hdr_len, int hdr_len_all, const int* d_pt_len,
+                              unsigned char* d_pkt, long long pkt_stride, int* d_pkt_len,
+                              int* d_status, void* stream) {
+    int rc = seal_ragged_args(c, k, m, groups, d_bb, d_data, d_data_off, d_parity, d_par_off,
+                              d_hdr, hdr_stride, d_hdr_len, hdr_len_all, d_pkt, pkt_stride,
+                              d_pkt_len);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const hipStream_t st = pick(c, stream);
+    if (encode && (rc = encode_ragged_impl(c, k, m, groups,
+                                           {(const int32_t*)d_bb, d_data_off, d_par_off}, d_data,
+                                           d_parity, (int32_t*)d_status, st)))
+        return rc;
+    QF_HIP(qfec::launch_null_seal_groups_ragged(
+        k, m, groups, (const int32_t*)d_bb, d_data, d_data_off, d_parity, d_par_off, encode, d_hdr,
+        hdr_stride, (const int32_t*)d_hdr_len, hdr_len_all, (const int32_t*)d_pt_len, d_pkt,
+        pkt_stride, (int32_t*)d_pkt_len, st));
+    return 0;
+}
+
+int qfec_seal_groups_batch_ragged(qfec_ctx* c, int k, int m, long long groups, const int* d_bb,
+                                  const unsigned char* d_data, const long long* d_data_off,
+                                  const unsigned char* d_parity, const long long* d_par_off,
+                                  const unsigned char* d_hdr, long long hdr_stride,
+                                  const int* d_hdr_len, int hdr_len_all, const int* d_pt_len,
+                                  unsigned char* d_pkt, long long pkt_stride, int* d_pkt_len,
+                                  void* stream) {
+    return seal_groups_ragged(c, k, m, groups, d_bb, d_data, d_data_off,
+                              (unsigned char*)d_parity, d_par_off, false, d_hdr, hdr_stride,
+                              d_hdr_len, hdr_len_all, d_pt_len, d_pkt, pkt_stride, d_pkt_len,
+                              nullptr, stream);
+}
+
+int qfec_encode_seal_groups_batch_ragged(qfec_ctx* c, int k, int m, long long groups,
+                                         const int* d_bb, const unsigned char* d_data,
+                                         const long long* d_data_off, unsigned char* d_parity,
+                                         const long long* d_par_off, const unsigned char* d_hdr,
+                                         long long hdr_stride, const int* d_hdr_len,
+                                         int hdr_len_all, const int* d_pt_len,
+                                         unsigned char* d_pkt, long long pkt_stride,
+                                         int* d_pkt_len, int* d_status, void* stream) {
+    return seal_groups_ragged(c, k, m, groups, d_bb, d_data, d_data_off, d_parity, d_par_off, true,
+                              d_hdr, hdr_stride, d_hdr_len, hdr_len_all, d_pt_len, d_pkt,
+                              pkt_stride, d_pkt_len, d_status, stream);
+}
+
+// open_decode_impl over the packed layout.  The caller holds the workspace bracket.
+static int open_decode_ragged_impl(qfec_ctx* c, int k, int m, long long groups, const int32_t* d_bb,
+                                   const uint8_t* d_pkt, long long pkt_stride,
+                                   const int32_t* d_pkt_len, const int32_t* d_ad_len,
+                                   int ad_len_all, uint8_t* d_blocks,
+                                   const long long* d_blocks_off, uint8_t* d_rows,
+                                   int32_t* d_open_len, uint8_t* d_rec,
+                                   const long long* d_rec_off, uint8_t* d_rec_rows,
+                                   int32_t* d_status, hipStream_t st) {
+    QF_HIP(qfec::launch_open_groups_ragged(k, m, groups, d_bb, d_pkt, pkt_stride, d_pkt_len,
+                                           d_ad_len, ad_len_all, d_blocks, d_blocks_off, d_rows,
+                                           d_open_len, st));
+    int rc = decode_ragged_impl(c, k, m, groups, {d_bb, d_blocks_off, d_rec_off}, d_blocks, d_rows,
+                                d_rec, d_rec_rows, d_status, st);
+    if (rc) return rc;
+    QF_HIP(qfec::launch_open_status(k, std::min(k, m), groups, d_rows, d_rec_rows, d_status, st));
+    return 0;
+}
+
+int qfec_open_decode_batch_ragged(qfec_ctx* c, int k, int m, long long groups, const int* d_bb,
+                                  const unsigned char* d_pkt, long long pkt_stride,
+                                  const int* d_pkt_len, const int* d_ad_len, int ad_len_all,
+                                  unsigned char* d_blocks, const long long* d_blocks_off,
+                                  unsigned char* d_rows, int* d_open_len, unsigned char* d_rec,
+                                  const long long* d_rec_off, unsigned char* d_rec_rows,
+                                  int* d_status, void* stream) {
+    int rc = ragged_check(c, k, m, groups, d_bb, d_blocks, d_blocks_off, d_rec, d_rec_off);
+    if (rc) return rc;
+    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
+    if (!d_pkt || !d_pkt_len || !d_rows || !d_open_len || !d_rec_rows) return fail(-2, "null buffer");
+    if (pkt_stride <= 0) return fail(-2, "bad pkt_stride");
+    if (!d_ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    if (groups == 0) return 0;
+    const hipStream_t st = pick(c, stream);
+    return with_workspace(c, st, [&] {
+        return open_decode_ragged_impl(c, k, m, groups, (const int32_t*)d_bb, d_pkt, pkt_stride,
+                                       (const int32_t*)d_pkt_len, (const int32_t*)d_ad_len,
+                                       ad_len_all, d_blocks, d_blocks_off, d_rows,
+                                       (int32_t*)d_open_len, d_rec, d_rec_off, d_rec_rows,
+                                       (int32_t*)d_status, st);
+    });
+}
+
+// The packed offsets of n blocks of bb[g] bytes per group, every group rounded up to 16 bytes:
+// the layout of a buffer the host forms keep on the device (the sender's parity, the
+// receiver's blocks).  -2 on bb[g] < 1.
+static int packed_offsets(long long G, const int* bb, int n, std::vector<long long>* off) {
+    off->resize((size_t)G);
+    long long at = 0;
+    for (long long g = 0; g < G; ++g) {
+        if (bb[g] < 1) return fail(-2, "bb[g] < 1");
+        (*off)[(size_t)g] = at;
+        at += ((long long)n * bb[g] + 15) & ~15LL;
+    }
+    return 0;
+}
+
+// Sender, host to host, ragged: qfec_encode_seal_groups_batch_host with a block size per group.
+// The parity is laid out on the device and never leaves it.
+int qfec_encode_seal_groups_batch_ragged_host(qfec_ctx* c, int k, int m, long long groups,
+                                              const int* h_bb, const unsigned char* h_data,
+                                              const long long* h_data_off,
+                                              const unsigned char* h_hdr, long long hdr_stride,
+                                              const int* h_hdr_len, int hdr_len_all,
+                                              const int* h_pt_len, unsigned char* h_pkt,
+                                              long long pkt_stride, int* h_pkt_len,
+                                              int* h_status) {
+    const unsigned char* dummy = (const unsigned char*)16;   // non-null for the argument check
+    // (host data is staged, so its own alignment does not matter either)
+    int rc = seal_ragged_args(c, k, m, groups, h_bb, h_data ? dummy : nullptr, h_data_off, dummy,
+                              (const long long*)dummy, h_hdr, hdr_stride, h_hdr_len, hdr_len_all,
+                              h_pkt, pkt_stride, h_pkt_len);
+    if (rc) return rc;
+    if (groups == 0) return 0;
+    if (hdr_stride <= 0 && h_hdr) return fail(-2, "host headers need a row stride > 0");
+    if (pkt_stride <= 0) return fail(-2, "host packets need a row stride > 0");
+    std::vector<long long> par_off;
+    if ((rc = packed_offsets(groups, h_bb, m, &par_off))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const long long np = k + m;
+    const size_t hdr_g = h_hdr ? (size_t)np * hdr_stride : 0;
+    const size_t pkt_g = (size_t)np * pkt_stride, len_g = (size_t)np * sizeof(int32_t);
+    const size_t small = sizeof(int32_t) * 2 + 2 * sizeof(long long) + hdr_g + pkt_g +
+                         len_g * (1 + (h_hdr_len ? 1 : 0) + (h_pt_len ? 1 : 0));
+    RaggedChunks ch;
+    if ((rc = ragged_chunks(c, k, m, groups, h_bb, h_data_off, par_off.data(), small, &ch)))
+        return rc;
+    const size_t bytes = ch.max_in + ch.max_out + ch.max_groups * small + kCarveSlack;
+    return host_pipeline_guard(c, [&] {
+        return host_pipeline_chunks(
+            c, bytes,
+            [&](long long g0) { return ch.next(g0); },
+            [&](long long g0, long long n, uint8_t* buf, int phase) -> int {
+                const size_t in_b = (size_t)ch.in_span(h_data_off, h_bb, g0, g0 + n, k);
+                const size_t par_b = (size_t)ch.in_span(par_off.data(), h_bb, g0, g0 + n, m);
+                Carve cv{buf};
+                uint8_t* dd = cv.take(in_b);
+                uint8_t* dp = cv.take(par_b);
+                int32_t* dbb = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
+                long long* dio = (long long*)cv.take((size_t)n * sizeof(long long));
+                long long* dpo = (long long*)cv.take((size_t)n * sizeof(long long));
+                int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
+                uint8_t* dh = h_hdr ? cv.take((size_t)n * hdr_g) : nullptr;
+                uint8_t* dk = cv.take((size_t)n * pkt_g);
+                int32_t* dkl = (int32_t*)cv.take((size_t)n * len_g);
+                int32_t* dhl = h_hdr_len ? (int32_t*)cv.take((size_t)n * len_g) : nullptr;
+                int32_t* dpl = h_pt_len ? (int32_t*)cv.take((size_t)n * len_g) : nullptr;
+                const size_t p0 = (size_t)g0 * np, pn = (size_t)n * np;
+                if (phase == 0) {
+                    QF_HIP(hipMemcpyAsync(dd, h_data + h_data_off[g0], in_b, hipMemcpyHostToDevice,
+                                          c->s_in));
+                    QF_HIP(hipMemcpyAsync(dbb, h_bb + g0, (size_t)n * sizeof(int32_t),
+                                          hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(dio, ch.in_rel.data() + g0, (size_t)n * sizeof(long long),
+                                          hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(dpo, ch.out_rel.data() + g0, (size_t)n * sizeof(long long),
+                                          hipMemcpyHostToDevice, c->s_in));
+                    if (dh)
+                        QF_HIP(hipMemcpyAsync(dh, h_hdr + p0 * hdr_stride, pn * hdr_stride,
+                                              hipMemcpyHostToDevice, c->s_in));
+                    if (dhl)
+                        QF_HIP(hipMemcpyAsync(dhl, h_hdr_len + p0, pn * sizeof(int32_t),
+                                              hipMemcpyHostToDevice, c->s_in));
+                    if (dpl)
+                        QF_HIP(hipMemcpyAsync(dpl, h_pt_len + p0, pn * sizeof(int32_t),
+                                              hipMemcpyHostToDevice, c->s_in));
+                } else if (phase == 1) {
+                    const int r = encode_ragged_impl(c, k, m, n, {dbb, dio, dpo}, dd, dp, ds,
+                                                     c->stream);
+                    if (r) return r;
+                    // rows come back whole: zeros past each packet and in rejected rows
+                    QF_HIP(hipMemsetAsync(dk, 0, pn * pkt_stride, c->stream));
+                    QF_HIP(qfec::launch_null_seal_groups_ragged(
+                        k, m, n, dbb, dd, dio, dp, dpo, true, dh, dh ? hdr_stride : 0, dhl,
+                        dh ? hdr_len_all : 0, dpl, dk, pkt_stride, dkl, c->stream));
+                } else {
+                    QF_HIP(hipMemcpyAsync(h_pkt + p0 * pkt_stride, dk, pn * pkt_stride,
+                                          hipMemcpyDeviceToHost, c->s_out));
+                    QF_HIP(hipMemcpyAsync(h_pkt_len + p0, dkl, pn * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, c->s_out));
+                    if (h_status)
+                        QF_HIP(hipMemcpyAsync(h_status + g0, ds, (size_t)n * sizeof(int32_t),
+                                              hipMemcpyDeviceToHost, c->s_out));
+                }
+                return 0;
+            });
+    });
+}
+
+// Receiver, host to host, ragged: qfec_open_decode_batch_host with a block size per group.  The
+// blocks are laid out on the device; h_rec is the caller's packed buffer, and the bytes of it
+// the call does not write keep the caller's values (staged in, as the ragged host decode).
+int qfec_open_decode_batch_ragged_host(qfec_ctx* c, int k, int m, long long groups,
+                                       const int* h_bb, const unsigned char* h_pkt,
+                                       long long pkt_stride, const int* h_pkt_len,
+                                       const int* h_ad_len, int ad_len_all, unsigned char* h_rec,
+                                       const long long* h_rec_off, unsigned char* h_rec_rows,
+                                       int* h_status, int* h_open_len) {
+    int rc = check_common(c, k, m, 1, groups < 0 ? 0 : groups);
+    if (rc) return rc;
+    if (groups < 0) return fail(-2, "groups < 0");
+    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
+    if (!h_bb || !h_pkt || !h_pkt_len || !h_rec || !h_rec_off || !h_rec_rows)
+        return fail(-2, "null buffer");
+    if (groups == 0) return 0;
+    if (pkt_stride <= 0) return fail(-2, "bad pkt_stride");
+    if (!h_ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
+    std::vector<long long> blk_off;
+    if ((rc = packed_offsets(groups, h_bb, k, &blk_off))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const long long np = k + m;
+    const int rmax = std::min(k, m);
+    const size_t pkt_g = (size_t)np * pkt_stride, len_g = (size_t)np * sizeof(int32_t);
+    const size_t small = sizeof(int32_t) * 2 + 2 * sizeof(long long) + pkt_g +
+                         len_g * (2 + (h_ad_len ? 1 : 0)) + (size_t)k + (size_t)rmax;
+    RaggedChunks ch;
+    if ((rc = ragged_chunks(c, k, rmax, groups, h_bb, blk_off.data(), h_rec_off, small, &ch)))
+        return rc;
+    const size_t bytes = ch.max_in + ch.max_out + ch.max_groups * small + kCarveSlack;
+    return host_pipeline_guard(c, [&] {
+        return host_pipeline_chunks(
+            c, bytes,
+            [&](long long g0) { return ch.next(g0); },
+            [&](long long g0, long long n, uint8_t* buf, int phase) -> int {
+                const size_t blk_b = (size_t)ch.in_span(blk_off.data(), h_bb, g0, g0 + n, k);
+                const size_t rec_b = (size_t)ch.in_span(h_rec_off, h_bb, g0, g0 + n, rmax);
+                Carve cv{buf};
+                uint8_t* db = cv.take(blk_b);
+                uint8_t* dre = cv.take(rec_b);
+                int32_t* dbb = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
+                long long* dbo = (long long*)cv.take((size_t)n * sizeof(long long));
+                long long* dro = (long long*)cv.take((size_t)n * sizeof(long long));
+                int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
+                uint8_t* dk = cv.take((size_t)n * pkt_g);
+                int32_t* dkl = (int32_t*)cv.take((size_t)n * len_g);
+                int32_t* dal = h_ad_len ? (int32_t*)cv.take((size_t)n * len_g) : nullptr;
+                int32_t* dol = (int32_t*)cv.take((size_t)n * len_g);
+                uint8_t* dr = cv.take((size_t)n * k);
+                uint8_t* drr = cv.take((size_t)n * rmax);
+                unsigned char* rec = h_rec + h_rec_off[g0];
+                const size_t p0 = (size_t)g0 * np, pn = (size_t)n * np;
+                if (phase == 0) {
+                    QF_HIP(hipMemcpyAsync(dk, h_pkt + p0 * pkt_stride, pn * pkt_stride,
+                                          hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(dkl, h_pkt_len + p0, pn * sizeof(int32_t),
+                                          hipMemcpyHostToDevice, c->s_in));
+                    if (dal)
+                        QF_HIP(hipMemcpyAsync(dal, h_ad_len + p0, pn * sizeof(int32_t),
+                                              hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(dre, rec, rec_b, hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(dbb, h_bb + g0, (size_t)n * sizeof(int32_t),
+                                          hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(dbo, ch.in_rel.data() + g0, (size_t)n * sizeof(long long),
+                                          hipMemcpyHostToDevice, c->s_in));
+                    QF_HIP(hipMemcpyAsync(dro, ch.out_rel.data() + g0, (size_t)n * sizeof(long long),
+                                          hipMemcpyHostToDevice, c->s_in));
+                } else if (phase == 1) {
+                    return open_decode_ragged_impl(c, k, m, n, dbb, dk, pkt_stride, dkl, dal,
+                                                   ad_len_all, db, dbo, dr, dol, dre, dro, drr, ds,
+                                                   c->stream);
+                } else {
+                    QF_HIP(hipMemcpyAsync(rec, dre, rec_b, hipMemcpyDeviceToHost, c->s_out));
+                    QF_HIP(hipMemcpyAsync(h_rec_rows + (size_t)g0 * rmax, drr, (size_t)n * rmax,
+                                          hipMemcpyDeviceToHost, c->s_out));
+                    if (h_status)
+                        QF_HIP(hipMemcpyAsync(h_status + g0, ds, (size_t)n * sizeof(int32_t),
+                                              hipMemcpyDeviceToHost, c->s_out));
+                    if (h_open_len)
+                        QF_HIP(hipMemcpyAsync(h_open_len + p0, dol, pn * sizeof(int32_t),
+                                              hipMemcpyDeviceToHost, c->s_out));
+                }
+                return 0;
+            });
+    });
 }
 
 int qfec_synth_fill(void* d_dst, unsigned long long bytes, unsigned long long seed,

@@ -293,6 +293,14 @@ hipError_t launch_gf_psyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
 // Ragged batches (gf_ragged.hip): the groups share (k, m), each has its own block size.
 // Group g's input blocks are [k][bb[g]] at in + in_off[g] and its outputs [n][bb[g]] at
 // out + out_off[g] (byte offsets, multiples of 16; all three arrays in device memory).
+// The groups a ragged encode rejects (status -1, XOR parity only, cauchy_256.cpp:1519-1534;
+// k + m > 256 is a call-level matter): asked by the encode (xor_ragged_kernel, which writes
+// the status) and by the seal that follows it (pp_null.hip, which then seals none of the
+// group's packets), so the two cannot disagree.
+__host__ __device__ inline bool ragged_encode_rejects(int k, int m, int bb) {
+    return m > 1 && k > 1 && (bb & 7) != 0;
+}
+
 struct RaggedView {
     const int32_t* bb;
     const long long* in_off;

@@ -179,7 +179,8 @@ __global__ __launch_bounds__(256) void xor_ragged_kernel(
         if (DECODE) {
             if (eidx[g] == 255) continue;
         } else {
-            const bool bad = mode == 1 || (mode == 2 && (bb & 7) != 0);
+            // mode 2 is the m > 1 encode's
+            const bool bad = mode == 1 || (mode == 2 && ragged_encode_rejects(k, 2, bb));
             if (status && lane == 0) status[g] = bad ? -1 : 0;
             if (mode == 2 && !bad) continue;
         }

@@ -30,6 +30,12 @@
 // sealed in one launch, and the receiver's open that writes each data packet's plaintext
 // straight into its block slot, followed by one wave per group that fills the holes with the
 // opened FEC packets and writes the row tags the decode reads.
+//
+// Ragged forms of the grouped kernels (a block size per group, the packed layout of
+// gf_ragged.hip): the same kernel bodies, tile_stream and chain, instantiated with a row
+// lookup that reads bb[g] and the group's byte offset per lane (RaggedRows, RaggedSlots); the
+// uniform instantiations (PtRows, UniSlots) carry no run-time branch for them.  A tile that
+// mixes block sizes runs its window loop to its longest packet.
 #include "fec_kernels.h"
 #include "pp_null.h"
 
@@ -515,13 +521,53 @@ __device__ __forceinline__ const uint8_t* pt_row(const PtRows& r, long long p) {
     const int i = (int)(p - g * per);
     return i < r.ka ? r.a + (g * r.ka + i) * r.stride : r.b + (g * r.kb + (i - r.ka)) * r.stride;
 }
+__device__ __forceinline__ int pt_len_of(const PtRows&, const int32_t* pt_len, int pt_all,
+                                         long long p) {
+    return len_of(pt_len, pt_all, p);
+}
+__device__ __forceinline__ bool pt_fits(const PtRows& r, long long, int pl) {
+    return r.stride == 0 || pl <= r.stride;
+}
+
+// Plaintext rows of a ragged batch: packet p = g * (ka + kb) + i reads block i of group g's
+// [ka][bb[g]] at a + a_off[g] for i < ka, block i - ka of its [kb][bb[g]] at b + b_off[g]
+// otherwise.  The 64 packets of a wave come from several groups, so g, bb[g] and the offsets
+// are per lane.  pt_len == nullptr: every plaintext is its whole block.  A group with
+// bb[g] < 1 has no rows, and neither has, when the seal follows the encode (enc), a group
+// the encode rejected: none of their packets fits.
+struct RaggedRows {
+    const uint8_t* a;
+    const uint8_t* b;
+    const long long* a_off;
+    const long long* b_off;
+    const int32_t* bb;
+    int ka, kb;
+    bool enc;
+};
+
+__device__ __forceinline__ const uint8_t* pt_row(const RaggedRows& r, long long p) {
+    const int per = r.ka + r.kb;
+    const long long g = p / per;
+    const int i = (int)(p - g * per);
+    const long long bb = r.bb[g];
+    return i < r.ka ? r.a + r.a_off[g] + i * bb : r.b + r.b_off[g] + (i - r.ka) * bb;
+}
+__device__ __forceinline__ int pt_len_of(const RaggedRows& r, const int32_t* pt_len, int,
+                                         long long p) {
+    return pt_len ? pt_len[p] : r.bb[p / (r.ka + r.kb)];
+}
+__device__ __forceinline__ bool pt_fits(const RaggedRows& r, long long p, int pl) {
+    const int bb = r.bb[p / (r.ka + r.kb)];
+    return bb >= 1 && pl <= bb && !(r.enc && ragged_encode_rejects(r.ka, r.kb, bb));
+}
 
 // One wave seals 64 packets (one per lane): the AD through the lane's own streamer (a few
-// bytes), the plaintext through the wave's LDS tile (tile_stream), then the tag.
-template <class H>
+// bytes), the plaintext through the wave's LDS tile (tile_stream), then the tag.  R: where the
+// plaintext rows are (PtRows, RaggedRows).
+template <class H, class R>
 __global__ __launch_bounds__(64) void null_seal_kernel(
     long long n, const uint8_t* __restrict__ ad, long long ad_stride,
-    const int32_t* __restrict__ ad_len, int ad_all, PtRows pr, const int32_t* __restrict__ pt_len,
+    const int32_t* __restrict__ ad_len, int ad_all, R pr, const int32_t* __restrict__ pt_len,
     int pt_all, uint8_t* out, long long out_stride, int32_t* out_len) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
@@ -529,11 +575,11 @@ __global__ __launch_bounds__(64) void null_seal_kernel(
     int al = 0, pl = 0;
     if (i < n) {
         al = len_of(ad_len, ad_all, i);
-        pl = len_of(pt_len, pt_all, i);
+        pl = pt_len_of(pr, pt_len, pt_all, i);
         // a row longer than its stride would read the next packet's bytes (or past the buffer
         // for the last one): rejected like a packet that does not fit
         ok = al >= 0 && pl >= 0 && (ad_stride == 0 || al <= ad_stride) &&
-             (pr.stride == 0 || pl <= pr.stride) && (long long)al + 12 + pl <= out_stride;
+             pt_fits(pr, i, pl) && (long long)al + 12 + pl <= out_stride;
         out_len[i] = ok ? al + 12 + pl : -1;
     }
     uint8_t* o = out + (ok ? i : 0) * out_stride;
@@ -634,12 +680,40 @@ __device__ int fec_pre_slot(const int32_t* __restrict__ pkt_len,
     return -1;
 }
 
+// Where the receiver's block slots are and how long they are.  Uniform: blocks [G][k][bb].
+struct UniSlots {
+    int bb;
+    __device__ __forceinline__ int size(long long) const { return bb; }
+    __device__ __forceinline__ uint8_t* slot(uint8_t* blocks, long long g, int k, int s,
+                                             int bb_) const {
+        return blocks + (g * k + s) * (long long)bb_;
+    }
+};
+// Ragged: group g's [k][bb[g]] at blocks + off[g].  A wave's 64 packets come from several
+// groups, so the size and the offset are per lane.  A group with bb[g] < 1 (and the lanes
+// past the last group) get size -1: no packet passes the length checks then (open_len_ok), so
+// none of it is written and every row of it is tagged 255.
+struct RaggedSlots {
+    const int32_t* bb;
+    const long long* off;
+    long long groups;
+    __device__ __forceinline__ int size(long long g) const {
+        const int b = g < groups ? bb[g] : -1;
+        return b < 1 ? -1 : b;
+    }
+    __device__ __forceinline__ uint8_t* slot(uint8_t* blocks, long long g, int, int s,
+                                             int bb_) const {
+        return blocks + off[g] + s * (long long)bb_;
+    }
+};
+
 // Receiver, grouped: packet p = g * (k + m) + i, one wave per 64 packets; a data packet's
 // plaintext goes to its block slot, zero-padded to bb, through the wave's LDS tile, and so
 // does an FEC packet's, into the hole it fills if the tags change nothing (fec_pre_slot).
-template <class H>
+// S: the slots (UniSlots, RaggedSlots).
+template <class H, class S>
 __global__ __launch_bounds__(64) void open_group_kernel(
-    int k, int m, int bb, long long n, const uint8_t* __restrict__ pkt, long long pkt_stride,
+    int k, int m, S sl, long long n, const uint8_t* __restrict__ pkt, long long pkt_stride,
     const int32_t* __restrict__ pkt_len, const int32_t* __restrict__ ad_len, int ad_all,
     uint8_t* blocks, int32_t* open_len) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -647,6 +721,7 @@ __global__ __launch_bounds__(64) void open_group_kernel(
     const int per = k + m;
     const long long g = p / per;
     const int i = (int)(p - g * per);
+    const int bb = sl.size(g);
     bool ok = false;
     int al = 0, cl = 0;
     if (p < n) {
@@ -665,8 +740,7 @@ __global__ __launch_bounds__(64) void open_group_kernel(
     const int slot = !ok ? -1 : i < k ? i
                    : fec_pre_slot(pkt_len, ad_len, ad_all, g, i, k, m, bb, pkt_stride);
     tile_stream(h, ok ? c + 12 : nullptr, ok ? cl - 12 : 0,
-                slot >= 0 ? blocks + (g * k + slot) * (long long)bb : nullptr, slot >= 0 ? bb : 0,
-                smem);
+                slot >= 0 ? sl.slot(blocks, g, k, slot, bb) : nullptr, slot >= 0 ? bb : 0, smem);
     if (!ok) return;
     uint32_t t0, t1, t2;
     h.tag(t0, t1, t2);
@@ -703,8 +777,9 @@ constexpr int kAsmWaves = 4;
 // reports the group as malformed, status -3).  The open has already written each FEC packet
 // into the hole the length checks alone give it (fec_pre_slot); a pair the tag checks
 // changed is copied here.
+template <class S>
 __global__ __launch_bounds__(kAsmWaves * 64) void open_assemble_kernel(
-    int k, int m, int bb, long long groups, const uint8_t* __restrict__ pkt, long long pkt_stride,
+    int k, int m, S sl, long long groups, const uint8_t* __restrict__ pkt, long long pkt_stride,
     const int32_t* __restrict__ pkt_len, const int32_t* __restrict__ ad_len, int ad_all,
     const int32_t* __restrict__ open_len, uint8_t* blocks, uint8_t* rows) {
     __shared__ uint8_t lavail[kAsmWaves][256], lhole[kAsmWaves][256];
@@ -712,6 +787,7 @@ __global__ __launch_bounds__(kAsmWaves * 64) void open_assemble_kernel(
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long long g = (long long)blockIdx.x * kAsmWaves + w;
     if (g >= groups) return;   // uniform over the wave; no workgroup barrier below
+    const int bb = sl.size(g);
     const int per = k + m;
     const int32_t* ol = open_len + g * per;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -767,7 +843,7 @@ __global__ __launch_bounds__(kAsmWaves * 64) void open_assemble_kernel(
         if (pr < nph && phole[w][pr] == i) continue;   // written there by the open
         const long long p = g * per + k + j;
         const uint8_t* src = pkt + p * pkt_stride + len_of(ad_len, ad_all, p) + 12;
-        wave_copy_pad(blocks + (g * k + i) * (long long)bb, src, ol[k + j], bb, lane);
+        wave_copy_pad(sl.slot(blocks, g, k, i, bb), src, ol[k + j], bb, lane);
     }
 }
 
@@ -803,7 +879,6 @@ unsigned tile_grid(long long n) {   // one wave (kTilePackets packets) per workg
 
 }  // namespace
 
-#define QPP_GO(KERNEL, ...) qlaunch(KERNEL<Fnv>, __VA_ARGS__)
 
 hipError_t launch_null_seal_h(long long n, const uint8_t* ad, long long ad_stride,
                               const int32_t* ad_len, int ad_all, const uint8_t* pt,
@@ -814,7 +889,7 @@ hipError_t launch_null_seal_h(long long n, const uint8_t* ad, long long ad_strid
     if (!pp_grid_ok(n)) return hipErrorInvalidValue;
     const PtRows pr{nullptr, pt, pt_stride, 0, 1};
     note_kernel("null_seal_kernel");
-    QPP_GO(null_seal_kernel, dim3(tile_grid(n)), dim3(64), kTileBytes, st, n, ad, ad_stride,
+    qlaunch((null_seal_kernel<Fnv, PtRows>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, n, ad, ad_stride,
            ad_len, ad_all, pr, pt_len, pt_all, out, out_stride, out_len);
     return hipGetLastError();
 }
@@ -837,7 +912,7 @@ hipError_t launch_null_seal_groups(int k, int m, int bb, long long groups,
     if (!pp_grid_ok(n)) return hipErrorInvalidValue;
     const PtRows pr{data, parity, bb, k, m};
     note_kernel("null_seal_kernel<groups>");
-    QPP_GO(null_seal_kernel, dim3(tile_grid(n)), dim3(64), kTileBytes, st, n, hdr, hdr_stride,
+    qlaunch((null_seal_kernel<Fnv, PtRows>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, n, hdr, hdr_stride,
            hdr_len, hdr_all, pr, pt_len, pt_all, out, out_stride, out_len);
     return hipGetLastError();
 }
@@ -849,7 +924,7 @@ hipError_t launch_null_open_h(long long n, const uint8_t* pkt, long long pkt_str
     if (n <= 0) return hipSuccess;
     if (!pp_grid_ok(n)) return hipErrorInvalidValue;
     note_kernel("null_open_kernel");
-    QPP_GO(null_open_kernel, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, n, pkt, pkt_stride,
+    qlaunch(null_open_kernel<Fnv>, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, n, pkt, pkt_stride,
            pkt_len, pkt_all, ad_len, ad_all, out, out_stride, out_len);
     return hipGetLastError();
 }
@@ -872,10 +947,48 @@ hipError_t launch_open_groups(int k, int m, int bb, long long groups,
     const long long wg = (groups + kAsmWaves - 1) / kAsmWaves;
     if (wg > 0x7fffffffLL) return hipErrorInvalidValue;
     note_kernel("open_group_kernel + open_assemble_kernel");
-    QPP_GO(open_group_kernel, dim3(tile_grid(n)), dim3(64), kTileBytes, st, k, m, bb, n, pkt,
-           pkt_stride, pkt_len, ad_len, ad_all, blocks, open_len);
-    qlaunch(open_assemble_kernel, dim3((unsigned)wg), dim3(kAsmWaves * 64), 0, st, k, m, bb,
-            groups, pkt, pkt_stride, pkt_len, ad_len, ad_all, open_len, blocks, rows);
+    const UniSlots sl{bb};
+    qlaunch((open_group_kernel<Fnv, UniSlots>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, k, m,
+           sl, n, pkt, pkt_stride, pkt_len, ad_len, ad_all, blocks, open_len);
+    qlaunch(open_assemble_kernel<UniSlots>, dim3((unsigned)wg), dim3(kAsmWaves * 64), 0, st, k, m,
+            sl, groups, pkt, pkt_stride, pkt_len, ad_len, ad_all, open_len, blocks, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_null_seal_groups_ragged(int k, int m, long long groups, const int32_t* bb,
+                                          const uint8_t* data, const long long* data_off,
+                                          const uint8_t* parity, const long long* par_off,
+                                          bool after_encode, const uint8_t* hdr,
+                                          long long hdr_stride, const int32_t* hdr_len,
+                                          int hdr_all, const int32_t* pt_len, uint8_t* out,
+                                          long long out_stride, int32_t* out_len,
+                                          hipStream_t st) {
+    const long long n = groups * (k + m);
+    if (n <= 0) return hipSuccess;
+    if (!pp_grid_ok(n)) return hipErrorInvalidValue;
+    const RaggedRows pr{data, parity, data_off, par_off, bb, k, m, after_encode};
+    note_kernel("null_seal_kernel<ragged>");
+    qlaunch((null_seal_kernel<Fnv, RaggedRows>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, n,
+           hdr, hdr_stride, hdr_len, hdr_all, pr, pt_len, 0, out, out_stride, out_len);
+    return hipGetLastError();
+}
+
+hipError_t launch_open_groups_ragged(int k, int m, long long groups, const int32_t* bb,
+                                     const uint8_t* pkt, long long pkt_stride,
+                                     const int32_t* pkt_len, const int32_t* ad_len, int ad_all,
+                                     uint8_t* blocks, const long long* blocks_off, uint8_t* rows,
+                                     int32_t* open_len, hipStream_t st) {
+    const long long n = groups * (k + m);
+    if (n <= 0) return hipSuccess;
+    if (k + m > 256 || !pp_grid_ok(n)) return hipErrorInvalidValue;
+    const long long wg = (groups + kAsmWaves - 1) / kAsmWaves;
+    if (wg > 0x7fffffffLL) return hipErrorInvalidValue;
+    note_kernel("open_group_kernel<ragged> + open_assemble_kernel<ragged>");
+    const RaggedSlots sl{bb, blocks_off, groups};
+    qlaunch((open_group_kernel<Fnv, RaggedSlots>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, k,
+           m, sl, n, pkt, pkt_stride, pkt_len, ad_len, ad_all, blocks, open_len);
+    qlaunch(open_assemble_kernel<RaggedSlots>, dim3((unsigned)wg), dim3(kAsmWaves * 64), 0, st, k,
+            m, sl, groups, pkt, pkt_stride, pkt_len, ad_len, ad_all, open_len, blocks, rows);
     return hipGetLastError();
 }
 hipError_t launch_open_status(int k, int rmax, long long groups, const uint8_t* rows,
@@ -886,6 +999,5 @@ hipError_t launch_open_status(int k, int rmax, long long groups, const uint8_t* 
             rows, rec_rows, status);
     return hipGetLastError();
 }
-#undef QPP_GO
 
 }  // namespace qfec

@@ -293,6 +293,80 @@ class FecEngine:
         if rc:
             raise FecError(rc, "qfec_open_decode_batch")
 
+    # ragged packet protection: the two calls above over the packed layout, a block size per
+    # group (include/quic_fec.h, "Ragged packet protection")
+    @staticmethod
+    def _ragged_pp_args(k, m, bb, offs, packets):
+        """_ragged_args plus the dense per-packet arguments: `packets` maps a name to
+        (tensor or int or None, dtype, 1 for a [G*(k+m)] array / 2 for [G*(k+m)][stride]
+        rows).  Every array has exactly one entry or row per packet."""
+        G = FecEngine._ragged_args(bb, *offs)
+        n = G * (k + m)
+        for name, (t, dtype, dim) in packets.items():
+            if t is None or isinstance(t, int):
+                continue
+            if t.dtype != dtype:
+                raise TypeError(f"{name}: dtype {t.dtype}, expected {dtype}")
+            if t.dim() != dim or t.shape[0] != n:
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {n} packets "
+                                 f"(G = {G}, k + m = {k + m})")
+        return G
+
+    def seal_groups_ragged(self, k, m, bb, data, data_off, parity, par_off, hdr, hdr_len, pt_len,
+                           pkt, pkt_len, encode=False, status=None, stream=None):
+        """seal_groups with a block size per group: packet p = g*(k+m)+i takes its plaintext
+        from block i of data + data_off[g] ([k][bb[g]]) for i < k, else block i-k of parity +
+        par_off[g].  bb int32 [G], offsets int64 [G], data / parity flat uint8; hdr, pkt,
+        pkt_len dense by packet as in seal_groups; pt_len int32 [G*(k+m)] or None (whole
+        blocks).  encode=True first encodes into parity (status: optional int32 [G], -1 for
+        the groups the encode rejects, none of whose packets is sealed)."""
+        import torch
+        G = FecEngine._ragged_pp_args(k, m, bb, (data_off, par_off), {
+            "hdr": (hdr, torch.uint8, 2), "hdr_len": (hdr_len, torch.int32, 1),
+            "pt_len": (pt_len, torch.int32, 1), "pkt": (pkt, torch.uint8, 2),
+            "pkt_len": (pkt_len, torch.int32, 1)})
+        if status is not None and (status.dtype != torch.int32 or status.shape != (G,)):
+            raise TypeError("status must be an int32 [G] device tensor")
+        if isinstance(pt_len, int):
+            raise TypeError("pt_len: an int32 [G*(k+m)] tensor, or None for whole blocks")
+        h, h_all = self._lens(hdr_len)
+        args = (self._h, k, m, G, _dptr(bb), _dptr(data), _dptr(data_off), _dptr(parity),
+                _dptr(par_off), _dptr(hdr), hdr.stride(0) if hdr is not None else 0, h, h_all,
+                _dptr(pt_len), _dptr(pkt), pkt.stride(0), _dptr(pkt_len))
+        if encode:
+            rc = self.lib.qfec_encode_seal_groups_batch_ragged(*args, _dptr(status),
+                                                               _stream(stream, data))
+        else:
+            if status is not None:
+                raise ValueError("status is the encode's: pass it with encode=True")
+            rc = self.lib.qfec_seal_groups_batch_ragged(*args, _stream(stream, data))
+        if rc:
+            raise FecError(rc, "qfec_encode_seal_groups_batch_ragged" if encode
+                           else "qfec_seal_groups_batch_ragged")
+
+    def open_decode_ragged(self, k, m, bb, pkt, pkt_len, ad_len, blocks, blocks_off, rows,
+                           open_len, rec, rec_off, rec_rows, status=None, stream=None):
+        """open_decode with a block size per group: blocks + blocks_off[g] receives
+        [k][bb[g]], rec + rec_off[g] up to [min(k,m)][bb[g]] (flat uint8, offsets int64 [G]);
+        pkt, pkt_len, open_len dense by packet, rows [G][k], rec_rows [G][min(k,m)]."""
+        import torch
+        G = FecEngine._ragged_pp_args(k, m, bb, (blocks_off, rec_off), {
+            "pkt": (pkt, torch.uint8, 2), "pkt_len": (pkt_len, torch.int32, 1),
+            "ad_len": (ad_len, torch.int32, 1), "open_len": (open_len, torch.int32, 1)})
+        rmax = min(k, m)
+        for name, t, dtype, shape in (("rows", rows, torch.uint8, (G, k)),
+                                      ("rec_rows", rec_rows, torch.uint8, (G, rmax)),
+                                      ("status", status, torch.int32, (G,))):
+            if t is not None and (t.dtype != dtype or tuple(t.shape) != shape):
+                raise TypeError(f"{name} must be a {dtype} {shape} device tensor")
+        a, a_all = self._lens(ad_len)
+        rc = self.lib.qfec_open_decode_batch_ragged(
+            self._h, k, m, G, _dptr(bb), _dptr(pkt), pkt.stride(0), _dptr(pkt_len), a, a_all,
+            _dptr(blocks), _dptr(blocks_off), _dptr(rows), _dptr(open_len), _dptr(rec),
+            _dptr(rec_off), _dptr(rec_rows), _dptr(status), _stream(stream, pkt))
+        if rc:
+            raise FecError(rc, "qfec_open_decode_batch_ragged")
+
     # host-pointer batch calls (synchronous; include H2D/D2H)
     def encode_host(self, k, m, block_bytes, data):
         data = np.ascontiguousarray(data, dtype=np.uint8)
@@ -496,24 +570,28 @@ def ragged_layout(k, m, bb):
     return offs[0], offs[1], offs[2], tuple(int(t) for t in totals)
 
 
-def _hcheck_ragged(k, nout, bb_h, in_h, in_off_h, out_h, out_off_h):
-    """Host arguments of a ragged call: bb int32 [G], offsets int64 [G], flat uint8 buffers that
-    hold every group the offsets name."""
+def _hcheck_ragged_one(n_blocks, bb_h, buf_h, off_h, name):
+    """One packed host buffer of a ragged call: bb int32 [G] (every size >= 1), offsets int64
+    [G] (non-negative multiples of 16), a flat uint8 buffer that holds every group the offsets
+    name (n_blocks blocks each)."""
     import torch
     G = bb_h.shape[0] if isinstance(bb_h, torch.Tensor) and bb_h.dim() == 1 else None
     _hcheck(bb_h, "bb", torch.int32, (G,))
-    _hcheck(in_off_h, "in_off", torch.int64, (G,))
-    _hcheck(out_off_h, "out_off", torch.int64, (G,))
-    _hcheck(in_h, "in", torch.uint8, (None,))
-    _hcheck(out_h, "out", torch.uint8, (None,))
+    _hcheck(off_h, f"{name}_off", torch.int64, (G,))
+    _hcheck(buf_h, name, torch.uint8, (None,))
     if int(bb_h.min()) < 1:
         raise ValueError("bb: every block size must be >= 1")
-    bb64 = bb_h.to(torch.int64)
-    for name, buf, off, n in (("in", in_h, in_off_h, k), ("out", out_h, out_off_h, nout)):
-        if int(off.min()) < 0 or int((off % 16).max()) != 0:
-            raise ValueError(f"{name}_off: offsets must be non-negative multiples of 16")
-        if int((off + n * bb64).max()) > buf.numel():
-            raise ValueError(f"{name}: buffer of {buf.numel()} bytes is too short for its groups")
+    if int(off_h.min()) < 0 or int((off_h % 16).max()) != 0:
+        raise ValueError(f"{name}_off: offsets must be non-negative multiples of 16")
+    if int((off_h + n_blocks * bb_h.to(torch.int64)).max()) > buf_h.numel():
+        raise ValueError(f"{name}: buffer of {buf_h.numel()} bytes is too short for its groups")
+    return G
+
+
+def _hcheck_ragged(k, nout, bb_h, in_h, in_off_h, out_h, out_off_h):
+    """Host arguments of a ragged codec call: its input and its output buffer."""
+    G = _hcheck_ragged_one(k, bb_h, in_h, in_off_h, "in")
+    _hcheck_ragged_one(nout, bb_h, out_h, out_off_h, "out")
     return G
 
 
@@ -551,6 +629,64 @@ def decode_ragged_recovered_host_into(engine, k, m, bb_h, blocks_h, blocks_off_h
         None if status_h is None else _hptr(status_h))
     if rc:
         raise FecError(rc, "qfec_decode_batch_ragged_recovered_host")
+    return rc
+
+
+def encode_seal_groups_ragged_host_into(engine, k, m, bb_h, data_h, data_off_h, hdr_h, hdr_len,
+                                        pt_len, pkt_h, pkt_len_h, status_h=None):
+    """Sender, host to host, a block size per group (qfec_encode_seal_groups_batch_ragged_host):
+    bb int32 [G], data flat uint8 with offsets int64 [G] (ascending, as ragged_layout gives
+    them); hdr [G*(k+m)][hdr_stride] (or None), pkt [G*(k+m)][pkt_stride], pkt_len int32
+    [G*(k+m)], pt_len int32 [G*(k+m)] or None (whole blocks); status: optional int32 [G]."""
+    import torch
+    G = _hcheck_ragged_one(k, bb_h, data_h, data_off_h, "data")
+    n = G * (k + m)
+    if hdr_h is not None:
+        _hcheck(hdr_h, "hdr", torch.uint8, (n, None))
+    _hcheck_lens(hdr_len, "hdr_len", n)
+    if pt_len is not None:
+        _hcheck(pt_len, "pt_len", torch.int32, (n,))
+    _hcheck(pkt_h, "pkt", torch.uint8, (n, None))
+    _hcheck(pkt_len_h, "pkt_len", torch.int32, (n,))
+    if status_h is not None:
+        _hcheck(status_h, "status", torch.int32, (G,))
+    h, h_all = _hlens(hdr_len)
+    rc = engine.lib.qfec_encode_seal_groups_batch_ragged_host(
+        engine._h, k, m, G, _hptr(bb_h), _hptr(data_h), _hptr(data_off_h),
+        None if hdr_h is None else _hptr(hdr_h), 0 if hdr_h is None else hdr_h.stride(0), h,
+        h_all, None if pt_len is None else _hptr(pt_len), _hptr(pkt_h), pkt_h.stride(0),
+        _hptr(pkt_len_h), None if status_h is None else _hptr(status_h))
+    if rc:
+        raise FecError(rc, "qfec_encode_seal_groups_batch_ragged_host")
+    return rc
+
+
+def open_decode_ragged_host_into(engine, k, m, bb_h, pkt_h, pkt_len_h, ad_len, rec_h, rec_off_h,
+                                 rec_rows_h, status_h=None, open_len_h=None):
+    """Receiver, host to host, a block size per group (qfec_open_decode_batch_ragged_host):
+    wire packets pkt [G*(k+m)][stride], pkt_len int32 (< 0: not received) -> rec (flat uint8,
+    group g's up to [min(k,m)][bb[g]] at rec_off[g]; bytes not written keep their values),
+    rec_rows [G][min(k,m)], status [G], open_len [G*(k+m)]."""
+    import torch
+    rmax = min(k, m)
+    G = _hcheck_ragged_one(rmax, bb_h, rec_h, rec_off_h, "rec")
+    n = G * (k + m)
+    _hcheck(pkt_h, "pkt", torch.uint8, (n, None))
+    _hcheck(pkt_len_h, "pkt_len", torch.int32, (n,))
+    _hcheck_lens(ad_len, "ad_len", n)
+    _hcheck(rec_rows_h, "rec_rows", torch.uint8, (G, rmax))
+    if status_h is not None:
+        _hcheck(status_h, "status", torch.int32, (G,))
+    if open_len_h is not None:
+        _hcheck(open_len_h, "open_len", torch.int32, (n,))
+    a, a_all = _hlens(ad_len)
+    rc = engine.lib.qfec_open_decode_batch_ragged_host(
+        engine._h, k, m, G, _hptr(bb_h), _hptr(pkt_h), pkt_h.stride(0), _hptr(pkt_len_h), a,
+        a_all, _hptr(rec_h), _hptr(rec_off_h), _hptr(rec_rows_h),
+        None if status_h is None else _hptr(status_h),
+        None if open_len_h is None else _hptr(open_len_h))
+    if rc:
+        raise FecError(rc, "qfec_open_decode_batch_ragged_host")
     return rc
 
 

@@ -15,7 +15,14 @@ probability 0.7, otherwise uniform over the multiples of 8 in [48, 1352].
 Reference point: the ragged path with every bb = 1352 against the uniform compiled path.
 Outputs of the two paths are compared byte for byte at the timed size before anything is timed.
 
+--pp: the same workload through the protected paths, wire packets at both ends (whole-block
+plaintexts, 16-byte headers; the receiver loses `losses` data packets per group):
+  ragged    one qfec_encode_seal_groups_batch_ragged / qfec_open_decode_batch_ragged call
+  buckets   one qfec_encode_seal_groups_batch / qfec_open_decode_batch per distinct bb
+and every bb = 1352 against the one uniform call: the price of run-time shapes.
+
   python tools/ragged_bench.py --out profiles/ragged/ragged_bench.json
+  python tools/ragged_bench.py --pp --out profiles/ragged/ragged_pp_bench.json
 """
 import argparse
 import json
@@ -52,6 +59,9 @@ def main():
     ap.add_argument("--seed", type=int, default=2025)
     ap.add_argument("--codes", default="32,4,2 10,1,1",
                     help="space-separated k,m,losses triples (default: the two measured codes)")
+    ap.add_argument("--pp", action="store_true",
+                    help="the protected paths: ragged encode + seal and open -> decode against "
+                         "one uniform protected call per distinct bb")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.reps < 20:
@@ -194,13 +204,164 @@ def main():
         results.append(line)
         print(json.dumps(line), flush=True)
 
+    def run_pp(k, m, r, bb, label):
+        """--pp: the protected paths.  Sender: encode + seal of every packet (whole-block
+        plaintexts, 16-byte headers); receiver: open -> decode with data packets 0 .. r-1 of
+        every group lost.  ragged: one qfec_encode_seal_groups_batch_ragged /
+        qfec_open_decode_batch_ragged call; buckets: one qfec_encode_seal_groups_batch /
+        qfec_open_decode_batch per distinct bb on pre-gathered buffers."""
+        G, per, rmax, H = len(bb), k + m, min(k, m), 16
+        n = G * per
+        stride = H + 12 + int(bb.max())
+        assert stride % 4 == 0
+        d_off, p_off, r_off, tot = fec.ragged_layout(k, m, bb)
+        data = torch.empty(tot[0], dtype=torch.uint8, device="cuda")
+        fec.synth_fill(data, seed=args.seed)
+        par = torch.zeros(tot[1], dtype=torch.uint8, device="cuda")
+        rec = torch.zeros(tot[2], dtype=torch.uint8, device="cuda")
+        blocks = torch.zeros(tot[0], dtype=torch.uint8, device="cuda")
+        bb_d = torch.from_numpy(bb).cuda()
+        d_off_d, p_off_d, r_off_d = (torch.from_numpy(o).cuda() for o in (d_off, p_off, r_off))
+        hdr = torch.randint(0, 256, (n, H), dtype=torch.uint8, device="cuda")
+        pkt = torch.zeros((n, stride), dtype=torch.uint8, device="cuda")
+        pkt_len = torch.zeros(n, dtype=torch.int32, device="cuda")
+        est = torch.zeros(G, dtype=torch.int32, device="cuda")
+        rows = torch.zeros((G, k), dtype=torch.uint8, device="cuda")
+        ol = torch.zeros(n, dtype=torch.int32, device="cuda")
+        rr = torch.zeros((G, rmax), dtype=torch.uint8, device="cuda")
+        st = torch.zeros(G, dtype=torch.int32, device="cuda")
+
+        def ragged_seal():
+            eng.seal_groups_ragged(k, m, bb_d, data, d_off_d, par, p_off_d, hdr, H, None, pkt,
+                                   pkt_len, encode=True, status=est)
+
+        ragged_seal()
+        kern = {"ragged_seal": fec.last_kernels()}
+        torch.cuda.synchronize()
+        assert int(est.abs().max()) == 0 and int(pkt_len.min()) >= H + 12
+        wire_len = pkt_len.clone().view(G, per)
+        wire_len[:, :r] = -1                                  # data packets 0 .. r-1 lost
+        wire_len = wire_len.view(n)
+
+        def ragged_open():
+            eng.open_decode_ragged(k, m, bb_d, pkt, wire_len, H, blocks, d_off_d, rows, ol, rec,
+                                   r_off_d, rr, status=st)
+
+        ragged_open()
+        kern["ragged_open"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        assert int(st.abs().max()) == 0
+
+        buckets = []
+        for b in np.unique(bb):
+            idx = np.nonzero(bb == b)[0]
+            b, Gb = int(b), len(idx)
+            pidx = torch.from_numpy((idx[:, None] * per + np.arange(per)[None, :]).ravel()).cuda()
+            bs = H + 12 + b
+            buckets.append(dict(
+                bb=b, G=Gb, idx=idx, pidx=pidx,
+                data=torch.stack(views(data, d_off[idx], [k * b] * Gb)).view(Gb, k, b),
+                hdr=hdr[pidx].contiguous(),
+                wire=pkt[pidx][:, :bs].contiguous(), wire_len=wire_len[pidx].contiguous(),
+                par=torch.zeros((Gb, m, b), dtype=torch.uint8, device="cuda"),
+                pkt=torch.zeros((Gb * per, bs), dtype=torch.uint8, device="cuda"),
+                pkt_len=torch.zeros(Gb * per, dtype=torch.int32, device="cuda"),
+                blocks=torch.zeros((Gb, k, b), dtype=torch.uint8, device="cuda"),
+                rows=torch.zeros((Gb, k), dtype=torch.uint8, device="cuda"),
+                ol=torch.zeros(Gb * per, dtype=torch.int32, device="cuda"),
+                rec=torch.zeros((Gb, rmax, b), dtype=torch.uint8, device="cuda"),
+                rr=torch.zeros((Gb, rmax), dtype=torch.uint8, device="cuda"),
+                st=torch.zeros(Gb, dtype=torch.int32, device="cuda")))
+        nb = len(buckets)
+
+        def bucket_seal(ev=None, base=0):
+            for i, B in enumerate(buckets):
+                f = lambda: eng.seal_groups(k, m, B["bb"], B["data"], B["par"], B["hdr"], H,
+                                            B["bb"], B["pkt"], B["pkt_len"], encode=True)
+                timed(ev, base + i, f) if ev else f()
+
+        def bucket_open(ev=None, base=0):
+            for i, B in enumerate(buckets):
+                f = lambda: eng.open_decode(k, m, B["bb"], B["wire"], B["wire_len"], H,
+                                            B["blocks"], B["rows"], B["ol"], B["rec"], B["rr"],
+                                            status=B["st"])
+                timed(ev, base + i, f) if ev else f()
+
+        # the same bytes from both paths, at the timed size
+        bucket_seal()
+        kern["bucket_seal"] = fec.last_kernels()
+        bucket_open()
+        kern["bucket_open"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        for B in buckets:
+            idx, b, Gb = B["idx"], B["bb"], B["G"]
+            assert torch.equal(B["pkt"], B["wire"]), "sealed packets differ between the paths"
+            assert torch.equal(B["pkt_len"], pkt_len[B["pidx"]]), "packet lengths differ"
+            assert torch.equal(B["ol"], ol[B["pidx"]]), "open lengths differ"
+            got = torch.stack(views(rec, r_off[idx], [r * b] * Gb)).view(Gb, r, b)
+            assert torch.equal(got, B["rec"][:, :r]), "recovered blocks differ between the paths"
+            assert torch.equal(got, B["data"][:, :r]), "recovered blocks are not the lost data"
+
+        ev = DeviceEvents(2 * (2 + 2 * nb))
+        t = {x: [] for x in ("ragged_seal", "ragged_open", "bucket_seal", "bucket_open")}
+        wall = {x: [] for x in t}
+
+        def walled(name, fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            wall[name].append((time.perf_counter() - t0) * 1e3)
+
+        for rep in range(args.warmup + args.reps):
+            order = [("ragged_seal", lambda: timed(ev, 0, ragged_seal)),
+                     ("bucket_seal", lambda: bucket_seal(ev, 2)),
+                     ("ragged_open", lambda: timed(ev, 1, ragged_open)),
+                     ("bucket_open", lambda: bucket_open(ev, 2 + nb))]
+            if rep % 2:
+                order = [order[1], order[0], order[3], order[2]]
+            for name, fn in order:
+                walled(name, fn)
+            if rep < args.warmup:
+                for x in wall:
+                    wall[x].clear()
+                continue
+            t["ragged_seal"].append(ev.elapsed_ms(0, 1))
+            t["ragged_open"].append(ev.elapsed_ms(2, 3))
+            t["bucket_seal"].append(sum(ev.elapsed_ms(2 * (2 + i), 2 * (2 + i) + 1)
+                                        for i in range(nb)))
+            t["bucket_open"].append(sum(ev.elapsed_ms(2 * (2 + nb + i), 2 * (2 + nb + i) + 1)
+                                        for i in range(nb)))
+        ev.close()
+        total = int(bb.astype(np.int64).sum())
+        # wire bytes: every packet sealed / every received packet opened
+        nbytes = {"seal": per * (total + G * (H + 12)), "open": (per - r) * (total + G * (H + 12))}
+        line = dict(config=label, mode="pp", k=k, m=m, losses=r, groups=G, packets=n,
+                    distinct_bb=nb, uniform_calls_per_phase=nb, reps=args.reps, kernels=kern,
+                    wire_bytes=nbytes)
+        for name, v in t.items():
+            med = statistics.median(v)
+            by = nbytes["seal" if name.endswith("seal") else "open"]
+            line[name] = dict(kernel_ms_median=round(med, 4), kernel_ms_min=round(min(v), 4),
+                              kernel_ms_max=round(max(v), 4),
+                              wall_ms_median=round(statistics.median(wall[name]), 4),
+                              wire_GBps=round(by / (med * 1e-3) / 1e9, 1))
+        for ph in ("seal", "open"):
+            line[f"{ph}_kernel_speedup_vs_buckets"] = round(
+                line[f"bucket_{ph}"]["kernel_ms_median"] / line[f"ragged_{ph}"]["kernel_ms_median"], 3)
+            line[f"{ph}_wall_speedup_vs_buckets"] = round(
+                line[f"bucket_{ph}"]["wall_ms_median"] / line[f"ragged_{ph}"]["wall_ms_median"], 3)
+        results.append(line)
+        print(json.dumps(line), flush=True)
+
     G = args.groups
     mixed = draw_sizes(G, args.seed)
     flat = np.full(G, 1352, np.int32)
+    run = run_pp if args.pp else run_config
     for k, m, r in (tuple(int(v) for v in c.split(",")) for c in args.codes.split()):
-        run_config(k, m, r, mixed, f"mixed ({k},{m})")
+        run(k, m, r, mixed, f"mixed ({k},{m})")
         # the price of run-time shapes: every bb = 1352, one bucket = the compiled path (A / B)
-        run_config(k, m, r, flat, f"all-1352 ({k},{m})")
+        run(k, m, r, flat, f"all-1352 ({k},{m})")
     eng.close()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
