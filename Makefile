@@ -20,11 +20,11 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden \
 DCOLK := e63 e83 d62 d82
 # preset syndrome-decode instantiations, one object per code (gf_psyn.h)
 PSYNK := 1010 1015 1020 1515 55
-SRCS := $(CSRC)/fec_kernels.hip $(CSRC)/decode_prep.hip $(CSRC)/xor_dma.hip $(CSRC)/gf_stream.hip $(CSRC)/gf_bsyn.hip $(CSRC)/gf_psyn.hip $(PSYNK:%=$(CSRC)/gf_psyn_%.hip) $(CSRC)/gf_dcol.hip $(DCOLK:%=$(CSRC)/gf_dcol_%.hip) $(CSRC)/gf_ragged.hip $(CSRC)/pp_null.hip $(CSRC)/fec_api.cpp $(CSRC)/fec_ragged_host.cpp $(CSRC)/fec_group.cpp $(CSRC)/fec_wire.cpp
+SRCS := $(CSRC)/fec_kernels.hip $(CSRC)/decode_prep.hip $(CSRC)/xor_dma.hip $(CSRC)/gf_stream.hip $(CSRC)/gf_bsyn.hip $(CSRC)/gf_psyn.hip $(PSYNK:%=$(CSRC)/gf_psyn_%.hip) $(CSRC)/gf_dcol.hip $(DCOLK:%=$(CSRC)/gf_dcol_%.hip) $(CSRC)/gf_ragged.hip $(CSRC)/pp_null.hip $(CSRC)/fec_api.cpp $(CSRC)/fec_host.cpp $(CSRC)/fec_host_plan.cpp $(CSRC)/fec_group.cpp $(CSRC)/fec_wire.cpp
 # the headers every object depends on; the rest (include/*.h, pp_null.h, ...) are tracked per
 # object by -MMD below, so a public-header edit rebuilds only the host files that include it
 HDRS := $(CSRC)/fec_kernels.h $(CSRC)/gf256.h $(CSRC)/gf_bitslice.h
-OBJS := $(ROOT)build/fec_kernels.o $(ROOT)build/decode_prep.o $(ROOT)build/xor_dma.o $(ROOT)build/gf_stream.o $(ROOT)build/gf_bsyn.o $(ROOT)build/gf_psyn.o $(PSYNK:%=$(ROOT)build/gf_psyn_%.o) $(ROOT)build/gf_dcol.o $(DCOLK:%=$(ROOT)build/gf_dcol_%.o) $(ROOT)build/gf_ragged.o $(ROOT)build/pp_null.o $(ROOT)build/fec_api.o $(ROOT)build/fec_ragged_host.o $(ROOT)build/fec_group.o $(ROOT)build/fec_wire.o
+OBJS := $(ROOT)build/fec_kernels.o $(ROOT)build/decode_prep.o $(ROOT)build/xor_dma.o $(ROOT)build/gf_stream.o $(ROOT)build/gf_bsyn.o $(ROOT)build/gf_psyn.o $(PSYNK:%=$(ROOT)build/gf_psyn_%.o) $(ROOT)build/gf_dcol.o $(DCOLK:%=$(ROOT)build/gf_dcol_%.o) $(ROOT)build/gf_ragged.o $(ROOT)build/pp_null.o $(ROOT)build/fec_api.o $(ROOT)build/fec_host.o $(ROOT)build/fec_host_plan.o $(ROOT)build/fec_group.o $(ROOT)build/fec_wire.o
 
 # Build guard (tools/check_stubs.py): every kernel stub a host pass registers has device code
 # in the same object.  Run after each HIP compile (the object is deleted on a mismatch) and on
@@ -57,13 +57,14 @@ $(TOOL): $(ROOT)tools/loopback/fec_loopback.cpp $(LIB) $(ROOT)include/quic_fec_g
 	g++ -O2 -std=c++17 -Wall -I$(ROOT)include -o $@ $< -L$(ROOT)quic_amd -lquic_fec \
 	    -Wl,-rpath,'$$ORIGIN/..' -ldl -lpthread
 
-# Host-code sanitizer check of the ragged layout and packing: a stand-alone program (its own
-# main, no HIP, not loaded into Python) built with ASan + UBSan; `make ragged-check` runs it.
+# Host-code sanitizer check of the ragged layout, the packing and the host batches' staging
+# plan: a stand-alone program (its own main, no HIP, not loaded into Python) built with ASan +
+# UBSan; `make ragged-check` runs it.
 RPCK := $(ROOT)quic_amd/bin/ragged_pack_check
-$(RPCK): $(ROOT)tools/ragged_pack_check.cpp $(CSRC)/fec_ragged_host.cpp $(CSRC)/fec_ragged_host.h $(ROOT)include/quic_fec.h
+$(RPCK): $(ROOT)tools/ragged_pack_check.cpp $(CSRC)/fec_host_plan.cpp $(CSRC)/fec_host_plan.h $(ROOT)include/quic_fec.h
 	@mkdir -p $(ROOT)quic_amd/bin
 	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-sanitize-recover=all \
-	    -I$(ROOT)include -I$(CSRC) -o $@ $(ROOT)tools/ragged_pack_check.cpp $(CSRC)/fec_ragged_host.cpp
+	    -I$(ROOT)include -I$(CSRC) -o $@ $(ROOT)tools/ragged_pack_check.cpp $(CSRC)/fec_host_plan.cpp
 
 .PHONY: ragged-check
 ragged-check: $(RPCK)
@@ -152,14 +153,20 @@ $(ROOT)build/fec_api.o: $(CSRC)/fec_api.cpp $(HDRS) $(TABLES)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
 
+# the host-pointer entry points and their pipeline
+$(ROOT)build/fec_host.o: $(CSRC)/fec_host.cpp $(HDRS)
+	@mkdir -p $(ROOT)build
+	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
+	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
+
 $(ROOT)build/fec_group.o: $(CSRC)/fec_group.cpp $(HDRS)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
 
-# host-only (no HIP): the ragged layout and the queue's packing; also linked alone by the
-# sanitizer check below
-$(ROOT)build/fec_ragged_host.o: $(CSRC)/fec_ragged_host.cpp $(CSRC)/fec_ragged_host.h $(ROOT)include/quic_fec.h
+# host-only (no HIP): the ragged layout, the queue's packing and the staging plan of the host
+# batches; also linked alone by the sanitizer check above
+$(ROOT)build/fec_host_plan.o: $(CSRC)/fec_host_plan.cpp $(CSRC)/fec_host_plan.h $(ROOT)include/quic_fec.h
 	@mkdir -p $(ROOT)build
 	g++ -O2 -std=c++17 -fPIC -fvisibility=hidden -DQFEC_BUILD -Wall -MMD -MP -c $< -o $@
 

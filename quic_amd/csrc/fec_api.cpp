@@ -1,26 +1,20 @@
-// fec_api.cpp — host side of libquic_fec.so: the C ABI in include/quic_fec.h.
+// fec_api.cpp — host side of libquic_fec.so: the C ABI in include/quic_fec.h, except its
+// host-pointer batches (fec_host.cpp).
 //
 // Owns per-device contexts (stream, coefficient tables, decode workspace, pinned
 // staging) and maps the reference's per-group codec calls (cauchy_256.h) and the batched
 // calls onto the gfx950 kernels in fec_kernels.hip.  There is no CPU compute path: every
 // parity / recovered byte is produced on the GPU; if the device is unusable the calls
 // fail with a negative code.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <tuple>
-#include <vector>
 
-#include "../../include/quic_fec.h"
-#include "fec_kernels.h"
+#include "fec_internal.h"
 #include "gf256.h"
 #include "pp_null.h"
+
+using namespace qfec;
 
 // ------------------------------------------------------------- Cauchy table blob
 // quic_amd/data/cauchy_256_tables.bin (tools/gen_cauchy_tables.py) embedded at build time:
@@ -51,22 +45,6 @@ enum {
 thread_local std::string g_err;
 thread_local std::string g_kernels;   // kernels launched by this thread's last call
 thread_local std::string g_grids;     // "name=grid" of its persistent kernels
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-int hip_fail(hipError_t e, const char* what) {
-    g_err = std::string(what) + ": " + hipGetErrorString(e);
-    return -100 - (int)e;
-}
-
-#define QF_HIP(expr)                                   \
-    do {                                               \
-        hipError_t _e = (expr);                        \
-        if (_e != hipSuccess) return hip_fail(_e, #expr); \
-    } while (0)
 
 bool blob_ok() { return (qfec_cauchy_blob_end - qfec_cauchy_blob) == T_SIZE; }
 
@@ -114,86 +92,19 @@ int stream_encode_rc(int k, int m, int bb, bool aligned, const qfec::Tune& t) {
 // with 16 against 0.544 ms).
 int decode_rc(int rmax) { return std::min(pow2_at_least(rmax), 8); }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= n) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; n = 0; }
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) n = bytes;
-        return e;
-    }
-};
-
-struct HostBuf {
-    void* p = nullptr;
-    size_t n = 0;
-    ~HostBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= n) return hipSuccess;
-        if (p) { (void)hipHostFree(p); p = nullptr; n = 0; }
-        hipError_t e = hipHostMalloc(&p, bytes, 0);
-        if (e == hipSuccess) n = bytes;
-        return e;
-    }
-};
-
 }  // namespace
 
-// One decode workspace: the prep's per-group tables and the in-place scratch.
-struct Workspace {
-    DevBuf dcoef, dslots, dnout, dscratch;
-    // graph workspace: a buffer outgrown by a later capture is kept (not freed) until the
-    // context is destroyed, since the graphs captured before still name it
-    bool keep = false;
-    std::vector<std::unique_ptr<DevBuf>> retired;
-    hipError_t ensure(DevBuf& b, size_t bytes) {
-        if (bytes <= b.n) return hipSuccess;
-        if (keep && b.p) {
-            auto old = std::make_unique<DevBuf>();
-            std::swap(old->p, b.p);
-            std::swap(old->n, b.n);
-            retired.push_back(std::move(old));
-        }
-        return b.ensure(bytes);
-    }
-};
+int qfec::fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
 
-struct qfec_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    qfec::Tune tune;
-    // Decode workspaces.  Eager calls share `ws`; they may enqueue on any stream: every
-    // eager use records ws_ev after its kernels, and a use on another stream waits for it, so
-    // eager uses are ordered across streams (ws_begin / ws_end).  Calls captured into a graph
-    // use `ws_graph` instead, so a replay (on whatever stream it is launched) never shares
-    // tables with an eager call; graphs captured on one context share ws_graph, so their
-    // replays must be ordered with each other (include/quic_fec.h).
-    hipEvent_t ws_ev = nullptr;      // on ws_helper, after the last eager use
-    hipEvent_t ws_tmp = nullptr;     // on the last eager use's stream
-    hipStream_t ws_helper = nullptr;
-    hipStream_t ws_stream = nullptr;
-    bool ws_used = false;
-    // encode coefficient tables keyed by (k, m, rc): [nchunk][k][rcp]; decode cenc by (k, m)
-    std::map<std::tuple<int, int, int>, std::unique_ptr<DevBuf>> enc_tab;
-    std::map<std::pair<int, int>, std::unique_ptr<DevBuf>> cenc_tab;
-    Workspace ws, ws_graph;
-    HostBuf h_stage;
-    DevBuf d_stage;
-    // host-pointer batches: copy-in / copy-out streams around `stream` (compute), NB
-    // rotating device staging buffers so H2D, kernels and D2H of successive chunks overlap
-    static constexpr int NB = 3;
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    hipEvent_t ev_in[NB] = {}, ev_done[NB] = {}, ev_out[NB] = {};
-    DevBuf pbuf[NB];
-    std::mutex mu;   // one caller at a time per context (the reference is single-threaded)
-};
+int qfec::hip_fail(hipError_t e, const char* what) {
+    g_err = std::string(what) + ": " + hipGetErrorString(e);
+    return -100 - (int)e;
+}
 
-namespace {
-
-int set_device(qfec_ctx* c) {
+int qfec::set_device(qfec_ctx* c) {
     g_kernels.clear();
     g_grids.clear();
     qfec::launch_timing().first = true;
@@ -208,14 +119,14 @@ int set_device(qfec_ctx* c) {
 // stream is still eager; ws_begin waits on it when a use arrives on another stream, whatever
 // that previous stream is doing now (it may have started a capture since).  A use on the
 // same stream as the last needs no wait (stream order).
-int ws_begin(qfec_ctx* c, hipStream_t st) {
+int qfec::ws_begin(qfec_ctx* c, hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     QF_HIP(hipStreamIsCapturing(st, &cs));
     if (cs != hipStreamCaptureStatusNone) return 0;
     if (c->ws_used && c->ws_stream != st) QF_HIP(hipStreamWaitEvent(st, c->ws_ev, 0));
     return 0;
 }
-int ws_end(qfec_ctx* c, hipStream_t st) {
+int qfec::ws_end(qfec_ctx* c, hipStream_t st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     QF_HIP(hipStreamIsCapturing(st, &cs));
     if (cs != hipStreamCaptureStatusNone) return 0;
@@ -231,17 +142,7 @@ int ws_end(qfec_ctx* c, hipStream_t st) {
     return 0;
 }
 
-// The bracket of one C entry point whose kernels on `st` use the decode workspace: applied
-// once per call, around everything the call enqueues.  ws_end runs whenever ws_begin
-// succeeded, also when the body fails after it has enqueued work.
-template <class F>
-int with_workspace(qfec_ctx* c, hipStream_t st, F&& body) {
-    int r = ws_begin(c, st);
-    if (r) return r;
-    r = body();
-    const int r2 = ws_end(c, st);
-    return r ? r : r2;
-}
+namespace {
 
 // The workspace of a call on `st`: the graph workspace while `st` is capturing.
 Workspace& ws_for(qfec_ctx* c, hipStream_t st) {
@@ -333,7 +234,9 @@ int reserve_workspace(Workspace& W, const DecodePlan& p, long long groups, bool 
     return 0;
 }
 
-int check_common(qfec_ctx* c, int k, int m, int bb, long long groups) {
+}  // namespace
+
+int qfec::check_common(qfec_ctx* c, int k, int m, int bb, long long groups) {
     if (!c) return fail(-2, "null context");
     if (!blob_ok()) return fail(-2, "embedded Cauchy tables have the wrong size");
     if (k < 1 || m < 1 || bb < 1 || groups < 0) return fail(-2, "bad k / m / block_bytes / groups");
@@ -341,8 +244,8 @@ int check_common(qfec_ctx* c, int k, int m, int bb, long long groups) {
     return 0;
 }
 
-int encode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d_data,
-                uint8_t* d_par, hipStream_t st) {
+int qfec::encode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d_data,
+                      uint8_t* d_par, hipStream_t st) {
     if (G == 0) return 0;
     if (k <= 1) {   // cauchy_256.cpp:1508-1516
         QF_HIP(qfec::launch_replicate(d_data, d_par, m, bb, G, st));
@@ -351,7 +254,7 @@ int encode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d
     // P0 = XOR of the data (:1519-1523).  For m == 1 that is the whole answer; for
     // m > 1 with unsupported parameters the reference still writes it before
     // returning -1 (:1532-1534).
-    if (m == 1 || k + m > 256 || bb % 8 != 0) {
+    if (m == 1 || encode_p0_only(k, m, bb)) {
         QF_HIP(qfec::launch_xor_encode(d_data, d_par, k, bb, G, (long long)m * bb, st, c->tune));
         return m == 1 ? 0 : fail(-1, "unsupported (k + m > 256 or block_bytes % 8 != 0)");
     }
@@ -375,23 +278,11 @@ int encode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d
     return 0;
 }
 
-// Where a decode writes.  Slot layout (qfec_decode_batch): recovered blocks go back into their
-// slots of out [G][k][bb] (which may be the blocks themselves) and rows [G][k] gets every
-// slot's row tag.  Compact layout (qfec_decode_batch_recovered): recovered block j of group g
-// goes to out + (g * rmax + j) * bb and its data row to rows[g * rmax + j] (ascending, 255
-// past the erasure count); blocks and row tags are left as they are.  This is what the
-// receiver consumes (getRevivedPackets, quic_fec_group.cc:280-293, only extracts the missing
-// packets), and the writes are dense.
-struct DecodeOut {
-    uint8_t* out;
-    uint8_t* rows;
-    bool compact;
-};
-
 // The one decode dispatch: which kernels a (k, m, bb) decode runs, for either layout.  The
 // caller holds the workspace bracket (with_workspace).
-int decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d_blocks,
-                const uint8_t* d_rows_in, DecodeOut o, int32_t* d_status, hipStream_t st) {
+int qfec::decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d_blocks,
+                      const uint8_t* d_rows_in, DecodeOut o, int32_t* d_status,
+                      hipStream_t st) {
     if (G == 0) return 0;
     const DecodePlan p = decode_plan(k, m, bb);
     const int rmax = p.rmax, rc = p.rc;
@@ -476,92 +367,7 @@ int decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d
     return 0;
 }
 
-// Carves consecutive 256-byte aligned sub-buffers out of one staging buffer.
-struct Carve {
-    uint8_t* p;
-    uint8_t* take(size_t bytes) {
-        uint8_t* r = p;
-        p += (bytes + 255) & ~(size_t)255;
-        return r;
-    }
-};
-constexpr size_t kCarveSlack = 16 * 256;   // alignment padding of up to 16 sub-buffers
-
-// Host-pointer batches, chunked and pipelined: chunk i's H2D (s_in), kernels (stream)
-// and D2H (s_out) are ordered by events, and NB staging buffers rotate, so the copy-in of
-// chunk i + 1 and the copy-out of chunk i - 1 overlap the kernels of chunk i (PCIe is
-// full duplex).  The kernels of all chunks stay on one stream, so the decode workspace is
-// never shared by two chunks in flight.  Chunk size: the host_chunk_mb option (64 MiB), and
-// at least the host_min_groups option's groups (512).
-// fn(g0, n, buf, phase): phase 0 enqueues the H2D, 1 the kernels, 2 the D2H.
-// next(g0): groups in the chunk that starts at group g0 (0: no group left); `bytes`: the
-// staging one chunk needs at most.
-template <class N, class F>
-int host_pipeline_chunks(qfec_ctx* c, size_t bytes, N&& next, F&& fn) {
-    if (!c->s_in) {
-        QF_HIP(hipStreamCreateWithFlags(&c->s_in, hipStreamNonBlocking));
-        QF_HIP(hipStreamCreateWithFlags(&c->s_out, hipStreamNonBlocking));
-        for (int b = 0; b < qfec_ctx::NB; ++b) {
-            QF_HIP(hipEventCreateWithFlags(&c->ev_in[b], hipEventDisableTiming));
-            QF_HIP(hipEventCreateWithFlags(&c->ev_done[b], hipEventDisableTiming));
-            QF_HIP(hipEventCreateWithFlags(&c->ev_out[b], hipEventDisableTiming));
-        }
-    }
-    for (int b = 0; b < qfec_ctx::NB; ++b) QF_HIP(c->pbuf[b].ensure(bytes));
-    int i = 0;
-    long long n = 0;
-    for (long long g0 = 0; (n = next(g0)) > 0; g0 += n, ++i) {
-        const int b = i % qfec_ctx::NB;
-        uint8_t* buf = (uint8_t*)c->pbuf[b].p;
-        if (i >= qfec_ctx::NB) QF_HIP(hipStreamWaitEvent(c->s_in, c->ev_out[b], 0));
-        int r = fn(g0, n, buf, 0);
-        if (r) return r;
-        QF_HIP(hipEventRecord(c->ev_in[b], c->s_in));
-        QF_HIP(hipStreamWaitEvent(c->stream, c->ev_in[b], 0));
-        if ((r = fn(g0, n, buf, 1))) return r;
-        QF_HIP(hipEventRecord(c->ev_done[b], c->stream));
-        QF_HIP(hipStreamWaitEvent(c->s_out, c->ev_done[b], 0));
-        if ((r = fn(g0, n, buf, 2))) return r;
-        QF_HIP(hipEventRecord(c->ev_out[b], c->s_out));
-    }
-    QF_HIP(hipStreamSynchronize(c->s_out));
-    return 0;
-}
-
-template <class F>
-int host_pipeline_body(qfec_ctx* c, long long groups, size_t per_group, F&& fn) {
-    // at least host_min_groups groups per chunk (up to 2 GiB of staging per buffer): a
-    // 64 MiB chunk of D's 1.2 MB groups is 54 groups, too few to fill the device (D at
-    // 16,384 groups: 16.1 GiB/s with 64 MiB chunks, 22.9 with 256 MiB, 23.3 with 1 GiB).
-    // Both are options, so a caller (and the tests) can still force small chunks.
-    const size_t target = (size_t)std::max(1, c->tune.host_chunk_mb) << 20;
-    const long long by_bytes = (long long)(target / per_group);
-    const long long floor_g = std::min<long long>(std::max(1, c->tune.host_min_groups),
-                                                  (long long)((2ull << 30) / per_group));
-    const long long chunk =
-        std::max<long long>(1, std::min<long long>(groups, std::max(by_bytes, floor_g)));
-    return host_pipeline_chunks(
-        c, (size_t)chunk * per_group + kCarveSlack,
-        [&](long long g0) { return std::min(chunk, groups - g0); }, fn);
-}
-
-// On any error, drain all three streams before returning, so no copy of an earlier chunk
-// still writes into the caller's host buffers after the call has returned.
-template <class B>
-int host_pipeline_guard(qfec_ctx* c, B&& body) {
-    // the kernels of every chunk run on the context stream: order them after the last eager
-    // use of the decode workspace, and the next use after them
-    const int r = with_workspace(c, c->stream, body);
-    if (r)
-        for (hipStream_t s : {c->s_in, c->stream, c->s_out})
-            if (s) (void)hipStreamSynchronize(s);
-    return r;
-}
-
-template <class F>
-int host_pipeline(qfec_ctx* c, long long groups, size_t per_group, F&& fn) {
-    return host_pipeline_guard(c, [&] { return host_pipeline_body(c, groups, per_group, fn); });
-}
+namespace {
 
 // Default context for the single-group drop-ins (created on the caller's current device;
 // QFEC_DEVICE names another, read once when the context is first needed).
@@ -624,14 +430,13 @@ int resident_blocks(const void* kern, int threads, size_t lds) {
 }
 }  // namespace qfec
 
-namespace {
-
 // NullDecrypter on every packet of each group, placement into the receive set, the
 // recovered-blocks decode, the unfilled-group status (qfec_open_decode_batch)
-int open_decode_impl(qfec_ctx* c, int k, int m, int bb, long long groups, const uint8_t* d_pkt,
-                     long long pkt_stride, const int* d_pkt_len, const int* d_ad_len,
-                     int ad_len_all, uint8_t* d_blocks, uint8_t* d_rows, int* d_open_len,
-                     uint8_t* d_rec, uint8_t* d_rec_rows, int* d_status, hipStream_t st) {
+int qfec::open_decode_impl(qfec_ctx* c, int k, int m, int bb, long long groups,
+                           const uint8_t* d_pkt, long long pkt_stride, const int* d_pkt_len,
+                           const int* d_ad_len, int ad_len_all, uint8_t* d_blocks,
+                           uint8_t* d_rows, int* d_open_len, uint8_t* d_rec, uint8_t* d_rec_rows,
+                           int* d_status, hipStream_t st) {
     QF_HIP(qfec::launch_open_groups(k, m, bb, groups, d_pkt, pkt_stride,
                                     (const int32_t*)d_pkt_len, (const int32_t*)d_ad_len,
                                     ad_len_all, d_blocks, d_rows, (int32_t*)d_open_len, st));
@@ -642,6 +447,8 @@ int open_decode_impl(qfec_ctx* c, int k, int m, int bb, long long groups, const 
                                     (int32_t*)d_status, st));
     return 0;
 }
+
+namespace {
 
 // The options of qfec_ctx_set_option / qfec_ctx_get_option: a member of the context's Tune, the
 // values it accepts (lo > hi: read only, set does not know the name) and any further rule.
@@ -684,6 +491,7 @@ const Opt* find_option(const char* name) {
 }  // namespace
 
 // ======================================================================== C ABI
+// (the internal qfec:: functions defined among the entry points keep their C++ linkage)
 extern "C" {
 
 int qfec_version(void) { return 1; }
@@ -871,19 +679,20 @@ int qfec_encode_seal_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
 
 // Every packet of each group, data and FEC, in one launch (quic_packet_creator.cc:733-736
 // seals each data packet, :948-953 each FEC packet); packet (g, i) = g * (k + m) + i.
-static int seal_groups_args(qfec_ctx* c, int k, int m, int bb, long long groups,
-                            const unsigned char* d_data, const unsigned char* d_parity,
-                            const unsigned char* d_hdr, long long hdr_stride, const int* d_hdr_len,
-                            int hdr_len_all, const int* d_pt_len, int pt_len_all,
-                            const unsigned char* d_pkt, long long pkt_stride, const int* d_pkt_len) {
+extern "C++" int qfec::seal_groups_args(qfec_ctx* c, int k, int m, int bb, long long groups,
+                                        std::initializer_list<const void*> required,
+                                        const unsigned char* hdr, long long hdr_stride,
+                                        const int* hdr_len, int hdr_len_all, const int* pt_len,
+                                        int pt_len_all, const unsigned char* pkt,
+                                        long long pkt_stride) {
     int rc = check_common(c, k, m, bb, groups);
     if (rc) return rc;
     if (k + m > 256) return fail(-2, "k + m > 256");
-    if (groups && (!d_data || !d_parity || !d_pkt || !d_pkt_len || (!d_hdr && (d_hdr_len || hdr_len_all))))
+    if (groups && (any_null(required) || (!hdr && (hdr_len || hdr_len_all))))
         return fail(-2, "null buffer");
     if (hdr_stride < 0 || pkt_stride < 0) return fail(-2, "bad stride");
-    if (!d_pt_len && (pt_len_all < 0 || pt_len_all > bb)) return fail(-2, "pt_len_all outside 0..block_bytes");
-    if ((((uintptr_t)d_pkt) | (uintptr_t)pkt_stride) & 3) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
+    if (!pt_len && (pt_len_all < 0 || pt_len_all > bb)) return fail(-2, "pt_len_all outside 0..block_bytes");
+    if ((((uintptr_t)pkt) | (uintptr_t)pkt_stride) & 3) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
     return 0;
 }
 
@@ -892,8 +701,9 @@ int qfec_seal_groups_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
                            const unsigned char* d_hdr, long long hdr_stride, const int* d_hdr_len,
                            int hdr_len_all, const int* d_pt_len, int pt_len_all,
                            unsigned char* d_pkt, long long pkt_stride, int* d_pkt_len, void* stream) {
-    int rc = seal_groups_args(c, k, m, bb, groups, d_data, d_parity, d_hdr, hdr_stride, d_hdr_len,
-                              hdr_len_all, d_pt_len, pt_len_all, d_pkt, pkt_stride, d_pkt_len);
+    int rc = seal_groups_args(c, k, m, bb, groups, {d_data, d_parity, d_pkt, d_pkt_len}, d_hdr,
+                              hdr_stride, d_hdr_len, hdr_len_all, d_pt_len, pt_len_all, d_pkt,
+                              pkt_stride);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
@@ -910,8 +720,9 @@ int qfec_encode_seal_groups_batch(qfec_ctx* c, int k, int m, int bb, long long g
                                   const int* d_hdr_len, int hdr_len_all, const int* d_pt_len,
                                   int pt_len_all, unsigned char* d_pkt, long long pkt_stride,
                                   int* d_pkt_len, void* stream) {
-    int rc = seal_groups_args(c, k, m, bb, groups, d_data, d_parity, d_hdr, hdr_stride, d_hdr_len,
-                              hdr_len_all, d_pt_len, pt_len_all, d_pkt, pkt_stride, d_pkt_len);
+    int rc = seal_groups_args(c, k, m, bb, groups, {d_data, d_parity, d_pkt, d_pkt_len}, d_hdr,
+                              hdr_stride, d_hdr_len, hdr_len_all, d_pt_len, pt_len_all, d_pkt,
+                              pkt_stride);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
@@ -948,257 +759,6 @@ int qfec_open_decode_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
     });
 }
 
-int qfec_decode_batch_recovered_host(qfec_ctx* c, int k, int m, int bb, long long groups,
-                                     const unsigned char* h_blocks, const unsigned char* h_rows,
-                                     unsigned char* h_rec, unsigned char* h_rec_rows,
-                                     int* h_status) {
-    int rc = check_common(c, k, m, bb, groups);
-    if (rc) return rc;
-    if (groups == 0) return 0;
-    if (!h_blocks || !h_rows || !h_rec || !h_rec_rows) return fail(-2, "null buffer");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    const int rmax = std::min(k, m);
-    const size_t blk_g = (size_t)k * bb, rec_g = (size_t)rmax * bb;
-    // per group: blocks, recovered blocks, row tags, recovered rows, status
-    const size_t per = blk_g + rec_g + k + rmax + sizeof(int32_t);
-    return host_pipeline(c, groups, per, [&](long long g0, long long n, uint8_t* buf,
-                                             int phase) -> int {
-        Carve cv{buf};
-        uint8_t* db = cv.take((size_t)n * blk_g);
-        uint8_t* dre = cv.take((size_t)n * rec_g);
-        uint8_t* dr = cv.take((size_t)n * k);
-        uint8_t* drr = cv.take((size_t)n * rmax);
-        int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
-        if (phase == 0) {
-            QF_HIP(hipMemcpyAsync(db, h_blocks + (size_t)g0 * blk_g, (size_t)n * blk_g,
-                                  hipMemcpyHostToDevice, c->s_in));
-            QF_HIP(hipMemcpyAsync(dr, h_rows + (size_t)g0 * k, (size_t)n * k,
-                                  hipMemcpyHostToDevice, c->s_in));
-        } else if (phase == 1) {
-            return decode_impl(c, k, m, bb, n, db, dr, {dre, drr, true}, ds, c->stream);
-        } else {
-            QF_HIP(hipMemcpyAsync(h_rec + (size_t)g0 * rec_g, dre, (size_t)n * rec_g,
-                                  hipMemcpyDeviceToHost, c->s_out));
-            QF_HIP(hipMemcpyAsync(h_rec_rows + (size_t)g0 * rmax, drr, (size_t)n * rmax,
-                                  hipMemcpyDeviceToHost, c->s_out));
-            if (h_status)
-                QF_HIP(hipMemcpyAsync(h_status + g0, ds, (size_t)n * sizeof(int32_t),
-                                      hipMemcpyDeviceToHost, c->s_out));
-        }
-        return 0;
-    });
-}
-
-// Sender, host memory to host memory: data blocks and packet headers in, every sealed packet
-// of each group out (the parity never leaves the device).  Chunked and pipelined as the
-// other host batches: H2D of chunk i + 1 and D2H of chunk i - 1 overlap chunk i's encode and
-// seal.
-int qfec_encode_seal_groups_batch_host(qfec_ctx* c, int k, int m, int bb, long long groups,
-                                       const unsigned char* h_data, const unsigned char* h_hdr,
-                                       long long hdr_stride, const int* h_hdr_len,
-                                       int hdr_len_all, const int* h_pt_len, int pt_len_all,
-                                       unsigned char* h_pkt, long long pkt_stride,
-                                       int* h_pkt_len) {
-    const unsigned char* dummy = (const unsigned char*)16;   // non-null for the argument check
-    int rc = seal_groups_args(c, k, m, bb, groups, h_data, dummy, h_hdr, hdr_stride, h_hdr_len,
-                              hdr_len_all, h_pt_len, pt_len_all, h_pkt, pkt_stride, h_pkt_len);
-    if (rc) return rc;
-    if (groups == 0) return 0;
-    if (hdr_stride <= 0 && h_hdr) return fail(-2, "host headers need a row stride > 0");
-    if (pkt_stride <= 0) return fail(-2, "host packets need a row stride > 0");
-    // the encode's -1 (cauchy_256.cpp:1530-1534): no packet is sealed, as on the device path
-    // (the parity rows past P0 would be stale staging bytes sent with valid tags)
-    if (m > 1 && k > 1 && (k + m > 256 || bb % 8 != 0))
-        return fail(-1, "unsupported (k + m > 256 or block_bytes % 8 != 0)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    const long long np = k + m;                        // packets per group
-    const size_t in_g = (size_t)k * bb, par_g = (size_t)m * bb;
-    const size_t hdr_g = h_hdr ? (size_t)np * hdr_stride : 0;
-    const size_t pkt_g = (size_t)np * pkt_stride;
-    const size_t len_g = (size_t)np * sizeof(int32_t);
-    const size_t per = in_g + par_g + hdr_g + pkt_g + len_g * (1 + (h_hdr_len ? 1 : 0) + (h_pt_len ? 1 : 0));
-    rc = host_pipeline(c, groups, per, [&](long long g0, long long n, uint8_t* buf,
-                                           int phase) -> int {
-        Carve cv{buf};
-        uint8_t* dd = cv.take((size_t)n * in_g);
-        uint8_t* dp = cv.take((size_t)n * par_g);
-        uint8_t* dh = h_hdr ? cv.take((size_t)n * hdr_g) : nullptr;
-        uint8_t* dk = cv.take((size_t)n * pkt_g);
-        int32_t* dkl = (int32_t*)cv.take((size_t)n * len_g);
-        int32_t* dhl = h_hdr_len ? (int32_t*)cv.take((size_t)n * len_g) : nullptr;
-        int32_t* dpl = h_pt_len ? (int32_t*)cv.take((size_t)n * len_g) : nullptr;
-        const size_t p0 = (size_t)g0 * np, pn = (size_t)n * np;
-        if (phase == 0) {
-            QF_HIP(hipMemcpyAsync(dd, h_data + (size_t)g0 * in_g, (size_t)n * in_g,
-                                  hipMemcpyHostToDevice, c->s_in));
-            if (dh)
-                QF_HIP(hipMemcpyAsync(dh, h_hdr + p0 * hdr_stride, pn * hdr_stride,
-                                      hipMemcpyHostToDevice, c->s_in));
-            if (dhl)
-                QF_HIP(hipMemcpyAsync(dhl, h_hdr_len + p0, pn * sizeof(int32_t),
-                                      hipMemcpyHostToDevice, c->s_in));
-            if (dpl)
-                QF_HIP(hipMemcpyAsync(dpl, h_pt_len + p0, pn * sizeof(int32_t),
-                                      hipMemcpyHostToDevice, c->s_in));
-        } else if (phase == 1) {
-            const int r = encode_impl(c, k, m, bb, n, dd, dp, c->stream);
-            if (r) return r;
-            // packet rows are copied back whole: zero the staging rows first, so the bytes of
-            // a row past its packet are zeros (as the device path leaves them untouched), not
-            // an earlier chunk's packets
-            QF_HIP(hipMemsetAsync(dk, 0, pn * pkt_stride, c->stream));
-            QF_HIP(qfec::launch_null_seal_groups(k, m, bb, n, dd, dp, dh,
-                                                 dh ? hdr_stride : 0, dhl, dh ? hdr_len_all : 0,
-                                                 dpl, pt_len_all, dk, pkt_stride, dkl, c->stream));
-        } else {
-            QF_HIP(hipMemcpyAsync(h_pkt + p0 * pkt_stride, dk, pn * pkt_stride,
-                                  hipMemcpyDeviceToHost, c->s_out));
-            QF_HIP(hipMemcpyAsync(h_pkt_len + p0, dkl, pn * sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, c->s_out));
-        }
-        return 0;
-    });
-    return rc;
-}
-
-// Receiver, host memory to host memory: wire packets in, the recovered blocks (and, if asked,
-// each packet's open length) out.  Chunked and pipelined as the other host batches.
-int qfec_open_decode_batch_host(qfec_ctx* c, int k, int m, int bb, long long groups,
-                                const unsigned char* h_pkt, long long pkt_stride,
-                                const int* h_pkt_len, const int* h_ad_len, int ad_len_all,
-                                unsigned char* h_rec, unsigned char* h_rec_rows, int* h_status,
-                                int* h_open_len) {
-    int rc = check_common(c, k, m, bb, groups);
-    if (rc) return rc;
-    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
-    if (groups == 0) return 0;
-    if (!h_pkt || !h_pkt_len || !h_rec || !h_rec_rows) return fail(-2, "null buffer");
-    if (pkt_stride <= 0) return fail(-2, "bad pkt_stride");
-    if (!h_ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    const long long np = k + m;
-    const int rmax = std::min(k, m);
-    const size_t pkt_g = (size_t)np * pkt_stride, len_g = (size_t)np * sizeof(int32_t);
-    const size_t blk_g = (size_t)k * bb, rec_g = (size_t)rmax * bb;
-    const size_t per = pkt_g + len_g * (2 + (h_ad_len ? 1 : 0)) + blk_g + k + rec_g + rmax +
-                       sizeof(int32_t);
-    return host_pipeline(c, groups, per, [&](long long g0, long long n, uint8_t* buf,
-                                             int phase) -> int {
-        Carve cv{buf};
-        uint8_t* dk = cv.take((size_t)n * pkt_g);
-        int32_t* dkl = (int32_t*)cv.take((size_t)n * len_g);
-        int32_t* dal = h_ad_len ? (int32_t*)cv.take((size_t)n * len_g) : nullptr;
-        int32_t* dol = (int32_t*)cv.take((size_t)n * len_g);
-        uint8_t* db = cv.take((size_t)n * blk_g);
-        uint8_t* dr = cv.take((size_t)n * k);
-        uint8_t* dre = cv.take((size_t)n * rec_g);
-        uint8_t* drr = cv.take((size_t)n * rmax);
-        int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
-        const size_t p0 = (size_t)g0 * np, pn = (size_t)n * np;
-        if (phase == 0) {
-            QF_HIP(hipMemcpyAsync(dk, h_pkt + p0 * pkt_stride, pn * pkt_stride,
-                                  hipMemcpyHostToDevice, c->s_in));
-            QF_HIP(hipMemcpyAsync(dkl, h_pkt_len + p0, pn * sizeof(int32_t),
-                                  hipMemcpyHostToDevice, c->s_in));
-            if (dal)
-                QF_HIP(hipMemcpyAsync(dal, h_ad_len + p0, pn * sizeof(int32_t),
-                                      hipMemcpyHostToDevice, c->s_in));
-        } else if (phase == 1) {
-            return open_decode_impl(c, k, m, bb, n, dk, pkt_stride, dkl, dal, ad_len_all, db, dr,
-                                    dol, dre, drr, ds, c->stream);
-        } else {
-            QF_HIP(hipMemcpyAsync(h_rec + (size_t)g0 * rec_g, dre, (size_t)n * rec_g,
-                                  hipMemcpyDeviceToHost, c->s_out));
-            QF_HIP(hipMemcpyAsync(h_rec_rows + (size_t)g0 * rmax, drr, (size_t)n * rmax,
-                                  hipMemcpyDeviceToHost, c->s_out));
-            if (h_status)
-                QF_HIP(hipMemcpyAsync(h_status + g0, ds, (size_t)n * sizeof(int32_t),
-                                      hipMemcpyDeviceToHost, c->s_out));
-            if (h_open_len)
-                QF_HIP(hipMemcpyAsync(h_open_len + p0, dol, pn * sizeof(int32_t),
-                                      hipMemcpyDeviceToHost, c->s_out));
-        }
-        return 0;
-    });
-}
-
-int qfec_encode_batch_host(qfec_ctx* c, int k, int m, int bb, long long groups,
-                           const unsigned char* h_data, unsigned char* h_parity) {
-    int rc = check_common(c, k, m, bb, groups);
-    if (rc) return rc;
-    if (groups == 0) return 0;
-    if (!h_data || !h_parity) return fail(-2, "null buffer");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    // On the reference's -1 path only P0 is written (cauchy_256.cpp:1519-1534): copy back
-    // only row 0 of each group so the caller's other recovery rows stay untouched.
-    const bool p0_only = m > 1 && k > 1 && (k + m > 256 || bb % 8 != 0);
-    const size_t in_g = (size_t)k * bb, out_g = (size_t)m * bb;
-    int result = 0;
-    rc = host_pipeline(c, groups, in_g + out_g, [&](long long g0, long long n, uint8_t* buf,
-                                                     int phase) -> int {
-        Carve cv{buf};
-        uint8_t* dd = cv.take((size_t)n * in_g);
-        uint8_t* dp = cv.take((size_t)n * out_g);
-        if (phase == 0) {
-            QF_HIP(hipMemcpyAsync(dd, h_data + (size_t)g0 * in_g, (size_t)n * in_g,
-                                  hipMemcpyHostToDevice, c->s_in));
-        } else if (phase == 1) {
-            const int r = encode_impl(c, k, m, bb, n, dd, dp, c->stream);
-            if (r < -1) return r;
-            if (r) result = r;
-        } else if (p0_only) {
-            QF_HIP(hipMemcpy2DAsync(h_parity + (size_t)g0 * out_g, out_g, dp, out_g, bb, n,
-                                    hipMemcpyDeviceToHost, c->s_out));
-        } else {
-            QF_HIP(hipMemcpyAsync(h_parity + (size_t)g0 * out_g, dp, (size_t)n * out_g,
-                                  hipMemcpyDeviceToHost, c->s_out));
-        }
-        return 0;
-    });
-    return rc ? rc : result;
-}
-
-int qfec_decode_batch_host(qfec_ctx* c, int k, int m, int bb, long long groups,
-                           unsigned char* h_blocks, unsigned char* h_rows, int* h_status) {
-    int rc = check_common(c, k, m, bb, groups);
-    if (rc) return rc;
-    if (groups == 0) return 0;
-    if (!h_blocks || !h_rows) return fail(-2, "null buffer");
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    const size_t blk_g = (size_t)k * bb;
-    // per group: blocks, row tags, status
-    const size_t per = blk_g + k + sizeof(int32_t);
-    return host_pipeline(c, groups, per, [&](long long g0, long long n, uint8_t* buf,
-                                             int phase) -> int {
-        Carve cv{buf};
-        uint8_t* db = cv.take((size_t)n * blk_g);
-        uint8_t* dr = cv.take((size_t)n * k);
-        int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
-        if (phase == 0) {
-            QF_HIP(hipMemcpyAsync(db, h_blocks + (size_t)g0 * blk_g, (size_t)n * blk_g,
-                                  hipMemcpyHostToDevice, c->s_in));
-            QF_HIP(hipMemcpyAsync(dr, h_rows + (size_t)g0 * k, (size_t)n * k,
-                                  hipMemcpyHostToDevice, c->s_in));
-        } else if (phase == 1) {
-            return decode_impl(c, k, m, bb, n, db, dr, {db, dr, false}, ds, c->stream);
-        } else {
-            QF_HIP(hipMemcpyAsync(h_blocks + (size_t)g0 * blk_g, db, (size_t)n * blk_g,
-                                  hipMemcpyDeviceToHost, c->s_out));
-            QF_HIP(hipMemcpyAsync(h_rows + (size_t)g0 * k, dr, (size_t)n * k,
-                                  hipMemcpyDeviceToHost, c->s_out));
-            if (h_status)
-                QF_HIP(hipMemcpyAsync(h_status + g0, ds, (size_t)n * sizeof(int32_t),
-                                      hipMemcpyDeviceToHost, c->s_out));
-        }
-        return 0;
-    });
-}
-
 // ---- ragged batches: the groups share (k, m), each has its own block_bytes (gf_ragged.hip).
 // Nothing here reads d_bb or the offsets back: every per-group decision is the kernels'.
 // Output chunk of the ragged kernels: at most 4.  Their loops around the unit leave no room
@@ -1206,9 +766,9 @@ int qfec_decode_batch_host(qfec_ctx* c, int k, int m, int bb, long long groups,
 // against the (32, 4) encode's 0.86 ms for less data); more chunks re-read the group from L2.
 static int ragged_rc(int rc) { return std::min(rc, 4); }
 
-static int encode_ragged_impl(qfec_ctx* c, int k, int m, long long G, qfec::RaggedView v,
-                              const uint8_t* d_data, uint8_t* d_par, int32_t* d_status,
-                              hipStream_t st) {
+extern "C++" int qfec::encode_ragged_impl(qfec_ctx* c, int k, int m, long long G, RaggedView v,
+                                          const uint8_t* d_data, uint8_t* d_par, int32_t* d_status,
+                                          hipStream_t st) {
     if (G == 0) return 0;
     if (k <= 1) {   // cauchy_256.cpp:1508-1516
         QF_HIP(qfec::launch_copy_ragged(d_data, d_par, v, nullptr, nullptr, d_status, m, G, false,
@@ -1233,9 +793,10 @@ static int encode_ragged_impl(qfec_ctx* c, int k, int m, long long G, qfec::Ragg
 }
 
 // The caller holds the workspace bracket (with_workspace).
-static int decode_ragged_impl(qfec_ctx* c, int k, int m, long long G, qfec::RaggedView v,
-                              const uint8_t* d_blocks, const uint8_t* d_rows_in, uint8_t* d_rec,
-                              uint8_t* d_rec_rows, int32_t* d_status, hipStream_t st) {
+extern "C++" int qfec::decode_ragged_impl(qfec_ctx* c, int k, int m, long long G, RaggedView v,
+                                          const uint8_t* d_blocks, const uint8_t* d_rows_in,
+                                          uint8_t* d_rec, uint8_t* d_rec_rows, int32_t* d_status,
+                                          hipStream_t st) {
     if (G == 0) return 0;
     // the prep's tables do not depend on the block size: plan and prep with the smallest valid
     // one, the per-group size only enters the apply and the status fix-up
@@ -1273,12 +834,19 @@ static int decode_ragged_impl(qfec_ctx* c, int k, int m, long long G, qfec::Ragg
     return 0;
 }
 
-static int ragged_check(qfec_ctx* c, int k, int m, long long groups, const void* bb,
-                        const void* a, const void* a_off, const void* b, const void* b_off) {
+extern "C++" int qfec::ragged_preface(qfec_ctx* c, int k, int m, long long groups) {
     int rc = check_common(c, k, m, 1, groups < 0 ? 0 : groups);
     if (rc) return rc;
     if (groups < 0) return fail(-2, "groups < 0");
-    if (!bb || !a || !a_off || !b || !b_off) return fail(-2, "null buffer");
+    return 0;
+}
+
+// The device forms: the packed arrays a and b are read in place, in 16-byte columns.
+static int ragged_check(qfec_ctx* c, int k, int m, long long groups, const void* bb,
+                        const void* a, const void* a_off, const void* b, const void* b_off) {
+    int rc = ragged_preface(c, k, m, groups);
+    if (rc) return rc;
+    if (any_null({bb, a, a_off, b, b_off})) return fail(-2, "null buffer");
     if ((((uintptr_t)a) | (uintptr_t)b) & 15) return fail(-2, "ragged base pointers must be 16-byte aligned");
     return 0;
 }
@@ -1314,176 +882,13 @@ int qfec_decode_batch_ragged_recovered(qfec_ctx* c, int k, int m, long long grou
     });
 }
 
-// Host-pointer ragged batches.  The chunks of the pipeline are cut on group boundaries by
-// bytes (the host_chunk_mb option; a chunk holds at least one group): chunk c stages the span
-// of its groups' inputs and the span of their outputs, and the offsets it hands the kernels
-// are relative to its first group.  The output span is first filled with the caller's bytes,
-// so the copy back returns every byte the kernels did not write (gaps, groups with a negative
-// status, entries past a group's erasure count) as it was.
-struct RaggedChunks {
-    std::vector<long long> first;          // chunk c = groups [first[c], first[c + 1])
-    std::vector<long long> in_rel, out_rel;  // [G] offsets relative to the chunk's first group
-    size_t max_in = 0, max_out = 0, max_groups = 0;
-    long long in_span(const long long* off, const int* bb, long long g0, long long g1, int n) const {
-        return off[g1 - 1] + (long long)n * bb[g1 - 1] - off[g0];
-    }
-    // groups in the chunk that starts at group g0 (0: no group left); asked in ascending order
-    size_t ci = 0;
-    long long next(long long g0) {
-        if (g0 >= first.back()) return 0;
-        while (first[ci] != g0) ++ci;
-        return first[ci + 1] - g0;
-    }
-};
-
-static int ragged_chunks(qfec_ctx* c, int n_in, int n_out, long long G, const int* bb,
-                         const long long* in_off, const long long* out_off, size_t small_per_group,
-                         RaggedChunks* rc) {
-    for (long long g = 0; g < G; ++g) {
-        if (bb[g] < 1) return fail(-2, "bb[g] < 1");
-        if (in_off[g] < 0 || out_off[g] < 0 || ((in_off[g] | out_off[g]) & 15))
-            return fail(-2, "ragged offsets must be non-negative multiples of 16");
-        if (g && (in_off[g] < in_off[g - 1] + (long long)n_in * bb[g - 1] ||
-                  out_off[g] < out_off[g - 1] + (long long)n_out * bb[g - 1]))
-            return fail(-2, "host ragged batches need ascending, non-overlapping offsets");
-    }
-    const long long target = (long long)std::max(1, c->tune.host_chunk_mb) << 20;
-    rc->in_rel.resize((size_t)G);
-    rc->out_rel.resize((size_t)G);
-    long long g0 = 0;
-    rc->first.push_back(0);
-    auto close = [&](long long g1) {
-        rc->max_in = std::max(rc->max_in, (size_t)rc->in_span(in_off, bb, g0, g1, n_in));
-        rc->max_out = std::max(rc->max_out, (size_t)rc->in_span(out_off, bb, g0, g1, n_out));
-        rc->max_groups = std::max(rc->max_groups, (size_t)(g1 - g0));
-    };
-    for (long long g = 0; g < G; ++g) {
-        const long long bytes = rc->in_span(in_off, bb, g0, g + 1, n_in) +
-                                rc->in_span(out_off, bb, g0, g + 1, n_out) +
-                                (g + 1 - g0) * (long long)small_per_group;
-        if (g > g0 && bytes > target) {
-            close(g);
-            g0 = g;
-            rc->first.push_back(g);
-        }
-        rc->in_rel[(size_t)g] = in_off[g] - in_off[g0];
-        rc->out_rel[(size_t)g] = out_off[g] - out_off[g0];
-    }
-    close(G);
-    rc->first.push_back(G);
-    return 0;
-}
-
-// Shared by the two host entry points: decode adds the row tags in and the recovered rows out.
-static int ragged_host(qfec_ctx* c, int k, int m, long long G, const int* h_bb,
-                       const unsigned char* h_in, const long long* h_in_off,
-                       const unsigned char* h_rows, unsigned char* h_out,
-                       const long long* h_out_off, unsigned char* h_rec_rows, int* h_status,
-                       bool decode) {
-    const int n_out = decode ? std::min(k, m) : m;
-    const size_t small = sizeof(int32_t) * 2 + 2 * sizeof(long long) +
-                         (decode ? (size_t)k + (size_t)n_out : 0);
-    RaggedChunks ch;
-    int rc = ragged_chunks(c, k, n_out, G, h_bb, h_in_off, h_out_off, small, &ch);
-    if (rc) return rc;
-    const size_t bytes = ch.max_in + ch.max_out + ch.max_groups * small + kCarveSlack;
-    int result = 0;
-    rc = host_pipeline_guard(c, [&] {
-        return host_pipeline_chunks(
-            c, bytes,
-            [&](long long g0) { return ch.next(g0); },
-            [&](long long g0, long long n, uint8_t* buf, int phase) -> int {
-                const size_t in_b = (size_t)ch.in_span(h_in_off, h_bb, g0, g0 + n, k);
-                const size_t out_b = (size_t)ch.in_span(h_out_off, h_bb, g0, g0 + n, n_out);
-                Carve cv{buf};
-                uint8_t* di = cv.take(in_b);
-                uint8_t* dout = cv.take(out_b);
-                int32_t* dbb = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
-                long long* dio = (long long*)cv.take((size_t)n * sizeof(long long));
-                long long* doo = (long long*)cv.take((size_t)n * sizeof(long long));
-                int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
-                uint8_t* dr = decode ? cv.take((size_t)n * k) : nullptr;
-                uint8_t* drr = decode ? cv.take((size_t)n * n_out) : nullptr;
-                const unsigned char* src = h_in + h_in_off[g0];
-                unsigned char* dst = h_out + h_out_off[g0];
-                if (phase == 0) {
-                    QF_HIP(hipMemcpyAsync(di, src, in_b, hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(dout, dst, out_b, hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(dbb, h_bb + g0, (size_t)n * sizeof(int32_t),
-                                          hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(dio, ch.in_rel.data() + g0, (size_t)n * sizeof(long long),
-                                          hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(doo, ch.out_rel.data() + g0, (size_t)n * sizeof(long long),
-                                          hipMemcpyHostToDevice, c->s_in));
-                    if (decode)
-                        QF_HIP(hipMemcpyAsync(dr, h_rows + (size_t)g0 * k, (size_t)n * k,
-                                              hipMemcpyHostToDevice, c->s_in));
-                } else if (phase == 1) {
-                    const qfec::RaggedView v{dbb, dio, doo};
-                    if (decode)
-                        return decode_ragged_impl(c, k, m, n, v, di, dr, dout, drr, ds, c->stream);
-                    const int r = encode_ragged_impl(c, k, m, n, v, di, dout, ds, c->stream);
-                    if (r < -1) return r;
-                    if (r) result = r;
-                } else {
-                    QF_HIP(hipMemcpyAsync(dst, dout, out_b, hipMemcpyDeviceToHost, c->s_out));
-                    if (decode)
-                        QF_HIP(hipMemcpyAsync(h_rec_rows + (size_t)g0 * n_out, drr,
-                                              (size_t)n * n_out, hipMemcpyDeviceToHost, c->s_out));
-                    if (h_status)
-                        QF_HIP(hipMemcpyAsync(h_status + g0, ds, (size_t)n * sizeof(int32_t),
-                                              hipMemcpyDeviceToHost, c->s_out));
-                }
-                return 0;
-            });
-    });
-    return rc ? rc : result;
-}
-
-int qfec_encode_batch_ragged_host(qfec_ctx* c, int k, int m, long long groups, const int* h_bb,
-                                  const unsigned char* h_data, const long long* h_data_off,
-                                  unsigned char* h_parity, const long long* h_par_off,
-                                  int* h_status) {
-    int rc = check_common(c, k, m, 1, groups < 0 ? 0 : groups);
-    if (rc) return rc;
-    if (groups < 0) return fail(-2, "groups < 0");
-    if (!h_bb || !h_data || !h_data_off || !h_parity || !h_par_off) return fail(-2, "null buffer");
-    if (groups == 0) return 0;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    return ragged_host(c, k, m, groups, h_bb, h_data, h_data_off, nullptr, h_parity, h_par_off,
-                       nullptr, h_status, false);
-}
-
-int qfec_decode_batch_ragged_recovered_host(qfec_ctx* c, int k, int m, long long groups,
-                                            const int* h_bb, const unsigned char* h_blocks,
-                                            const long long* h_blocks_off,
-                                            const unsigned char* h_rows, unsigned char* h_rec,
-                                            const long long* h_rec_off,
-                                            unsigned char* h_rec_rows, int* h_status) {
-    int rc = check_common(c, k, m, 1, groups < 0 ? 0 : groups);
-    if (rc) return rc;
-    if (groups < 0) return fail(-2, "groups < 0");
-    if (!h_bb || !h_blocks || !h_blocks_off || !h_rows || !h_rec || !h_rec_off || !h_rec_rows)
-        return fail(-2, "null buffer");
-    if (groups == 0) return 0;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    return ragged_host(c, k, m, groups, h_bb, h_blocks, h_blocks_off, h_rows, h_rec, h_rec_off,
-                       h_rec_rows, h_status, true);
-}
-
 // ---- ragged packet protection: the protected paths over the packed layout (pp_null.hip's
 // ragged kernels around encode_ragged_impl / decode_ragged_impl).  Packets stay dense by
 // packet index; only the blocks are packed.
-static int seal_ragged_args(qfec_ctx* c, int k, int m, long long groups, const int* bb,
-                            const unsigned char* data, const long long* data_off,
-                            const unsigned char* parity, const long long* par_off,
-                            const unsigned char* hdr, long long hdr_stride, const int* hdr_len,
-                            int hdr_len_all, const unsigned char* pkt, long long pkt_stride,
-                            const int* pkt_len) {
-    int rc = ragged_check(c, k, m, groups, bb, data, data_off, parity, par_off);
-    if (rc) return rc;
+extern "C++" int qfec::seal_ragged_pkt_args(int k, int m, const unsigned char* hdr,
+                                            long long hdr_stride, const int* hdr_len,
+                                            int hdr_len_all, const unsigned char* pkt,
+                                            long long pkt_stride, const int* pkt_len) {
     if (k + m > 256) return fail(-2, "k + m > 256");
     if (!pkt || !pkt_len || (!hdr && (hdr_len || hdr_len_all))) return fail(-2, "null buffer");
     if (hdr_stride < 0 || pkt_stride < 0) return fail(-2, "bad stride");
@@ -1498,10 +903,11 @@ static int seal_groups_ragged(qfec_ctx* c, int k, int m, long long groups, const
                               const int* d_hdr_len, int hdr_len_all, const int* d_pt_len,
                               unsigned char* d_pkt, long long pkt_stride, int* d_pkt_len,
                               int* d_status, void* stream) {
-    int rc = seal_ragged_args(c, k, m, groups, d_bb, d_data, d_data_off, d_parity, d_par_off,
-                              d_hdr, hdr_stride, d_hdr_len, hdr_len_all, d_pkt, pkt_stride,
-                              d_pkt_len);
+    int rc = ragged_check(c, k, m, groups, d_bb, d_data, d_data_off, d_parity, d_par_off);
     if (rc) return rc;
+    if ((rc = seal_ragged_pkt_args(k, m, d_hdr, hdr_stride, d_hdr_len, hdr_len_all, d_pkt,
+                                   pkt_stride, d_pkt_len)))
+        return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     const hipStream_t st = pick(c, stream);
@@ -1543,14 +949,14 @@ int qfec_encode_seal_groups_batch_ragged(qfec_ctx* c, int k, int m, long long gr
 }
 
 // open_decode_impl over the packed layout.  The caller holds the workspace bracket.
-static int open_decode_ragged_impl(qfec_ctx* c, int k, int m, long long groups, const int32_t* d_bb,
-                                   const uint8_t* d_pkt, long long pkt_stride,
-                                   const int32_t* d_pkt_len, const int32_t* d_ad_len,
-                                   int ad_len_all, uint8_t* d_blocks,
-                                   const long long* d_blocks_off, uint8_t* d_rows,
-                                   int32_t* d_open_len, uint8_t* d_rec,
-                                   const long long* d_rec_off, uint8_t* d_rec_rows,
-                                   int32_t* d_status, hipStream_t st) {
+extern "C++" int qfec::open_decode_ragged_impl(qfec_ctx* c, int k, int m, long long groups,
+                                               const int32_t* d_bb, const uint8_t* d_pkt,
+                                               long long pkt_stride, const int32_t* d_pkt_len,
+                                               const int32_t* d_ad_len, int ad_len_all,
+                                               uint8_t* d_blocks, const long long* d_blocks_off,
+                                               uint8_t* d_rows, int32_t* d_open_len, uint8_t* d_rec,
+                                               const long long* d_rec_off, uint8_t* d_rec_rows,
+                                               int32_t* d_status, hipStream_t st) {
     QF_HIP(qfec::launch_open_groups_ragged(k, m, groups, d_bb, d_pkt, pkt_stride, d_pkt_len,
                                            d_ad_len, ad_len_all, d_blocks, d_blocks_off, d_rows,
                                            d_open_len, st));
@@ -1584,201 +990,6 @@ int qfec_open_decode_batch_ragged(qfec_ctx* c, int k, int m, long long groups, c
                                        ad_len_all, d_blocks, d_blocks_off, d_rows,
                                        (int32_t*)d_open_len, d_rec, d_rec_off, d_rec_rows,
                                        (int32_t*)d_status, st);
-    });
-}
-
-// The packed offsets of n blocks of bb[g] bytes per group, every group rounded up to 16 bytes:
-// the layout of a buffer the host forms keep on the device (the sender's parity, the
-// receiver's blocks).  -2 on bb[g] < 1.
-static int packed_offsets(long long G, const int* bb, int n, std::vector<long long>* off) {
-    off->resize((size_t)G);
-    long long at = 0;
-    for (long long g = 0; g < G; ++g) {
-        if (bb[g] < 1) return fail(-2, "bb[g] < 1");
-        (*off)[(size_t)g] = at;
-        at += ((long long)n * bb[g] + 15) & ~15LL;
-    }
-    return 0;
-}
-
-// Sender, host to host, ragged: qfec_encode_seal_groups_batch_host with a block size per group.
-// The parity is laid out on the device and never leaves it.
-int qfec_encode_seal_groups_batch_ragged_host(qfec_ctx* c, int k, int m, long long groups,
-                                              const int* h_bb, const unsigned char* h_data,
-                                              const long long* h_data_off,
-                                              const unsigned char* h_hdr, long long hdr_stride,
-                                              const int* h_hdr_len, int hdr_len_all,
-                                              const int* h_pt_len, unsigned char* h_pkt,
-                                              long long pkt_stride, int* h_pkt_len,
-                                              int* h_status) {
-    const unsigned char* dummy = (const unsigned char*)16;   // non-null for the argument check
-    // (host data is staged, so its own alignment does not matter either)
-    int rc = seal_ragged_args(c, k, m, groups, h_bb, h_data ? dummy : nullptr, h_data_off, dummy,
-                              (const long long*)dummy, h_hdr, hdr_stride, h_hdr_len, hdr_len_all,
-                              h_pkt, pkt_stride, h_pkt_len);
-    if (rc) return rc;
-    if (groups == 0) return 0;
-    if (hdr_stride <= 0 && h_hdr) return fail(-2, "host headers need a row stride > 0");
-    if (pkt_stride <= 0) return fail(-2, "host packets need a row stride > 0");
-    std::vector<long long> par_off;
-    if ((rc = packed_offsets(groups, h_bb, m, &par_off))) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    const long long np = k + m;
-    const size_t hdr_g = h_hdr ? (size_t)np * hdr_stride : 0;
-    const size_t pkt_g = (size_t)np * pkt_stride, len_g = (size_t)np * sizeof(int32_t);
-    const size_t small = sizeof(int32_t) * 2 + 2 * sizeof(long long) + hdr_g + pkt_g +
-                         len_g * (1 + (h_hdr_len ? 1 : 0) + (h_pt_len ? 1 : 0));
-    RaggedChunks ch;
-    if ((rc = ragged_chunks(c, k, m, groups, h_bb, h_data_off, par_off.data(), small, &ch)))
-        return rc;
-    const size_t bytes = ch.max_in + ch.max_out + ch.max_groups * small + kCarveSlack;
-    return host_pipeline_guard(c, [&] {
-        return host_pipeline_chunks(
-            c, bytes,
-            [&](long long g0) { return ch.next(g0); },
-            [&](long long g0, long long n, uint8_t* buf, int phase) -> int {
-                const size_t in_b = (size_t)ch.in_span(h_data_off, h_bb, g0, g0 + n, k);
-                const size_t par_b = (size_t)ch.in_span(par_off.data(), h_bb, g0, g0 + n, m);
-                Carve cv{buf};
-                uint8_t* dd = cv.take(in_b);
-                uint8_t* dp = cv.take(par_b);
-                int32_t* dbb = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
-                long long* dio = (long long*)cv.take((size_t)n * sizeof(long long));
-                long long* dpo = (long long*)cv.take((size_t)n * sizeof(long long));
-                int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
-                uint8_t* dh = h_hdr ? cv.take((size_t)n * hdr_g) : nullptr;
-                uint8_t* dk = cv.take((size_t)n * pkt_g);
-                int32_t* dkl = (int32_t*)cv.take((size_t)n * len_g);
-                int32_t* dhl = h_hdr_len ? (int32_t*)cv.take((size_t)n * len_g) : nullptr;
-                int32_t* dpl = h_pt_len ? (int32_t*)cv.take((size_t)n * len_g) : nullptr;
-                const size_t p0 = (size_t)g0 * np, pn = (size_t)n * np;
-                if (phase == 0) {
-                    QF_HIP(hipMemcpyAsync(dd, h_data + h_data_off[g0], in_b, hipMemcpyHostToDevice,
-                                          c->s_in));
-                    QF_HIP(hipMemcpyAsync(dbb, h_bb + g0, (size_t)n * sizeof(int32_t),
-                                          hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(dio, ch.in_rel.data() + g0, (size_t)n * sizeof(long long),
-                                          hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(dpo, ch.out_rel.data() + g0, (size_t)n * sizeof(long long),
-                                          hipMemcpyHostToDevice, c->s_in));
-                    if (dh)
-                        QF_HIP(hipMemcpyAsync(dh, h_hdr + p0 * hdr_stride, pn * hdr_stride,
-                                              hipMemcpyHostToDevice, c->s_in));
-                    if (dhl)
-                        QF_HIP(hipMemcpyAsync(dhl, h_hdr_len + p0, pn * sizeof(int32_t),
-                                              hipMemcpyHostToDevice, c->s_in));
-                    if (dpl)
-                        QF_HIP(hipMemcpyAsync(dpl, h_pt_len + p0, pn * sizeof(int32_t),
-                                              hipMemcpyHostToDevice, c->s_in));
-                } else if (phase == 1) {
-                    const int r = encode_ragged_impl(c, k, m, n, {dbb, dio, dpo}, dd, dp, ds,
-                                                     c->stream);
-                    if (r) return r;
-                    // rows come back whole: zeros past each packet and in rejected rows
-                    QF_HIP(hipMemsetAsync(dk, 0, pn * pkt_stride, c->stream));
-                    QF_HIP(qfec::launch_null_seal_groups_ragged(
-                        k, m, n, dbb, dd, dio, dp, dpo, true, dh, dh ? hdr_stride : 0, dhl,
-                        dh ? hdr_len_all : 0, dpl, dk, pkt_stride, dkl, c->stream));
-                } else {
-                    QF_HIP(hipMemcpyAsync(h_pkt + p0 * pkt_stride, dk, pn * pkt_stride,
-                                          hipMemcpyDeviceToHost, c->s_out));
-                    QF_HIP(hipMemcpyAsync(h_pkt_len + p0, dkl, pn * sizeof(int32_t),
-                                          hipMemcpyDeviceToHost, c->s_out));
-                    if (h_status)
-                        QF_HIP(hipMemcpyAsync(h_status + g0, ds, (size_t)n * sizeof(int32_t),
-                                              hipMemcpyDeviceToHost, c->s_out));
-                }
-                return 0;
-            });
-    });
-}
-
-// Receiver, host to host, ragged: qfec_open_decode_batch_host with a block size per group.  The
-// blocks are laid out on the device; h_rec is the caller's packed buffer, and the bytes of it
-// the call does not write keep the caller's values (staged in, as the ragged host decode).
-int qfec_open_decode_batch_ragged_host(qfec_ctx* c, int k, int m, long long groups,
-                                       const int* h_bb, const unsigned char* h_pkt,
-                                       long long pkt_stride, const int* h_pkt_len,
-                                       const int* h_ad_len, int ad_len_all, unsigned char* h_rec,
-                                       const long long* h_rec_off, unsigned char* h_rec_rows,
-                                       int* h_status, int* h_open_len) {
-    int rc = check_common(c, k, m, 1, groups < 0 ? 0 : groups);
-    if (rc) return rc;
-    if (groups < 0) return fail(-2, "groups < 0");
-    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
-    if (!h_bb || !h_pkt || !h_pkt_len || !h_rec || !h_rec_off || !h_rec_rows)
-        return fail(-2, "null buffer");
-    if (groups == 0) return 0;
-    if (pkt_stride <= 0) return fail(-2, "bad pkt_stride");
-    if (!h_ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
-    std::vector<long long> blk_off;
-    if ((rc = packed_offsets(groups, h_bb, k, &blk_off))) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    const long long np = k + m;
-    const int rmax = std::min(k, m);
-    const size_t pkt_g = (size_t)np * pkt_stride, len_g = (size_t)np * sizeof(int32_t);
-    const size_t small = sizeof(int32_t) * 2 + 2 * sizeof(long long) + pkt_g +
-                         len_g * (2 + (h_ad_len ? 1 : 0)) + (size_t)k + (size_t)rmax;
-    RaggedChunks ch;
-    if ((rc = ragged_chunks(c, k, rmax, groups, h_bb, blk_off.data(), h_rec_off, small, &ch)))
-        return rc;
-    const size_t bytes = ch.max_in + ch.max_out + ch.max_groups * small + kCarveSlack;
-    return host_pipeline_guard(c, [&] {
-        return host_pipeline_chunks(
-            c, bytes,
-            [&](long long g0) { return ch.next(g0); },
-            [&](long long g0, long long n, uint8_t* buf, int phase) -> int {
-                const size_t blk_b = (size_t)ch.in_span(blk_off.data(), h_bb, g0, g0 + n, k);
-                const size_t rec_b = (size_t)ch.in_span(h_rec_off, h_bb, g0, g0 + n, rmax);
-                Carve cv{buf};
-                uint8_t* db = cv.take(blk_b);
-                uint8_t* dre = cv.take(rec_b);
-                int32_t* dbb = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
-                long long* dbo = (long long*)cv.take((size_t)n * sizeof(long long));
-                long long* dro = (long long*)cv.take((size_t)n * sizeof(long long));
-                int32_t* ds = (int32_t*)cv.take((size_t)n * sizeof(int32_t));
-                uint8_t* dk = cv.take((size_t)n * pkt_g);
-                int32_t* dkl = (int32_t*)cv.take((size_t)n * len_g);
-                int32_t* dal = h_ad_len ? (int32_t*)cv.take((size_t)n * len_g) : nullptr;
-                int32_t* dol = (int32_t*)cv.take((size_t)n * len_g);
-                uint8_t* dr = cv.take((size_t)n * k);
-                uint8_t* drr = cv.take((size_t)n * rmax);
-                unsigned char* rec = h_rec + h_rec_off[g0];
-                const size_t p0 = (size_t)g0 * np, pn = (size_t)n * np;
-                if (phase == 0) {
-                    QF_HIP(hipMemcpyAsync(dk, h_pkt + p0 * pkt_stride, pn * pkt_stride,
-                                          hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(dkl, h_pkt_len + p0, pn * sizeof(int32_t),
-                                          hipMemcpyHostToDevice, c->s_in));
-                    if (dal)
-                        QF_HIP(hipMemcpyAsync(dal, h_ad_len + p0, pn * sizeof(int32_t),
-                                              hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(dre, rec, rec_b, hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(dbb, h_bb + g0, (size_t)n * sizeof(int32_t),
-                                          hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(dbo, ch.in_rel.data() + g0, (size_t)n * sizeof(long long),
-                                          hipMemcpyHostToDevice, c->s_in));
-                    QF_HIP(hipMemcpyAsync(dro, ch.out_rel.data() + g0, (size_t)n * sizeof(long long),
-                                          hipMemcpyHostToDevice, c->s_in));
-                } else if (phase == 1) {
-                    return open_decode_ragged_impl(c, k, m, n, dbb, dk, pkt_stride, dkl, dal,
-                                                   ad_len_all, db, dbo, dr, dol, dre, dro, drr, ds,
-                                                   c->stream);
-                } else {
-                    QF_HIP(hipMemcpyAsync(rec, dre, rec_b, hipMemcpyDeviceToHost, c->s_out));
-                    QF_HIP(hipMemcpyAsync(h_rec_rows + (size_t)g0 * rmax, drr, (size_t)n * rmax,
-                                          hipMemcpyDeviceToHost, c->s_out));
-                    if (h_status)
-                        QF_HIP(hipMemcpyAsync(h_status + g0, ds, (size_t)n * sizeof(int32_t),
-                                              hipMemcpyDeviceToHost, c->s_out));
-                    if (h_open_len)
-                        QF_HIP(hipMemcpyAsync(h_open_len + p0, dol, pn * sizeof(int32_t),
-                                              hipMemcpyDeviceToHost, c->s_out));
-                }
-                return 0;
-            });
     });
 }
 

@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "../../include/quic_fec_group.h"
-#include "fec_ragged_host.h"
+#include "fec_host_plan.h"
 
 namespace qfec {
 

@@ -1,0 +1,145 @@
+// fec_host_plan.cpp — host-only part of the host-pointer batches: the packed layout, the
+// queue's packing, and the staging plan (stages, chunks, carve).  Plain C++ (no HIP), so the
+// sanitizer check under tools/ links it alone.
+#include "fec_host_plan.h"
+
+#include <algorithm>
+#include <cstring>
+
+#include "../../include/quic_fec.h"
+
+namespace {
+
+// running = roundup16(running + n * bb); false on overflow
+bool advance(long long* running, long long n, long long bb) {
+    long long bytes, end;
+    if (__builtin_mul_overflow(n, bb, &bytes)) return false;
+    if (__builtin_add_overflow(*running, bytes, &end)) return false;
+    if (__builtin_add_overflow(end, 15LL, &end)) return false;
+    *running = end & ~15LL;
+    return true;
+}
+
+// *end = off + n * bb; false on overflow
+bool block_end(long long off, long long n, long long bb, long long* end) {
+    long long bytes;
+    return !__builtin_mul_overflow(n, bb, &bytes) && !__builtin_add_overflow(off, bytes, end);
+}
+
+size_t one_stage_bytes(const qfec::StageList& L, const qfec::Stage& s, long long g0, long long n) {
+    if (!s.present) return 0;
+    if (!s.off) return (size_t)n * s.per_group;
+    const long long last = g0 + n - 1;
+    return (size_t)(s.off[last] + (long long)s.nblk * L.bb[last] - s.off[g0]);
+}
+
+}  // namespace
+
+extern "C" int qfec_ragged_layout(int k, int m, long long groups, const int* bb,
+                                  long long* data_off, long long* par_off, long long* rec_off,
+                                  long long totals[3]) {
+    if (k < 1 || m < 1 || groups < 0 || (groups && !bb)) return -2;
+    const long long nblk[3] = {k, m, k < m ? k : m};
+    long long* const off[3] = {data_off, par_off, rec_off};
+    long long run[3] = {0, 0, 0};
+    for (long long g = 0; g < groups; ++g) {
+        if (bb[g] < 1) return -2;
+        for (int a = 0; a < 3; ++a) {
+            if (off[a]) off[a][g] = run[a];
+            if (!advance(&run[a], nblk[a], bb[g])) return -2;
+        }
+    }
+    if (totals)
+        for (int a = 0; a < 3; ++a) totals[a] = run[a];
+    return 0;
+}
+
+namespace qfec {
+
+int ragged_pack(int k, int m, bool decode, const std::vector<const unsigned char*>& blocks,
+                const std::vector<int>& bb, RaggedPack* p) {
+    const size_t G = blocks.size();
+    if (bb.size() != G || !p) return -2;
+    p->bb = bb;
+    p->in_off.assign(G, 0);
+    p->out_off.assign(G, 0);
+    long long totals[3] = {0, 0, 0};
+    const int r = qfec_ragged_layout(k, m, (long long)G, bb.data(), p->in_off.data(),
+                                     decode ? nullptr : p->out_off.data(),
+                                     decode ? p->out_off.data() : nullptr, totals);
+    if (r) return r;
+    p->in.resize((size_t)totals[0]);
+    p->out.assign((size_t)totals[decode ? 2 : 1], 0);
+    for (size_t g = 0; g < G; ++g)
+        memcpy(p->in.data() + p->in_off[g], blocks[g], (size_t)k * bb[g]);
+    return 0;
+}
+
+size_t stage_bytes(const StageList& L, long long g0, long long n) {
+    size_t sum = 0;
+    for (int i = 0; i < L.n; ++i) sum += one_stage_bytes(L, L.s[i], g0, n);
+    return sum;
+}
+
+size_t stage_carve(StageList& L, long long g0, long long n, uint8_t* base) {
+    size_t at = 0;
+    for (int i = 0; i < L.n; ++i) {
+        Stage& s = L.s[i];
+        s.bytes = one_stage_bytes(L, s, g0, n);
+        s.dev = s.present && base ? base + at : nullptr;   // no base: sizes only
+        if (s.present) at += (s.bytes + 255) & ~(size_t)255;
+    }
+    return at;
+}
+
+size_t staging_bytes(StageList& L, const Chunks& ch) {
+    size_t most = 0;
+    for (long long i = 0; i < ch.count(); ++i)
+        most = std::max(most, stage_carve(L, ch.begin(i), ch.begin(i + 1) - ch.begin(i), nullptr));
+    return most;
+}
+
+long long uniform_chunk(long long groups, size_t per_group, int host_chunk_mb,
+                        int host_min_groups) {
+    // at least host_min_groups groups per chunk (up to 2 GiB of staging per buffer): a
+    // 64 MiB chunk of D's 1.2 MB groups is 54 groups, too few to fill the device (D at
+    // 16,384 groups: 16.1 GiB/s with 64 MiB chunks, 22.9 with 256 MiB, 23.3 with 1 GiB).
+    // Both are options, so a caller (and the tests) can still force small chunks.
+    const size_t target = (size_t)std::max(1, host_chunk_mb) << 20;
+    const long long by_bytes = (long long)(target / per_group);
+    const long long floor_g = std::min<long long>(std::max(1, host_min_groups),
+                                                  (long long)((2ull << 30) / per_group));
+    return std::max<long long>(1, std::min<long long>(groups, std::max(by_bytes, floor_g)));
+}
+
+int ragged_chunks(const StageList& L, const Stage& in, const Stage& out, long long G,
+                  long long target, Chunks* ch, const char** msg) {
+    const int* bb = L.bb;
+    long long in_end = 0, out_end = 0;   // ends of group g - 1
+    for (long long g = 0; g < G; ++g) {
+        if (bb[g] < 1) return *msg = "bb[g] < 1", -2;
+        if (in.off[g] < 0 || out.off[g] < 0 || ((in.off[g] | out.off[g]) & 15))
+            return *msg = "ragged offsets must be non-negative multiples of 16", -2;
+        if ((g && (in.off[g] < in_end || out.off[g] < out_end)) ||
+            !block_end(in.off[g], in.nblk, bb[g], &in_end) ||
+            !block_end(out.off[g], out.nblk, bb[g], &out_end))
+            return *msg = "host ragged batches need ascending, non-overlapping offsets", -2;
+    }
+    ch->groups = G;
+    ch->in_rel.resize((size_t)G);
+    ch->out_rel.resize((size_t)G);
+    long long g0 = 0;
+    ch->first.push_back(0);
+    for (long long g = 0; g < G; ++g) {
+        if (g > g0 && (long long)stage_bytes(L, g0, g + 1 - g0) > target) {
+            g0 = g;
+            ch->first.push_back(g);
+        }
+        ch->in_rel[(size_t)g] = in.off[g] - in.off[g0];
+        ch->out_rel[(size_t)g] = out.off[g] - out.off[g0];
+    }
+    ch->first.push_back(G);
+    return 0;
+}
+
+}  // namespace qfec

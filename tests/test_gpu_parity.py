@@ -410,6 +410,25 @@ def test_host_pipeline_many_chunks(tuned_engine, oracle, k, m, r):
     assert st.abs().max() == 0
 
 
+@pytest.mark.parametrize("k,m,bb,G", [(10, 3, 1350, 241), (250, 7, 16, 1025)])
+def test_host_encode_unsupported_many_chunks(tuned_engine, oracle, k, m, bb, G):
+    """The host encode on the encode's -1 path (block_bytes % 8 != 0, k + m > 256) copies back
+    only row 0 of each group: row 0 is the XOR parity, every other parity row keeps the caller's
+    bytes.  Just over 4 MiB of staging in 1 MiB chunks, so every one of the NB = 3 rotating
+    buffers is reused."""
+    import torch
+    engine = tuned_engine
+    engine.set_option("host_chunk_mb", 1)
+    engine.set_option("host_min_groups", 1)
+    assert G * (k + m) * bb > 4 << 20
+    data = synth.group_data(700 + k, k, bb, G)
+    p_or, rc_or = oracle.encode_batch(k, m, bb, data)
+    parity = torch.full((G, m, bb), FILL, dtype=torch.uint8)
+    rc = fec.encode_host_into(engine, k, m, bb, torch.from_numpy(data), parity)
+    assert rc == rc_or == -1
+    np.testing.assert_array_equal(parity.numpy(), parity_written(p_or, -1))
+
+
 # ------------------------------------------- gf_stream ring (many groups per wave)
 @pytest.fixture
 def tuned_engine():

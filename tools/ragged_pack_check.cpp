@@ -1,16 +1,19 @@
-// ragged_pack_check — host-code sanitizer check of the ragged layout and the queue's packing.
+// ragged_pack_check — host-code sanitizer check of the ragged layout, the queue's packing and
+// the staging plan of the host-pointer batches.
 //
 // Stand-alone (its own main, no GPU, no HIP): built from this file and
-// quic_amd/csrc/fec_ragged_host.cpp with -fsanitize=address,undefined (`make ragged-check`).
-// It calls qfec_ragged_layout and qfec::ragged_pack on random sizes and checks offsets and
-// bounds; out-of-bounds copies or overflowing arithmetic abort under the sanitizers.
+// quic_amd/csrc/fec_host_plan.cpp with -fsanitize=address,undefined (`make ragged-check`).
+// It calls qfec_ragged_layout, qfec::ragged_pack and the planning functions of the host
+// pipeline (chunks, stage sizes, carve) on random sizes and checks offsets and bounds;
+// out-of-bounds copies or overflowing arithmetic abort under the sanitizers.
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <random>
 #include <vector>
 
-#include "fec_ragged_host.h"
+#include "fec_host_plan.h"
 #include "quic_fec.h"
 
 static int g_fail = 0;
@@ -80,6 +83,195 @@ static void check_pack(int k, int m, bool decode, const std::vector<int>& bb, st
     for (unsigned char b : pk.out) CHECK(b == 0);
 }
 
+// ---- the staging plan of the host-pointer batches (fec_host.cpp declares these lists)
+using qfec::Chunks;
+using qfec::Stage;
+using qfec::StageList;
+
+enum Body { DEC_REC, SEAL, OPEN, ENC, DEC, R_ENC, R_DEC, R_SEAL, R_OPEN, N_BODIES };
+
+// A stage list shaped like the body of one host entry point; `opt`: its optional arrays are
+// present.  The ragged shapes name their two packed stages.
+static void declare(int body, bool opt, int k, int m, int bb, size_t stride,
+                    const long long* in_off, const long long* out_off, StageList& L, Stage** in,
+                    Stage** out) {
+    const int rmax = k < m ? k : m;
+    const size_t np = (size_t)(k + m), len_g = np * 4;
+    auto ragged = [&](int n_out) {
+        *in = &L.packed(in_off, k);
+        *out = &L.packed(out_off, n_out);
+        for (size_t b : {4, 8, 8, 4}) L.dense(b);   // bb, in_rel, out_rel, status
+    };
+    auto seal_pkts = [&] {
+        L.dense(np * stride, opt);
+        L.dense(np * stride);
+        L.dense(len_g);
+        L.dense(len_g, opt);
+        L.dense(len_g, opt);
+    };
+    auto open_pkts = [&] {
+        L.dense(np * stride);
+        L.dense(len_g);
+        L.dense(len_g, opt);
+        L.dense(len_g);
+    };
+    switch (body) {
+    case DEC_REC:
+        for (size_t b : {(size_t)k * bb, (size_t)rmax * bb, (size_t)k, (size_t)rmax, (size_t)4})
+            L.dense(b);
+        break;
+    case SEAL:
+        L.dense((size_t)k * bb);
+        L.dense((size_t)m * bb);
+        seal_pkts();
+        break;
+    case OPEN:
+        open_pkts();
+        for (size_t b : {(size_t)k * bb, (size_t)k, (size_t)rmax * bb, (size_t)rmax, (size_t)4})
+            L.dense(b);
+        break;
+    case ENC:
+        L.dense((size_t)k * bb);
+        L.dense((size_t)m * bb).rows((size_t)m * bb, bb);
+        break;
+    case DEC:
+        for (size_t b : {(size_t)k * bb, (size_t)k, (size_t)4}) L.dense(b);
+        break;
+    case R_ENC: ragged(m); break;
+    case R_DEC:
+        ragged(rmax);
+        L.dense(k);
+        L.dense(rmax);
+        break;
+    case R_SEAL:
+        ragged(m);
+        seal_pkts();
+        break;
+    case R_OPEN:
+        ragged(rmax);
+        open_pkts();
+        L.dense(k);
+        L.dense(rmax);
+        break;
+    }
+}
+
+// Every chunk's carve: aligned, disjoint, in declaration order, inside the staging size the
+// same list produced.  The block has exactly that size and every sub-buffer is written in
+// full, so an overrun is an ASan error.
+static void check_carve(StageList& L, const Chunks& ch) {
+    const size_t total = qfec::staging_bytes(L, ch);
+    std::vector<uint8_t> block(total);
+    for (long long i = 0; i < ch.count(); ++i) {
+        const long long g0 = ch.begin(i), n = ch.begin(i + 1) - g0;
+        CHECK(n >= 1);
+        CHECK(qfec::stage_carve(L, g0, n, block.data()) <= total);
+        uint8_t* end = block.data();
+        for (int j = 0; j < L.n; ++j) {
+            const Stage& s = L.s[j];
+            if (!s.present) {
+                CHECK(!s.dev && s.bytes == 0);
+                continue;
+            }
+            CHECK((s.dev - block.data()) % 256 == 0);
+            CHECK(s.dev >= end);
+            end = s.dev + s.bytes;
+            CHECK(end <= block.data() + total);
+            memset(s.dev, 0xA5, s.bytes);
+        }
+    }
+}
+
+static void check_uniform(int k, int m, std::mt19937& rng) {
+    for (int body = DEC_REC; body <= DEC; ++body)
+        for (int opt = 0; opt < 2; ++opt) {
+            StageList L;
+            const int bb = 1 + (int)(rng() % 2100);
+            declare(body, opt, k, m, bb, 4 * (1 + rng() % 400), nullptr, nullptr, L, nullptr,
+                    nullptr);
+            Chunks ch;
+            const long long G = 1 + rng() % 300;
+            ch.groups = G;
+            ch.uniform =
+                qfec::uniform_chunk(G, qfec::stage_bytes(L, 0, 1), 1, 1 + (int)(rng() % 8));
+            CHECK(ch.begin(0) == 0 && ch.begin(ch.count()) == G);
+            check_carve(L, ch);
+        }
+}
+
+static void check_ragged(int k, int m, const std::vector<int>& bb, std::mt19937& rng) {
+    const long long G = (long long)bb.size();
+    if (G == 0) return;
+    for (int body = R_ENC; body < N_BODIES; ++body)
+        for (int opt = 0; opt < 2; ++opt)
+            for (long long target : {1LL << 20, 64LL << 10}) {
+                const int n_out = (body == R_ENC || body == R_SEAL) ? m : (k < m ? k : m);
+                // packed offsets with random 16-byte gaps between the groups
+                std::vector<long long> in_off(G), out_off(G);
+                long long ri = 0, ro = 0;
+                for (long long g = 0; g < G; ++g) {
+                    in_off[g] = ri += 16 * (rng() % 4);
+                    out_off[g] = ro += 16 * (rng() % 4);
+                    ri = up16(ri + (long long)k * bb[g]);
+                    ro = up16(ro + (long long)n_out * bb[g]);
+                }
+                StageList L{bb.data()};
+                Stage *in = nullptr, *out = nullptr;
+                declare(body, opt, k, m, 0, 4 * (1 + rng() % 400), in_off.data(), out_off.data(), L,
+                        &in, &out);
+                Chunks ch;
+                const char* msg = nullptr;
+                CHECK(qfec::ragged_chunks(L, *in, *out, G, target, &ch, &msg) == 0);
+                CHECK(ch.count() >= 1 && ch.begin(0) == 0 && ch.begin(ch.count()) == G);
+                for (long long i = 0; i < ch.count(); ++i) {
+                    const long long g0 = ch.begin(i), n = ch.begin(i + 1) - g0;
+                    CHECK(n >= 1);
+                    if (n > 1) CHECK((long long)qfec::stage_bytes(L, g0, n) <= target);
+                    for (long long g = g0; g < g0 + n; ++g) {
+                        CHECK(ch.in_rel[g] == in_off[g] - in_off[g0]);
+                        CHECK(ch.out_rel[g] == out_off[g] - out_off[g0]);
+                    }
+                }
+                check_carve(L, ch);
+            }
+}
+
+// ragged_chunks on G groups of (k = 4, m = 2); exact-size inputs, so a read past them is caught
+static int chunk_rc(std::vector<int> bb, std::vector<long long> in_off,
+                    std::vector<long long> out_off, const char** msg) {
+    StageList L{bb.data()};
+    Stage& in = L.packed(in_off.data(), 4);
+    Stage& out = L.packed(out_off.data(), 2);
+    Chunks ch;
+    return qfec::ragged_chunks(L, in, out, (long long)bb.size(), 1 << 20, &ch, msg);
+}
+
+static void check_plan_errors() {
+    const char* msg = nullptr;
+    const char* const asc = "host ragged batches need ascending, non-overlapping offsets";
+    const char* const mult = "ragged offsets must be non-negative multiples of 16";
+    CHECK(chunk_rc({8, 8}, {0, 32}, {0, 16}, &msg) == 0);
+    CHECK(chunk_rc({8, 0}, {0, 32}, {0, 16}, &msg) == -2 && !strcmp(msg, "bb[g] < 1"));
+    CHECK(chunk_rc({-3, 8}, {0, 32}, {0, 16}, &msg) == -2 && !strcmp(msg, "bb[g] < 1"));
+    CHECK(chunk_rc({8, 8}, {-16, 32}, {0, 16}, &msg) == -2 && !strcmp(msg, mult));
+    CHECK(chunk_rc({8, 8}, {0, 32}, {0, 24}, &msg) == -2 && !strcmp(msg, mult));
+    CHECK(chunk_rc({8, 8}, {32, 0}, {0, 16}, &msg) == -2 && !strcmp(msg, asc));    // descending
+    CHECK(chunk_rc({8, 8}, {0, 16}, {0, 16}, &msg) == -2 && !strcmp(msg, asc));    // overlapping
+    CHECK(chunk_rc({8, 8}, {0, 32}, {0, 0}, &msg) == -2 && !strcmp(msg, asc));
+    const long long top = LLONG_MAX & ~15LL;   // a group there ends past INT64_MAX
+    CHECK(chunk_rc({8, 8}, {0, top}, {0, 16}, &msg) == -2 && !strcmp(msg, asc));
+    CHECK(chunk_rc({8, 8}, {0, 32}, {top, top}, &msg) == -2 && !strcmp(msg, asc));
+    CHECK(chunk_rc({8}, {top}, {0}, &msg) == -2 && !strcmp(msg, asc));
+    // the uniform chunk size, by hand from max(1, min(G, max(target / per, min(min_groups,
+    // 2 GiB / per)))) at 64 MiB / 512 groups
+    CHECK(qfec::uniform_chunk(65536, 48672, 64, 512) == 1378);     // B encode: 67108864 / 48672
+    CHECK(qfec::uniform_chunk(16384, 1297152, 64, 512) == 512);    // D encode: 51 by bytes
+    CHECK(qfec::uniform_chunk(100, 48672, 64, 512) == 100);
+    CHECK(qfec::uniform_chunk(100, 1297152, 64, 512) == 100);
+    CHECK(qfec::uniform_chunk(65536, (size_t)3 << 30, 64, 512) == 1);
+    CHECK(qfec::uniform_chunk(241, 17550, 1, 1) == 59);            // 1048576 / 17550
+}
+
 int main() {
     std::mt19937 rng(20240607);
     const int codes[][2] = {{10, 1}, {3, 2}, {5, 5}, {32, 4}, {10, 20}, {1, 3}, {250, 5}, {10, 10}};
@@ -91,8 +283,11 @@ int main() {
             check_layout(c[0], c[1], bb);
             check_pack(c[0], c[1], false, bb, rng);
             check_pack(c[0], c[1], true, bb, rng);
+            check_uniform(c[0], c[1], rng);
+            check_ragged(c[0], c[1], bb, rng);
         }
     }
+    check_plan_errors();
     // errors: a size < 1, bad arguments, overflow of the running offset
     {
         const int bad[3] = {8, 0, 8};
