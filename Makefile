@@ -103,12 +103,12 @@ WJGEN := $(ROOT)build/gen/win_jump.h
 $(WJGEN): $(ROOT)tools/gen_win_jump.py
 	python3 $(ROOT)tools/gen_win_jump.py && touch $@
 
-$(ROOT)build/gf_stream.o: $(CSRC)/gf_stream.hip $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
+$(ROOT)build/gf_stream.o: $(CSRC)/gf_stream.hip $(CSRC)/compiled_codes.h $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
 
-$(ROOT)build/gf_bsyn.o: $(CSRC)/gf_bsyn.hip $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
+$(ROOT)build/gf_bsyn.o: $(CSRC)/gf_bsyn.hip $(CSRC)/compiled_codes.h $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
@@ -117,12 +117,12 @@ $(ROOT)build/gf_bsyn.o: $(CSRC)/gf_bsyn.hip $(CSRC)/gf_counted.h $(CSRC)/gf_winj
 # the branches' identical loads into one load with a computed index, which leaves the
 # arrays in scratch memory (VMEM outside the counted waits)
 PSYNFLAGS := -mllvm -simplifycfg-sink-common=false
-$(ROOT)build/gf_psyn.o: $(CSRC)/gf_psyn.hip $(CSRC)/gf_psyn.h $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
+$(ROOT)build/gf_psyn.o: $(CSRC)/gf_psyn.hip $(CSRC)/gf_psyn.h $(CSRC)/compiled_codes.h $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) $(PSYNFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
 
-$(ROOT)build/gf_psyn_%.o: $(CSRC)/gf_psyn_%.hip $(CSRC)/gf_psyn.h $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
+$(ROOT)build/gf_psyn_%.o: $(CSRC)/gf_psyn_%.hip $(CSRC)/gf_psyn.h $(CSRC)/compiled_codes.h $(CSRC)/gf_counted.h $(CSRC)/gf_winjump.h $(HDRS) $(GEN) $(WJGEN)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) $(PSYNFLAGS) $(SAVE_ASM) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }

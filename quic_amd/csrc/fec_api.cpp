@@ -73,19 +73,9 @@ int cauchy_rows(int k, int m, uint8_t* out) {
     return 0;
 }
 
-int pow2_at_least(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-int encode_rc(int m, const qfec::Tune& t) { return std::min(pow2_at_least(m), t.enc_rc); }
-// Encode table rows: gf_apply's chunk (<= 8), or 16 where gf_stream takes 9..16 outputs in
-// one unit (m <= 8: one unit of m outputs; more than 16: chunks of 8; compiled codes read no
-// table)
-int stream_encode_rc(int k, int m, int bb, bool aligned, const qfec::Tune& t) {
-    if (m > 8 && m <= 16 && aligned && qfec::gf_stream_supported(k, m, bb, 16, false, t)) return 16;
-    return encode_rc(m, t);
-}
+using qfec::encode_rc;
+using qfec::pow2_at_least;
+using qfec::stream_encode_rc;
 // Output chunk of a decode.  gf_stream decodes in units of 8 recovered blocks: a group with
 // at most 8 losses leaves its second unit empty, and empty units read nothing, while one unit
 // of 16 accumulators halves the occupancy for every group ((10, 10) at 5 losses: 0.615 ms
@@ -263,7 +253,7 @@ int qfec::encode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint
     const uint8_t* tab = nullptr;
     int rcode = get_enc_table(c, k, m, rc, &tab);
     if (rcode) return rcode;
-    if ((m <= rc || rc == 8) && qfec::gf_stream_supported(k, m, bb, rc, false, c->tune) &&
+    if ((m <= rc || rc == 8) && qfec::gf_stream_supported(k, bb, rc, c->tune) &&
         aligned) {
         QF_HIP(qfec::launch_gf_stream(d_data, d_par, tab, nullptr, nullptr, k, m, bb, G, rc, 0, 0,
                                       (long long)m * bb, false, st, c->tune));
@@ -353,7 +343,7 @@ int qfec::decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint
         QF_HIP(W.ensure(W.dscratch, (size_t)G * p.scratch));
         dst = (uint8_t*)W.dscratch.p;
     }
-    if (qfec::gf_stream_supported(k, m, bb, rc, true, c->tune) && aligned)
+    if (qfec::gf_stream_supported(k, bb, rc, c->tune) && aligned)
         QF_HIP(qfec::launch_gf_stream(d_blocks, dst, w.coef, direct ? w.slots : nullptr, w.nout,
                                       k, m, bb, G, rc, rmax, p.tab_gstride,
                                       (long long)(direct ? k : rmax) * bb, true, st, c->tune));

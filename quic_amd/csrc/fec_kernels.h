@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 namespace qfec {
 
@@ -26,20 +27,20 @@ struct Tune {
     int stream = 1;           // m > 1, small blocks: gf_stream (0: gf_apply)
     int stream_ring = 8;      // gf_stream: 1 KiB ring slots per wave (4..36), + 2 mirrored
     int stream_grid = 0;      // gf_stream: grid cap in workgroups (0: CUs x per-CU fit)
-    int stream_static = 1;    // gf_ring: compile-time ring schedule (B/C and preset encodes)
-    int ring_wide = 1;        // gf_ring preset encodes: LDS-staged 8-byte parity stores
-    int ring_split = 1;       // gf_ring (10, 20) encode: two units of 10 parity rows per group
-    int psyn_wide = 1;        // gf_psyn wide recovered-block stores: 1 (10, 10), 2 all
+    int stream_static = 1;    // gf_ring: compile-time ring schedule (the codes of compiled_codes.h)
+    int ring_wide = 1;        // gf_ring: LDS-staged 8-byte parity stores (the rows' ring_wide)
+    int ring_split = 1;       // gf_ring: two units of m / 2 parity rows per group (ring_split rows)
+    int psyn_wide = 1;        // gf_psyn wide recovered-block stores: 1 the psyn_wide rows, 2 all
     int const_enc = 1;        // encode kernels specialised for fixed (k, m) where compiled
     int pd = 2;               // gf_apply: register pipeline depth (1..3)
     int flat = 1;             // gf_apply: lane-flat encode
     int enc_rc = 8;           // gf_apply: encode outputs per wave (2, 4, 8)
     int prep_lane = 1;        // decode prep with 4 lanes per group when it applies
-    int bsyn = 1;             // (32, 4) x 1352 B decode: compiled syndrome kernel gf_bsyn
-                              //   (0: the run-time gf_stream decode)
+    int bsyn = 1;             // compiled syndrome decode gf_bsyn (the Syn::bsyn row of
+                              //   compiled_codes.h; 0: the run-time gf_stream decode)
     int bsyn_depth = 3;       // gf_bsyn: blocks in flight per wave (3, 5, 7; 3: 5 waves/SIMD)
-    int psyn = 1;             // QuicR presets with m >= 7 and (5, 5) at 1352 B: compiled syndrome decode
-                              //   gf_psyn (0: the run-time gf_stream decode)
+    int psyn = 1;             // compiled syndrome decode gf_psyn (the Syn::psyn rows of
+                              //   compiled_codes.h; 0: the run-time gf_stream decode)
     int dcol = 1;             // (128, 16) x 9008 B: gf_dcol (one wave per column tile, all 16
                               //   rows; 0: gf_apply)
     int dcol_grid = 0;        // gf_dcol: grid cap in workgroups (0: CUs x per-CU fit)
@@ -48,7 +49,7 @@ struct Tune {
     // device holds at once, so the hardware hands the last ones to whichever CU frees first
     // (0: the resident persistent grid, every wave walking groups g0, g0 + W, ...; -1: the
     // measured choice)
-    int ring_wg = -1;         // gf_ring encodes (-1: 1 for (32,4), (10,10), (5,5), (250,5))
+    int ring_wg = -1;         // gf_ring encodes (-1: the row's ring_wg in compiled_codes.h)
     int bsyn_wg = -1;         // gf_bsyn decode (-1: 2)
     int psyn_wg = 0;          // gf_psyn decodes
     int stream_wg = -1;       // gf_stream (run-time coefficients: the (250, 5) decode, other shapes;
@@ -105,6 +106,19 @@ struct TimingMute {
     TimingMute() { launch_timing().muted = true; }
     ~TimingMute() { launch_timing().muted = false; }
 };
+
+// Run-time value -> template argument: calls f(std::integral_constant<int, V>{}) for the V among
+// Vs that equals v.  False: v is none of them, f was not called.
+template <int... Vs, class F>
+inline bool dispatch_value(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+// The same for a flag: f(std::true_type{}) or f(std::false_type{}).
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // Every kernel of the library is launched through this.
 template <typename F, typename... Args>
@@ -216,6 +230,14 @@ hipError_t launch_rows_k1(const uint8_t* rows_in, uint8_t* rows_out, int32_t* st
 hipError_t launch_gf_encode(const uint8_t* data, uint8_t* parity, const uint8_t* coef,
                             int k, int m, int bb, long long groups, int rc, hipStream_t st,
                             const Tune& t);
+// Its chunk (outputs per wave) for m parity rows: the power of two that holds them, capped
+// at enc_rc.
+inline int pow2_at_least(int v) {
+    int p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+inline int encode_rc(int m, const Tune& t) { return std::min(pow2_at_least(m), t.enc_rc); }
 
 // Decode prep: per group, sort blocks, invert the erasure submatrix in GF(256) and
 // emit the r x k recovery coefficients (syndrome: the syn:: table instead).  cenc is the
@@ -246,10 +268,17 @@ hipError_t launch_xor_dma(const uint8_t* in, uint8_t* out, const uint8_t* eidx,
                           int bb, long long groups, long long out_gstride, bool decode,
                           hipStream_t st, const Tune& t, bool compact = false);
 
-// Per-wave LDS-ring streaming kernel for bb = 1352, one output chunk (gf_stream.hip).
-bool gf_stream_supported(int k, int m, int bb, int rc, bool decode, const Tune& t);
-// (k, m) codes whose gf_stream encode is compiled at this block size (no coefficient table)
-bool gf_stream_compiled(int k, int m, int bb);
+// Per-wave LDS-ring streaming kernels (gf_stream.hip), bb a multiple of 8 up to 2048, `in`
+// 16-byte aligned.  Encode (decode false): the m parity rows of each group; the codes of
+// compiled_codes.h run compiled (gf_ring_kernel, or gf_stream_kernel<encode,compiled>) and read
+// no table, every other code reads coef, the shared table built for rc = stream_encode_rc().
+// Decode: up to rmax recovered blocks per group in chunks of rc (2, 4, 8) from the prep's
+// per-group tables, through slots (slot layout) or densely (slots null).
+bool gf_stream_supported(int k, int bb, int rc, const Tune& t);
+// Encode table rows: gf_apply's chunk (<= 8), or 16 where gf_stream takes 9..16 outputs in
+// one unit (m <= 8: one unit of m outputs; more than 16: chunks of 8; compiled codes read no
+// table).  aligned: the data pointer is 16-byte aligned (otherwise gf_apply encodes).
+int stream_encode_rc(int k, int m, int bb, bool aligned, const Tune& t);
 hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef,
                             const uint8_t* slots, const int32_t* nout, int k, int m, int bb,
                             long long groups, int rc, int rmax, long long coef_gstride,
@@ -269,7 +298,7 @@ hipError_t launch_gf_dcol_syndrome(const uint8_t* in, uint8_t* out, const uint8_
                                    int rmax, long long tab_gstride, long long out_gstride,
                                    hipStream_t st, const Tune& t);
 
-// Syndrome decode of the compiled (32, 4) x 1352-byte code: prep (bsyn:: table, one lane per
+// Syndrome decode of the Syn::bsyn code of compiled_codes.h, (32, 4) x 1352 bytes: prep (bsyn:: table, one lane per
 // group; reads the row tags as dwords) and the block pass + r x r solve (gf_bsyn.hip).
 bool gf_bsyn_supported(int k, int m, int bb, int rmax, const Tune& t);
 hipError_t launch_decode_prep_bsyn(const PrepIO& io, const uint8_t* cenc, int k, int m, int bb,
@@ -279,8 +308,8 @@ hipError_t launch_gf_bsyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
                           int m, int bb, long long groups, int rmax, long long out_gstride,
                           hipStream_t st, const Tune& t);
 
-// Syndrome decode of the compiled QuicR preset codes with m >= 7 and (5, 5) at 1352-byte
-// blocks: prep (psyn:: table, 16 lanes per group) and the block pass + in-place Gauss-Jordan
+// Syndrome decode of the Syn::psyn codes of compiled_codes.h (QuicR presets at 1352-byte
+// blocks): prep (psyn:: table, 16 lanes per group) and the block pass + in-place Gauss-Jordan
 // replay (gf_psyn.hip).
 bool gf_psyn_supported(int k, int m, int bb, int rmax, const Tune& t);
 hipError_t launch_decode_prep_psyn(const PrepIO& io, const uint8_t* cenc, int k, int m, int bb,

@@ -417,11 +417,12 @@ static void xor_flat_launch(const uint8_t* in, uint8_t* out, const uint8_t* eidx
     const int nu = (bb + VS - 1) / VS;
     const unsigned total = (unsigned)(G * nu);
     const unsigned nb = (total + 255) / 256;
-    switch (k) {
-        case 10: qlaunch((xor_flat_kernel<VS, 10, DECODE>), dim3(nb), dim3(256), 0, st, in, out, eidx, k, bb, nu, total, igs, ogs, es); break;
-        case 32: qlaunch((xor_flat_kernel<VS, 32, DECODE>), dim3(nb), dim3(256), 0, st, in, out, eidx, k, bb, nu, total, igs, ogs, es); break;
-        default: qlaunch((xor_flat_kernel<VS, 0, DECODE>), dim3(nb), dim3(256), 0, st, in, out, eidx, k, bb, nu, total, igs, ogs, es); break;
-    }
+    // k at compile time for configs A and B/C, else at run time
+    const auto go = [&](auto KC) {
+        qlaunch((xor_flat_kernel<VS, decltype(KC)::value, DECODE>), dim3(nb), dim3(256), 0, st, in,
+                out, eidx, k, bb, nu, total, igs, ogs, es);
+    };
+    if (!dispatch_value<10, 32>(k, go)) go(std::integral_constant<int, 0>{});
 }
 
 template <bool DECODE>
@@ -529,32 +530,23 @@ static hipError_t gf_apply_dispatch(const uint8_t* in, uint8_t* out, const uint8
     if (pd < 1 || pd > 3) return hipErrorInvalidValue;
     note_kernel(DECODE ? "gf_apply_kernel<decode>"
                        : (flat ? "gf_apply_kernel<encode,flat>" : "gf_apply_kernel<encode>"));
-#define QF_ARGS in, out, coef, slots, nout, k, m, bb, nw, ntiles, nchunk, rmax, coef_gstride, \
-                out_gstride, tu, flat_lanes
-#define QF_LAUNCH(RCV)                                                                        \
-    do {                                                                                      \
-        if (flat) {                                                                           \
-            if constexpr (!DECODE)                                                            \
-                qlaunch((gf_apply_kernel<RCV, false, false, 2, true>), dim3(nb), dim3(nthr), 0, st, QF_ARGS);    \
-        } else if (s >= 4 && pd == 3)                                                         \
-            qlaunch((gf_apply_kernel<RCV, DECODE, false, 3>), dim3(nb), dim3(nthr), 0, st, QF_ARGS);             \
-        else if (s >= 4 && pd == 1)                                                           \
-            qlaunch((gf_apply_kernel<RCV, DECODE, false, 1>), dim3(nb), dim3(nthr), 0, st, QF_ARGS);             \
-        else if (s >= 4)                                                                      \
-            qlaunch((gf_apply_kernel<RCV, DECODE, false, 2>), dim3(nb), dim3(nthr), 0, st, QF_ARGS);             \
-        else                                                                                  \
-            qlaunch((gf_apply_kernel<RCV, DECODE, true, 1>), dim3(nb), dim3(nthr), 0, st, QF_ARGS);              \
-    } while (0)
-    switch (rc) {
-        case 1: QF_LAUNCH(1); break;
-        case 2: QF_LAUNCH(2); break;
-        case 4: QF_LAUNCH(4); break;
-        case 8: QF_LAUNCH(8); break;
-        case 16: QF_LAUNCH(16); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef QF_LAUNCH
-#undef QF_ARGS
+    const auto go = [&](auto kern) {
+        qlaunch(kern, dim3(nb), dim3(nthr), 0, st, in, out, coef, slots, nout, k, m, bb, nw, ntiles,
+                nchunk, rmax, coef_gstride, out_gstride, tu, flat_lanes);
+    };
+    const bool known = dispatch_value<1, 2, 4, 8, 16>(rc, [&](auto RC) {
+        constexpr int rcv = decltype(RC)::value;
+        if (flat) {
+            if constexpr (!DECODE) go(gf_apply_kernel<rcv, false, false, 2, true>);
+        } else if (s < 4) {
+            go(gf_apply_kernel<rcv, DECODE, true, 1>);
+        } else {
+            dispatch_value<1, 2, 3>(pd, [&](auto PD) {
+                go(gf_apply_kernel<rcv, DECODE, false, decltype(PD)::value>);
+            });
+        }
+    });
+    if (!known) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

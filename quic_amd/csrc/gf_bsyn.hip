@@ -30,6 +30,7 @@
 // blocks 1 .. D - 1.  tests/test_isa.py checks the compiler adds no VMEM instruction or
 // vmcnt wait of its own.
 #include "cauchy_const.h"
+#include "compiled_codes.h"
 #include "fec_kernels.h"
 #include "gf256.h"
 #include "gf_bitslice.h"
@@ -281,11 +282,11 @@ __global__ __launch_bounds__(kBsynWaves * 64) void gf_bsyn_kernel(
 
 // ------------------------------------------------------------------ launchers
 namespace {
-constexpr int kBsynS = 169;   // bb = 1352: 1350-byte payloads (BASELINE configs B, C)
+constexpr int kBsynS = kCompiledS;   // bb = 1352: 1350-byte payloads (BASELINE configs B, C)
 }  // namespace
 
 bool gf_bsyn_supported(int k, int m, int bb, int rmax, const Tune& t) {
-    return t.bsyn && t.const_enc && k == 32 && m == 4 && bb == 8 * kBsynS && rmax <= kBsynRC;
+    return t.bsyn && t.const_enc && rmax <= kBsynRC && find_code(k, m, bb, Syn::bsyn);
 }
 
 hipError_t launch_gf_bsyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
@@ -309,15 +310,15 @@ hipError_t launch_gf_bsyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
     if (!grid) return hipErrorInvalidValue;
     note_kernel("gf_bsyn_kernel<decode,k32m4>");
     // recovered blocks stored non-temporal (B decode 0.655 -> 0.631 ms)
-#define QB_GO(DV)                                                                             \
-    qlaunch((gf_bsyn_kernel<32, 4, kBsynS, DV, true>), dim3(grid), dim3(kBsynWaves * 64), lds, \
-            st, in, out, tab, cenc, slots, nout, groups, rmax, out_gstride)
-    switch (D) {
-        case 3: QB_GO(3); break;
-        case 5: QB_GO(5); break;
-        default: QB_GO(7); break;
-    }
-#undef QB_GO
+    with_code(k, m, [&](auto I) {
+        constexpr CompiledCode c = kCompiledCodes[decltype(I)::value];
+        if constexpr (c.syn == Syn::bsyn)
+            dispatch_value<3, 5, 7>(D, [&](auto DV) {
+                qlaunch((gf_bsyn_kernel<c.k, c.m, kBsynS, decltype(DV)::value, true>), dim3(grid),
+                        dim3(kBsynWaves * 64), lds, st, in, out, tab, cenc, slots, nout, groups,
+                        rmax, out_gstride);
+            });
+    });
     return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@
 // preset code's variants, so the codes build in parallel.
 #pragma once
 #include "cauchy_const.h"
+#include "compiled_codes.h"
 #include "fec_kernels.h"
 #include "gf256.h"
 #include "gf_bitslice.h"
@@ -324,7 +325,7 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
 
 }  // namespace
 
-constexpr int kPsynS = 169;   // bb = 1352: 1350-byte payloads
+constexpr int kPsynS = kCompiledS;   // bb = 1352: 1350-byte payloads
 
 // launch arguments of one preset code's variants (gf_psyn_<k><m>.hip)
 struct PsynLaunch {
@@ -332,31 +333,33 @@ struct PsynLaunch {
     long long groups; int rmax; long long out_gstride; hipStream_t st; const Tune *t;
     int k; size_t lds; bool wide;
 };
-hipError_t psyn_go_1010(const PsynLaunch& a);
-hipError_t psyn_go_1015(const PsynLaunch& a);
-hipError_t psyn_go_1020(const PsynLaunch& a);
-hipError_t psyn_go_1515(const PsynLaunch& a);
-hipError_t psyn_go_55(const PsynLaunch& a);
 
 // One code's kernel: ring depth 5, no register prefetch, solve products by nibble jumps,
 // non-temporal stores (the other variants measured slower, 3.7).
 // The grid is the workgroups one CU holds at once (the runtime's occupancy answer for this
 // kernel, cached per kernel: the codes differ in VGPRs) times the CUs.
-#define QP_DEFINE_GO(NAME, KV, MV)                                                             \
-    hipError_t NAME(const PsynLaunch& a) {                                                     \
-        const Tune& t = *a.t;                                                                  \
-        constexpr int RCV = KV < MV ? KV : MV;                                                 \
-        const auto kern = a.wide ? gf_psyn_kernel<KV, MV, RCV, kPsynS, 5, true>               \
-                                 : gf_psyn_kernel<KV, MV, RCV, kPsynS, 5, false>;             \
-        const unsigned grid = persistent_grid(                                                 \
-            a.groups, kPsynWaves,                                                              \
-            (long long)t.cus * resident_blocks((const void*)kern, kPsynWaves * 64, a.lds),     \
-            t.psyn_wg, t.stream_grid, a.k);                                                    \
-        if (!grid) return hipErrorInvalidValue;                                                \
-        note_grid("gf_psyn_kernel", grid);                                                     \
-        qlaunch(kern, dim3(grid), dim3(kPsynWaves * 64), a.lds, a.st, a.in, a.out, a.tab,      \
-                a.cenc, a.slots, a.nout, a.groups, a.rmax, a.out_gstride);                    \
-        return hipGetLastError();                                                              \
-    }
+// Each Syn::psyn row of compiled_codes.h has its instantiation in its own object
+// (gf_psyn_<k><m>.hip), declared here, so no other object compiles a gf_psyn_kernel.
+template <int K, int M>
+hipError_t psyn_go(const PsynLaunch& a) {
+    const Tune& t = *a.t;
+    constexpr int RC = K < M ? K : M;
+    const auto kern = a.wide ? gf_psyn_kernel<K, M, RC, kPsynS, 5, true>
+                             : gf_psyn_kernel<K, M, RC, kPsynS, 5, false>;
+    const unsigned grid = persistent_grid(
+        a.groups, kPsynWaves,
+        (long long)t.cus * resident_blocks((const void*)kern, kPsynWaves * 64, a.lds), t.psyn_wg,
+        t.stream_grid, a.k);
+    if (!grid) return hipErrorInvalidValue;
+    note_grid("gf_psyn_kernel", grid);
+    qlaunch(kern, dim3(grid), dim3(kPsynWaves * 64), a.lds, a.st, a.in, a.out, a.tab, a.cenc,
+            a.slots, a.nout, a.groups, a.rmax, a.out_gstride);
+    return hipGetLastError();
+}
+extern template hipError_t psyn_go<5, 5>(const PsynLaunch&);
+extern template hipError_t psyn_go<10, 10>(const PsynLaunch&);
+extern template hipError_t psyn_go<10, 15>(const PsynLaunch&);
+extern template hipError_t psyn_go<10, 20>(const PsynLaunch&);
+extern template hipError_t psyn_go<15, 15>(const PsynLaunch&);
 
 }  // namespace qfec

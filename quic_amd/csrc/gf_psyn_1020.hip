@@ -2,5 +2,5 @@
 #include "gf_psyn.h"
 
 namespace qfec {
-QP_DEFINE_GO(psyn_go_1020, 10, 20)
+template hipError_t psyn_go<10, 20>(const PsynLaunch&);
 }  // namespace qfec

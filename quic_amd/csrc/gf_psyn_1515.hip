@@ -2,5 +2,5 @@
 #include "gf_psyn.h"
 
 namespace qfec {
-QP_DEFINE_GO(psyn_go_1515, 15, 15)
+template hipError_t psyn_go<15, 15>(const PsynLaunch&);
 }  // namespace qfec

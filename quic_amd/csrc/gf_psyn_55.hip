@@ -2,5 +2,5 @@
 #include "gf_psyn.h"
 
 namespace qfec {
-QP_DEFINE_GO(psyn_go_55, 5, 5)
+template hipError_t psyn_go<5, 5>(const PsynLaunch&);
 }  // namespace qfec

@@ -286,19 +286,16 @@ hipError_t launch_gf_ragged(const uint8_t* in, uint8_t* out, RaggedView v, const
     if (units <= 0) return hipSuccess;
     if (units > 0x7fffffffLL) return hipErrorInvalidValue;
     note_kernel(decode ? "gf_ragged_kernel<decode>" : "gf_ragged_kernel<encode>");
-#define QF_RAGGED(RCV, DEC)                                                                    \
-    do {                                                                                       \
-        const unsigned nb = ragged_grid((const void*)gf_ragged_kernel<RCV, DEC>, 256, units, t); \
-        note_grid("gf_ragged_kernel", nb);                                                     \
-        qlaunch((gf_ragged_kernel<RCV, DEC>), dim3(nb), dim3(256), 0, st, in, v.in_off, out,    \
-                v.out_off, v.bb, coef, nout, k, m, nchunk, coef_gstride, units);               \
-    } while (0)
-    switch (rc) {
-        case 2: if (decode) QF_RAGGED(2, true); else QF_RAGGED(2, false); break;
-        case 4: if (decode) QF_RAGGED(4, true); else QF_RAGGED(4, false); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef QF_RAGGED
+    const bool known = dispatch_value<2, 4>(rc, [&](auto RC) {
+        dispatch_bool(decode, [&](auto DEC) {
+            const auto kern = gf_ragged_kernel<decltype(RC)::value, decltype(DEC)::value>;
+            const unsigned nb = ragged_grid((const void*)kern, 256, units, t);
+            note_grid("gf_ragged_kernel", nb);
+            qlaunch(kern, dim3(nb), dim3(256), 0, st, in, v.in_off, out, v.out_off, v.bb, coef,
+                    nout, k, m, nchunk, coef_gstride, units);
+        });
+    });
+    if (!known) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -32,6 +32,7 @@
 // slots[g][j] (or j, recovered-blocks layout) and groups with nout == 0 are skipped.  All of
 // a group's blocks are in LDS before any of its stores, so in place is safe.
 #include "cauchy_const.h"
+#include "compiled_codes.h"
 #include "fec_kernels.h"
 #include "gf_bitslice.h"
 #include "gf_counted.h"
@@ -641,23 +642,18 @@ int gf_stream_min_ring(int bb) {
     return (max_o + 2 * bb + 1023) / 1024;
 }
 
-// Codes whose encode is compiled (cauchy_const.h coefficients, windowed form) at 1352-byte
-// blocks: BASELINE B/C's (32, 4) and the QuicR presets (quic_fec_group.cc:22-82).
-bool gf_stream_compiled(int k, int m, int bb) {
-    if (bb != 8 * 169) return false;
-    return (k == 32 && m == 4) || (k == 5 && m == 5) || (k == 10 && (m == 10 || m == 15 || m == 20)) ||
-           (k == 15 && m == 15) || (k == 250 && m == 5);
-}
-
-bool gf_stream_supported(int k, int m, int bb, int rc, bool decode, const Tune& t) {
-    (void)m;
-    (void)decode;
+bool gf_stream_supported(int k, int bb, int rc, const Tune& t) {
     if (!t.stream) return false;
     if (bb % 8 != 0 || bb < 8 || bb > 2048) return false;   // s <= 256: a word per lane
     if (rc != 2 && rc != 4 && rc != 8 && rc != 16) return false;
     if ((long long)k * bb < 16) return false;   // groups 8 mod 16 apart stream skewed
     if (t.stream_ring < gf_stream_min_ring(bb)) return false;   // gf_apply instead
     return true;
+}
+
+int stream_encode_rc(int k, int m, int bb, bool aligned, const Tune& t) {
+    if (m > 8 && m <= 16 && aligned && gf_stream_supported(k, bb, 16, t)) return 16;
+    return encode_rc(m, t);
 }
 
 #ifndef QF_KERNELS_ONLY   // (register-use experiments compile single instantiations)
@@ -667,23 +663,34 @@ hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef
                             long long out_gstride, bool decode, hipStream_t st,
                             const Tune& t) {
     if (groups <= 0) return hipSuccess;
-    if (!gf_stream_supported(k, m, bb, rc, decode, t)) return hipErrorInvalidValue;
+    if (!gf_stream_supported(k, bb, rc, t)) return hipErrorInvalidValue;
     if (((uintptr_t)in & 15) != 0 || ((uintptr_t)slots & 3) != 0) return hipErrorInvalidValue;
     const int R = t.stream_ring;
     if (R < 4 || R > 36) return hipErrorInvalidValue;
+    const int s = bb / 8;
+    // the row of a compiled encode (BASELINE configs B/C and the QuicR presets at 1350-byte
+    // payloads): the code is fixed at compile time and no table is read
+    const CompiledCode* const code =
+        !decode && t.const_enc && s == kCompiledS ? find_code(k, m) : nullptr;
+    const bool out8 = (((uintptr_t)out | (uintptr_t)out_gstride) & 7) == 0;
     // wide (LDS-staged 8-byte) parity stores: measured faster only for the (5, 5) encode
     // (0.203 -> 0.180 ms; within +-5 % on the other presets)
-    const bool wide_enc = !decode && t.const_enc && k == 5 && m == 5 && bb == 1352 &&
-                          (((uintptr_t)out | (uintptr_t)out_gstride) & 7) == 0;
+    const bool wide_enc = code && code->stream_wide && out8;
     const size_t lds = (size_t)kStreamWaves * ((R + kMirror) * 1024 + (wide_enc ? kStreamStage : 0));
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     const int per_cu = (int)((160 * 1024) / lds);
-    // units: (group, chunk of rc outputs); encode chunks of 8 for m > 8 (m <= 8: one chunk
-    // of exactly m outputs), decode chunks of rc for rmax > rc
-    const int s = bb / 8;
-    const bool compiled = !decode && t.const_enc && gf_stream_compiled(k, m, bb);
-    const int nchunk = decode ? (rmax + rc - 1) / rc
-                              : (compiled || m <= 8 || (rc == 16 && m <= 16)) ? 1 : (m + 7) / 8;
+    // units: (group, chunk of outputs).  Decode: chunks of rc for rmax > rc.  A compiled encode:
+    // one unit.  A table encode: the table is the one stream_encode_rc() asks for (rows of
+    // max(4, rc) bytes), and a unit is every output where they fit its rows, else a chunk of 8
+    int nchunk = 1, enc_rc = 0;
+    if (decode) {
+        nchunk = (rmax + rc - 1) / rc;
+    } else if (!code) {
+        enc_rc = stream_encode_rc(k, m, bb, true, t);
+        if (std::max(rc, 4) != std::max(enc_rc, 4) || (m > enc_rc && enc_rc != 8))
+            return hipErrorInvalidValue;
+        if (m > enc_rc) nchunk = (m + 7) / 8;
+    }
     const long long units = groups * nchunk;
     // oversubscribed: about swg units per wave ((250, 5) decode 5.02 -> 4.36 ms, DESIGN.md
     // section 4.5); large groups only by default
@@ -693,160 +700,98 @@ hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef
         persistent_grid(units, kStreamWaves, (long long)t.cus * per_cu, swg, t.stream_grid,
                         ((long long)k * bb + 8 + 1023) / 1024);
     if (!grid) return hipErrorInvalidValue;
-    const unsigned threads = kStreamWaves * 64;
-#define QS_GO(RCV, SV, DEC, RCPV, KCV)                                                        \
-    qlaunch((gf_stream_kernel<RCV, SV, DEC, RCPV, KCV>), dim3(grid), dim3(threads), \
-                       lds, st, in, out, coef, slots, nout, groups, k, m, rmax, coef_gstride,   \
-                       out_gstride, R, s, nchunk)
-#define QS_GOJ(RCV, SV, DEC, RCPV, KCV)                                                       \
-    qlaunch((gf_stream_kernel<RCV, SV, DEC, RCPV, KCV, true>), dim3(grid), dim3(threads), \
-                       lds, st, in, out, coef, slots, nout, groups, k, m, rmax, coef_gstride,   \
-                       out_gstride, R, s, nchunk)
-#define QS_DECJ(SV)                                       \
-    switch (rc) {                                         \
-        case 2: QS_GOJ(2, SV, true, 4, 0); break;         \
-        case 4: QS_GOJ(4, SV, true, 4, 0); break;         \
-        case 8: QS_GOJ(8, SV, true, 8, 0); break;         \
-        default: return hipErrorInvalidValue;             \
-    }
-#define QS_DEC(SV)                                        \
-    switch (rc) {                                         \
-        case 2: QS_GO(2, SV, true, 4, 0); break;          \
-        case 4: QS_GO(4, SV, true, 4, 0); break;          \
-        case 8: QS_GO(8, SV, true, 8, 0); break;          \
-        default: return hipErrorInvalidValue;             \
-    }
-    // encode: one output per register set, RC = m; the table row stride is max(4, rc)
-#define QS_ENC(SV)                                        \
-    switch (m) {                                          \
-        case 2: QS_GO(2, SV, false, 4, 0); break;         \
-        case 3: QS_GO(3, SV, false, 4, 0); break;         \
-        case 4: QS_GO(4, SV, false, 4, 0); break;         \
-        case 5: QS_GO(5, SV, false, 8, 0); break;         \
-        case 6: QS_GO(6, SV, false, 8, 0); break;         \
-        case 7: QS_GO(7, SV, false, 8, 0); break;         \
-        case 8: QS_GO(8, SV, false, 8, 0); break;         \
-        default: QS_GO(8, SV, false, 8, 0); break;        \
-    }
     // the static ring schedule is an encode only: a rolled decode on it measured slower than
     // gf_stream's (0.644 vs 0.619 ms on config B)
-    const bool ring_shape = (k == 32 && m == 4) || (k == 10 && (m == 10 || m == 15 || m == 20)) ||
-                            (k == 250 && m == 5) || (k == 15 && m == 15) || (k == 5 && m == 5);
-    if (t.stream_static && !decode && s == 169 && ring_shape && t.const_enc) {
-        // the fixed B/C shape and the even-k QuicR presets: compile-time ring schedule
-        // (gf_ring_kernel)
-        // wide (LDS-staged 8-byte) parity stores: 3 store instructions per block instead of
-        // 16, so the group's store count stays under the 63 a counted wait can name.  Not for
-        // (10, 20): 290 VGPRs, one wave per SIMD (0.754 vs 0.673 ms); B/C keep 4 x 16 stores
-        // 
-        // (10, 20) in two units of 10 parity rows per group (ring_split): 10 accumulators
-        // per wave instead of 20, so wide stores fit the registers
-        const bool rsplit = t.ring_split && k == 10 && m == 20;
-        const bool rwide = t.ring_wide && !(k == 32 && m == 4) && (rsplit || !(k == 10 && m == 20)) &&
-                           (((uintptr_t)out | (uintptr_t)out_gstride) & 7) == 0;
-        const size_t rlds = (size_t)kRingWaves * (RingShape<169>::RB + (rwide ? kStreamStage : 0));
-        // oversubscribed: about rwg units per wave; measured faster for these encodes
+    if (code && t.stream_static) {
+        // compile-time ring schedule (gf_ring_kernel).  Wide (LDS-staged 8-byte) parity stores:
+        // 3 store instructions per block instead of 16, so the group's store count stays under
+        // the 63 a counted wait can name.  Which rows take them, and which split a group into
+        // two units of m / 2 parity rows (half the accumulators per wave, so wide stores fit
+        // the registers): compiled_codes.h, DESIGN.md section 3.3
+        const bool rsplit = t.ring_split && code->ring_split;
+        const bool rwide = t.ring_wide && (rsplit || code->ring_wide) && out8;
+        const size_t rlds = (size_t)kRingWaves * (RingShape<kCompiledS>::RB + (rwide ? kStreamStage : 0));
+        // oversubscribed: about rwg units per wave; measured faster for some of these encodes
         // (B 0.58 -> 0.55 ms, (10,10) 0.361 -> 0.330; (10,20) and (15,15) no better,
         // DESIGN.md section 4.5)
-        const int rwg = t.ring_wg >= 0 ? t.ring_wg
-                        : ((k == 32 && m == 4) || (k == 10 && m == 10) || (k == 5 && m == 5) ||
-                           (k == 250 && m == 5)) ? 1 : 0;
+        const int rwg = t.ring_wg >= 0 ? t.ring_wg : code->ring_wg;
         const unsigned rgrid = persistent_grid(groups * (rsplit ? 2 : 1), kRingWaves,
                                                (long long)t.cus * (int)((160 * 1024) / rlds), rwg,
                                                t.stream_grid);
         if (!rgrid) return hipErrorInvalidValue;
-        if (rsplit) {
-            note_kernel("gf_ring_kernel<encode,k10m20,split>");
-            if (rwide)
-                qlaunch((gf_ring_kernel<10, 169, 10, false, 20, true, true, 2>), dim3(rgrid),
-                        dim3(kRingWaves * 64), rlds, st, in, out, coef, slots, nout, groups, rmax,
-                        coef_gstride, out_gstride);
-            else
-                qlaunch((gf_ring_kernel<10, 169, 10, false, 20, true, false, 2>), dim3(rgrid),
-                        dim3(kRingWaves * 64), rlds, st, in, out, coef, slots, nout, groups, rmax,
-                        coef_gstride, out_gstride);
-            return hipGetLastError();
-        }
-#define QR_GO1(KV, MCV, WV)                                                                     \
-    qlaunch((gf_ring_kernel<KV, 169, MCV, false, MCV, true, WV>), dim3(rgrid),                   \
-                       dim3(kRingWaves * 64), rlds, st, in, out, coef, slots, nout, groups, rmax, \
-                       coef_gstride, out_gstride)
-#define QR_GO(KV, MCV)                  \
-    do {                                \
-        if (rwide) QR_GO1(KV, MCV, true); \
-        else QR_GO1(KV, MCV, false);      \
-    } while (0)
+        char name[64];
+        snprintf(name, sizeof name, "gf_ring_kernel<encode,k%dm%d%s>", k, m, rsplit ? ",split" : "");
+        note_kernel(name);
+        const auto go = [&](auto kern) {
+            qlaunch(kern, dim3(rgrid), dim3(kRingWaves * 64), rlds, st, in, out, coef, slots, nout,
+                    groups, rmax, coef_gstride, out_gstride);
+        };
         // nt parity stores (plain: 0.673 vs 0.578 ms on B)
-        switch (k * 256 + m) {
-            case 32 * 256 + 4: note_kernel("gf_ring_kernel<encode,k32m4>"); QR_GO1(32, 4, false); break;
-            case 10 * 256 + 10: note_kernel("gf_ring_kernel<encode,k10m10>"); QR_GO(10, 10); break;
-            case 10 * 256 + 15: note_kernel("gf_ring_kernel<encode,k10m15>"); QR_GO(10, 15); break;
-            case 250 * 256 + 5: note_kernel("gf_ring_kernel<encode,k250m5>"); QR_GO(250, 5); break;
-            case 15 * 256 + 15: note_kernel("gf_ring_kernel<encode,k15m15>"); QR_GO(15, 15); break;
-            case 5 * 256 + 5: note_kernel("gf_ring_kernel<encode,k5m5>"); QR_GO(5, 5); break;
-            default: note_kernel("gf_ring_kernel<encode,k10m20>"); QR_GO1(10, 20, false); break;
-        }
-#undef QR_GO
-#undef QR_GO1
+        with_code(k, m, [&](auto I) {
+            constexpr CompiledCode c = kCompiledCodes[decltype(I)::value];
+            if constexpr (c.ring_split) {
+                if (rsplit) {
+                    if (rwide) go(gf_ring_kernel<c.k, kCompiledS, c.m / 2, false, c.m, true, true, 2>);
+                    else go(gf_ring_kernel<c.k, kCompiledS, c.m / 2, false, c.m, true, false, 2>);
+                    return;
+                }
+            }
+            if constexpr (c.ring_wide) {
+                if (rwide) {
+                    go(gf_ring_kernel<c.k, kCompiledS, c.m, false, c.m, true, true>);
+                    return;
+                }
+            }
+            go(gf_ring_kernel<c.k, kCompiledS, c.m, false, c.m, true, false>);
+        });
         return hipGetLastError();
     }
-    if (decode) {
-        if (s == 169) {
-            note_kernel("gf_stream_kernel<decode>");
-            QS_DECJ(169)
-        } else {
-            note_kernel("gf_stream_kernel<decode,s>");
-            QS_DEC(0)
-        }
-    } else {
-        if (compiled) {
-            // BASELINE configs B/C and the QuicR presets at 1350-byte payloads: the code is
-            // fixed at compile time (windowed form, every output in one unit)
-            note_kernel("gf_stream_kernel<encode,compiled>");
-            if (wide_enc) {
-                qlaunch((gf_stream_kernel<5, 169, false, 8, 5, false, true>), dim3(grid),
-                        dim3(threads), lds, st, in, out, coef, slots, nout, groups, k, m, rmax,
-                        coef_gstride, out_gstride, R, s, nchunk);
-                return hipGetLastError();
+    const unsigned threads = kStreamWaves * 64;
+    const auto go = [&](auto kern) {
+        qlaunch(kern, dim3(grid), dim3(threads), lds, st, in, out, coef, slots, nout, groups, k, m,
+                rmax, coef_gstride, out_gstride, R, s, nchunk);
+    };
+    if (code) {
+        // windowed form, every output in one unit
+        note_kernel("gf_stream_kernel<encode,compiled>");
+        with_code(k, m, [&](auto I) {
+            constexpr CompiledCode c = kCompiledCodes[decltype(I)::value];
+            if constexpr (c.stream_wide) {
+                if (wide_enc) {
+                    go(gf_stream_kernel<c.m, kCompiledS, false, c.rcpt(), c.k, false, true>);
+                    return;
+                }
             }
-            switch (k * 256 + m) {
-                case 32 * 256 + 4: QS_GO(4, 169, false, 4, 32); break;
-                case 5 * 256 + 5: QS_GO(5, 169, false, 8, 5); break;
-                case 10 * 256 + 10: QS_GO(10, 169, false, 12, 10); break;
-                case 10 * 256 + 15: QS_GO(15, 169, false, 16, 10); break;
-                case 10 * 256 + 20: QS_GO(20, 169, false, 20, 10); break;
-                case 15 * 256 + 15: QS_GO(15, 169, false, 16, 15); break;
-                case 250 * 256 + 5: QS_GO(5, 169, false, 8, 250); break;
-                default: return hipErrorInvalidValue;
-            }
-            return hipGetLastError();
-        }
-        if (m > 8) {
-            // one unit of up to 16 outputs (table rows of 16), or chunks of 8
-            if (rc == 16 && m <= 16) {
-                note_kernel(s == 169 ? "gf_stream_kernel<encode>" : "gf_stream_kernel<encode,s>");
-                if (s == 169) QS_GO(16, 169, false, 16, 0);
-                else QS_GO(16, 0, false, 16, 0);
-                return hipGetLastError();
-            }
-            if (rc != 8) return hipErrorInvalidValue;
-        } else if ((rc < 4 ? 4 : rc) != (m <= 4 ? 4 : 8)) {
-            return hipErrorInvalidValue;
-        }
-        if (s == 169) {
-            note_kernel("gf_stream_kernel<encode>");
-            QS_ENC(169)
-        } else {
-            note_kernel("gf_stream_kernel<encode,s>");
-            QS_ENC(0)
-        }
+            go(gf_stream_kernel<c.m, kCompiledS, false, c.rcpt(), c.k>);
+        });
+        return hipGetLastError();
     }
-#undef QS_ENC
-#undef QS_DEC
-#undef QS_DECJ
-#undef QS_GOJ
-#undef QS_GO
-    return hipGetLastError();
+    // S at compile time for 1352-byte blocks, else s at run time
+    bool ok = true;
+    dispatch_bool(s == kCompiledS, [&](auto fixed) {
+        constexpr int sv = decltype(fixed)::value ? kCompiledS : 0;
+        if (decode) {
+            // nibble jumps (NJ) where S is fixed
+            note_kernel(sv ? "gf_stream_kernel<decode>" : "gf_stream_kernel<decode,s>");
+            ok = dispatch_value<2, 4, 8>(rc, [&](auto RC) {
+                constexpr int rcv = decltype(RC)::value;
+                go(gf_stream_kernel<rcv, sv, true, (rcv <= 4 ? 4 : 8), 0, sv != 0>);
+            });
+            return;
+        }
+        note_kernel(sv ? "gf_stream_kernel<encode>" : "gf_stream_kernel<encode,s>");
+        if (enc_rc == 16) {   // one unit of up to 16 outputs (table rows of 16)
+            go(gf_stream_kernel<16, sv, false, 16, 0>);
+            return;
+        }
+        // one output per register set, RC = m; chunks of 8 (and any other m) run RC = 8
+        const auto enc = [&](auto RC) {
+            constexpr int rcv = decltype(RC)::value;
+            go(gf_stream_kernel<rcv, sv, false, (rcv <= 4 ? 4 : 8), 0>);
+        };
+        if (!dispatch_value<2, 3, 4, 5, 6, 7, 8>(m, enc)) enc(std::integral_constant<int, 8>{});
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 #endif

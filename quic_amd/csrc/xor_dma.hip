@@ -224,12 +224,12 @@ template <bool DECODE, bool FUSED, bool COMPACT = false>
 hipError_t xor_dispatch(const XorPlan& p, const uint8_t* in, uint8_t* out, const uint8_t* eidx,
                         const uint8_t* rows_in, uint8_t* rows_out, int32_t* status, int k,
                         int bb, long long G, long long ogs, hipStream_t st, int cus) {
-    switch (p.nslot) {
-        case 2: return xor_go<DECODE, FUSED, COMPACT, 2, 1>(p, in, out, eidx, rows_in, rows_out, status, k, bb, G, ogs, st, cus);
-        case 3: return xor_go<DECODE, FUSED, COMPACT, 3, 1>(p, in, out, eidx, rows_in, rows_out, status, k, bb, G, ogs, st, cus);
-        case 4: return xor_go<DECODE, FUSED, COMPACT, 4, 1>(p, in, out, eidx, rows_in, rows_out, status, k, bb, G, ogs, st, cus);
-        default: return hipErrorInvalidValue;
-    }
+    hipError_t e = hipErrorInvalidValue;
+    dispatch_value<2, 3, 4>(p.nslot, [&](auto NSLOT) {
+        e = xor_go<DECODE, FUSED, COMPACT, decltype(NSLOT)::value, 1>(
+            p, in, out, eidx, rows_in, rows_out, status, k, bb, G, ogs, st, cus);
+    });
+    return e;
 }
 
 }  // namespace
