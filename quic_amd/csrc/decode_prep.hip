@@ -998,8 +998,8 @@ hipError_t launch_decode_prep(const PrepIO& io, const uint8_t* cenc, int k, int 
     int nwv = 4;
     while (nwv > 1 && fixed + (size_t)nwv * scratch > 64 * 1024) nwv >>= 1;
     const size_t lds = fixed + (size_t)nwv * scratch;
-    const long long want = (groups + nwv - 1) / nwv;
-    const unsigned nb = (unsigned)std::min<long long>(want, (long long)t.cus * 16);
+    const unsigned nb = persistent_grid(groups, nwv, (long long)t.cus * 16, 0, 0);
+    if (!nb) return hipErrorInvalidValue;
     note_kernel(syndrome ? "decode_prep_kernel<syndrome>" : "decode_prep_kernel");
     note_grid("decode_prep_kernel", nb);
     qlaunch((decode_prep_kernel), dim3(nb), dim3(nwv * 64), lds, st, io.rows_in, io.rows_out,

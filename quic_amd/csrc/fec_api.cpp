@@ -253,18 +253,14 @@ int qfec::encode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint
     const uint8_t* tab = nullptr;
     int rcode = get_enc_table(c, k, m, rc, &tab);
     if (rcode) return rcode;
-    if ((m <= rc || rc == 8) && qfec::gf_stream_supported(k, bb, rc, c->tune) &&
-        aligned) {
-        QF_HIP(qfec::launch_gf_stream(d_data, d_par, tab, nullptr, nullptr, k, m, bb, G, rc, 0, 0,
-                                      (long long)m * bb, false, st, c->tune));
-        return 0;
-    }
-    if (qfec::gf_dcol_supported(k, m, bb, c->tune) && ((uintptr_t)d_data & 15) == 0) {
-        QF_HIP(qfec::launch_gf_dcol_encode(d_data, d_par, k, m, bb, G, (long long)m * bb, st,
-                                           c->tune));
-        return 0;
-    }
-    QF_HIP(qfec::launch_gf_encode(d_data, d_par, tab, k, m, bb, G, rc, st, c->tune));
+    const qfec::Apply a{d_data, d_par, tab, nullptr, nullptr, nullptr, k, m, bb, G, rc, 0, 0,
+                        (long long)m * bb, st, &c->tune};
+    if ((m <= rc || rc == 8) && qfec::gf_stream_supported(k, bb, rc, c->tune) && aligned)
+        QF_HIP(qfec::launch_gf_stream(a, false));
+    else if (qfec::gf_dcol_supported(k, m, bb, c->tune) && aligned)
+        QF_HIP(qfec::launch_gf_dcol_encode(a));
+    else
+        QF_HIP(qfec::launch_gf_encode(a));
     return 0;
 }
 
@@ -299,24 +295,21 @@ int qfec::decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint
     // through the slot table, and the stride between the groups of `out`
     const qfec::PrepIO io{d_rows_in, o.compact ? nullptr : o.rows, o.compact ? o.rows : nullptr,
                           d_status, w};
-    const uint8_t* const slots = o.compact ? nullptr : w.slots;
-    const long long out_gstride = (long long)(o.compact ? rmax : k) * bb;
+    qfec::Apply a{d_blocks, o.out, w.coef, cenc, o.compact ? nullptr : w.slots, w.nout, k, m, bb,
+                  G, rc, rmax, p.tab_gstride, (long long)(o.compact ? rmax : k) * bb, st, &c->tune};
     const bool aligned = ((uintptr_t)d_blocks & 15) == 0;
     // The compiled codes.  In each, a group's stores follow all of its reads, so the slot
     // layout in place needs no scratch.
     if (qfec::gf_dcol_supported(k, m, bb, c->tune) && rmax <= 16 && aligned) {
         // compiled (128, 16) code: syndromes, then the r x r solve
         QF_HIP(qfec::launch_decode_prep(io, cenc, k, m, bb, rc, rmax, G, st, c->tune, true));
-        QF_HIP(qfec::launch_gf_dcol_syndrome(d_blocks, o.out, w.coef, slots, w.nout, cenc, k, m,
-                                             bb, G, rmax, p.tab_gstride, out_gstride, st,
-                                             c->tune));
+        QF_HIP(qfec::launch_gf_dcol_syndrome(a));
         return 0;
     }
     if (qfec::gf_psyn_supported(k, m, bb, rmax, c->tune) && aligned) {
         // compiled QuicR preset code: syndromes of every parity row, then Gauss-Jordan in place
         QF_HIP(qfec::launch_decode_prep_psyn(io, cenc, k, m, bb, rmax, G, st));
-        QF_HIP(qfec::launch_gf_psyn(d_blocks, o.out, w.coef, cenc, slots, w.nout, k, m, bb, G,
-                                    rmax, out_gstride, st, c->tune));
+        QF_HIP(qfec::launch_gf_psyn(a));
         return 0;
     }
     if (qfec::gf_bsyn_supported(k, m, bb, rmax, c->tune) && aligned &&
@@ -325,8 +318,7 @@ int qfec::decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint
         // the r x r solve.  Its prep reads the row tags as dwords; tags at any other address
         // take the run-time path below (decode_prep_wide_kernel reads them bytewise)
         QF_HIP(qfec::launch_decode_prep_bsyn(io, cenc, k, m, bb, rmax, G, st));
-        QF_HIP(qfec::launch_gf_bsyn(d_blocks, o.out, w.coef, cenc, slots, w.nout, k, m, bb, G,
-                                    rmax, out_gstride, st, c->tune));
+        QF_HIP(qfec::launch_gf_bsyn(a));
         return 0;
     }
     // The run-time codes: the prep's coefficients, applied in chunks of rc recovered blocks.
@@ -338,22 +330,18 @@ int qfec::decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint
     // several chunks (units on different waves) a later chunk would read slots an earlier one
     // already overwrote, so it is the dense decode into scratch, then the scatter.
     const bool direct = !o.compact && (p.nchunk == 1 || o.out != d_blocks);
-    uint8_t* dst = o.out;
     if (!o.compact && !direct) {
         QF_HIP(W.ensure(W.dscratch, (size_t)G * p.scratch));
-        dst = (uint8_t*)W.dscratch.p;
+        a.out = (uint8_t*)W.dscratch.p;
+        a.slots = nullptr;
+        a.out_gstride = (long long)rmax * bb;
     }
     if (qfec::gf_stream_supported(k, bb, rc, c->tune) && aligned)
-        QF_HIP(qfec::launch_gf_stream(d_blocks, dst, w.coef, direct ? w.slots : nullptr, w.nout,
-                                      k, m, bb, G, rc, rmax, p.tab_gstride,
-                                      (long long)(direct ? k : rmax) * bb, true, st, c->tune));
-    else if (direct)
-        QF_HIP(qfec::launch_gf_decode(d_blocks, dst, w, k, m, bb, G, rc, rmax, st, c->tune));
+        QF_HIP(qfec::launch_gf_stream(a, true));
     else
-        QF_HIP(qfec::launch_gf_decode_scratch(d_blocks, dst, w, k, m, bb, G, rc, rmax, st,
-                                              c->tune));
-    if (dst != o.out)
-        QF_HIP(qfec::launch_scatter_recovered(dst, o.out, w, k, bb, rmax, G, st));
+        QF_HIP(qfec::launch_gf_decode(a));
+    if (a.out != o.out)
+        QF_HIP(qfec::launch_scatter_recovered(a.out, o.out, w, k, bb, rmax, G, st));
     return 0;
 }
 
@@ -422,19 +410,13 @@ int resident_blocks(const void* kern, int threads, size_t lds) {
 
 // NullDecrypter on every packet of each group, placement into the receive set, the
 // recovered-blocks decode, the unfilled-group status (qfec_open_decode_batch)
-int qfec::open_decode_impl(qfec_ctx* c, int k, int m, int bb, long long groups,
-                           const uint8_t* d_pkt, long long pkt_stride, const int* d_pkt_len,
-                           const int* d_ad_len, int ad_len_all, uint8_t* d_blocks,
-                           uint8_t* d_rows, int* d_open_len, uint8_t* d_rec, uint8_t* d_rec_rows,
-                           int* d_status, hipStream_t st) {
-    QF_HIP(qfec::launch_open_groups(k, m, bb, groups, d_pkt, pkt_stride,
-                                    (const int32_t*)d_pkt_len, (const int32_t*)d_ad_len,
-                                    ad_len_all, d_blocks, d_rows, (int32_t*)d_open_len, st));
-    int rc = decode_impl(c, k, m, bb, groups, d_blocks, d_rows, {d_rec, d_rec_rows, true},
-                         (int32_t*)d_status, st);
+int qfec::open_decode_impl(qfec_ctx* c, int k, int m, int bb, long long groups, Rows pkt,
+                           Rows ad, uint8_t* d_blocks, uint8_t* d_rows, int32_t* d_open_len,
+                           DecodeOut rec, int32_t* d_status, hipStream_t st) {
+    QF_HIP(qfec::launch_open_groups(k, m, bb, groups, pkt, ad, d_blocks, d_rows, d_open_len, st));
+    int rc = decode_impl(c, k, m, bb, groups, d_blocks, d_rows, rec, d_status, st);
     if (rc) return rc;
-    QF_HIP(qfec::launch_open_status(k, std::min(k, m), groups, d_rows, d_rec_rows,
-                                    (int32_t*)d_status, st));
+    QF_HIP(qfec::launch_open_status(k, std::min(k, m), groups, d_rows, rec.rows, d_status, st));
     return 0;
 }
 
@@ -621,9 +603,9 @@ int qfec_null_seal_batch(qfec_ctx* c, long long n, const unsigned char* d_ad, lo
     std::lock_guard<std::mutex> lk(c->mu);
     int rc;
     if ((rc = set_device(c))) return rc;
-    QF_HIP(qfec::launch_null_seal_h(n, d_ad, ad_stride, (const int32_t*)d_ad_len, ad_len_all, d_pt,
-                                  pt_stride, (const int32_t*)d_pt_len, pt_len_all, d_out,
-                                  out_stride, (int32_t*)d_out_len, pick(c, stream)));
+    QF_HIP(qfec::launch_null_seal(n, rows_of(d_ad, ad_stride, d_ad_len, ad_len_all),
+                                  rows_of(d_pt, pt_stride, d_pt_len, pt_len_all),
+                                  rows_out_of(d_out, out_stride, d_out_len), pick(c, stream)));
     return 0;
 }
 
@@ -638,9 +620,9 @@ int qfec_null_open_batch(qfec_ctx* c, long long n, const unsigned char* d_pkt, l
     std::lock_guard<std::mutex> lk(c->mu);
     int rc;
     if ((rc = set_device(c))) return rc;
-    QF_HIP(qfec::launch_null_open_h(n, d_pkt, pkt_stride, (const int32_t*)d_pkt_len, pkt_len_all,
-                                  (const int32_t*)d_ad_len, ad_len_all, d_out, out_stride,
-                                  (int32_t*)d_out_len, pick(c, stream)));
+    QF_HIP(qfec::launch_null_open(n, rows_of(d_pkt, pkt_stride, d_pkt_len, pkt_len_all),
+                                  rows_of(nullptr, 0, d_ad_len, ad_len_all),
+                                  rows_out_of(d_out, out_stride, d_out_len), pick(c, stream)));
     return 0;
 }
 
@@ -661,28 +643,41 @@ int qfec_encode_seal_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
     // SerializeFec (quic_packet_creator.cc:935-957): parity packets from the group's encode,
     // each sealed with its packet header as the associated data; packet (g, i) = g * m + i
     if ((rc = encode_impl(c, k, m, bb, groups, d_data, d_parity, st))) return rc;
-    QF_HIP(qfec::launch_null_seal_h(groups * m, d_hdr, hdr_stride, (const int32_t*)d_hdr_len,
-                                  hdr_len_all, d_parity, bb, nullptr, bb, d_pkt, pkt_stride,
-                                  (int32_t*)d_pkt_len, st));
+    QF_HIP(qfec::launch_null_seal(groups * m, rows_of(d_hdr, hdr_stride, d_hdr_len, hdr_len_all),
+                                  Rows{d_parity, bb, nullptr, bb},
+                                  rows_out_of(d_pkt, pkt_stride, d_pkt_len), st));
     return 0;
 }
 
 // Every packet of each group, data and FEC, in one launch (quic_packet_creator.cc:733-736
 // seals each data packet, :948-953 each FEC packet); packet (g, i) = g * (k + m) + i.
 extern "C++" int qfec::seal_groups_args(qfec_ctx* c, int k, int m, int bb, long long groups,
-                                        std::initializer_list<const void*> required,
-                                        const unsigned char* hdr, long long hdr_stride,
-                                        const int* hdr_len, int hdr_len_all, const int* pt_len,
-                                        int pt_len_all, const unsigned char* pkt,
-                                        long long pkt_stride) {
+                                        std::initializer_list<const void*> required, Rows hdr,
+                                        const int* pt_len, int pt_len_all, RowsOut pkt) {
     int rc = check_common(c, k, m, bb, groups);
     if (rc) return rc;
     if (k + m > 256) return fail(-2, "k + m > 256");
-    if (groups && (any_null(required) || (!hdr && (hdr_len || hdr_len_all))))
+    if (groups && (any_null(required) || (!hdr.p && (hdr.len || hdr.len_all))))
         return fail(-2, "null buffer");
-    if (hdr_stride < 0 || pkt_stride < 0) return fail(-2, "bad stride");
+    if (hdr.stride < 0 || pkt.stride < 0) return fail(-2, "bad stride");
     if (!pt_len && (pt_len_all < 0 || pt_len_all > bb)) return fail(-2, "pt_len_all outside 0..block_bytes");
-    if ((((uintptr_t)pkt) | (uintptr_t)pkt_stride) & 3) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
+    if ((((uintptr_t)pkt.p) | (uintptr_t)pkt.stride) & 3) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
+    return 0;
+}
+
+// The two device forms: seal alone, or after the encode.
+static int seal_groups(qfec_ctx* c, int k, int m, int bb, long long groups,
+                       const unsigned char* d_data, unsigned char* d_parity, bool encode, Rows hdr,
+                       const int* d_pt_len, int pt_len_all, RowsOut pkt, void* stream) {
+    int rc = seal_groups_args(c, k, m, bb, groups, {d_data, d_parity, pkt.p, pkt.len}, hdr,
+                              d_pt_len, pt_len_all, pkt);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const hipStream_t st = pick(c, stream);
+    if (encode && (rc = encode_impl(c, k, m, bb, groups, d_data, d_parity, st))) return rc;
+    QF_HIP(qfec::launch_null_seal_groups(k, m, bb, groups, d_data, d_parity, hdr,
+                                         (const int32_t*)d_pt_len, pt_len_all, pkt, st));
     return 0;
 }
 
@@ -691,17 +686,9 @@ int qfec_seal_groups_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
                            const unsigned char* d_hdr, long long hdr_stride, const int* d_hdr_len,
                            int hdr_len_all, const int* d_pt_len, int pt_len_all,
                            unsigned char* d_pkt, long long pkt_stride, int* d_pkt_len, void* stream) {
-    int rc = seal_groups_args(c, k, m, bb, groups, {d_data, d_parity, d_pkt, d_pkt_len}, d_hdr,
-                              hdr_stride, d_hdr_len, hdr_len_all, d_pt_len, pt_len_all, d_pkt,
-                              pkt_stride);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    QF_HIP(qfec::launch_null_seal_groups(k, m, bb, groups, d_data, d_parity, d_hdr, hdr_stride,
-                                         (const int32_t*)d_hdr_len, hdr_len_all,
-                                         (const int32_t*)d_pt_len, pt_len_all, d_pkt, pkt_stride,
-                                         (int32_t*)d_pkt_len, pick(c, stream)));
-    return 0;
+    return seal_groups(c, k, m, bb, groups, d_data, (unsigned char*)d_parity, false,
+                       rows_of(d_hdr, hdr_stride, d_hdr_len, hdr_len_all), d_pt_len, pt_len_all,
+                       rows_out_of(d_pkt, pkt_stride, d_pkt_len), stream);
 }
 
 int qfec_encode_seal_groups_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
@@ -710,19 +697,9 @@ int qfec_encode_seal_groups_batch(qfec_ctx* c, int k, int m, int bb, long long g
                                   const int* d_hdr_len, int hdr_len_all, const int* d_pt_len,
                                   int pt_len_all, unsigned char* d_pkt, long long pkt_stride,
                                   int* d_pkt_len, void* stream) {
-    int rc = seal_groups_args(c, k, m, bb, groups, {d_data, d_parity, d_pkt, d_pkt_len}, d_hdr,
-                              hdr_stride, d_hdr_len, hdr_len_all, d_pt_len, pt_len_all, d_pkt,
-                              pkt_stride);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if ((rc = set_device(c))) return rc;
-    const hipStream_t st = pick(c, stream);
-    if ((rc = encode_impl(c, k, m, bb, groups, d_data, d_parity, st))) return rc;
-    QF_HIP(qfec::launch_null_seal_groups(k, m, bb, groups, d_data, d_parity, d_hdr, hdr_stride,
-                                         (const int32_t*)d_hdr_len, hdr_len_all,
-                                         (const int32_t*)d_pt_len, pt_len_all, d_pkt, pkt_stride,
-                                         (int32_t*)d_pkt_len, st));
-    return 0;
+    return seal_groups(c, k, m, bb, groups, d_data, d_parity, true,
+                       rows_of(d_hdr, hdr_stride, d_hdr_len, hdr_len_all), d_pt_len, pt_len_all,
+                       rows_out_of(d_pkt, pkt_stride, d_pkt_len), stream);
 }
 
 // Receiver: open every packet of each group (quic_framer.cc:657 decrypts before the group
@@ -743,9 +720,10 @@ int qfec_open_decode_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
     if ((rc = set_device(c))) return rc;
     const hipStream_t st = pick(c, stream);
     return with_workspace(c, st, [&] {
-        return open_decode_impl(c, k, m, bb, groups, d_pkt, pkt_stride, d_pkt_len, d_ad_len,
-                                ad_len_all, d_blocks, d_rows, d_open_len, d_rec, d_rec_rows,
-                                d_status, st);
+        return open_decode_impl(c, k, m, bb, groups, rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
+                                rows_of(nullptr, 0, d_ad_len, ad_len_all), d_blocks, d_rows,
+                                (int32_t*)d_open_len, {d_rec, d_rec_rows, true},
+                                (int32_t*)d_status, st);
     });
 }
 
@@ -777,8 +755,9 @@ extern "C++" int qfec::encode_ragged_impl(qfec_ctx* c, int k, int m, long long G
     // the groups with bb % 8 != 0: P0 and status -1; every other group: the GF encode
     QF_HIP(qfec::launch_xor_ragged(d_data, d_par, v, nullptr, d_status, k, G, false, 2, st,
                                    c->tune));
-    QF_HIP(qfec::launch_gf_ragged(d_data, d_par, v, tab, nullptr, k, m, G, rc, (m + rc - 1) / rc,
-                                  0, false, st, c->tune));
+    const qfec::Apply a{d_data, d_par, tab, nullptr, nullptr, nullptr, k, m, 0, G, rc, 0, 0, 0, st,
+                        &c->tune};
+    QF_HIP(qfec::launch_gf_ragged(a, v, (m + rc - 1) / rc, false));
     return 0;
 }
 
@@ -819,8 +798,9 @@ extern "C++" int qfec::decode_ragged_impl(qfec_ctx* c, int k, int m, long long G
     if (k + m > 256) return 0;   // every group is a no-op or status -1
     QF_HIP(qfec::launch_ragged_decode_status(v.bb, d_rows_in, d_rec_rows, d_status, w.nout, k,
                                              p.rmax, G, st));
-    QF_HIP(qfec::launch_gf_ragged(d_blocks, d_rec, v, w.coef, w.nout, k, m, G, p.rc, p.nchunk,
-                                  p.tab_gstride, true, st, c->tune));
+    const qfec::Apply a{d_blocks, d_rec, w.coef, cenc, nullptr, w.nout, k, m, 0, G, p.rc, p.rmax,
+                        p.tab_gstride, 0, st, &c->tune};
+    QF_HIP(qfec::launch_gf_ragged(a, v, p.nchunk, true));
     return 0;
 }
 
@@ -875,40 +855,30 @@ int qfec_decode_batch_ragged_recovered(qfec_ctx* c, int k, int m, long long grou
 // ---- ragged packet protection: the protected paths over the packed layout (pp_null.hip's
 // ragged kernels around encode_ragged_impl / decode_ragged_impl).  Packets stay dense by
 // packet index; only the blocks are packed.
-extern "C++" int qfec::seal_ragged_pkt_args(int k, int m, const unsigned char* hdr,
-                                            long long hdr_stride, const int* hdr_len,
-                                            int hdr_len_all, const unsigned char* pkt,
-                                            long long pkt_stride, const int* pkt_len) {
+extern "C++" int qfec::seal_ragged_pkt_args(int k, int m, Rows hdr, RowsOut pkt) {
     if (k + m > 256) return fail(-2, "k + m > 256");
-    if (!pkt || !pkt_len || (!hdr && (hdr_len || hdr_len_all))) return fail(-2, "null buffer");
-    if (hdr_stride < 0 || pkt_stride < 0) return fail(-2, "bad stride");
-    if ((((uintptr_t)pkt) | (uintptr_t)pkt_stride) & 3) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
+    if (!pkt.p || !pkt.len || (!hdr.p && (hdr.len || hdr.len_all))) return fail(-2, "null buffer");
+    if (hdr.stride < 0 || pkt.stride < 0) return fail(-2, "bad stride");
+    if ((((uintptr_t)pkt.p) | (uintptr_t)pkt.stride) & 3) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
     return 0;
 }
 
-static int seal_groups_ragged(qfec_ctx* c, int k, int m, long long groups, const int* d_bb,
-                              const unsigned char* d_data, const long long* d_data_off,
-                              unsigned char* d_parity, const long long* d_par_off, bool encode,
-                              const unsigned char* d_hdr, long long hdr_stride,
-                              const int* d_hdr_len, int hdr_len_all, const int* d_pt_len,
-                              unsigned char* d_pkt, long long pkt_stride, int* d_pkt_len,
-                              int* d_status, void* stream) {
-    int rc = ragged_check(c, k, m, groups, d_bb, d_data, d_data_off, d_parity, d_par_off);
+// v: the data (in_off) and the parity (out_off)
+static int seal_groups_ragged(qfec_ctx* c, int k, int m, long long groups, RaggedView v,
+                              const unsigned char* d_data, unsigned char* d_parity, bool encode,
+                              Rows hdr, const int* d_pt_len, RowsOut pkt, int* d_status,
+                              void* stream) {
+    int rc = ragged_check(c, k, m, groups, v.bb, d_data, v.in_off, d_parity, v.out_off);
     if (rc) return rc;
-    if ((rc = seal_ragged_pkt_args(k, m, d_hdr, hdr_stride, d_hdr_len, hdr_len_all, d_pkt,
-                                   pkt_stride, d_pkt_len)))
-        return rc;
+    if ((rc = seal_ragged_pkt_args(k, m, hdr, pkt))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     const hipStream_t st = pick(c, stream);
-    if (encode && (rc = encode_ragged_impl(c, k, m, groups,
-                                           {(const int32_t*)d_bb, d_data_off, d_par_off}, d_data,
-                                           d_parity, (int32_t*)d_status, st)))
+    if (encode &&
+        (rc = encode_ragged_impl(c, k, m, groups, v, d_data, d_parity, (int32_t*)d_status, st)))
         return rc;
-    QF_HIP(qfec::launch_null_seal_groups_ragged(
-        k, m, groups, (const int32_t*)d_bb, d_data, d_data_off, d_parity, d_par_off, encode, d_hdr,
-        hdr_stride, (const int32_t*)d_hdr_len, hdr_len_all, (const int32_t*)d_pt_len, d_pkt,
-        pkt_stride, (int32_t*)d_pkt_len, st));
+    QF_HIP(qfec::launch_null_seal_groups_ragged(k, m, groups, v, d_data, d_parity, encode, hdr,
+                                                (const int32_t*)d_pt_len, pkt, st));
     return 0;
 }
 
@@ -919,10 +889,10 @@ int qfec_seal_groups_batch_ragged(qfec_ctx* c, int k, int m, long long groups, c
                                   const int* d_hdr_len, int hdr_len_all, const int* d_pt_len,
                                   unsigned char* d_pkt, long long pkt_stride, int* d_pkt_len,
                                   void* stream) {
-    return seal_groups_ragged(c, k, m, groups, d_bb, d_data, d_data_off,
-                              (unsigned char*)d_parity, d_par_off, false, d_hdr, hdr_stride,
-                              d_hdr_len, hdr_len_all, d_pt_len, d_pkt, pkt_stride, d_pkt_len,
-                              nullptr, stream);
+    return seal_groups_ragged(c, k, m, groups, {(const int32_t*)d_bb, d_data_off, d_par_off},
+                              d_data, (unsigned char*)d_parity, false,
+                              rows_of(d_hdr, hdr_stride, d_hdr_len, hdr_len_all), d_pt_len,
+                              rows_out_of(d_pkt, pkt_stride, d_pkt_len), nullptr, stream);
 }
 
 int qfec_encode_seal_groups_batch_ragged(qfec_ctx* c, int k, int m, long long groups,
@@ -933,25 +903,22 @@ int qfec_encode_seal_groups_batch_ragged(qfec_ctx* c, int k, int m, long long gr
                                          int hdr_len_all, const int* d_pt_len,
                                          unsigned char* d_pkt, long long pkt_stride,
                                          int* d_pkt_len, int* d_status, void* stream) {
-    return seal_groups_ragged(c, k, m, groups, d_bb, d_data, d_data_off, d_parity, d_par_off, true,
-                              d_hdr, hdr_stride, d_hdr_len, hdr_len_all, d_pt_len, d_pkt,
-                              pkt_stride, d_pkt_len, d_status, stream);
+    return seal_groups_ragged(c, k, m, groups, {(const int32_t*)d_bb, d_data_off, d_par_off},
+                              d_data, d_parity, true,
+                              rows_of(d_hdr, hdr_stride, d_hdr_len, hdr_len_all), d_pt_len,
+                              rows_out_of(d_pkt, pkt_stride, d_pkt_len), d_status, stream);
 }
 
 // open_decode_impl over the packed layout.  The caller holds the workspace bracket.
 extern "C++" int qfec::open_decode_ragged_impl(qfec_ctx* c, int k, int m, long long groups,
-                                               const int32_t* d_bb, const uint8_t* d_pkt,
-                                               long long pkt_stride, const int32_t* d_pkt_len,
-                                               const int32_t* d_ad_len, int ad_len_all,
-                                               uint8_t* d_blocks, const long long* d_blocks_off,
+                                               RaggedView v, Rows pkt, Rows ad, uint8_t* d_blocks,
                                                uint8_t* d_rows, int32_t* d_open_len, uint8_t* d_rec,
-                                               const long long* d_rec_off, uint8_t* d_rec_rows,
-                                               int32_t* d_status, hipStream_t st) {
-    QF_HIP(qfec::launch_open_groups_ragged(k, m, groups, d_bb, d_pkt, pkt_stride, d_pkt_len,
-                                           d_ad_len, ad_len_all, d_blocks, d_blocks_off, d_rows,
-                                           d_open_len, st));
-    int rc = decode_ragged_impl(c, k, m, groups, {d_bb, d_blocks_off, d_rec_off}, d_blocks, d_rows,
-                                d_rec, d_rec_rows, d_status, st);
+                                               uint8_t* d_rec_rows, int32_t* d_status,
+                                               hipStream_t st) {
+    QF_HIP(qfec::launch_open_groups_ragged(k, m, groups, v, pkt, ad, d_blocks, d_rows, d_open_len,
+                                           st));
+    int rc = decode_ragged_impl(c, k, m, groups, v, d_blocks, d_rows, d_rec, d_rec_rows, d_status,
+                                st);
     if (rc) return rc;
     QF_HIP(qfec::launch_open_status(k, std::min(k, m), groups, d_rows, d_rec_rows, d_status, st));
     return 0;
@@ -975,10 +942,11 @@ int qfec_open_decode_batch_ragged(qfec_ctx* c, int k, int m, long long groups, c
     if (groups == 0) return 0;
     const hipStream_t st = pick(c, stream);
     return with_workspace(c, st, [&] {
-        return open_decode_ragged_impl(c, k, m, groups, (const int32_t*)d_bb, d_pkt, pkt_stride,
-                                       (const int32_t*)d_pkt_len, (const int32_t*)d_ad_len,
-                                       ad_len_all, d_blocks, d_blocks_off, d_rows,
-                                       (int32_t*)d_open_len, d_rec, d_rec_off, d_rec_rows,
+        return open_decode_ragged_impl(c, k, m, groups,
+                                       {(const int32_t*)d_bb, d_blocks_off, d_rec_off},
+                                       rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
+                                       rows_of(nullptr, 0, d_ad_len, ad_len_all), d_blocks, d_rows,
+                                       (int32_t*)d_open_len, d_rec, d_rec_rows,
                                        (int32_t*)d_status, st);
     });
 }

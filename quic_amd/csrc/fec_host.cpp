@@ -174,8 +174,9 @@ int qfec_encode_seal_groups_batch_host(qfec_ctx* c, int k, int m, int bb, long l
                                        int hdr_len_all, const int* h_pt_len, int pt_len_all,
                                        unsigned char* h_pkt, long long pkt_stride,
                                        int* h_pkt_len) {
-    int rc = seal_groups_args(c, k, m, bb, groups, {h_data, h_pkt, h_pkt_len}, h_hdr, hdr_stride,
-                              h_hdr_len, hdr_len_all, h_pt_len, pt_len_all, h_pkt, pkt_stride);
+    int rc = seal_groups_args(c, k, m, bb, groups, {h_data, h_pkt, h_pkt_len},
+                              rows_of(h_hdr, hdr_stride, h_hdr_len, hdr_len_all), h_pt_len,
+                              pt_len_all, rows_out_of(h_pkt, pkt_stride, h_pkt_len));
     if (rc) return rc;
     if (groups == 0) return 0;
     if (hdr_stride <= 0 && h_hdr) return fail(-2, "host headers need a row stride > 0");
@@ -203,10 +204,11 @@ int qfec_encode_seal_groups_batch_host(qfec_ctx* c, int k, int m, int bb, long l
         // a row past its packet are zeros (as the device path leaves them untouched), not
         // an earlier chunk's packets
         QF_HIP(hipMemsetAsync(dk.dev, 0, dk.bytes, c->stream));
-        QF_HIP(launch_null_seal_groups(k, m, bb, n, dd.dev, dp.dev, dh.dev,
-                                       dh.dev ? hdr_stride : 0, dhl.as<int32_t>(),
-                                       dh.dev ? hdr_len_all : 0, dpl.as<int32_t>(), pt_len_all,
-                                       dk.dev, pkt_stride, dkl.as<int32_t>(), c->stream));
+        const Rows hdr{dh.dev, dh.dev ? hdr_stride : 0, dhl.as<int32_t>(),
+                       dh.dev ? hdr_len_all : 0};
+        QF_HIP(launch_null_seal_groups(k, m, bb, n, dd.dev, dp.dev, hdr, dpl.as<int32_t>(),
+                                       pt_len_all, {dk.dev, pkt_stride, dkl.as<int32_t>()},
+                                       c->stream));
         return 0;
     });
 }
@@ -241,9 +243,10 @@ int qfec_open_decode_batch_host(qfec_ctx* c, int k, int m, int bb, long long gro
     Stage& drr = L.dense(rmax).out(h_rec_rows);
     Stage& ds = L.dense(sizeof(int32_t)).out(h_status);
     return host_pipeline_uniform(c, L, groups, [&](long long n) {
-        return open_decode_impl(c, k, m, bb, n, dk.dev, pkt_stride, dkl.as<int>(), dal.as<int>(),
-                                ad_len_all, db.dev, dr.dev, dol.as<int>(), dre.dev, drr.dev,
-                                ds.as<int>(), c->stream);
+        return open_decode_impl(c, k, m, bb, n, {dk.dev, pkt_stride, dkl.as<int32_t>(), 0},
+                                {nullptr, 0, dal.as<int32_t>(), ad_len_all}, db.dev, dr.dev,
+                                dol.as<int32_t>(), {dre.dev, drr.dev, true}, ds.as<int32_t>(),
+                                c->stream);
     });
 }
 
@@ -355,8 +358,8 @@ int qfec_encode_seal_groups_batch_ragged_host(qfec_ctx* c, int k, int m, long lo
     if (rc) return rc;
     // (host data is staged, so its own alignment does not matter)
     if (!h_bb || !h_data || !h_data_off) return fail(-2, "null buffer");
-    if ((rc = seal_ragged_pkt_args(k, m, h_hdr, hdr_stride, h_hdr_len, hdr_len_all, h_pkt,
-                                   pkt_stride, h_pkt_len)))
+    if ((rc = seal_ragged_pkt_args(k, m, rows_of(h_hdr, hdr_stride, h_hdr_len, hdr_len_all),
+                                   rows_out_of(h_pkt, pkt_stride, h_pkt_len))))
         return rc;
     if (groups == 0) return 0;
     if (hdr_stride <= 0 && h_hdr) return fail(-2, "host headers need a row stride > 0");
@@ -384,10 +387,11 @@ int qfec_encode_seal_groups_batch_ragged_host(qfec_ctx* c, int k, int m, long lo
         if (r) return r;
         // rows come back whole: zeros past each packet and in rejected rows
         QF_HIP(hipMemsetAsync(dk.dev, 0, dk.bytes, c->stream));
-        QF_HIP(launch_null_seal_groups_ragged(
-            k, m, n, v.bb, dd.dev, v.in_off, dp.dev, v.out_off, true, dh.dev,
-            dh.dev ? hdr_stride : 0, dhl.as<int32_t>(), dh.dev ? hdr_len_all : 0,
-            dpl.as<int32_t>(), dk.dev, pkt_stride, dkl.as<int32_t>(), c->stream));
+        const Rows hdr{dh.dev, dh.dev ? hdr_stride : 0, dhl.as<int32_t>(),
+                       dh.dev ? hdr_len_all : 0};
+        QF_HIP(launch_null_seal_groups_ragged(k, m, n, v, dd.dev, dp.dev, true, hdr,
+                                              dpl.as<int32_t>(),
+                                              {dk.dev, pkt_stride, dkl.as<int32_t>()}, c->stream));
         return 0;
     });
 }
@@ -427,10 +431,10 @@ int qfec_open_decode_batch_ragged_host(qfec_ctx* c, int k, int m, long long grou
     Stage& dr = L.dense(k);
     Stage& drr = L.dense(rmax).out(h_rec_rows);
     return host_pipeline_ragged(c, L, groups, db, dre, rs, [&](long long n) {
-        const RaggedView v = rs.view();
-        return open_decode_ragged_impl(c, k, m, n, v.bb, dk.dev, pkt_stride, dkl.as<int32_t>(),
-                                       dal.as<int32_t>(), ad_len_all, db.dev, v.in_off, dr.dev,
-                                       dol.as<int32_t>(), dre.dev, v.out_off, drr.dev,
+        return open_decode_ragged_impl(c, k, m, n, rs.view(),
+                                       {dk.dev, pkt_stride, dkl.as<int32_t>(), 0},
+                                       {nullptr, 0, dal.as<int32_t>(), ad_len_all}, db.dev, dr.dev,
+                                       dol.as<int32_t>(), dre.dev, drr.dev,
                                        rs.status.as<int32_t>(), c->stream);
     });
 }

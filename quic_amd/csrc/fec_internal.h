@@ -131,15 +131,20 @@ inline bool any_null(std::initializer_list<const void*> ptrs) {
         if (!p) return true;
     return false;
 }
+// The C entry points build their packet arrays (Rows / RowsOut, fec_kernels.h) once, from
+// their `const int*` / `unsigned char*` arguments; nothing below them casts.
+inline Rows rows_of(const unsigned char* p, long long stride, const int* len, int len_all) {
+    return {p, stride, (const int32_t*)len, len_all};
+}
+inline RowsOut rows_out_of(unsigned char* p, long long stride, int* len) {
+    return {p, stride, (int32_t*)len};
+}
 // qfec_[encode_]seal_groups_batch[_host]; `required`: the arrays this form cannot do without
 int seal_groups_args(qfec_ctx* c, int k, int m, int bb, long long groups,
-                     std::initializer_list<const void*> required, const unsigned char* hdr,
-                     long long hdr_stride, const int* hdr_len, int hdr_len_all, const int* pt_len,
-                     int pt_len_all, const unsigned char* pkt, long long pkt_stride);
+                     std::initializer_list<const void*> required, Rows hdr, const int* pt_len,
+                     int pt_len_all, RowsOut pkt);
 // the packet side of the ragged seals, after the form's own checks of the block arrays
-int seal_ragged_pkt_args(int k, int m, const unsigned char* hdr, long long hdr_stride,
-                         const int* hdr_len, int hdr_len_all, const unsigned char* pkt,
-                         long long pkt_stride, const int* pkt_len);
+int seal_ragged_pkt_args(int k, int m, Rows hdr, RowsOut pkt);
 
 // ---- the dispatch: which kernels a call runs on `st` (fec_api.cpp)
 // Where a decode writes.  Slot layout (qfec_decode_batch): recovered blocks go back into their
@@ -164,20 +169,19 @@ int encode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d
 // The decodes: the caller holds the workspace bracket (with_workspace).
 int decode_impl(qfec_ctx* c, int k, int m, int bb, long long G, const uint8_t* d_blocks,
                 const uint8_t* d_rows_in, DecodeOut o, int32_t* d_status, hipStream_t st);
-int open_decode_impl(qfec_ctx* c, int k, int m, int bb, long long groups, const uint8_t* d_pkt,
-                     long long pkt_stride, const int* d_pkt_len, const int* d_ad_len,
-                     int ad_len_all, uint8_t* d_blocks, uint8_t* d_rows, int* d_open_len,
-                     uint8_t* d_rec, uint8_t* d_rec_rows, int* d_status, hipStream_t st);
+// pkt: the wire packets; ad: their associated-data lengths; rec: the compact DecodeOut
+int open_decode_impl(qfec_ctx* c, int k, int m, int bb, long long groups, Rows pkt, Rows ad,
+                     uint8_t* d_blocks, uint8_t* d_rows, int32_t* d_open_len, DecodeOut rec,
+                     int32_t* d_status, hipStream_t st);
 int encode_ragged_impl(qfec_ctx* c, int k, int m, long long G, RaggedView v, const uint8_t* d_data,
                        uint8_t* d_par, int32_t* d_status, hipStream_t st);
 int decode_ragged_impl(qfec_ctx* c, int k, int m, long long G, RaggedView v,
                        const uint8_t* d_blocks, const uint8_t* d_rows_in, uint8_t* d_rec,
                        uint8_t* d_rec_rows, int32_t* d_status, hipStream_t st);
-int open_decode_ragged_impl(qfec_ctx* c, int k, int m, long long groups, const int32_t* d_bb,
-                            const uint8_t* d_pkt, long long pkt_stride, const int32_t* d_pkt_len,
-                            const int32_t* d_ad_len, int ad_len_all, uint8_t* d_blocks,
-                            const long long* d_blocks_off, uint8_t* d_rows, int32_t* d_open_len,
-                            uint8_t* d_rec, const long long* d_rec_off, uint8_t* d_rec_rows,
-                            int32_t* d_status, hipStream_t st);
+// v: the blocks (in_off) and the recovered blocks (out_off)
+int open_decode_ragged_impl(qfec_ctx* c, int k, int m, long long groups, RaggedView v, Rows pkt,
+                            Rows ad, uint8_t* d_blocks, uint8_t* d_rows, int32_t* d_open_len,
+                            uint8_t* d_rec, uint8_t* d_rec_rows, int32_t* d_status,
+                            hipStream_t st);
 
 }  // namespace qfec

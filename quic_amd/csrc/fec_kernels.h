@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <utility>
 
 namespace qfec {
 
@@ -89,6 +90,24 @@ inline unsigned persistent_grid(long long units, int waves, long long resident, 
     return grid;
 }
 
+// Workgroups one CU holds of a kernel that needs `lds` bytes each (160 KiB per CU), at most
+// `cap` (what the registers or the wave slots allow), at least 1.
+inline int lds_blocks_per_cu(size_t lds, int cap = 1 << 30) {
+    return std::max(1, std::min((int)((160 * 1024) / lds), cap));
+}
+
+// The ragged kernels' grid (gf_ragged.hip).  A different rule from persistent_grid on purpose:
+// oversubscribed at about two units per wave once the device is full, but never fewer
+// workgroups than the device holds (`resident`) while there are units for them, where
+// persistent_grid's wg cap replaces the resident one.
+inline unsigned ragged_grid(long long units, long long resident) {
+    const long long per_wg = 4;
+    const long long all = (units + per_wg - 1) / per_wg;
+    const long long two = (units + 2 * per_wg - 1) / (2 * per_wg);
+    const long long nb = std::max<long long>(1, std::min(all, std::max(resident, two)));
+    return (unsigned)std::min<long long>(nb, 0x7fffffffLL);
+}
+
 // Kernel timing hook (qfec_set_timing_events, per thread).  While a stop event is set, each
 // engine call records `start` at the start of its first kernel and `stop` at the end of
 // every kernel (the last record wins), through hipExtLaunchKernel: the events bracket the
@@ -149,6 +168,42 @@ struct PrepIO {
                               //   255 past the group's erasure count; null in the slot layout
     int32_t* status;          // [G] or null
     DecodeWork w;
+};
+
+// What every GF(256) apply launcher takes.  An encode leaves cenc, slots and nout null and
+// rmax, tab_gstride 0; its tab is the shared table.  A decode's tab is the prep's per-group
+// table (coefficients, or the syn:: / bsyn:: / psyn:: table) at tab + g * tab_gstride; slots
+// null: recovered blocks written densely.  The launchers hand the kernels the members as
+// scalar arguments; the struct itself is never a kernel argument.
+struct Apply {
+    const uint8_t* in;
+    uint8_t* out;
+    const uint8_t* tab;
+    const uint8_t* cenc;
+    const uint8_t* slots;
+    const int32_t* nout;
+    int k, m, bb;
+    long long groups;
+    int rc, rmax;
+    long long tab_gstride, out_gstride;
+    hipStream_t st;
+    const Tune* t;
+};
+
+// A packet array: row i at p + i * stride, len[i] bytes of it (len null: len_all for every
+// row).  Where only the lengths of a call's rows matter (the associated data of an open is the
+// head of its packet), p and stride stay null.
+struct Rows {
+    const uint8_t* p;
+    long long stride;
+    const int32_t* len;
+    int len_all;
+};
+// Its writable twin: the lengths are an output too.  p and stride must be 4-byte aligned.
+struct RowsOut {
+    uint8_t* p;
+    long long stride;
+    int32_t* len;
 };
 
 // Syndrome table (decode prep in syndrome mode, read by gf_dcol's syndrome decode), one per
@@ -227,9 +282,7 @@ hipError_t launch_rows_k1(const uint8_t* rows_in, uint8_t* rows_out, int32_t* st
 
 // Bit-sliced GF(256) apply.  Encode: coef is the shared [nchunk][k][RCP] table built
 // from the Cauchy matrix (row 0 = ones), outputs are parity rows chunk*RC + j.
-hipError_t launch_gf_encode(const uint8_t* data, uint8_t* parity, const uint8_t* coef,
-                            int k, int m, int bb, long long groups, int rc, hipStream_t st,
-                            const Tune& t);
+hipError_t launch_gf_encode(const Apply& a);
 // Its chunk (outputs per wave) for m parity rows: the power of two that holds them, capped
 // at enc_rc.
 inline int pow2_at_least(int v) {
@@ -247,15 +300,11 @@ hipError_t launch_decode_prep(const PrepIO& io, const uint8_t* cenc, int k, int 
                               const Tune& t, bool syndrome = false);
 
 // Decode apply: recovered block j of group g = sum_pos coef[g][..][pos][j] (x) blocks[g][pos],
-// written to out[g][slots[g][j]].
-hipError_t launch_gf_decode(const uint8_t* blocks, uint8_t* out, DecodeWork w, int k, int m,
-                            int bb, long long groups, int rc, int rmax, hipStream_t st,
-                            const Tune& t);
+// written to out[g][slots[g][j]], or densely (slots null: out is [G][rmax][bb]).
+hipError_t launch_gf_decode(const Apply& a);
 
-// In-place decode when rmax > rc: apply into scratch [G][rmax][bb], then scatter to slots.
-hipError_t launch_gf_decode_scratch(const uint8_t* blocks, uint8_t* scratch, DecodeWork w,
-                                   int k, int m, int bb, long long groups, int rc, int rmax,
-                                   hipStream_t st, const Tune& t);
+// In-place decode when rmax > rc: the dense apply into scratch [G][rmax][bb], then this
+// scatter to the slots.
 hipError_t launch_scatter_recovered(const uint8_t* scratch, uint8_t* out, DecodeWork w, int k,
                                    int bb, int rmax, long long groups, hipStream_t st);
 
@@ -271,7 +320,7 @@ hipError_t launch_xor_dma(const uint8_t* in, uint8_t* out, const uint8_t* eidx,
 // Per-wave LDS-ring streaming kernels (gf_stream.hip), bb a multiple of 8 up to 2048, `in`
 // 16-byte aligned.  Encode (decode false): the m parity rows of each group; the codes of
 // compiled_codes.h run compiled (gf_ring_kernel, or gf_stream_kernel<encode,compiled>) and read
-// no table, every other code reads coef, the shared table built for rc = stream_encode_rc().
+// no table, every other code reads tab, the shared table built for rc = stream_encode_rc().
 // Decode: up to rmax recovered blocks per group in chunks of rc (2, 4, 8) from the prep's
 // per-group tables, through slots (slot layout) or densely (slots null).
 bool gf_stream_supported(int k, int bb, int rc, const Tune& t);
@@ -279,34 +328,21 @@ bool gf_stream_supported(int k, int bb, int rc, const Tune& t);
 // one unit (m <= 8: one unit of m outputs; more than 16: chunks of 8; compiled codes read no
 // table).  aligned: the data pointer is 16-byte aligned (otherwise gf_apply encodes).
 int stream_encode_rc(int k, int m, int bb, bool aligned, const Tune& t);
-hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef,
-                            const uint8_t* slots, const int32_t* nout, int k, int m, int bb,
-                            long long groups, int rc, int rmax, long long coef_gstride,
-                            long long out_gstride, bool decode, hipStream_t st,
-                            const Tune& t);
+hipError_t launch_gf_stream(const Apply& a, bool decode);
 
 
 // One wave per column tile computing all 16 rows (gf_dcol.hip): encode of the compiled
 // (128, 16) x 9008-byte code, and its syndrome decode from the syn:: table.
 bool gf_dcol_supported(int k, int m, int bb, const Tune& t);
-hipError_t launch_gf_dcol_encode(const uint8_t* in, uint8_t* out, int k, int m, int bb,
-                                 long long groups, long long out_gstride, hipStream_t st,
-                                 const Tune& t);
-hipError_t launch_gf_dcol_syndrome(const uint8_t* in, uint8_t* out, const uint8_t* tab,
-                                   const uint8_t* slots, const int32_t* nout,
-                                   const uint8_t* cenc, int k, int m, int bb, long long groups,
-                                   int rmax, long long tab_gstride, long long out_gstride,
-                                   hipStream_t st, const Tune& t);
+hipError_t launch_gf_dcol_encode(const Apply& a);
+hipError_t launch_gf_dcol_syndrome(const Apply& a);
 
 // Syndrome decode of the Syn::bsyn code of compiled_codes.h, (32, 4) x 1352 bytes: prep (bsyn:: table, one lane per
 // group; reads the row tags as dwords) and the block pass + r x r solve (gf_bsyn.hip).
 bool gf_bsyn_supported(int k, int m, int bb, int rmax, const Tune& t);
 hipError_t launch_decode_prep_bsyn(const PrepIO& io, const uint8_t* cenc, int k, int m, int bb,
                                    int rmax, long long groups, hipStream_t st);
-hipError_t launch_gf_bsyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
-                          const uint8_t* cenc, const uint8_t* slots, const int32_t* nout, int k,
-                          int m, int bb, long long groups, int rmax, long long out_gstride,
-                          hipStream_t st, const Tune& t);
+hipError_t launch_gf_bsyn(const Apply& a);
 
 // Syndrome decode of the Syn::psyn codes of compiled_codes.h (QuicR presets at 1352-byte
 // blocks): prep (psyn:: table, 16 lanes per group) and the block pass + in-place Gauss-Jordan
@@ -314,10 +350,7 @@ hipError_t launch_gf_bsyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
 bool gf_psyn_supported(int k, int m, int bb, int rmax, const Tune& t);
 hipError_t launch_decode_prep_psyn(const PrepIO& io, const uint8_t* cenc, int k, int m, int bb,
                                    int rmax, long long groups, hipStream_t st);
-hipError_t launch_gf_psyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
-                          const uint8_t* cenc, const uint8_t* slots, const int32_t* nout, int k,
-                          int m, int bb, long long groups, int rmax, long long out_gstride,
-                          hipStream_t st, const Tune& t);
+hipError_t launch_gf_psyn(const Apply& a);
 
 // Ragged batches (gf_ragged.hip): the groups share (k, m), each has its own block size.
 // Group g's input blocks are [k][bb[g]] at in + in_off[g] and its outputs [n][bb[g]] at
@@ -337,11 +370,8 @@ struct RaggedView {
 };
 // m > 1, the groups with bb % 8 == 0 (the others are skipped).  Encode: coef is the shared
 // [nchunk][k][max(rc, 4)] table; decode: the prep's per-group tables, outputs o < nout[g] in
-// the recovered-blocks layout.  rc 2 or 4.
-hipError_t launch_gf_ragged(const uint8_t* in, uint8_t* out, RaggedView v, const uint8_t* coef,
-                            const int32_t* nout, int k, int m, long long groups, int rc,
-                            int nchunk, long long coef_gstride, bool decode, hipStream_t st,
-                            const Tune& t);
+// the recovered-blocks layout.  rc 2 or 4; a.bb, a.cenc, a.slots and a.out_gstride are not read.
+hipError_t launch_gf_ragged(const Apply& a, RaggedView v, int nchunk, bool decode);
 // XOR of each group's k blocks.  Encode modes: 0 every group, status 0; 1 every group, status
 // -1; 2 only the groups with bb % 8 != 0 (status -1, the rest 0).  Decode: the recovered block
 // of the groups with eidx[g] != 255 (m1_prep_kernel's erased slot).
@@ -365,17 +395,5 @@ hipError_t launch_synth_fill(uint8_t* dst, unsigned long long bytes, unsigned lo
 hipError_t launch_synth_gather(const uint8_t* data, const uint8_t* parity, const int16_t* src,
                                uint8_t* blocks, int k, int m, int bb, long long groups,
                                hipStream_t st);
-
-// Packet protection (pp_null.hip): NullEncrypter seal / NullDecrypter open over n packets.
-// Per-packet lengths come from the arrays, or from the `_all` scalar when an array is null.
-// out and out_stride must be 4-byte aligned.
-hipError_t launch_null_seal(long long n, const uint8_t* ad, long long ad_stride,
-                            const int32_t* ad_len, int ad_all, const uint8_t* pt,
-                            long long pt_stride, const int32_t* pt_len, int pt_all, uint8_t* out,
-                            long long out_stride, int32_t* out_len, hipStream_t st);
-hipError_t launch_null_open(long long n, const uint8_t* pkt, long long pkt_stride,
-                            const int32_t* pkt_len, int pkt_all, const int32_t* ad_len,
-                            int ad_all, uint8_t* out, long long out_stride, int32_t* out_len,
-                            hipStream_t st);
 
 }  // namespace qfec

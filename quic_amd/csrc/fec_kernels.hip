@@ -107,15 +107,6 @@ __global__ __launch_bounds__(256) void xor_flat_kernel(
     }
 }
 
-#define QF_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define QF_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    static_assert(N >= 0 && N <= 63, "vmcnt is 6 bits on gfx9");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // Tiny blocks (bb < 4): one byte per lane.
 template <bool DECODE>
 __global__ __launch_bounds__(256) void xor_bytes_kernel(
@@ -461,11 +452,7 @@ hipError_t launch_xor_decode(const uint8_t* blocks, uint8_t* out, const uint8_t*
         // single launch: the DMA kernel also does the erased-slot / missing-row bookkeeping
         return launch_xor_dma(blocks, out, nullptr, rows_in, rows_out, status, k, bb, groups, ogs,
                               true, st, t, compact);
-    note_kernel("m1_prep_kernel");
-    qlaunch((m1_prep_kernel), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, rows_in, rows_out, status,
-                                                                     eidx, k, groups,
-                                                                     compact ? 1 : 0);
-    hipError_t e = hipGetLastError();
+    const hipError_t e = launch_m1_prep(rows_in, rows_out, status, eidx, k, groups, compact, st);
     if (e != hipSuccess) return e;
     return xor_any<true>(blocks, out, eidx, k, bb, groups, gb, ogs, st, t, compact ? 0 : bb);
 }
@@ -509,12 +496,12 @@ hipError_t launch_rows_k1(const uint8_t* rows_in, uint8_t* rows_out, int32_t* st
     return hipGetLastError();
 }
 
+// nchunk: the chunks of rc outputs (encode: of m, decode: of rmax)
 template <bool DECODE>
-static hipError_t gf_apply_dispatch(const uint8_t* in, uint8_t* out, const uint8_t* coef,
-                                    const uint8_t* slots, const int32_t* nout, int k, int m,
-                                    int bb, long long groups, int rc, int nchunk, int rmax,
-                                    long long coef_gstride, long long out_gstride,
-                                    hipStream_t st, const Tune& t) {
+static hipError_t gf_apply_dispatch(const Apply& a, int nchunk) {
+    const Tune& t = *a.t;
+    const int bb = a.bb, rc = a.rc;
+    const long long groups = a.groups;
     const int s = bb / 8;
     const int nw = (s + 3) / 4;
     const int ntiles = (nw + 63) / 64;
@@ -531,8 +518,8 @@ static hipError_t gf_apply_dispatch(const uint8_t* in, uint8_t* out, const uint8
     note_kernel(DECODE ? "gf_apply_kernel<decode>"
                        : (flat ? "gf_apply_kernel<encode,flat>" : "gf_apply_kernel<encode>"));
     const auto go = [&](auto kern) {
-        qlaunch(kern, dim3(nb), dim3(nthr), 0, st, in, out, coef, slots, nout, k, m, bb, nw, ntiles,
-                nchunk, rmax, coef_gstride, out_gstride, tu, flat_lanes);
+        qlaunch(kern, dim3(nb), dim3(nthr), 0, a.st, a.in, a.out, a.tab, a.slots, a.nout, a.k, a.m,
+                bb, nw, ntiles, nchunk, a.rmax, a.tab_gstride, a.out_gstride, tu, flat_lanes);
     };
     const bool known = dispatch_value<1, 2, 4, 8, 16>(rc, [&](auto RC) {
         constexpr int rcv = decltype(RC)::value;
@@ -550,22 +537,12 @@ static hipError_t gf_apply_dispatch(const uint8_t* in, uint8_t* out, const uint8
     return hipGetLastError();
 }
 
-hipError_t launch_gf_encode(const uint8_t* data, uint8_t* parity, const uint8_t* coef, int k,
-                            int m, int bb, long long groups, int rc, hipStream_t st,
-                            const Tune& t) {
-    const int nchunk = (m + rc - 1) / rc;
-    return gf_apply_dispatch<false>(data, parity, coef, nullptr, nullptr, k, m, bb, groups, rc,
-                                    nchunk, 0, 0, (long long)m * bb, st, t);
+hipError_t launch_gf_encode(const Apply& a) {
+    return gf_apply_dispatch<false>(a, (a.m + a.rc - 1) / a.rc);
 }
 
-hipError_t launch_gf_decode(const uint8_t* blocks, uint8_t* out, DecodeWork w, int k, int m,
-                            int bb, long long groups, int rc, int rmax, hipStream_t st,
-                            const Tune& t) {
-    const int nchunk = (rmax + rc - 1) / rc;
-    const int rcp = rc < 4 ? 4 : rc;
-    return gf_apply_dispatch<true>(blocks, out, w.coef, w.slots, w.nout, k, m, bb, groups, rc,
-                                   nchunk, rmax, (long long)nchunk * k * rcp,
-                                   (long long)k * bb, st, t);
+hipError_t launch_gf_decode(const Apply& a) {
+    return gf_apply_dispatch<true>(a, (a.rmax + a.rc - 1) / a.rc);
 }
 
 hipError_t launch_scatter_recovered(const uint8_t* scratch, uint8_t* out, DecodeWork w, int k,
@@ -577,16 +554,6 @@ hipError_t launch_scatter_recovered(const uint8_t* scratch, uint8_t* out, Decode
                                                                       w.nout, k, bb, rmax,
                                                                       units);
     return hipGetLastError();
-}
-
-hipError_t launch_gf_decode_scratch(const uint8_t* blocks, uint8_t* scratch, DecodeWork w,
-                                   int k, int m, int bb, long long groups, int rc, int rmax,
-                                   hipStream_t st, const Tune& t) {
-    const int nchunk = (rmax + rc - 1) / rc;
-    const int rcp = rc < 4 ? 4 : rc;
-    return gf_apply_dispatch<true>(blocks, scratch, w.coef, nullptr, w.nout, k, m, bb, groups,
-                                   rc, nchunk, rmax, (long long)nchunk * k * rcp,
-                                   (long long)rmax * bb, st, t);
 }
 
 hipError_t launch_synth_fill(uint8_t* dst, unsigned long long bytes, unsigned long long seed,

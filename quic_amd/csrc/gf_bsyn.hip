@@ -289,24 +289,24 @@ bool gf_bsyn_supported(int k, int m, int bb, int rmax, const Tune& t) {
     return t.bsyn && t.const_enc && rmax <= kBsynRC && find_code(k, m, bb, Syn::bsyn);
 }
 
-hipError_t launch_gf_bsyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
-                          const uint8_t* cenc, const uint8_t* slots, const int32_t* nout, int k,
-                          int m, int bb, long long groups, int rmax, long long out_gstride,
-                          hipStream_t st, const Tune& t) {
-    if (groups <= 0) return hipSuccess;
-    if (!gf_bsyn_supported(k, m, bb, rmax, t)) return hipErrorInvalidValue;
-    if ((((uintptr_t)in) & 15) || ((((uintptr_t)tab) | (uintptr_t)cenc | (uintptr_t)slots) & 3))
+hipError_t launch_gf_bsyn(const Apply& a) {
+    const Tune& t = *a.t;
+    const int k = a.k, m = a.m;
+    if (a.groups <= 0) return hipSuccess;
+    if (!gf_bsyn_supported(k, m, a.bb, a.rmax, t)) return hipErrorInvalidValue;
+    if ((((uintptr_t)a.in) & 15) ||
+        ((((uintptr_t)a.tab) | (uintptr_t)a.cenc | (uintptr_t)a.slots) & 3))
         return hipErrorInvalidValue;
     using SH = SubrowShape<kBsynS>;
     const int D = t.bsyn_depth;
     if (D != 3 && D != 5 && D != 7) return hipErrorInvalidValue;
     const size_t lds = (size_t)kBsynWaves * (D + 1) * SH::BUFB;
-    const int per_cu = std::max(1, std::min((int)((160 * 1024) / lds), 20 / kBsynWaves));
+    const int per_cu = lds_blocks_per_cu(lds, 20 / kBsynWaves);
     // oversubscribed: about bwg groups per wave (B decode 0.60-0.61 -> 0.53-0.60 ms, DESIGN.md
     // section 4.5)
     const int bwg = t.bsyn_wg >= 0 ? t.bsyn_wg : 2;
     const unsigned grid =
-        persistent_grid(groups, kBsynWaves, (long long)t.cus * per_cu, bwg, t.stream_grid, k);
+        persistent_grid(a.groups, kBsynWaves, (long long)t.cus * per_cu, bwg, t.stream_grid, k);
     if (!grid) return hipErrorInvalidValue;
     note_kernel("gf_bsyn_kernel<decode,k32m4>");
     // recovered blocks stored non-temporal (B decode 0.655 -> 0.631 ms)
@@ -315,8 +315,8 @@ hipError_t launch_gf_bsyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
         if constexpr (c.syn == Syn::bsyn)
             dispatch_value<3, 5, 7>(D, [&](auto DV) {
                 qlaunch((gf_bsyn_kernel<c.k, c.m, kBsynS, decltype(DV)::value, true>), dim3(grid),
-                        dim3(kBsynWaves * 64), lds, st, in, out, tab, cenc, slots, nout, groups,
-                        rmax, out_gstride);
+                        dim3(kBsynWaves * 64), lds, a.st, a.in, a.out, a.tab, a.cenc, a.slots,
+                        a.nout, a.groups, a.rmax, a.out_gstride);
             });
     });
     return hipGetLastError();

@@ -16,6 +16,7 @@
 
 namespace qfec {
 
+#define QF_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
 #define QF_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 template <int N>

@@ -489,21 +489,20 @@ constexpr int kDcolS = 1126;   // bb = 9008: 9000-byte payloads (BASELINE config
 
 // One instantiation of gf_dcol_kernel per translation unit (gf_dcol_<e|d><D><C>.hip): each
 // takes minutes to compile, and separate objects build in parallel.
-#define QD_LAUNCH_ARGS                                                                          \
-    dim3 grid, size_t lds, hipStream_t st, const uint8_t *in, uint8_t *out, const uint8_t *tab, \
-        const uint8_t *slots, const int32_t *nout, const uint8_t *cenc, long long groups,       \
-        int rmax, long long in_bytes, long long tab_gstride, long long out_gstride
-hipError_t dcol_go_e63(QD_LAUNCH_ARGS);
-hipError_t dcol_go_e83(QD_LAUNCH_ARGS);
-hipError_t dcol_go_d62(QD_LAUNCH_ARGS);
-hipError_t dcol_go_d82(QD_LAUNCH_ARGS);
-
-#define QD_DEFINE_GO(NAME, DV, DEC, C, ...)                                                     \
-    hipError_t NAME(QD_LAUNCH_ARGS) {                                                           \
-        qlaunch((gf_dcol_kernel<kDcolS, DV, DEC, C, ##__VA_ARGS__>), grid, dim3(kDcWaves * 64),  \
-                lds, st, in,                                                                    \
-                out, tab, slots, nout, cenc, groups, rmax, in_bytes, tab_gstride, out_gstride); \
-        return hipGetLastError();                                                               \
-    }
+// Each is declared here and instantiated there, so no other object compiles a gf_dcol_kernel.
+// The encode reads no table: its kernel gets null pointers, whatever the block carries.
+template <int D, bool DECODE, int CACHE>
+hipError_t dcol_go(const Apply& a, unsigned grid, size_t lds) {
+    const uint8_t* const none = nullptr;
+    qlaunch((gf_dcol_kernel<kDcolS, D, DECODE, CACHE>), dim3(grid), dim3(kDcWaves * 64), lds, a.st,
+            a.in, a.out, DECODE ? a.tab : none, DECODE ? a.slots : none,
+            DECODE ? a.nout : nullptr, DECODE ? a.cenc : none, a.groups, DECODE ? a.rmax : 0,
+            a.groups * (long long)a.k * a.bb, DECODE ? a.tab_gstride : 0LL, a.out_gstride);
+    return hipGetLastError();
+}
+extern template hipError_t dcol_go<6, false, 3>(const Apply&, unsigned, size_t);
+extern template hipError_t dcol_go<8, false, 3>(const Apply&, unsigned, size_t);
+extern template hipError_t dcol_go<6, true, 2>(const Apply&, unsigned, size_t);
+extern template hipError_t dcol_go<8, true, 2>(const Apply&, unsigned, size_t);
 
 }  // namespace qfec

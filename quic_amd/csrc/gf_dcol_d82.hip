@@ -3,5 +3,5 @@
 #include "gf_dcol.h"
 
 namespace qfec {
-QD_DEFINE_GO(dcol_go_d82, 8, true, 2)
+template hipError_t dcol_go<8, true, 2>(const Apply&, unsigned, size_t);
 }  // namespace qfec

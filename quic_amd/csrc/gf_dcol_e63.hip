@@ -3,5 +3,5 @@
 #include "gf_dcol.h"
 
 namespace qfec {
-QD_DEFINE_GO(dcol_go_e63, 6, false, 3)
+template hipError_t dcol_go<6, false, 3>(const Apply&, unsigned, size_t);
 }  // namespace qfec

@@ -327,13 +327,6 @@ __global__ __launch_bounds__(kPsynWaves * 64) void gf_psyn_kernel(
 
 constexpr int kPsynS = kCompiledS;   // bb = 1352: 1350-byte payloads
 
-// launch arguments of one preset code's variants (gf_psyn_<k><m>.hip)
-struct PsynLaunch {
-    const uint8_t *in; uint8_t *out; const uint8_t *tab, *cenc, *slots; const int32_t *nout;
-    long long groups; int rmax; long long out_gstride; hipStream_t st; const Tune *t;
-    int k; size_t lds; bool wide;
-};
-
 // One code's kernel: ring depth 5, no register prefetch, solve products by nibble jumps,
 // non-temporal stores (the other variants measured slower, 3.7).
 // The grid is the workgroups one CU holds at once (the runtime's occupancy answer for this
@@ -341,25 +334,25 @@ struct PsynLaunch {
 // Each Syn::psyn row of compiled_codes.h has its instantiation in its own object
 // (gf_psyn_<k><m>.hip), declared here, so no other object compiles a gf_psyn_kernel.
 template <int K, int M>
-hipError_t psyn_go(const PsynLaunch& a) {
+hipError_t psyn_go(const Apply& a, size_t lds, bool wide) {
     const Tune& t = *a.t;
     constexpr int RC = K < M ? K : M;
-    const auto kern = a.wide ? gf_psyn_kernel<K, M, RC, kPsynS, 5, true>
-                             : gf_psyn_kernel<K, M, RC, kPsynS, 5, false>;
+    const auto kern = wide ? gf_psyn_kernel<K, M, RC, kPsynS, 5, true>
+                           : gf_psyn_kernel<K, M, RC, kPsynS, 5, false>;
     const unsigned grid = persistent_grid(
         a.groups, kPsynWaves,
-        (long long)t.cus * resident_blocks((const void*)kern, kPsynWaves * 64, a.lds), t.psyn_wg,
+        (long long)t.cus * resident_blocks((const void*)kern, kPsynWaves * 64, lds), t.psyn_wg,
         t.stream_grid, a.k);
     if (!grid) return hipErrorInvalidValue;
     note_grid("gf_psyn_kernel", grid);
-    qlaunch(kern, dim3(grid), dim3(kPsynWaves * 64), a.lds, a.st, a.in, a.out, a.tab, a.cenc,
+    qlaunch(kern, dim3(grid), dim3(kPsynWaves * 64), lds, a.st, a.in, a.out, a.tab, a.cenc,
             a.slots, a.nout, a.groups, a.rmax, a.out_gstride);
     return hipGetLastError();
 }
-extern template hipError_t psyn_go<5, 5>(const PsynLaunch&);
-extern template hipError_t psyn_go<10, 10>(const PsynLaunch&);
-extern template hipError_t psyn_go<10, 15>(const PsynLaunch&);
-extern template hipError_t psyn_go<10, 20>(const PsynLaunch&);
-extern template hipError_t psyn_go<15, 15>(const PsynLaunch&);
+extern template hipError_t psyn_go<5, 5>(const Apply&, size_t, bool);
+extern template hipError_t psyn_go<10, 10>(const Apply&, size_t, bool);
+extern template hipError_t psyn_go<10, 15>(const Apply&, size_t, bool);
+extern template hipError_t psyn_go<10, 20>(const Apply&, size_t, bool);
+extern template hipError_t psyn_go<15, 15>(const Apply&, size_t, bool);
 
 }  // namespace qfec

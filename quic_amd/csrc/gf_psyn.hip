@@ -55,30 +55,26 @@ bool gf_psyn_supported(int k, int m, int bb, int rmax, const Tune& t) {
     return t.psyn && t.const_enc && rmax <= 16 && find_code(k, m, bb, Syn::psyn);
 }
 
-hipError_t launch_gf_psyn(const uint8_t* in, uint8_t* out, const uint8_t* tab,
-                          const uint8_t* cenc, const uint8_t* slots, const int32_t* nout, int k,
-                          int m, int bb, long long groups, int rmax, long long out_gstride,
-                          hipStream_t st, const Tune& t) {
-    if (groups <= 0) return hipSuccess;
-    if (!gf_psyn_supported(k, m, bb, rmax, t)) return hipErrorInvalidValue;
-    if ((((uintptr_t)in) & 15) || ((((uintptr_t)tab) | (uintptr_t)cenc | (uintptr_t)slots) & 3))
+hipError_t launch_gf_psyn(const Apply& a) {
+    const Tune& t = *a.t;
+    if (a.groups <= 0) return hipSuccess;
+    if (!gf_psyn_supported(a.k, a.m, a.bb, a.rmax, t)) return hipErrorInvalidValue;
+    if ((((uintptr_t)a.in) & 15) ||
+        ((((uintptr_t)a.tab) | (uintptr_t)a.cenc | (uintptr_t)a.slots) & 3))
         return hipErrorInvalidValue;
     using SH = SubrowShape<kPsynS>;
-    PsynLaunch a;
-    a.in = in, a.out = out, a.tab = tab, a.cenc = cenc, a.slots = slots, a.nout = nout;
-    a.groups = groups, a.rmax = rmax, a.out_gstride = out_gstride, a.st = st, a.t = &t, a.k = k;
     // wide recovered-block stores: measured faster for (10, 10) (0.370-0.382 -> 0.348-0.356
     // ms) and (5, 5) (0.185 -> 0.156 ms); (15, 15) and (10, 20) unchanged, (10, 15) 0.392 ->
     // 0.410; so psyn_wide = 1 (default) takes them for the rows that say so and psyn_wide = 2
     // for every code; out 8-byte aligned
-    a.wide = (t.psyn_wide == 2 || (t.psyn_wide == 1 && find_code(k, m)->psyn_wide)) &&
-             ((((uintptr_t)out) | (uintptr_t)out_gstride) & 7) == 0;
-    a.lds = (size_t)kPsynWaves * ((5 + 1) * SH::BUFB + (a.wide ? kPsynStage : 0));   // ring depth 5
+    const bool wide = (t.psyn_wide == 2 || (t.psyn_wide == 1 && find_code(a.k, a.m)->psyn_wide)) &&
+                      ((((uintptr_t)a.out) | (uintptr_t)a.out_gstride) & 7) == 0;
+    const size_t lds = (size_t)kPsynWaves * ((5 + 1) * SH::BUFB + (wide ? kPsynStage : 0));   // ring depth 5
     note_kernel("gf_psyn_kernel<decode,preset>");
     hipError_t e = hipErrorInvalidValue;
-    with_code(k, m, [&](auto I) {
+    with_code(a.k, a.m, [&](auto I) {
         constexpr CompiledCode c = kCompiledCodes[decltype(I)::value];
-        if constexpr (c.syn == Syn::psyn) e = psyn_go<c.k, c.m>(a);
+        if constexpr (c.syn == Syn::psyn) e = psyn_go<c.k, c.m>(a, lds, wide);
     });
     return e;
 }

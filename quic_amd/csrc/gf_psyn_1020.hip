@@ -2,5 +2,5 @@
 #include "gf_psyn.h"
 
 namespace qfec {
-template hipError_t psyn_go<10, 20>(const PsynLaunch&);
+template hipError_t psyn_go<10, 20>(const Apply&, size_t, bool);
 }  // namespace qfec

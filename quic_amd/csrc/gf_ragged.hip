@@ -267,32 +267,23 @@ __global__ __launch_bounds__(256) void ragged_decode_status_kernel(
 }
 
 // ---------------------------------------------------------------------- launchers
-// Oversubscribed persistent grid: about two units per wave once the device is full, never
-// fewer workgroups than the device holds while there are units for them.
-static unsigned ragged_grid(const void* kern, int threads, long long units, const Tune& t) {
-    const long long per_wg = 4;
-    const long long all = (units + per_wg - 1) / per_wg;
-    const long long resident = (long long)t.cus * resident_blocks(kern, threads, 0);
-    const long long two = (units + 2 * per_wg - 1) / (2 * per_wg);
-    const long long nb = std::max<long long>(1, std::min(all, std::max(resident, two)));
-    return (unsigned)std::min<long long>(nb, 0x7fffffffLL);
+// ragged_grid (fec_kernels.h) against the workgroups of `kern` the device holds
+static unsigned ragged_grid_of(const void* kern, long long units, const Tune& t) {
+    return ragged_grid(units, (long long)t.cus * resident_blocks(kern, 256, 0));
 }
 
-hipError_t launch_gf_ragged(const uint8_t* in, uint8_t* out, RaggedView v, const uint8_t* coef,
-                            const int32_t* nout, int k, int m, long long groups, int rc,
-                            int nchunk, long long coef_gstride, bool decode, hipStream_t st,
-                            const Tune& t) {
-    const long long units = groups * nchunk;
+hipError_t launch_gf_ragged(const Apply& a, RaggedView v, int nchunk, bool decode) {
+    const long long units = a.groups * nchunk;
     if (units <= 0) return hipSuccess;
     if (units > 0x7fffffffLL) return hipErrorInvalidValue;
     note_kernel(decode ? "gf_ragged_kernel<decode>" : "gf_ragged_kernel<encode>");
-    const bool known = dispatch_value<2, 4>(rc, [&](auto RC) {
+    const bool known = dispatch_value<2, 4>(a.rc, [&](auto RC) {
         dispatch_bool(decode, [&](auto DEC) {
             const auto kern = gf_ragged_kernel<decltype(RC)::value, decltype(DEC)::value>;
-            const unsigned nb = ragged_grid((const void*)kern, 256, units, t);
+            const unsigned nb = ragged_grid_of((const void*)kern, units, *a.t);
             note_grid("gf_ragged_kernel", nb);
-            qlaunch(kern, dim3(nb), dim3(256), 0, st, in, v.in_off, out, v.out_off, v.bb, coef,
-                    nout, k, m, nchunk, coef_gstride, units);
+            qlaunch(kern, dim3(nb), dim3(256), 0, a.st, a.in, v.in_off, a.out, v.out_off, v.bb,
+                    a.tab, a.nout, a.k, a.m, nchunk, a.tab_gstride, units);
         });
     });
     if (!known) return hipErrorInvalidValue;
@@ -304,17 +295,13 @@ hipError_t launch_xor_ragged(const uint8_t* in, uint8_t* out, RaggedView v, cons
                              hipStream_t st, const Tune& t) {
     if (groups <= 0) return hipSuccess;
     note_kernel("xor_ragged_kernel");
-    if (decode) {
-        const unsigned nb = ragged_grid((const void*)xor_ragged_kernel<true>, 256, groups, t);
+    dispatch_bool(decode, [&](auto DEC) {
+        const auto kern = xor_ragged_kernel<decltype(DEC)::value>;
+        const unsigned nb = ragged_grid_of((const void*)kern, groups, t);
         note_grid("xor_ragged_kernel", nb);
-        qlaunch((xor_ragged_kernel<true>), dim3(nb), dim3(256), 0, st, in, v.in_off, out,
-                v.out_off, v.bb, eidx, status, k, groups, mode);
-    } else {
-        const unsigned nb = ragged_grid((const void*)xor_ragged_kernel<false>, 256, groups, t);
-        note_grid("xor_ragged_kernel", nb);
-        qlaunch((xor_ragged_kernel<false>), dim3(nb), dim3(256), 0, st, in, v.in_off, out,
-                v.out_off, v.bb, eidx, status, k, groups, mode);
-    }
+        qlaunch(kern, dim3(nb), dim3(256), 0, st, in, v.in_off, out, v.out_off, v.bb, eidx, status,
+                k, groups, mode);
+    });
     return hipGetLastError();
 }
 
@@ -322,15 +309,13 @@ hipError_t launch_copy_ragged(const uint8_t* in, uint8_t* out, RaggedView v,
                               const uint8_t* rows_in, uint8_t* rec_rows, int32_t* status, int m,
                               long long groups, bool decode, hipStream_t st, const Tune& t) {
     if (groups <= 0) return hipSuccess;
+    const unsigned nb = persistent_grid(groups, 4, (long long)t.cus * 16, 0, 0);
+    if (!nb) return hipErrorInvalidValue;
     note_kernel("copy_ragged_kernel");
-    const unsigned nb =
-        (unsigned)std::max<long long>(1, std::min<long long>((groups + 3) / 4, (long long)t.cus * 16));
-    if (decode)
-        qlaunch((copy_ragged_kernel<true>), dim3(nb), dim3(256), 0, st, in, v.in_off, out,
-                v.out_off, v.bb, rows_in, rec_rows, status, m, groups);
-    else
-        qlaunch((copy_ragged_kernel<false>), dim3(nb), dim3(256), 0, st, in, v.in_off, out,
-                v.out_off, v.bb, rows_in, rec_rows, status, m, groups);
+    dispatch_bool(decode, [&](auto DEC) {
+        qlaunch((copy_ragged_kernel<decltype(DEC)::value>), dim3(nb), dim3(256), 0, st, in,
+                v.in_off, out, v.out_off, v.bb, rows_in, rec_rows, status, m, groups);
+    });
     return hipGetLastError();
 }
 

@@ -40,8 +40,6 @@
 
 namespace qfec {
 
-#define QS_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-
 constexpr int kStreamWaves = 4;            // waves per workgroup (independent)
 constexpr int kMirror = 2;                 // mirrored slots: a block (<= 2 KiB + 3 B of
                                            // over-read) starting in the ring never wraps
@@ -452,7 +450,7 @@ __device__ __forceinline__ void gf_ring_run(const uint8_t* in, uint8_t* out, lon
             dma16<LAUX>(rs, ring + slot * 1024, p == NP - 1 ? vlast : v16);
         } else {
             const int off = min(p * 1024 + lane * 16, GBS - 16);
-            __builtin_amdgcn_global_load_lds(QS_GPTR(src + off), QF_LPTR(ring + slot * 1024), 16,
+            __builtin_amdgcn_global_load_lds(QF_GPTR(src + off), QF_LPTR(ring + slot * 1024), 16,
                                              0, LAUX);
         }
     };
@@ -657,14 +655,13 @@ int stream_encode_rc(int k, int m, int bb, bool aligned, const Tune& t) {
 }
 
 #ifndef QF_KERNELS_ONLY   // (register-use experiments compile single instantiations)
-hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef,
-                            const uint8_t* slots, const int32_t* nout, int k, int m, int bb,
-                            long long groups, int rc, int rmax, long long coef_gstride,
-                            long long out_gstride, bool decode, hipStream_t st,
-                            const Tune& t) {
+hipError_t launch_gf_stream(const Apply& a, bool decode) {
+    const Tune& t = *a.t;
+    const int k = a.k, m = a.m, bb = a.bb, rc = a.rc;
+    const long long groups = a.groups;
     if (groups <= 0) return hipSuccess;
     if (!gf_stream_supported(k, bb, rc, t)) return hipErrorInvalidValue;
-    if (((uintptr_t)in & 15) != 0 || ((uintptr_t)slots & 3) != 0) return hipErrorInvalidValue;
+    if (((uintptr_t)a.in & 15) != 0 || ((uintptr_t)a.slots & 3) != 0) return hipErrorInvalidValue;
     const int R = t.stream_ring;
     if (R < 4 || R > 36) return hipErrorInvalidValue;
     const int s = bb / 8;
@@ -672,19 +669,19 @@ hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef
     // payloads): the code is fixed at compile time and no table is read
     const CompiledCode* const code =
         !decode && t.const_enc && s == kCompiledS ? find_code(k, m) : nullptr;
-    const bool out8 = (((uintptr_t)out | (uintptr_t)out_gstride) & 7) == 0;
+    const bool out8 = (((uintptr_t)a.out | (uintptr_t)a.out_gstride) & 7) == 0;
     // wide (LDS-staged 8-byte) parity stores: measured faster only for the (5, 5) encode
     // (0.203 -> 0.180 ms; within +-5 % on the other presets)
     const bool wide_enc = code && code->stream_wide && out8;
     const size_t lds = (size_t)kStreamWaves * ((R + kMirror) * 1024 + (wide_enc ? kStreamStage : 0));
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const int per_cu = (int)((160 * 1024) / lds);
+    const int per_cu = lds_blocks_per_cu(lds);
     // units: (group, chunk of outputs).  Decode: chunks of rc for rmax > rc.  A compiled encode:
     // one unit.  A table encode: the table is the one stream_encode_rc() asks for (rows of
     // max(4, rc) bytes), and a unit is every output where they fit its rows, else a chunk of 8
     int nchunk = 1, enc_rc = 0;
     if (decode) {
-        nchunk = (rmax + rc - 1) / rc;
+        nchunk = (a.rmax + rc - 1) / rc;
     } else if (!code) {
         enc_rc = stream_encode_rc(k, m, bb, true, t);
         if (std::max(rc, 4) != std::max(enc_rc, 4) || (m > enc_rc && enc_rc != 8))
@@ -716,15 +713,15 @@ hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef
         // DESIGN.md section 4.5)
         const int rwg = t.ring_wg >= 0 ? t.ring_wg : code->ring_wg;
         const unsigned rgrid = persistent_grid(groups * (rsplit ? 2 : 1), kRingWaves,
-                                               (long long)t.cus * (int)((160 * 1024) / rlds), rwg,
+                                               (long long)t.cus * lds_blocks_per_cu(rlds), rwg,
                                                t.stream_grid);
         if (!rgrid) return hipErrorInvalidValue;
         char name[64];
         snprintf(name, sizeof name, "gf_ring_kernel<encode,k%dm%d%s>", k, m, rsplit ? ",split" : "");
         note_kernel(name);
         const auto go = [&](auto kern) {
-            qlaunch(kern, dim3(rgrid), dim3(kRingWaves * 64), rlds, st, in, out, coef, slots, nout,
-                    groups, rmax, coef_gstride, out_gstride);
+            qlaunch(kern, dim3(rgrid), dim3(kRingWaves * 64), rlds, a.st, a.in, a.out, a.tab,
+                    a.slots, a.nout, groups, a.rmax, a.tab_gstride, a.out_gstride);
         };
         // nt parity stores (plain: 0.673 vs 0.578 ms on B)
         with_code(k, m, [&](auto I) {
@@ -748,8 +745,8 @@ hipError_t launch_gf_stream(const uint8_t* in, uint8_t* out, const uint8_t* coef
     }
     const unsigned threads = kStreamWaves * 64;
     const auto go = [&](auto kern) {
-        qlaunch(kern, dim3(grid), dim3(threads), lds, st, in, out, coef, slots, nout, groups, k, m,
-                rmax, coef_gstride, out_gstride, R, s, nchunk);
+        qlaunch(kern, dim3(grid), dim3(threads), lds, a.st, a.in, a.out, a.tab, a.slots, a.nout,
+                groups, k, m, a.rmax, a.tab_gstride, a.out_gstride, R, s, nchunk);
     };
     if (code) {
         // windowed form, every output in one unit

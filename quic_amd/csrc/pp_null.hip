@@ -880,117 +880,80 @@ unsigned tile_grid(long long n) {   // one wave (kTilePackets packets) per workg
 }  // namespace
 
 
-hipError_t launch_null_seal_h(long long n, const uint8_t* ad, long long ad_stride,
-                              const int32_t* ad_len, int ad_all, const uint8_t* pt,
-                              long long pt_stride, const int32_t* pt_len, int pt_all,
-                              uint8_t* out, long long out_stride, int32_t* out_len,
-                              hipStream_t st) {
+// The three seals: n packets with AD rows ad, the plaintext rows pr (PtRows, RaggedRows).
+template <class R>
+static hipError_t seal_go(const char* name, long long n, Rows ad, R pr, const int32_t* pt_len,
+                          int pt_all, RowsOut out, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     if (!pp_grid_ok(n)) return hipErrorInvalidValue;
-    const PtRows pr{nullptr, pt, pt_stride, 0, 1};
-    note_kernel("null_seal_kernel");
-    qlaunch((null_seal_kernel<Fnv, PtRows>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, n, ad, ad_stride,
-           ad_len, ad_all, pr, pt_len, pt_all, out, out_stride, out_len);
+    note_kernel(name);
+    qlaunch((null_seal_kernel<Fnv, R>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, n, ad.p,
+            ad.stride, ad.len, ad.len_all, pr, pt_len, pt_all, out.p, out.stride, out.len);
     return hipGetLastError();
 }
 
-hipError_t launch_null_seal(long long n, const uint8_t* ad, long long ad_stride,
-                            const int32_t* ad_len, int ad_all, const uint8_t* pt,
-                            long long pt_stride, const int32_t* pt_len, int pt_all, uint8_t* out,
-                            long long out_stride, int32_t* out_len, hipStream_t st) {
-    return launch_null_seal_h(n, ad, ad_stride, ad_len, ad_all, pt, pt_stride, pt_len, pt_all,
-                              out, out_stride, out_len, st);
+hipError_t launch_null_seal(long long n, Rows ad, Rows pt, RowsOut out, hipStream_t st) {
+    return seal_go("null_seal_kernel", n, ad, PtRows{nullptr, pt.p, pt.stride, 0, 1}, pt.len,
+                   pt.len_all, out, st);
 }
 
-hipError_t launch_null_seal_groups(int k, int m, int bb, long long groups,
-                                   const uint8_t* data, const uint8_t* parity, const uint8_t* hdr,
-                                   long long hdr_stride, const int32_t* hdr_len, int hdr_all,
-                                   const int32_t* pt_len, int pt_all, uint8_t* out,
-                                   long long out_stride, int32_t* out_len, hipStream_t st) {
-    const long long n = groups * (k + m);
-    if (n <= 0) return hipSuccess;
-    if (!pp_grid_ok(n)) return hipErrorInvalidValue;
-    const PtRows pr{data, parity, bb, k, m};
-    note_kernel("null_seal_kernel<groups>");
-    qlaunch((null_seal_kernel<Fnv, PtRows>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, n, hdr, hdr_stride,
-           hdr_len, hdr_all, pr, pt_len, pt_all, out, out_stride, out_len);
-    return hipGetLastError();
+hipError_t launch_null_seal_groups(int k, int m, int bb, long long groups, const uint8_t* data,
+                                   const uint8_t* parity, Rows hdr, const int32_t* pt_len,
+                                   int pt_all, RowsOut out, hipStream_t st) {
+    return seal_go("null_seal_kernel<groups>", groups * (k + m), hdr,
+                   PtRows{data, parity, bb, k, m}, pt_len, pt_all, out, st);
 }
 
-hipError_t launch_null_open_h(long long n, const uint8_t* pkt, long long pkt_stride,
-                              const int32_t* pkt_len, int pkt_all, const int32_t* ad_len,
-                              int ad_all, uint8_t* out, long long out_stride, int32_t* out_len,
-                              hipStream_t st) {
+hipError_t launch_null_open(long long n, Rows pkt, Rows ad, RowsOut out, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     if (!pp_grid_ok(n)) return hipErrorInvalidValue;
     note_kernel("null_open_kernel");
-    qlaunch(null_open_kernel<Fnv>, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, n, pkt, pkt_stride,
-           pkt_len, pkt_all, ad_len, ad_all, out, out_stride, out_len);
+    qlaunch(null_open_kernel<Fnv>, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, n, pkt.p, pkt.stride,
+            pkt.len, pkt.len_all, ad.len, ad.len_all, out.p, out.stride, out.len);
     return hipGetLastError();
 }
 
-hipError_t launch_null_open(long long n, const uint8_t* pkt, long long pkt_stride,
-                            const int32_t* pkt_len, int pkt_all, const int32_t* ad_len,
-                            int ad_all, uint8_t* out, long long out_stride, int32_t* out_len,
-                            hipStream_t st) {
-    return launch_null_open_h(n, pkt, pkt_stride, pkt_len, pkt_all, ad_len, ad_all, out,
-                              out_stride, out_len, st);
-}
-
-hipError_t launch_open_groups(int k, int m, int bb, long long groups,
-                              const uint8_t* pkt, long long pkt_stride, const int32_t* pkt_len,
-                              const int32_t* ad_len, int ad_all, uint8_t* blocks,
-                              uint8_t* rows, int32_t* open_len, hipStream_t st) {
+// The two opens: the slots sl (UniSlots, RaggedSlots) of every group's blocks.
+template <class S>
+static hipError_t open_go(const char* name, int k, int m, long long groups, S sl, Rows pkt,
+                          Rows ad, uint8_t* blocks, uint8_t* rows, int32_t* open_len,
+                          hipStream_t st) {
     const long long n = groups * (k + m);
     if (n <= 0) return hipSuccess;
     if (k + m > 256 || !pp_grid_ok(n)) return hipErrorInvalidValue;
     const long long wg = (groups + kAsmWaves - 1) / kAsmWaves;
     if (wg > 0x7fffffffLL) return hipErrorInvalidValue;
-    note_kernel("open_group_kernel + open_assemble_kernel");
-    const UniSlots sl{bb};
-    qlaunch((open_group_kernel<Fnv, UniSlots>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, k, m,
-           sl, n, pkt, pkt_stride, pkt_len, ad_len, ad_all, blocks, open_len);
-    qlaunch(open_assemble_kernel<UniSlots>, dim3((unsigned)wg), dim3(kAsmWaves * 64), 0, st, k, m,
-            sl, groups, pkt, pkt_stride, pkt_len, ad_len, ad_all, open_len, blocks, rows);
+    note_kernel(name);
+    qlaunch((open_group_kernel<Fnv, S>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, k, m, sl, n,
+            pkt.p, pkt.stride, pkt.len, ad.len, ad.len_all, blocks, open_len);
+    qlaunch(open_assemble_kernel<S>, dim3((unsigned)wg), dim3(kAsmWaves * 64), 0, st, k, m, sl,
+            groups, pkt.p, pkt.stride, pkt.len, ad.len, ad.len_all, open_len, blocks, rows);
     return hipGetLastError();
 }
 
-hipError_t launch_null_seal_groups_ragged(int k, int m, long long groups, const int32_t* bb,
-                                          const uint8_t* data, const long long* data_off,
-                                          const uint8_t* parity, const long long* par_off,
-                                          bool after_encode, const uint8_t* hdr,
-                                          long long hdr_stride, const int32_t* hdr_len,
-                                          int hdr_all, const int32_t* pt_len, uint8_t* out,
-                                          long long out_stride, int32_t* out_len,
-                                          hipStream_t st) {
-    const long long n = groups * (k + m);
-    if (n <= 0) return hipSuccess;
-    if (!pp_grid_ok(n)) return hipErrorInvalidValue;
-    const RaggedRows pr{data, parity, data_off, par_off, bb, k, m, after_encode};
-    note_kernel("null_seal_kernel<ragged>");
-    qlaunch((null_seal_kernel<Fnv, RaggedRows>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, n,
-           hdr, hdr_stride, hdr_len, hdr_all, pr, pt_len, 0, out, out_stride, out_len);
-    return hipGetLastError();
+hipError_t launch_open_groups(int k, int m, int bb, long long groups, Rows pkt, Rows ad,
+                              uint8_t* blocks, uint8_t* rows, int32_t* open_len,
+                              hipStream_t st) {
+    return open_go("open_group_kernel + open_assemble_kernel", k, m, groups, UniSlots{bb}, pkt, ad,
+                   blocks, rows, open_len, st);
 }
 
-hipError_t launch_open_groups_ragged(int k, int m, long long groups, const int32_t* bb,
-                                     const uint8_t* pkt, long long pkt_stride,
-                                     const int32_t* pkt_len, const int32_t* ad_len, int ad_all,
-                                     uint8_t* blocks, const long long* blocks_off, uint8_t* rows,
-                                     int32_t* open_len, hipStream_t st) {
-    const long long n = groups * (k + m);
-    if (n <= 0) return hipSuccess;
-    if (k + m > 256 || !pp_grid_ok(n)) return hipErrorInvalidValue;
-    const long long wg = (groups + kAsmWaves - 1) / kAsmWaves;
-    if (wg > 0x7fffffffLL) return hipErrorInvalidValue;
-    note_kernel("open_group_kernel<ragged> + open_assemble_kernel<ragged>");
-    const RaggedSlots sl{bb, blocks_off, groups};
-    qlaunch((open_group_kernel<Fnv, RaggedSlots>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, k,
-           m, sl, n, pkt, pkt_stride, pkt_len, ad_len, ad_all, blocks, open_len);
-    qlaunch(open_assemble_kernel<RaggedSlots>, dim3((unsigned)wg), dim3(kAsmWaves * 64), 0, st, k,
-            m, sl, groups, pkt, pkt_stride, pkt_len, ad_len, ad_all, open_len, blocks, rows);
-    return hipGetLastError();
+hipError_t launch_null_seal_groups_ragged(int k, int m, long long groups, RaggedView v,
+                                          const uint8_t* data, const uint8_t* parity,
+                                          bool after_encode, Rows hdr, const int32_t* pt_len,
+                                          RowsOut out, hipStream_t st) {
+    return seal_go("null_seal_kernel<ragged>", groups * (k + m), hdr,
+                   RaggedRows{data, parity, v.in_off, v.out_off, v.bb, k, m, after_encode}, pt_len,
+                   0, out, st);
 }
+
+hipError_t launch_open_groups_ragged(int k, int m, long long groups, RaggedView v, Rows pkt,
+                                     Rows ad, uint8_t* blocks, uint8_t* rows, int32_t* open_len,
+                                     hipStream_t st) {
+    return open_go("open_group_kernel<ragged> + open_assemble_kernel<ragged>", k, m, groups,
+                   RaggedSlots{v.bb, v.in_off, groups}, pkt, ad, blocks, rows, open_len, st);
+}
+
 hipError_t launch_open_status(int k, int rmax, long long groups, const uint8_t* rows,
                               uint8_t* rec_rows, int32_t* status, hipStream_t st) {
     if (groups <= 0) return hipSuccess;

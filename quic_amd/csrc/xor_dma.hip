@@ -195,41 +195,12 @@ bool xor_plan(int k, int bb, const Tune& t, XorPlan* p) {
     return p->ndma <= 20;
 }
 
-template <bool DECODE, bool FUSED, bool COMPACT, int NSLOT, int N>
-hipError_t xor_go(const XorPlan& p, const uint8_t* in, uint8_t* out, const uint8_t* eidx,
-                  const uint8_t* rows_in, uint8_t* rows_out, int32_t* status, int k, int bb,
-                  long long G, long long ogs, hipStream_t st, int cus) {
-    if constexpr (N > 20 || (NSLOT - 1) * (N + (DECODE ? 1 : 0)) > 63) {
-        return hipErrorInvalidValue;
-    } else {
-        if (p.ndma != N)
-            return xor_go<DECODE, FUSED, COMPACT, NSLOT, N + 1>(p, in, out, eidx, rows_in, rows_out,
-                                                                status, k, bb, G, ogs, st, cus);
-        const long long want = (G + p.waves - 1) / p.waves;
-        const unsigned nb = (unsigned)std::min<long long>(want, (long long)cus);
-        // the wave's group count is a 32-bit SGPR value
-        if ((G + (long long)nb * p.waves - 1) / ((long long)nb * p.waves) >= (1LL << 31))
-            return hipErrorInvalidValue;
-        note_kernel(DECODE ? (COMPACT ? "xor_dma_kernel<decode,recovered>"
-                                      : "xor_dma_kernel<decode>")
-                           : "xor_dma_kernel<encode>");
-        note_grid("xor_dma_kernel", nb);
-        qlaunch((xor_dma_kernel<N, NSLOT, DECODE, FUSED, 0, COMPACT>), dim3(nb), dim3(p.waves * 64), p.lds, st, 
-            in, out, eidx, rows_in, rows_out, status, k, bb, G, ogs);
-        return hipGetLastError();
-    }
-}
-
-template <bool DECODE, bool FUSED, bool COMPACT = false>
-hipError_t xor_dispatch(const XorPlan& p, const uint8_t* in, uint8_t* out, const uint8_t* eidx,
-                        const uint8_t* rows_in, uint8_t* rows_out, int32_t* status, int k,
-                        int bb, long long G, long long ogs, hipStream_t st, int cus) {
-    hipError_t e = hipErrorInvalidValue;
-    dispatch_value<2, 3, 4>(p.nslot, [&](auto NSLOT) {
-        e = xor_go<DECODE, FUSED, COMPACT, decltype(NSLOT)::value, 1>(
-            p, in, out, eidx, rows_in, rows_out, status, k, bb, G, ogs, st, cus);
-    });
-    return e;
+// The DMA instructions per group a ring can have: 1 .. 20 (xor_plan), each its own kernel.
+// dispatch_value over index I + 1 of the sequence.
+using XorNdma = std::make_integer_sequence<int, 20>;
+template <int... I, class F>
+bool dispatch_ndma(std::integer_sequence<int, I...>, int v, F&& f) {
+    return dispatch_value<(I + 1)...>(v, f);
 }
 
 }  // namespace
@@ -248,23 +219,36 @@ hipError_t launch_xor_dma(const uint8_t* in, uint8_t* out, const uint8_t* eidx,
     if (groups <= 0) return hipSuccess;
     XorPlan p;
     if (!xor_plan(k, bb, t, &p)) return hipErrorInvalidValue;
-    // the grid cap: one workgroup per CU, or (xor_wg) about xor_wg groups per wave
-    const int cap = t.xor_wg > 0
-                        ? (int)std::min<long long>((groups + (long long)p.waves * t.xor_wg - 1) /
-                                                       ((long long)p.waves * t.xor_wg),
-                                                   0x7fffffffLL)
-                        : t.cus;
-    if (!decode)
-        return xor_dispatch<false, false>(p, in, out, eidx, rows_in, rows_out, status, k, bb,
-                                          groups, out_gstride, st, cap);
-    if (rows_in && compact)
-        return xor_dispatch<true, true, true>(p, in, out, eidx, rows_in, rows_out, status, k,
-                                              bb, groups, out_gstride, st, cap);
-    if (rows_in)
-        return xor_dispatch<true, true>(p, in, out, eidx, rows_in, rows_out, status, k, bb,
-                                        groups, out_gstride, st, cap);
-    return xor_dispatch<true, false>(p, in, out, eidx, rows_in, rows_out, status, k, bb, groups,
-                                     out_gstride, st, cap);
+    // one workgroup per CU, or (xor_wg) about xor_wg groups per wave; 0: a wave's group count
+    // (a 32-bit SGPR value) would overflow
+    const unsigned nb = persistent_grid(groups, p.waves, t.cus, t.xor_wg, 0);
+    if (!nb) return hipErrorInvalidValue;
+    hipError_t e = hipErrorInvalidValue;
+    const auto go = [&](auto DEC, auto FUSED, auto COMPACT) {
+        constexpr bool dec = decltype(DEC)::value, comp = decltype(COMPACT)::value;
+        dispatch_value<2, 3, 4>(p.nslot, [&](auto NSLOT) {
+            dispatch_ndma(XorNdma{}, p.ndma, [&](auto N) {
+                constexpr int ns = decltype(NSLOT)::value, n = decltype(N)::value;
+                static_assert((ns - 1) * (n + (dec ? 1 : 0)) <= 63, "the ring's counted waits");
+                note_kernel(dec ? (comp ? "xor_dma_kernel<decode,recovered>"
+                                        : "xor_dma_kernel<decode>")
+                                : "xor_dma_kernel<encode>");
+                note_grid("xor_dma_kernel", nb);
+                qlaunch((xor_dma_kernel<n, ns, dec, decltype(FUSED)::value, 0, comp>), dim3(nb),
+                        dim3(p.waves * 64), p.lds, st, in, out, eidx, rows_in, rows_out, status,
+                        k, bb, groups, out_gstride);
+                e = hipGetLastError();
+            });
+        });
+    };
+    // decode with rows_in (fused): the kernel also does the row bookkeeping
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    if (!decode) go(no, no, no);
+    else if (rows_in && compact) go(yes, yes, yes);
+    else if (rows_in) go(yes, yes, no);
+    else go(yes, no, no);
+    return e;
 }
 
 }  // namespace qfec

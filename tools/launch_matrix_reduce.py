@@ -42,6 +42,8 @@ def main(calls_path, trace_path):
         rows = sorted(csv.DictReader(fh), key=lambda r: (int(r["Start_Timestamp"]), int(r["Dispatch_Id"])))
     runs, inside = [], False   # one run of the library's kernels per call
     for r in rows:
+        if r["Kernel_Name"].startswith("__amd_rocclr_"):
+            continue   # the runtime's own copy / fill kernels inside a host form
         if "qfec" not in r["Kernel_Name"]:
             inside = False
             continue
