@@ -448,6 +448,101 @@ QFEC_API int qfec_open_decode_batch_ragged_host(
     int *h_open_len);
 
 /* ---------------------------------------------------------------------------------
+ * Framed groups: QuicFecGroup's wire format on the device.
+ *
+ * The group layer protects the block prefix || payload || zeros, prefix = the 16-bit
+ * little-endian (len | pn_len << 14) & 0xffff (quic_fec_group.cc:109-121), padded to
+ * bb = roundup8(max(len + 2)) (:344-352).  On the wire a data packet carries the payload alone;
+ * only FEC packets carry whole blocks.  The receiver prefixes each opened data packet again
+ * (:178-183) and cuts each revived packet out of its block by that prefix (:287-292).  The ragged
+ * protected calls above treat a data packet's plaintext as its block, so they are
+ * wire-compatible with the reference only for callers who frame the blocks themselves.  The
+ * calls here do the framing: payload rows in, wire packets out; wire packets in, revived
+ * payloads out.  Ragged only (a framed group has its own bb by construction).
+ *
+ * Rule: per group, a framed call is the ragged protected call on the framed blocks.  Blocks are
+ * packed as in the ragged batches; payload rows (d_pay + (g*k+i)*pay_stride, d_pay_len[g*k+i]
+ * bytes), revived rows (d_rev + (g*rmax+j)*rev_stride, rmax = min(k,m)), headers, packets and
+ * every per-packet array stay dense.  pn_len is the QuicPacketNumberLength value (1, 2, 4, 6):
+ * u8 per packet (d_pn_len [G*k] on the sender, [G*(k+m)] on the receiver), or, where the array
+ * is NULL, pn_len_all; the prefix keeps its low two bits (4 -> 0, 6 -> 2, as in the reference).
+ * What the rule fixes:
+ *   - sender: block (g, i) = prefix || payload || zeros to bb[g] bytes is written to
+ *     d_data + d_data_off[g] + i*bb[g] (d_data is an output), the groups are encoded, data packet
+ *     p = g*(k+m)+i is header || tag12 || payload (no prefix), FEC packet p is
+ *     header || tag12 || parity block i-k.
+ *   - a group is rejected when any of its k lengths is < 0, > 0x3fff, > pay_stride (pay_stride
+ *     != 0) or > bb[g] - 2, or when bb[g] < 8 (one predicate asked by the frame, the seal and the
+ *     status): d_status[g] = -3, all k + m d_pkt_len entries -1, and none of its blocks, parity
+ *     or packets is written.
+ *   - a group that frames but whose encode status is -1 (m > 1, k > 1, bb[g] % 8 != 0): its
+ *     blocks are framed, and the rest is as in qfec_encode_seal_groups_batch_ragged (XOR parity
+ *     in its first parity block, no packet sealed, d_status -1).
+ *   - receiver: a data packet's plaintext goes to slot + 2, zero-padded to bb[g] - 2, behind the
+ *     prefix made of its opened length and pn_len[p]; it is rejected (d_open_len -1) when longer
+ *     than bb[g] - 2.  An FEC packet's plaintext goes to slot + 0 and may be bb[g] long.
+ *     Everything else (rows, holes, the decode, every status) is qfec_open_decode_batch_ragged's.
+ *     bb[g] is the caller's: qfec_framed_rx_block_bytes gives the reference's value, which is
+ *     not a multiple of 8 for a group that received no FEC packet (such a group decodes with
+ *     status 0 only if it lost nothing).
+ *   - revived packets: for recovered block j of group g with d_rec_rows != 255 and d_status[g]
+ *     == 0, v = its prefix, len = min(v & 0x3fff, bb[g] - 2) (the reference reads past the block
+ *     there; the clamp is include/quic_fec_group.h's), d_rev row g*rmax+j = block[2 .. 2+len),
+ *     d_rev_len = len, d_rev_pn_len = v >> 14.  Bytes of the row past len are not written.
+ *     Every other entry, and a len above rev_stride: d_rev_len -1 and nothing else written.
+ *   - call-level limits, -2 before anything is enqueued: those of the ragged protected calls,
+ *     and a NULL d_pay / d_pay_len / d_rev / d_rev_len or a negative pay_stride / rev_stride.
+ *     d_pn_len, d_rev_pn_len, d_status may be NULL.  d_rev and rev_stride need no alignment.
+ *   - workspace, streams, graphs: both paths run in the decode-workspace bracket (the sender
+ *     keeps one int per group there); qfec_reserve(ctx, k, m, largest bb, groups) covers a
+ *     capture.
+ * Launches: sender one, the ragged encode's, one; receiver two, the ragged decode's, two.
+ * ------------------------------------------------------------------------------- */
+/* Host helper, no GPU: bb[g] = roundup8(max_i(pay_len[g*k+i] + 2)) (output), then the offsets
+ * and totals of qfec_ragged_layout for those sizes.  -2 on a length outside [0, 0x3fff]. */
+QFEC_API int qfec_framed_layout(int k, int m, long long groups, const int *pay_len, int *bb,
+                                long long *data_off, long long *par_off, long long *rec_off,
+                                long long totals[3]);
+/* Host helper, no GPU: bb[g] = the largest stored size among group g's received packets
+ * (pkt_len[p] >= 0 with at least 12 bytes behind the associated data): plaintext + 2 for a data
+ * packet, plaintext for an FEC packet (quic_fec_group.cc:264-265).  Not rounded; 0 when nothing
+ * was received.  ad_len may be NULL (ad_len_all). */
+QFEC_API int qfec_framed_rx_block_bytes(int k, int m, long long groups, const int *pkt_len,
+                                        const int *ad_len, int ad_len_all, int *bb);
+/* The sender's framing alone (for a caller who runs the bare codec): blocks from payload rows.
+ * d_status [G] (may be NULL): 0, or -3 for a rejected group. */
+QFEC_API int qfec_frame_blocks_batch_ragged(qfec_ctx *ctx, int k, long long groups,
+                                            const int *d_bb, const unsigned char *d_pay,
+                                            long long pay_stride, const int *d_pay_len,
+                                            const unsigned char *d_pn_len, int pn_len_all,
+                                            unsigned char *d_data, const long long *d_data_off,
+                                            int *d_status, void *stream);
+/* The receiver's extraction alone, after a recovered-layout ragged decode. */
+QFEC_API int qfec_extract_revived_batch_ragged(qfec_ctx *ctx, int k, int m, long long groups,
+                                               const int *d_bb, const unsigned char *d_rec,
+                                               const long long *d_rec_off,
+                                               const unsigned char *d_rec_rows,
+                                               const int *d_status, unsigned char *d_rev,
+                                               long long rev_stride, int *d_rev_len,
+                                               unsigned char *d_rev_pn_len, void *stream);
+/* Sender: frame -> qfec_encode_batch_ragged -> seal of every packet. */
+QFEC_API int qfec_frame_encode_seal_groups_batch_ragged(
+    qfec_ctx *ctx, int k, int m, long long groups, const int *d_bb, unsigned char *d_data,
+    const long long *d_data_off, unsigned char *d_parity, const long long *d_par_off,
+    const unsigned char *d_hdr, long long hdr_stride, const int *d_hdr_len, int hdr_len_all,
+    const unsigned char *d_pay, long long pay_stride, const int *d_pay_len,
+    const unsigned char *d_pn_len, int pn_len_all, unsigned char *d_pkt, long long pkt_stride,
+    int *d_pkt_len, int *d_status, void *stream);
+/* Receiver: framed open -> qfec_decode_batch_ragged_recovered -> extraction. */
+QFEC_API int qfec_open_decode_extract_batch_ragged(
+    qfec_ctx *ctx, int k, int m, long long groups, const int *d_bb, const unsigned char *d_pkt,
+    long long pkt_stride, const int *d_pkt_len, const int *d_ad_len, int ad_len_all,
+    const unsigned char *d_pn_len, int pn_len_all, unsigned char *d_blocks,
+    const long long *d_blocks_off, unsigned char *d_rows, int *d_open_len, unsigned char *d_rec,
+    const long long *d_rec_off, unsigned char *d_rec_rows, int *d_status, unsigned char *d_rev,
+    long long rev_stride, int *d_rev_len, unsigned char *d_rev_pn_len, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Support: the coefficient tables, a seeded synthetic workload, diagnostics.
  * ------------------------------------------------------------------------------- */
 /* Rows 1..m-1 of the Cauchy matrix the reference selects (cauchy_256.cpp:422-480),
@@ -469,7 +564,9 @@ QFEC_API const char *qfec_last_error(void);
  * calls name "gf_ragged_kernel<encode>", "gf_ragged_kernel<decode>", "xor_ragged_kernel" and
  * "copy_ragged_kernel"; the ragged protected calls add "null_seal_kernel<ragged>" and
  * "open_group_kernel<ragged> + open_assemble_kernel<ragged>" (the uniform grouped calls name
- * "null_seal_kernel<groups>" and "open_group_kernel + open_assemble_kernel"). */
+ * "null_seal_kernel<groups>" and "open_group_kernel + open_assemble_kernel"); the framed calls
+ * name "frame_blocks_kernel", "null_seal_kernel<framed>", "open_group_kernel<framed> +
+ * open_assemble_kernel<framed>" and "extract_revived_kernel". */
 QFEC_API const char *qfec_last_kernels(void);
 /* Grids of the persistent kernels the last call on this thread launched, as space-separated
  * "kernel=workgroups" entries (e.g. "gf_psyn_kernel=1024"); diagnostics and tests.  The general

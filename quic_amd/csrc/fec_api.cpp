@@ -951,6 +951,133 @@ int qfec_open_decode_batch_ragged(qfec_ctx* c, int k, int m, long long groups, c
     });
 }
 
+// ---- framed groups: QuicFecGroup's wire format around the ragged protected paths (pp_null.hip's
+// framed kernels).  Payload rows and revived payloads stay dense by packet; blocks are packed.
+static int framed_pay_args(const unsigned char* d_pay, long long pay_stride, const int* d_pay_len) {
+    if (!d_pay || !d_pay_len) return fail(-2, "null buffer");
+    if (pay_stride < 0) return fail(-2, "bad pay_stride");
+    return 0;
+}
+
+static int framed_rev_args(const unsigned char* d_rev, long long rev_stride, const int* d_rev_len) {
+    if (!d_rev || !d_rev_len) return fail(-2, "null buffer");
+    if (rev_stride < 0) return fail(-2, "bad rev_stride");
+    return 0;
+}
+
+int qfec_frame_blocks_batch_ragged(qfec_ctx* c, int k, long long groups, const int* d_bb,
+                                   const unsigned char* d_pay, long long pay_stride,
+                                   const int* d_pay_len, const unsigned char* d_pn_len,
+                                   int pn_len_all, unsigned char* d_data,
+                                   const long long* d_data_off, int* d_status, void* stream) {
+    int rc = ragged_preface(c, k, 1, groups);
+    if (rc) return rc;
+    if (any_null({d_bb, d_data, d_data_off})) return fail(-2, "null buffer");
+    if ((uintptr_t)d_data & 15) return fail(-2, "ragged base pointers must be 16-byte aligned");
+    if ((rc = framed_pay_args(d_pay, pay_stride, d_pay_len))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    QF_HIP(qfec::launch_frame_blocks_ragged(
+        k, groups, {(const int32_t*)d_bb, d_data_off, nullptr},
+        rows_of(d_pay, pay_stride, d_pay_len, 0), d_pn_len, pn_len_all, d_data, nullptr,
+        (int32_t*)d_status, pick(c, stream)));
+    return 0;
+}
+
+int qfec_extract_revived_batch_ragged(qfec_ctx* c, int k, int m, long long groups, const int* d_bb,
+                                      const unsigned char* d_rec, const long long* d_rec_off,
+                                      const unsigned char* d_rec_rows, const int* d_status,
+                                      unsigned char* d_rev, long long rev_stride, int* d_rev_len,
+                                      unsigned char* d_rev_pn_len, void* stream) {
+    int rc = ragged_preface(c, k, m, groups);
+    if (rc) return rc;
+    if (any_null({d_bb, d_rec, d_rec_off, d_rec_rows})) return fail(-2, "null buffer");
+    if ((rc = framed_rev_args(d_rev, rev_stride, d_rev_len))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    QF_HIP(qfec::launch_extract_revived(k, m, groups, {(const int32_t*)d_bb, nullptr, d_rec_off},
+                                        d_rec, d_rec_rows, (const int32_t*)d_status,
+                                        rows_out_of(d_rev, rev_stride, d_rev_len), d_rev_pn_len,
+                                        pick(c, stream)));
+    return 0;
+}
+
+// frame -> ragged encode -> framed seal.  The encode runs with the frame's sizes (0 for a group
+// the frame rejected, which every encode kernel skips), kept in the decode workspace's count
+// array: the call holds the workspace bracket like a decode.
+int qfec_frame_encode_seal_groups_batch_ragged(
+    qfec_ctx* c, int k, int m, long long groups, const int* d_bb, unsigned char* d_data,
+    const long long* d_data_off, unsigned char* d_parity, const long long* d_par_off,
+    const unsigned char* d_hdr, long long hdr_stride, const int* d_hdr_len, int hdr_len_all,
+    const unsigned char* d_pay, long long pay_stride, const int* d_pay_len,
+    const unsigned char* d_pn_len, int pn_len_all, unsigned char* d_pkt, long long pkt_stride,
+    int* d_pkt_len, int* d_status, void* stream) {
+    int rc = ragged_check(c, k, m, groups, d_bb, d_data, d_data_off, d_parity, d_par_off);
+    if (rc) return rc;
+    const Rows hdr = rows_of(d_hdr, hdr_stride, d_hdr_len, hdr_len_all);
+    const RowsOut pkt = rows_out_of(d_pkt, pkt_stride, d_pkt_len);
+    if ((rc = seal_ragged_pkt_args(k, m, hdr, pkt))) return rc;
+    if ((rc = framed_pay_args(d_pay, pay_stride, d_pay_len))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    if (groups == 0) return 0;
+    const hipStream_t st = pick(c, stream);
+    const Rows pay = rows_of(d_pay, pay_stride, d_pay_len, 0);
+    return with_workspace(c, st, [&] {
+        Workspace& W = ws_for(c, st);
+        QF_HIP(W.ensure(W.dnout, (size_t)groups * sizeof(int32_t)));
+        int32_t* eff = (int32_t*)W.dnout.p;
+        const RaggedView v{(const int32_t*)d_bb, d_data_off, d_par_off};
+        QF_HIP(qfec::launch_frame_blocks_ragged(k, groups, v, pay, d_pn_len, pn_len_all, d_data,
+                                                eff, nullptr, st));
+        const int r = encode_ragged_impl(c, k, m, groups, {eff, d_data_off, d_par_off}, d_data,
+                                         d_parity, (int32_t*)d_status, st);
+        if (r) return r;
+        QF_HIP(qfec::launch_null_seal_framed(k, m, groups, v, pay, d_parity, hdr, pkt,
+                                             (int32_t*)d_status, st));
+        return 0;
+    });
+}
+
+// framed open -> ragged recovered decode -> open_status -> extract
+int qfec_open_decode_extract_batch_ragged(
+    qfec_ctx* c, int k, int m, long long groups, const int* d_bb, const unsigned char* d_pkt,
+    long long pkt_stride, const int* d_pkt_len, const int* d_ad_len, int ad_len_all,
+    const unsigned char* d_pn_len, int pn_len_all, unsigned char* d_blocks,
+    const long long* d_blocks_off, unsigned char* d_rows, int* d_open_len, unsigned char* d_rec,
+    const long long* d_rec_off, unsigned char* d_rec_rows, int* d_status, unsigned char* d_rev,
+    long long rev_stride, int* d_rev_len, unsigned char* d_rev_pn_len, void* stream) {
+    int rc = ragged_check(c, k, m, groups, d_bb, d_blocks, d_blocks_off, d_rec, d_rec_off);
+    if (rc) return rc;
+    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
+    if (!d_pkt || !d_pkt_len || !d_rows || !d_open_len || !d_rec_rows) return fail(-2, "null buffer");
+    if (pkt_stride <= 0) return fail(-2, "bad pkt_stride");
+    if (!d_ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
+    if ((rc = framed_rev_args(d_rev, rev_stride, d_rev_len))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    if (groups == 0) return 0;
+    const hipStream_t st = pick(c, stream);
+    const RaggedView v{(const int32_t*)d_bb, d_blocks_off, d_rec_off};
+    return with_workspace(c, st, [&] {
+        QF_HIP(qfec::launch_open_groups_framed(k, m, groups, v,
+                                               rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
+                                               rows_of(nullptr, 0, d_ad_len, ad_len_all), d_pn_len,
+                                               pn_len_all, d_blocks, d_rows, (int32_t*)d_open_len,
+                                               st));
+        const int r = decode_ragged_impl(c, k, m, groups, v, d_blocks, d_rows, d_rec, d_rec_rows,
+                                         (int32_t*)d_status, st);
+        if (r) return r;
+        QF_HIP(qfec::launch_open_status(k, std::min(k, m), groups, d_rows, d_rec_rows,
+                                        (int32_t*)d_status, st));
+        QF_HIP(qfec::launch_extract_revived(k, m, groups, v, d_rec, d_rec_rows,
+                                            (const int32_t*)d_status,
+                                            rows_out_of(d_rev, rev_stride, d_rev_len),
+                                            d_rev_pn_len, st));
+        return 0;
+    });
+}
+
 int qfec_synth_fill(void* d_dst, unsigned long long bytes, unsigned long long seed,
                     unsigned long long byte_offset, void* stream) {
     qfec::TimingMute mute;
@@ -1051,8 +1178,11 @@ int qfec_reserve(qfec_ctx* c, int k, int m, int bb, long long groups) {
     if ((rc = set_device(c))) return rc;
     // both workspaces: the eager one and the one calls captured into a graph use
     const DecodePlan p = decode_plan(k, m, bb);
-    for (Workspace* W : {&c->ws, &c->ws_graph})
+    for (Workspace* W : {&c->ws, &c->ws_graph}) {
         if ((rc = reserve_workspace(*W, p, groups, true))) return rc;
+        // the framed sender's per-group sizes (any k, m)
+        QF_HIP(W->ensure(W->dnout, (size_t)groups * sizeof(int32_t)));
+    }
     if (m > 1 && k > 1 && k + m <= 256) {
         const uint8_t* t;
         if ((rc = get_enc_table(c, k, m, stream_encode_rc(k, m, bb, true, c->tune), &t))) return rc;

@@ -54,6 +54,43 @@ extern "C" int qfec_ragged_layout(int k, int m, long long groups, const int* bb,
     return 0;
 }
 
+// The block size getRedundancyPackets gives a group (quic_fec_group.cc:344-352): the largest
+// prefixed payload, rounded up to 8; then qfec_ragged_layout's offsets.
+extern "C" int qfec_framed_layout(int k, int m, long long groups, const int* pay_len, int* bb,
+                                  long long* data_off, long long* par_off, long long* rec_off,
+                                  long long totals[3]) {
+    if (k < 1 || m < 1 || groups < 0 || (groups && (!pay_len || !bb))) return -2;
+    for (long long g = 0; g < groups; ++g) {
+        int most = 0;
+        for (int i = 0; i < k; ++i) {
+            const int len = pay_len[g * k + i];
+            if (len < 0 || len > 0x3fff) return -2;
+            most = std::max(most, len);
+        }
+        bb[g] = (most + 2 + 7) & ~7;
+    }
+    return qfec_ragged_layout(k, m, groups, bb, data_off, par_off, rec_off, totals);
+}
+
+// The block size getRevivedPackets gives a group (quic_fec_group.cc:264-265): the largest
+// packet it stored, a data packet with its 2-byte prefix, an FEC packet as it is.
+extern "C" int qfec_framed_rx_block_bytes(int k, int m, long long groups, const int* pkt_len,
+                                          const int* ad_len, int ad_len_all, int* bb) {
+    if (k < 1 || m < 1 || groups < 0 || (groups && (!pkt_len || !bb))) return -2;
+    const long long per = (long long)k + m;
+    for (long long g = 0; g < groups; ++g) {
+        long long most = 0;
+        for (long long i = 0; i < per; ++i) {
+            const long long p = g * per + i;
+            const long long tl = pkt_len[p], al = ad_len ? ad_len[p] : ad_len_all;
+            if (tl < 0 || al < 0 || tl - al < 12) continue;   // not received, or no packet
+            most = std::max(most, tl - al - 12 + (i < k ? 2 : 0));
+        }
+        bb[g] = (int)std::min<long long>(most, 0x7fffffffLL);
+    }
+    return 0;
+}
+
 namespace qfec {
 
 int ragged_pack(int k, int m, bool decode, const std::vector<const unsigned char*>& blocks,

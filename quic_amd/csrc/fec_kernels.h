@@ -363,6 +363,24 @@ __host__ __device__ inline bool ragged_encode_rejects(int k, int m, int bb) {
     return m > 1 && k > 1 && (bb & 7) != 0;
 }
 
+// The groups the framed sender rejects (status -3, every pkt_len -1, none of its blocks, parity
+// or packets written): a payload length that has no 14-bit prefix, exceeds its row or does not
+// fit behind the prefix in a block, or a block too small to encode.  len: the group's k payload
+// lengths.  Asked by the frame kernel, by the framed seal and for the status (pp_null.hip), so
+// the three cannot disagree.
+__host__ __device__ inline bool framed_group_rejects(const int32_t* len, int k,
+                                                     long long pay_stride, int bb) {
+    // no early exit: the lanes of a wave ask for different groups, and a loop every lane runs
+    // to its end keeps the control flow uniform (a form that returned at the first bad length
+    // let a bb = 0 group through in the framed seal)
+    bool bad = bb < 8;
+    for (int i = 0; i < k; ++i) {
+        const int l = len[i];
+        bad |= (l < 0) | (l > 0x3fff) | ((pay_stride != 0) & (l > pay_stride)) | (l > bb - 2);
+    }
+    return bad;
+}
+
 struct RaggedView {
     const int32_t* bb;
     const long long* in_off;

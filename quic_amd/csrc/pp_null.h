@@ -47,6 +47,36 @@ hipError_t launch_open_groups_ragged(int k, int m, long long groups, RaggedView 
                                      Rows ad, uint8_t* blocks, uint8_t* rows, int32_t* open_len,
                                      hipStream_t st);
 
+// Framed forms (QuicFecGroup's wire format over the ragged layout).  A
+// data packet's block is prefix || payload || zeros, prefix = (len | pn_len << 14) & 0xffff,
+// little-endian; its wire packet carries the payload alone.  pay: payload row g * k + i, pay.len
+// [G * k] (device array, never null).  pn_len: u8 per packet, or null: pn_all for all.
+// Frame: block (g, i) at data + v.in_off[g] + i * bb[g].  A group framed_group_rejects names
+// (fec_kernels.h) is not written.  eff_bb [G] (may be null) receives bb[g], 0 for a rejected
+// group: the sizes the encode after it runs with; status [G] (may be null) 0 / -3.
+hipError_t launch_frame_blocks_ragged(int k, long long groups, RaggedView v, Rows pay,
+                                      const uint8_t* pn_len, int pn_all, uint8_t* data,
+                                      int32_t* eff_bb, int32_t* status, hipStream_t st);
+// Seal after the frame and the encode: PT of packet (g, i) = payload row g * k + i for i < k,
+// block i - k of parity + v.out_off[g] otherwise.  No packet of a group the frame or the encode
+// rejected is sealed (out.len -1); status [G] (may be null) gets -3 for the frame's.
+hipError_t launch_null_seal_framed(int k, int m, long long groups, RaggedView v, Rows pay,
+                                   const uint8_t* parity, Rows hdr, RowsOut out, int32_t* status,
+                                   hipStream_t st);
+// launch_open_groups_ragged, but a data packet's plaintext goes to slot + 2 behind its prefix
+// (opened length, pn_len [G * (k + m)] or pn_all) and may be at most bb[g] - 2 bytes long.
+hipError_t launch_open_groups_framed(int k, int m, long long groups, RaggedView v, Rows pkt,
+                                     Rows ad, const uint8_t* pn_len, int pn_all, uint8_t* blocks,
+                                     uint8_t* rows, int32_t* open_len, hipStream_t st);
+// After the decode: recovered block (g, j) at rec + v.out_off[g] + j * bb[g] with
+// rec_rows[g * rmax + j] != 255 and status[g] == 0 (status null: every group) -> its payload at
+// rev row g * rmax + j, rev.len its length (clamped to bb[g] - 2), rev_pn_len (may be null) the
+// prefix's top two bits; every other entry, and a payload longer than rev.stride: rev.len -1,
+// nothing else written.  rev.p and rev.stride need no alignment.
+hipError_t launch_extract_revived(int k, int m, long long groups, RaggedView v, const uint8_t* rec,
+                                  const uint8_t* rec_rows, const int32_t* status, RowsOut rev,
+                                  uint8_t* rev_pn_len, hipStream_t st);
+
 // After the decode of an open batch: groups with an unfilled slot get status -3 and no
 // recovered rows.
 hipError_t launch_open_status(int k, int rmax, long long groups, const uint8_t* rows,

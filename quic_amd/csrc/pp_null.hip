@@ -36,6 +36,13 @@
 // lookup that reads bb[g] and the group's byte offset per lane (RaggedRows, RaggedSlots); the
 // uniform instantiations (PtRows, UniSlots) carry no run-time branch for them.  A tile that
 // mixes block sizes runs its window loop to its longest packet.
+//
+// Framed forms (QuicFecGroup's wire format): a data packet's block is
+// prefix || payload || zeros, its wire packet carries the payload alone.  The same bodies with
+// FramedRows (the seal reads payload rows and parity blocks) and FramedSlots (the open places a
+// data plaintext two bytes into its slot and writes the prefix), plus the two kernels that only
+// move bytes through tile_stream: frame_blocks_kernel (payload rows -> blocks) and
+// extract_revived_kernel (recovered blocks -> payload rows).
 #include "fec_kernels.h"
 #include "pp_null.h"
 
@@ -561,9 +568,53 @@ __device__ __forceinline__ bool pt_fits(const RaggedRows& r, long long p, int pl
     return bb >= 1 && pl <= bb && !(r.enc && ragged_encode_rejects(r.ka, r.kb, bb));
 }
 
+// Only the framed seal writes a group status.
+__device__ __forceinline__ void pt_status(const PtRows&, long long) {}
+__device__ __forceinline__ void pt_status(const RaggedRows&, long long) {}
+
+// Rows of the framed sender: packet p = g * (ka + kb) + i reads payload row g * ka + i (pay.len
+// bytes of it: the wire packet carries no prefix) for i < ka, parity block i - ka of group g
+// (bb[g] bytes) otherwise.  No packet of a group the frame kernel rejected
+// (framed_group_rejects) or the encode rejected (ragged_encode_rejects) fits; the first lane of
+// a group the frame rejected writes its status, after the encode wrote one for every group.
+struct FramedRows {
+    Rows pay;
+    const uint8_t* par;
+    const long long* par_off;
+    const int32_t* bb;
+    int32_t* status;
+    int ka, kb;
+};
+
+__device__ __forceinline__ const uint8_t* pt_row(const FramedRows& r, long long p) {
+    const int per = r.ka + r.kb;
+    const long long g = p / per;
+    const int i = (int)(p - g * per);
+    return i < r.ka ? r.pay.p + (g * r.ka + i) * r.pay.stride
+                    : r.par + r.par_off[g] + (i - r.ka) * (long long)r.bb[g];
+}
+__device__ __forceinline__ int pt_len_of(const FramedRows& r, const int32_t*, int, long long p) {
+    const int per = r.ka + r.kb;
+    const long long g = p / per;
+    const int i = (int)(p - g * per);
+    return i < r.ka ? r.pay.len[g * r.ka + i] : r.bb[g];
+}
+__device__ __forceinline__ bool framed_rejects(const FramedRows& r, long long g) {
+    return framed_group_rejects(r.pay.len + g * r.ka, r.ka, r.pay.stride, r.bb[g]);
+}
+__device__ __forceinline__ bool pt_fits(const FramedRows& r, long long p, int) {
+    const long long g = p / (r.ka + r.kb);
+    return !framed_rejects(r, g) && !ragged_encode_rejects(r.ka, r.kb, r.bb[g]);
+}
+__device__ __forceinline__ void pt_status(const FramedRows& r, long long p) {
+    const int per = r.ka + r.kb;
+    const long long g = p / per;
+    if (r.status && p == g * per && framed_rejects(r, g)) r.status[g] = -3;
+}
+
 // One wave seals 64 packets (one per lane): the AD through the lane's own streamer (a few
 // bytes), the plaintext through the wave's LDS tile (tile_stream), then the tag.  R: where the
-// plaintext rows are (PtRows, RaggedRows).
+// plaintext rows are (PtRows, RaggedRows, FramedRows).
 template <class H, class R>
 __global__ __launch_bounds__(64) void null_seal_kernel(
     long long n, const uint8_t* __restrict__ ad, long long ad_stride,
@@ -581,6 +632,7 @@ __global__ __launch_bounds__(64) void null_seal_kernel(
         ok = al >= 0 && pl >= 0 && (ad_stride == 0 || al <= ad_stride) &&
              pt_fits(pr, i, pl) && (long long)al + 12 + pl <= out_stride;
         out_len[i] = ok ? al + 12 + pl : -1;
+        pt_status(pr, i);
     }
     uint8_t* o = out + (ok ? i : 0) * out_stride;
     H h;
@@ -650,13 +702,14 @@ __global__ __launch_bounds__(kPPThreads) void null_open_kernel(
 
 // The open's length checks alone (the tag is checked later): a packet that fails them is
 // rejected whatever its bytes.
+// lim: the longest plaintext the packet's slot takes (the slots' limit()).
 __device__ __forceinline__ bool open_len_ok(const int32_t* __restrict__ pkt_len,
                                             const int32_t* __restrict__ ad_len, int ad_all,
-                                            long long p, int bb, long long pkt_stride) {
+                                            long long p, int lim, long long pkt_stride) {
     const int tl = pkt_len[p];
     const int al = len_of(ad_len, ad_all, p);
     const int cl = tl - al;
-    return tl >= 0 && al >= 0 && cl >= 12 && cl - 12 <= bb && tl <= pkt_stride;
+    return tl >= 0 && al >= 0 && cl >= 12 && cl - 12 <= lim && tl <= pkt_stride;
 }
 
 // The slot FEC packet i (>= k) of group g is written to by the open, before any tag is known:
@@ -664,16 +717,17 @@ __device__ __forceinline__ bool open_len_ok(const int32_t* __restrict__ pkt_len,
 // ascending order as open_assemble_kernel matches them (the j-th available FEC packet fills
 // the j-th hole); -1 when it fills none.  Where a tag check then changes the match,
 // open_assemble_kernel copies the right packet over.
+// dlim, flim: the plaintext limits of the group's data and FEC packets.
 __device__ int fec_pre_slot(const int32_t* __restrict__ pkt_len,
                             const int32_t* __restrict__ ad_len, int ad_all, long long g, int i,
-                            int k, int m, int bb, long long pkt_stride) {
+                            int k, int m, int dlim, int flim, long long pkt_stride) {
     const long long p0 = g * (k + m);
     int j = 0;
 #pragma unroll 4
-    for (int q = k; q < i; ++q) j += open_len_ok(pkt_len, ad_len, ad_all, p0 + q, bb, pkt_stride) ? 1 : 0;
+    for (int q = k; q < i; ++q) j += open_len_ok(pkt_len, ad_len, ad_all, p0 + q, flim, pkt_stride) ? 1 : 0;
 #pragma unroll 8
     for (int x = 0; x < k; ++x) {
-        if (open_len_ok(pkt_len, ad_len, ad_all, p0 + x, bb, pkt_stride)) continue;
+        if (open_len_ok(pkt_len, ad_len, ad_all, p0 + x, dlim, pkt_stride)) continue;
         if (j == 0) return x;
         --j;
     }
@@ -688,6 +742,12 @@ struct UniSlots {
                                              int bb_) const {
         return blocks + (g * k + s) * (long long)bb_;
     }
+    // the longest plaintext a slot of size bb_ takes from a data (or FEC) packet, where in
+    // the slot it starts, and the framing written in front of it: none
+    __device__ __forceinline__ int limit(int bb_, bool) const { return bb_; }
+    __device__ __forceinline__ int lead(bool) const { return 0; }
+    __device__ __forceinline__ void prefix(uint8_t*, long long, int, int, int, int,
+                                           long long) const {}
 };
 // Ragged: group g's [k][bb[g]] at blocks + off[g].  A wave's 64 packets come from several
 // groups, so the size and the offset are per lane.  A group with bb[g] < 1 (and the lanes
@@ -705,12 +765,44 @@ struct RaggedSlots {
                                              int bb_) const {
         return blocks + off[g] + s * (long long)bb_;
     }
+    // the longest plaintext a slot of size bb_ takes from a data (or FEC) packet, where in
+    // the slot it starts, and the framing written in front of it: none
+    __device__ __forceinline__ int limit(int bb_, bool) const { return bb_; }
+    __device__ __forceinline__ int lead(bool) const { return 0; }
+    __device__ __forceinline__ void prefix(uint8_t*, long long, int, int, int, int,
+                                           long long) const {}
+};
+// Framed (QuicFecGroup's stored packets, quic_fec_group.cc:178-183): the ragged slots, but a
+// data packet's plaintext is a payload: it goes two bytes into its slot, behind the prefix
+// len | pn_len << 14 (16 bits, little-endian) that the lane writes itself, so it may be at most
+// bb[g] - 2 bytes long.  An FEC packet's plaintext is a whole block, as in RaggedSlots.
+struct FramedSlots {
+    RaggedSlots r;
+    const uint8_t* pn_len;   // [G * (k + m)], or null: pn_all
+    int pn_all;
+    __device__ __forceinline__ int size(long long g) const { return r.size(g); }
+    __device__ __forceinline__ uint8_t* slot(uint8_t* blocks, long long g, int k, int s,
+                                             int bb_) const {
+        return r.slot(blocks, g, k, s, bb_);
+    }
+    __device__ __forceinline__ int limit(int bb_, bool data) const {
+        return data ? bb_ - 2 : bb_;
+    }
+    __device__ __forceinline__ int lead(bool data) const { return data ? 2 : 0; }
+    // data packet i of group g opened len bytes: the prefix in front of them
+    __device__ __forceinline__ void prefix(uint8_t* blocks, long long g, int k, int i, int bb_,
+                                           int len, long long p) const {
+        uint8_t* s = slot(blocks, g, k, i, bb_);
+        const uint32_t v = (uint32_t)len | ((uint32_t)(pn_len ? pn_len[p] : pn_all) << 14);
+        gst8(s, v);
+        gst8(s + 1, v >> 8);
+    }
 };
 
 // Receiver, grouped: packet p = g * (k + m) + i, one wave per 64 packets; a data packet's
 // plaintext goes to its block slot, zero-padded to bb, through the wave's LDS tile, and so
 // does an FEC packet's, into the hole it fills if the tags change nothing (fec_pre_slot).
-// S: the slots (UniSlots, RaggedSlots).
+// S: the slots (UniSlots, RaggedSlots, FramedSlots).
 template <class H, class S>
 __global__ __launch_bounds__(64) void open_group_kernel(
     int k, int m, S sl, long long n, const uint8_t* __restrict__ pkt, long long pkt_stride,
@@ -722,13 +814,14 @@ __global__ __launch_bounds__(64) void open_group_kernel(
     const long long g = p / per;
     const int i = (int)(p - g * per);
     const int bb = sl.size(g);
+    const int lim = sl.limit(bb, i < k);   // the longest plaintext this packet's slot takes
     bool ok = false;
     int al = 0, cl = 0;
     if (p < n) {
         const int tl = pkt_len[p];
         al = len_of(ad_len, ad_all, p);
         cl = tl - al;
-        ok = tl >= 0 && al >= 0 && cl >= 12 && cl - 12 <= bb && tl <= pkt_stride;
+        ok = tl >= 0 && al >= 0 && cl >= 12 && cl - 12 <= lim && tl <= pkt_stride;
         if (!ok) open_len[p] = -1;
     }
     const uint8_t* pp = pkt + (ok ? p : 0) * pkt_stride;
@@ -738,10 +831,14 @@ __global__ __launch_bounds__(64) void open_group_kernel(
     Sink s;
     if (ok) span<true, false, 1>(h, s, pp, al);
     const int slot = !ok ? -1 : i < k ? i
-                   : fec_pre_slot(pkt_len, ad_len, ad_all, g, i, k, m, bb, pkt_stride);
+                   : fec_pre_slot(pkt_len, ad_len, ad_all, g, i, k, m, sl.limit(bb, true),
+                                  sl.limit(bb, false), pkt_stride);
+    const int lead = sl.lead(i < k);
     tile_stream(h, ok ? c + 12 : nullptr, ok ? cl - 12 : 0,
-                slot >= 0 ? sl.slot(blocks, g, k, slot, bb) : nullptr, slot >= 0 ? bb : 0, smem);
+                slot >= 0 ? sl.slot(blocks, g, k, slot, bb) + lead : nullptr,
+                slot >= 0 ? bb - lead : 0, smem);
     if (!ok) return;
+    if (i < k) sl.prefix(blocks, g, k, i, bb, cl - 12, p);
     uint32_t t0, t1, t2;
     h.tag(t0, t1, t2);
     open_len[p] = tag_matches(c, t0, t1, t2) ? cl - 12 : -1;
@@ -822,14 +919,16 @@ __global__ __launch_bounds__(kAsmWaves * 64) void open_assemble_kernel(
     int npa = 0, nph = 0;
     for (int b0 = 0; b0 < m; b0 += 64) {
         const int j = b0 + lane;
-        const bool v = j < m && open_len_ok(pkt_len, ad_len, ad_all, g * per + k + j, bb, pkt_stride);
+        const bool v = j < m && open_len_ok(pkt_len, ad_len, ad_all, g * per + k + j,
+                                            sl.limit(bb, false), pkt_stride);
         const unsigned long long bal = __ballot(v);
         if (j < m) prank[w][j] = v ? (uint8_t)(npa + __popcll(bal & below)) : (uint8_t)255;
         npa += __popcll(bal);
     }
     for (int b0 = 0; b0 < k; b0 += 64) {
         const int i = b0 + lane;
-        const bool miss = i < k && !open_len_ok(pkt_len, ad_len, ad_all, g * per + i, bb, pkt_stride);
+        const bool miss = i < k && !open_len_ok(pkt_len, ad_len, ad_all, g * per + i,
+                                                sl.limit(bb, true), pkt_stride);
         const unsigned long long bal = __ballot(miss);
         if (miss) phole[w][nph + __popcll(bal & below)] = (uint8_t)i;
         nph += __popcll(bal);
@@ -863,6 +962,84 @@ __global__ __launch_bounds__(kPPThreads) void open_status_kernel(long long group
     if (!unfilled) return;
     if (status) status[g] = -3;
     for (int j = 0; j < rmax; ++j) rec_rows[g * rmax + j] = 255;
+}
+
+// tile_stream with nothing to hash: the two kernels below only move bytes.
+struct NoHash {
+    __device__ __forceinline__ void byte(uint32_t) {}
+    __device__ __forceinline__ void word(uint32_t) {}
+};
+
+// Sender framing (appendLenToPayload, quic_fec_group.cc:109-121, and the padding of
+// getRedundancyPackets, :344-352): one lane per data packet q = g * k + i, 64 per wave.  Block
+// (g, i) at data + data_off[g] + i * bb[g] becomes prefix || payload || zeros: the payload
+// through the wave's tile, two bytes in, the prefix from the lane.  Nothing of a group
+// framed_group_rejects names is written.  The group's first lane writes eff[g] (null: not
+// wanted) = bb[g], or 0 for a rejected group, the size the encode that follows runs with, and
+// status[g] (null: not wanted) = 0 / -3.
+__global__ __launch_bounds__(64) __attribute__((flatten)) void frame_blocks_kernel(
+    int k, long long n, const uint8_t* __restrict__ pay, long long pay_stride,
+    const int32_t* __restrict__ pay_len, const uint8_t* __restrict__ pn_len, int pn_all,
+    uint8_t* data, const long long* __restrict__ data_off, const int32_t* __restrict__ bbs,
+    int32_t* eff, int32_t* status) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const long long q = (long long)blockIdx.x * 64 + threadIdx.x;
+    const long long g = q / k;
+    const int i = (int)(q - g * k);
+    bool ok = false;
+    int len = 0, bb = 0;
+    if (q < n) {
+        bb = bbs[g];
+        ok = !framed_group_rejects(pay_len + g * k, k, pay_stride, bb);
+        if (i == 0) {
+            if (eff) eff[g] = ok ? bb : 0;
+            if (status) status[g] = ok ? 0 : -3;
+        }
+        if (ok) len = pay_len[q];
+    }
+    uint8_t* blk = ok ? data + data_off[g] + i * (long long)bb : nullptr;
+    NoHash h;
+    tile_stream(h, ok ? pay + q * pay_stride : nullptr, len, ok ? blk + 2 : nullptr,
+                ok ? bb - 2 : 0, smem);
+    if (!ok) return;
+    const uint32_t v = (uint32_t)len | ((uint32_t)(pn_len ? pn_len[q] : pn_all) << 14);
+    gst8(blk, v);
+    gst8(blk + 1, v >> 8);
+}
+
+// Receiver framing (getRevivedPackets, quic_fec_group.cc:287-292): one lane per recovered
+// block q = g * rmax + j.  Where rec_rows[q] != 255 and the group's status is 0 (null: every
+// group's), the block's prefix v gives len = min(v & 0x3fff, bb[g] - 2) (the reference reads
+// past the block there; fec_group.cpp clamps the same way) and pn_len = v >> 14, and exactly
+// len bytes go from block + 2 to rev row q.  Every other entry, and a len above rev_stride:
+// rev_len -1 and nothing else written.
+__global__ __launch_bounds__(64) __attribute__((flatten)) void extract_revived_kernel(
+    int rmax, long long n, const uint8_t* __restrict__ rec, const long long* __restrict__ rec_off,
+    const int32_t* __restrict__ bbs, const uint8_t* __restrict__ rec_rows,
+    const int32_t* __restrict__ status, uint8_t* rev, long long rev_stride, int32_t* rev_len,
+    uint8_t* rev_pn_len) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const long long q = (long long)blockIdx.x * 64 + threadIdx.x;
+    const long long g = q / rmax;
+    const int j = (int)(q - g * rmax);
+    bool take = false;
+    int len = 0;
+    const uint8_t* blk = nullptr;
+    if (q < n) {
+        const int bb = bbs[g];
+        if (rec_rows[q] != 255 && (!status || status[g] == 0) && bb >= 2) {
+            blk = rec + rec_off[g] + j * (long long)bb;
+            const uint32_t v = blk[0] | ((uint32_t)blk[1] << 8);
+            len = min((int)(v & 0x3fffu), bb - 2);
+            take = len <= rev_stride;
+            if (take && rev_pn_len) rev_pn_len[q] = (uint8_t)(v >> 14);
+        }
+        rev_len[q] = take ? len : -1;
+    }
+    if (!take) len = 0;
+    NoHash h;
+    tile_stream(h, take ? blk + 2 : nullptr, len, take ? rev + q * rev_stride : nullptr, len,
+                smem);
 }
 
 unsigned pp_grid(long long n) {
@@ -952,6 +1129,46 @@ hipError_t launch_open_groups_ragged(int k, int m, long long groups, RaggedView 
                                      hipStream_t st) {
     return open_go("open_group_kernel<ragged> + open_assemble_kernel<ragged>", k, m, groups,
                    RaggedSlots{v.bb, v.in_off, groups}, pkt, ad, blocks, rows, open_len, st);
+}
+
+hipError_t launch_frame_blocks_ragged(int k, long long groups, RaggedView v, Rows pay,
+                                      const uint8_t* pn_len, int pn_all, uint8_t* data,
+                                      int32_t* eff_bb, int32_t* status, hipStream_t st) {
+    const long long n = groups * k;
+    if (n <= 0) return hipSuccess;
+    if (!pp_grid_ok(n)) return hipErrorInvalidValue;
+    note_kernel("frame_blocks_kernel");
+    qlaunch(frame_blocks_kernel, dim3(tile_grid(n)), dim3(64), kTileBytes, st, k, n, pay.p,
+            pay.stride, pay.len, pn_len, pn_all, data, v.in_off, v.bb, eff_bb, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_null_seal_framed(int k, int m, long long groups, RaggedView v, Rows pay,
+                                   const uint8_t* parity, Rows hdr, RowsOut out, int32_t* status,
+                                   hipStream_t st) {
+    return seal_go("null_seal_kernel<framed>", groups * (k + m), hdr,
+                   FramedRows{pay, parity, v.out_off, v.bb, status, k, m}, nullptr, 0, out, st);
+}
+
+hipError_t launch_open_groups_framed(int k, int m, long long groups, RaggedView v, Rows pkt,
+                                     Rows ad, const uint8_t* pn_len, int pn_all, uint8_t* blocks,
+                                     uint8_t* rows, int32_t* open_len, hipStream_t st) {
+    return open_go("open_group_kernel<framed> + open_assemble_kernel<framed>", k, m, groups,
+                   FramedSlots{RaggedSlots{v.bb, v.in_off, groups}, pn_len, pn_all}, pkt, ad,
+                   blocks, rows, open_len, st);
+}
+
+hipError_t launch_extract_revived(int k, int m, long long groups, RaggedView v, const uint8_t* rec,
+                                  const uint8_t* rec_rows, const int32_t* status, RowsOut rev,
+                                  uint8_t* rev_pn_len, hipStream_t st) {
+    const int rmax = std::min(k, m);
+    const long long n = groups * rmax;
+    if (n <= 0) return hipSuccess;
+    if (!pp_grid_ok(n)) return hipErrorInvalidValue;
+    note_kernel("extract_revived_kernel");
+    qlaunch(extract_revived_kernel, dim3(tile_grid(n)), dim3(64), kTileBytes, st, rmax, n, rec,
+            v.out_off, v.bb, rec_rows, status, rev.p, rev.stride, rev.len, rev_pn_len);
+    return hipGetLastError();
 }
 
 hipError_t launch_open_status(int k, int rmax, long long groups, const uint8_t* rows,

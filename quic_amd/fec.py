@@ -367,6 +367,127 @@ class FecEngine:
         if rc:
             raise FecError(rc, "qfec_open_decode_batch_ragged")
 
+    # framed groups: QuicFecGroup's wire format around the ragged protected calls
+    # (include/quic_fec.h, "Framed groups")
+    @staticmethod
+    def _framed_args(G, rows, arrays):
+        """Dense per-row arguments of a framed call: `arrays` maps a name to (tensor or int or
+        None, dtype, 1 for a [rows] array / 2 for [rows][stride] rows)."""
+        for name, (t, dtype, dim) in arrays.items():
+            if t is None or isinstance(t, int):
+                continue
+            if t.dtype != dtype:
+                raise TypeError(f"{name}: dtype {t.dtype}, expected {dtype}")
+            if t.dim() != dim or t.shape[0] != rows:
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {rows} rows (G = {G})")
+
+    @staticmethod
+    def _pn(pn_len):
+        """(array pointer, scalar) of a pn_len argument: a uint8 device tensor or an int."""
+        if isinstance(pn_len, int):
+            return None, pn_len
+        return _dptr(pn_len), 0
+
+    def frame_blocks_ragged(self, k, bb, pay, pay_len, pn_len, data, data_off, status=None,
+                            stream=None):
+        """Blocks from payload rows: block (g, i) at data + data_off[g] + i*bb[g] becomes
+        prefix || pay[g*k+i][:pay_len] || zeros.  pay uint8 [G*k][stride], pay_len int32 [G*k],
+        pn_len uint8 [G*k] or an int; status: optional int32 [G] (-3 for a rejected group, of
+        which nothing is written)."""
+        import torch
+        G = FecEngine._ragged_args(bb, data_off)
+        FecEngine._framed_args(G, G * k, {"pay": (pay, torch.uint8, 2),
+                                     "pay_len": (pay_len, torch.int32, 1),
+                                     "pn_len": (pn_len, torch.uint8, 1)})
+        if status is not None and (status.dtype != torch.int32 or status.shape != (G,)):
+            raise TypeError("status must be an int32 [G] device tensor")
+        pn, pn_all = self._pn(pn_len)
+        rc = self.lib.qfec_frame_blocks_batch_ragged(
+            self._h, k, G, _dptr(bb), _dptr(pay), pay.stride(0), _dptr(pay_len), pn, pn_all,
+            _dptr(data), _dptr(data_off), _dptr(status), _stream(stream, data))
+        if rc:
+            raise FecError(rc, "qfec_frame_blocks_batch_ragged")
+
+    def extract_revived_ragged(self, k, m, bb, rec, rec_off, rec_rows, status, rev, rev_len,
+                               rev_pn_len=None, stream=None):
+        """Revived payloads from recovered blocks: rev [G*rmax][stride] row g*rmax+j receives the
+        payload of recovered block j of group g, rev_len int32 [G*rmax] its length (-1: no such
+        block, or longer than the row), rev_pn_len uint8 [G*rmax] the prefix's top two bits.
+        status: int32 [G] or None (every group taken as decoded)."""
+        import torch
+        G = FecEngine._ragged_args(bb, rec_off)
+        rmax = min(k, m)
+        FecEngine._framed_args(G, G * rmax, {"rev": (rev, torch.uint8, 2),
+                                        "rev_len": (rev_len, torch.int32, 1),
+                                        "rev_pn_len": (rev_pn_len, torch.uint8, 1)})
+        for name, t, dtype, shape in (("rec_rows", rec_rows, torch.uint8, (G, rmax)),
+                                      ("status", status, torch.int32, (G,))):
+            if t is not None and (t.dtype != dtype or tuple(t.shape) != shape):
+                raise TypeError(f"{name} must be a {dtype} {shape} device tensor")
+        rc = self.lib.qfec_extract_revived_batch_ragged(
+            self._h, k, m, G, _dptr(bb), _dptr(rec), _dptr(rec_off), _dptr(rec_rows),
+            _dptr(status), _dptr(rev), rev.stride(0), _dptr(rev_len), _dptr(rev_pn_len),
+            _stream(stream, rec))
+        if rc:
+            raise FecError(rc, "qfec_extract_revived_batch_ragged")
+
+    def frame_encode_seal_ragged(self, k, m, bb, data, data_off, parity, par_off, hdr, hdr_len,
+                                 pay, pay_len, pn_len, pkt, pkt_len, status=None, stream=None):
+        """Sender: payload rows in, wire packets of the reference's format out.  Frames the
+        blocks into data (an output), encodes into parity, seals data packet p = g*(k+m)+i as
+        hdr[p] || tag12 || payload and FEC packet p as hdr[p] || tag12 || parity block.  pay,
+        pay_len, pn_len as in frame_blocks_ragged; hdr, pkt, pkt_len dense by packet as in
+        seal_groups_ragged; status: optional int32 [G] (0, -1 encode rejected, -3 framing
+        rejected)."""
+        import torch
+        G = FecEngine._ragged_pp_args(k, m, bb, (data_off, par_off), {
+            "hdr": (hdr, torch.uint8, 2), "hdr_len": (hdr_len, torch.int32, 1),
+            "pkt": (pkt, torch.uint8, 2), "pkt_len": (pkt_len, torch.int32, 1)})
+        FecEngine._framed_args(G, G * k, {"pay": (pay, torch.uint8, 2),
+                                     "pay_len": (pay_len, torch.int32, 1),
+                                     "pn_len": (pn_len, torch.uint8, 1)})
+        if status is not None and (status.dtype != torch.int32 or status.shape != (G,)):
+            raise TypeError("status must be an int32 [G] device tensor")
+        h, h_all = self._lens(hdr_len)
+        pn, pn_all = self._pn(pn_len)
+        rc = self.lib.qfec_frame_encode_seal_groups_batch_ragged(
+            self._h, k, m, G, _dptr(bb), _dptr(data), _dptr(data_off), _dptr(parity),
+            _dptr(par_off), _dptr(hdr), hdr.stride(0) if hdr is not None else 0, h, h_all,
+            _dptr(pay), pay.stride(0), _dptr(pay_len), pn, pn_all, _dptr(pkt), pkt.stride(0),
+            _dptr(pkt_len), _dptr(status), _stream(stream, data))
+        if rc:
+            raise FecError(rc, "qfec_frame_encode_seal_groups_batch_ragged")
+
+    def open_decode_extract_ragged(self, k, m, bb, pkt, pkt_len, ad_len, pn_len, blocks,
+                                   blocks_off, rows, open_len, rec, rec_off, rec_rows, rev,
+                                   rev_len, rev_pn_len=None, status=None, stream=None):
+        """Receiver: wire packets in, revived payloads out.  open_decode_ragged with a data
+        packet's plaintext placed behind its prefix (pn_len uint8 [G*(k+m)] or an int), then
+        extract_revived_ragged into rev / rev_len / rev_pn_len."""
+        import torch
+        G = FecEngine._ragged_pp_args(k, m, bb, (blocks_off, rec_off), {
+            "pkt": (pkt, torch.uint8, 2), "pkt_len": (pkt_len, torch.int32, 1),
+            "ad_len": (ad_len, torch.int32, 1), "open_len": (open_len, torch.int32, 1),
+            "pn_len": (pn_len, torch.uint8, 1)})
+        rmax = min(k, m)
+        FecEngine._framed_args(G, G * rmax, {"rev": (rev, torch.uint8, 2),
+                                        "rev_len": (rev_len, torch.int32, 1),
+                                        "rev_pn_len": (rev_pn_len, torch.uint8, 1)})
+        for name, t, dtype, shape in (("rows", rows, torch.uint8, (G, k)),
+                                      ("rec_rows", rec_rows, torch.uint8, (G, rmax)),
+                                      ("status", status, torch.int32, (G,))):
+            if t is not None and (t.dtype != dtype or tuple(t.shape) != shape):
+                raise TypeError(f"{name} must be a {dtype} {shape} device tensor")
+        a, a_all = self._lens(ad_len)
+        pn, pn_all = self._pn(pn_len)
+        rc = self.lib.qfec_open_decode_extract_batch_ragged(
+            self._h, k, m, G, _dptr(bb), _dptr(pkt), pkt.stride(0), _dptr(pkt_len), a, a_all, pn,
+            pn_all, _dptr(blocks), _dptr(blocks_off), _dptr(rows), _dptr(open_len), _dptr(rec),
+            _dptr(rec_off), _dptr(rec_rows), _dptr(status), _dptr(rev), rev.stride(0),
+            _dptr(rev_len), _dptr(rev_pn_len), _stream(stream, pkt))
+        if rc:
+            raise FecError(rc, "qfec_open_decode_extract_batch_ragged")
+
     # host-pointer batch calls (synchronous; include H2D/D2H)
     def encode_host(self, k, m, block_bytes, data):
         data = np.ascontiguousarray(data, dtype=np.uint8)
@@ -568,6 +689,52 @@ def ragged_layout(k, m, bb):
     if rc:
         raise ValueError(f"qfec_ragged_layout: rc={rc} (k={k} m={m}, a size < 1 or overflow)")
     return offs[0], offs[1], offs[2], tuple(int(t) for t in totals)
+
+
+def framed_layout(k, m, pay_len):
+    """The block sizes and the packed layout of framed groups (qfec_framed_layout; host only):
+    pay_len int32 [G*k] -> (bb, data_off, par_off, rec_off, totals) with
+    bb[g] = roundup8(max(pay_len of group g) + 2).  ValueError for a length outside
+    [0, 0x3fff]."""
+    pay_len = np.ascontiguousarray(pay_len, dtype=np.int32).reshape(-1)
+    if pay_len.size % k:
+        raise ValueError("pay_len must hold k lengths per group")
+    G = pay_len.size // k
+    bb = np.zeros(G, np.int32)
+    offs = [np.zeros(G, np.int64) for _ in range(3)]
+    totals = np.zeros(3, np.int64)
+    rc = load().qfec_framed_layout(k, m, G, pay_len.ctypes.data_as(ctypes.c_void_p),
+                                   bb.ctypes.data_as(ctypes.c_void_p),
+                                   *[o.ctypes.data_as(ctypes.c_void_p) for o in offs],
+                                   totals.ctypes.data_as(ctypes.c_void_p))
+    if rc:
+        raise ValueError(f"qfec_framed_layout: rc={rc} (k={k} m={m}, a length outside "
+                         "[0, 0x3fff] or overflow)")
+    return bb, offs[0], offs[1], offs[2], tuple(int(t) for t in totals)
+
+
+def framed_rx_block_bytes(k, m, pkt_len, ad_len):
+    """The block size the reference's receiver gives each group (qfec_framed_rx_block_bytes;
+    host only): pkt_len int32 [G*(k+m)] (< 0: not received), ad_len an int32 array of the same
+    shape or an int -> bb int32 [G], the largest stored packet (a data packet's plaintext + 2, an
+    FEC packet's plaintext), 0 for a group that received nothing."""
+    pkt_len = np.ascontiguousarray(pkt_len, dtype=np.int32).reshape(-1)
+    if pkt_len.size % (k + m):
+        raise ValueError("pkt_len must hold k + m lengths per group")
+    G = pkt_len.size // (k + m)
+    if isinstance(ad_len, (int, np.integer)):
+        a, a_all = None, int(ad_len)
+    else:
+        ad_len = np.ascontiguousarray(ad_len, dtype=np.int32).reshape(-1)
+        if ad_len.size != pkt_len.size:
+            raise ValueError("ad_len must hold one length per packet")
+        a, a_all = ad_len.ctypes.data_as(ctypes.c_void_p), 0
+    bb = np.zeros(G, np.int32)
+    rc = load().qfec_framed_rx_block_bytes(k, m, G, pkt_len.ctypes.data_as(ctypes.c_void_p), a,
+                                           a_all, bb.ctypes.data_as(ctypes.c_void_p))
+    if rc:
+        raise ValueError(f"qfec_framed_rx_block_bytes: rc={rc} (k={k} m={m})")
+    return bb
 
 
 def _hcheck_ragged_one(n_blocks, bb_h, buf_h, off_h, name):

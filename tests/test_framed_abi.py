@@ -1,0 +1,213 @@
+"""CPU: the framed entry points exist (library, header, ctypes table), the two host helpers
+agree with tests/ref_framing.py's block size rules, the wrappers check their arrays before any
+call, and the cases tests/test_gpu_framed.py runs on the GPU are what they claim to be (built
+from the oracle and ref_framing alone)."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from quic_amd import _lib, fec
+from tests import ref_framing as R
+from tests import test_gpu_framed as T
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOLS = ["qfec_framed_layout", "qfec_framed_rx_block_bytes", "qfec_frame_blocks_batch_ragged",
+           "qfec_extract_revived_batch_ragged", "qfec_frame_encode_seal_groups_batch_ragged",
+           "qfec_open_decode_extract_batch_ragged"]
+
+
+def test_symbols_exported_and_declared():
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True,
+                         text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
+    with open(os.path.join(ROOT, "include", "quic_fec.h")) as f:
+        text = f.read()
+    declared = set(re.findall(r"^QFEC_API\s+[\w\s\*]*?\b(\w+)\s*\(", text, re.M))
+    for s in SYMBOLS:
+        assert s in exported, s
+        assert s in declared, s
+        assert s in _lib.SIGNATURES, s
+    for name in ("frame_blocks_kernel", "null_seal_kernel<framed>", "open_group_kernel<framed>",
+                 "open_assemble_kernel<framed>", "extract_revived_kernel"):
+        assert name in text, name
+    for name in ("framed_layout", "framed_rx_block_bytes"):
+        assert callable(getattr(fec, name))
+    for name in ("frame_encode_seal_ragged", "open_decode_extract_ragged", "frame_blocks_ragged",
+                 "extract_revived_ragged"):
+        assert callable(getattr(fec.FecEngine, name))
+
+
+def test_null_context_is_minus_two():
+    L = _lib.load()
+    assert L.qfec_frame_blocks_batch_ragged(None, 10, 0, None, None, 0, None, None, 1, None, None,
+                                            None, None) == -2
+    assert L.qfec_extract_revived_batch_ragged(None, 10, 1, 0, None, None, None, None, None, None,
+                                               0, None, None, None) == -2
+    assert L.qfec_frame_encode_seal_groups_batch_ragged(
+        None, 10, 1, 0, None, None, None, None, None, None, 0, None, 0, None, 0, None, None, 1,
+        None, 1400, None, None, None) == -2
+    assert L.qfec_open_decode_extract_batch_ragged(
+        None, 10, 1, 0, None, None, 1400, None, None, 16, None, 1, None, None, None, None, None,
+        None, None, None, None, 0, None, None, None) == -2
+
+
+def test_framed_layout_vs_reference(oracle):
+    """bb agrees with ref_framing.redundancy's block size (the length of its parity packets) for
+    random length sets; the offsets are qfec_ragged_layout's for the same bb."""
+    rng = np.random.default_rng(1)
+    for k, m in ((5, 5), (10, 1), (3, 2)):
+        G = 6
+        lens = rng.integers(0, 1400, G * k).astype(np.int32)
+        lens[0] = 0x3fff
+        bb, d_off, p_off, r_off, totals = fec.framed_layout(k, m, lens)
+        for g in range(G):
+            sent = [(T.BASE + i, bytes(int(lens[g * k + i])), 1) for i in range(k)]
+            red, rc = R.redundancy(oracle, k, m, T.BASE, sent)
+            assert rc == 0 and {len(d) for _, d, _ in red} == {int(bb[g])}
+        e_d, e_p, e_r, e_tot = fec.ragged_layout(k, m, bb)
+        for got, exp in ((d_off, e_d), (p_off, e_p), (r_off, e_r)):
+            np.testing.assert_array_equal(got, exp)
+        assert totals == e_tot
+
+
+@pytest.mark.parametrize("lens,bb", [([0, 0, 0], 8), ([6, 0, 1], 8), ([7, 6, 0], 16),
+                                     ([1350, 3, 1349], 1352), ([0x3fff, 0, 0], 16392)])
+def test_framed_layout_pinned(lens, bb):
+    got = fec.framed_layout(3, 2, np.array(lens, np.int32))[0]
+    assert got.tolist() == [bb]
+
+
+def test_framed_layout_rejects_lengths():
+    for bad in (0x4000, -1):
+        with pytest.raises(ValueError):
+            fec.framed_layout(3, 2, np.array([5, bad, 7], np.int32))
+        lens = np.array([5, 5, 5, 5, bad, 5], np.int32)
+        bb = np.zeros(2, np.int32)
+        assert _lib.load().qfec_framed_layout(
+            3, 2, 2, lens.ctypes.data_as(ctypes.c_void_p), bb.ctypes.data_as(ctypes.c_void_p),
+            None, None, None, None) == -2
+    with pytest.raises(ValueError):
+        fec.framed_layout(3, 2, np.zeros(5, np.int32))         # not k lengths per group
+
+
+def test_framed_rx_block_bytes_vs_reference(oracle):
+    """Agrees with the bb inside ref_framing.revive (the largest stored packet) for receive sets
+    with FEC packets and without them; a group with nothing received gives 0."""
+    k, m, G = 5, 3, 8
+    rng = np.random.default_rng(2)
+    per = k + m
+    ad = rng.choice([0, 13, 16], G * per).astype(np.int32)
+    pt = rng.integers(0, 1351, G * per).astype(np.int32)
+    for g in range(G):
+        pt[g * per + k:(g + 1) * per] = T.up8(int(pt[g * per:g * per + k].max()) + 2)
+    pkt_len = ad + 12 + pt
+    gone = rng.random(G * per) < 0.3
+    gone[1 * per + k:2 * per] = True                           # group 1: no FEC packet
+    gone[2 * per:3 * per] = True                               # group 2: nothing at all
+    gone[3 * per:3 * per + k] = True                           # group 3: FEC packets only
+    pkt_len[gone] = -1
+    bb = fec.framed_rx_block_bytes(k, m, pkt_len, ad)
+    for g in range(G):
+        stored = [len(R.prefix(bytes(int(pt[g * per + i])), 1)) if i < k else int(pt[g * per + i])
+                  for i in range(per) if not gone[g * per + i]]
+        assert bb[g] == (max(stored) if stored else 0), g
+    assert bb[2] == 0 and bb[3] == pt[3 * per + k]
+    # one associated-data length for every packet
+    bb16 = fec.framed_rx_block_bytes(k, m, np.where(gone, -1, 16 + 12 + pt), 16)
+    np.testing.assert_array_equal(bb16, bb)
+    # a packet too short to hold a tag is not a packet
+    short = np.full(per, -1, np.int32)
+    short[0] = 16 + 11
+    assert fec.framed_rx_block_bytes(k, m, short, 16).tolist() == [0]
+
+
+def test_wrappers_check_arrays_before_the_call():
+    """dtype and rows of the payload, pn_len and revived arrays: the engine is never touched
+    (None), so a wrong argument cannot reach the library."""
+    import torch
+    k, m, G = 10, 1, 3
+    n, rmax = G * (k + m), 1
+    u8, i32, i64 = torch.uint8, torch.int32, torch.int64
+    bb = torch.full((G,), 1352, dtype=i32)
+    off = torch.arange(G, dtype=i64) * 16000
+    buf = torch.zeros(G * 16000, dtype=u8)
+    hdr, pkt = torch.zeros((n, 16), dtype=u8), torch.zeros((n, 1400), dtype=u8)
+    lens, plens = torch.zeros(n, dtype=i32), torch.zeros(G * k, dtype=i32)
+    pay, pn = torch.zeros((G * k, 1351), dtype=u8), torch.ones(G * k, dtype=u8)
+    good = dict(bb=bb, off=off, hdr=hdr, hdr_len=lens, pay=pay, pay_len=plens, pn=pn, pkt=pkt,
+                pkt_len=lens, st=torch.zeros(G, dtype=i32))
+    bad = [dict(bb=bb.to(i64)), dict(off=off[:-1]), dict(pay=pay[:-1]), dict(pay=pay.to(torch.int8)),
+           dict(pay_len=plens[:-1]), dict(pay_len=plens.to(i64)), dict(pn=pn[:-1]),
+           dict(pn=pn.to(i32)), dict(pkt=pkt[:-1]), dict(pkt_len=lens.to(i64)),
+           dict(hdr_len=lens[:-1]), dict(st=torch.zeros(G + 1, dtype=i32))]
+    for b in bad:
+        a = dict(good)
+        a.update(b)
+        with pytest.raises((TypeError, ValueError)):
+            fec.FecEngine.frame_encode_seal_ragged(None, k, m, a["bb"], buf, a["off"], buf,
+                                                   a["off"], a["hdr"], a["hdr_len"], a["pay"],
+                                                   a["pay_len"], a["pn"], a["pkt"], a["pkt_len"],
+                                                   status=a["st"])
+        if not set(b) & {"hdr_len", "pkt", "pkt_len"}:
+            with pytest.raises((TypeError, ValueError)):
+                fec.FecEngine.frame_blocks_ragged(None, k, a["bb"], a["pay"], a["pay_len"],
+                                                  a["pn"], buf, a["off"], status=a["st"])
+    rev, rl = torch.zeros((G * rmax, 1351), dtype=u8), torch.zeros(G * rmax, dtype=i32)
+    rpn = torch.zeros(G * rmax, dtype=u8)
+    good = dict(bb=bb, pkt=pkt, pkt_len=lens, ad_len=16, pn=torch.ones(n, dtype=u8), off=off,
+                rows=torch.zeros((G, k), dtype=u8), ol=lens, rr=torch.zeros((G, rmax), dtype=u8),
+                rev=rev, rl=rl, rpn=rpn, st=torch.zeros(G, dtype=i32))
+    bad = [dict(bb=bb[:-1]), dict(off=off.to(i32)), dict(pkt=pkt[:-1]), dict(pn=pn),
+           dict(pn=torch.ones(n, dtype=i32)), dict(ol=lens[:-1]), dict(rev=rev[:-1]),
+           dict(rev=rev.to(torch.int8)), dict(rl=rl.to(i64)), dict(rl=torch.zeros(G + 1, dtype=i32)),
+           dict(rpn=rpn.to(i32)), dict(rr=torch.zeros((G, rmax + 1), dtype=u8)),
+           dict(st=torch.zeros(G, dtype=i64))]
+    for b in bad:
+        a = dict(good)
+        a.update(b)
+        with pytest.raises((TypeError, ValueError)):
+            fec.FecEngine.open_decode_extract_ragged(
+                None, k, m, a["bb"], a["pkt"], a["pkt_len"], a["ad_len"], a["pn"], buf, a["off"],
+                a["rows"], a["ol"], buf, a["off"], a["rr"], a["rev"], a["rl"],
+                rev_pn_len=a["rpn"], status=a["st"])
+        if set(b) & {"bb", "off", "rev", "rl", "rpn", "rr", "st"}:
+            with pytest.raises((TypeError, ValueError)):
+                fec.FecEngine.extract_revived_ragged(None, k, m, a["bb"], buf, a["off"], a["rr"],
+                                                     a["st"], a["rev"], a["rl"], a["rpn"])
+
+
+@pytest.mark.parametrize("k,m", sorted(T.SHAPES))
+def test_gpu_cases_are_what_they_claim(oracle, k, m):
+    """The GPU tests' batches, from the oracle and ref_framing alone.  build_send asserts that
+    every group's block size and parity are ref_framing.redundancy's; build_recv asserts each
+    kind's outcome and that every revived payload is the lost one.  Here: the shapes, the
+    lengths and the tiles."""
+    G = T.SHAPES[(k, m)]
+    s = T.send_case(oracle, k, m)
+    c = T.recv_case(oracle, k, m)
+    assert s["G"] == G and s["n"] == G * (k + m)
+    assert set(s["pay_len"].tolist()) == set(T.LENS)
+    np.testing.assert_array_equal(s["bb"], fec.framed_layout(k, m, s["pay_len"])[0])
+    assert set(s["hdr_len"].tolist()) == set(T.HDR_LENS)
+    assert s["pay_stride"] in (1351, 1400)
+    if (k, m) not in T.PN_ALL:
+        assert set(s["pn"].tolist()) == set(T.PN)
+    # a tile of 64 packets mixes block sizes, groups straddle tiles, the last tile is partial
+    per = k + m
+    assert len({s["bbs"][p // per] for p in range(min(64, s["n"]))}) > 1
+    if 64 % per:
+        assert any((g * per) // 64 != ((g + 1) * per - 1) // 64 for g in range(G))
+    assert s["n"] % 64 != 0 and (G * k) % 64 != 0
+    # the receiver: every kind the shape has room for, lost packets recoverable unless 'unrec'
+    assert set(c["kinds"]) >= {"loss", "tagfail", "unrec", "nofec", "tamper"}
+    for g, kind in enumerate(c["kinds"]):
+        recoverable = kind != "unrec" and not (kind == "tagfail" and m == 1)
+        assert (c["status"][g] == 0) == recoverable, (g, kind)
+        if recoverable:
+            got = [int(x) for x in c["rec_rows"][g] if x != 255]
+            assert got == c["lost"][g]
+    assert (c["rbb"] % 8 != 0).any() and (c["rbb"] == s["bb"]).any()

@@ -134,6 +134,22 @@ def run_extra(k, m):
     call("r-open", lambda: eng.open_decode_ragged(
         k, m, d["bb"], d["pkt"], d["pkt_len"], HDR, d["rblocks"], d["d_off"], d["rows"],
         d["open_len"], d["rrec"], d["r_off"], d["rec_rows"], d["status"]))
+    # the framed paths: payloads of RAGGED_BB[g] - 2 bytes (the group of 12 frames, and the encode
+    # rejects it), the frame alone, frame + encode + seal, open + decode + extract, the extract
+    pay = torch.zeros((G * k, bb), dtype=torch.uint8, device="cuda")
+    pay_len = (bbs.repeat_interleave(k) - 2).to("cuda")
+    rev = torch.zeros((G * rmax, bb), dtype=torch.uint8, device="cuda")
+    rev_len = torch.zeros(G * rmax, dtype=torch.int32, device="cuda")
+    call("f-frame", lambda: eng.frame_blocks_ragged(k, d["bb"], pay, pay_len, 1, d["rdata"],
+                                                    d["d_off"], d["status"]))
+    call("f-seal", lambda: eng.frame_encode_seal_ragged(
+        k, m, d["bb"], d["rdata"], d["d_off"], d["rparity"], d["p_off"], d["hdr"], HDR, pay,
+        pay_len, 1, d["pkt"], d["pkt_len"], status=d["status"]))
+    call("f-open", lambda: eng.open_decode_extract_ragged(
+        k, m, d["bb"], d["pkt"], d["pkt_len"], HDR, 1, d["rblocks"], d["d_off"], d["rows"],
+        d["open_len"], d["rrec"], d["r_off"], d["rec_rows"], rev, rev_len, status=d["status"]))
+    call("f-extract", lambda: eng.extract_revived_ragged(
+        k, m, d["bb"], d["rrec"], d["r_off"], d["rec_rows"], d["status"], rev, rev_len))
     call("h-encode", lambda: fec.encode_host_into(eng, k, m, bb, h["data"], h["parity"]))
     call("h-decode", lambda: fec.decode_host_into(eng, k, m, bb, h["blocks"], h["rows"], h["status"]))
     call("h-recov", lambda: fec.decode_recovered_host_into(

@@ -21,8 +21,18 @@ plaintexts, 16-byte headers; the receiver loses `losses` data packets per group)
   buckets   one qfec_encode_seal_groups_batch / qfec_open_decode_batch per distinct bb
 and every bb = 1352 against the one uniform call: the price of run-time shapes.
 
+--framed: the price of framing on the device, on the mixed workload with
+payload lengths bb - 2 down to bb - 9:
+  framed    qfec_frame_encode_seal_groups_batch_ragged / qfec_open_decode_extract_batch_ragged
+  unframed  qfec_encode_seal_groups_batch_ragged / qfec_open_decode_batch_ragged on the same
+            (already framed) blocks
+The parity of the two routes is compared byte for byte first (the wire data packets differ on
+purpose: the framed ones carry no prefix).  The difference is set against the bytes the frame and
+extract kernels move.
+
   python tools/ragged_bench.py --out profiles/ragged/ragged_bench.json
   python tools/ragged_bench.py --pp --out profiles/ragged/ragged_pp_bench.json
+  python tools/ragged_bench.py --framed --out profiles/ragged/framed_bench.json
 """
 import argparse
 import json
@@ -62,6 +72,8 @@ def main():
     ap.add_argument("--pp", action="store_true",
                     help="the protected paths: ragged encode + seal and open -> decode against "
                          "one uniform protected call per distinct bb")
+    ap.add_argument("--framed", action="store_true",
+                    help="the framed protected paths against the unframed ragged ones")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.reps < 20:
@@ -354,11 +366,130 @@ def main():
         results.append(line)
         print(json.dumps(line), flush=True)
 
+    def run_framed(k, m, r, bb, label):
+        """--framed: frame -> encode -> seal against encode -> seal, and open -> decode ->
+        extract against open -> decode, the same groups, data packets 0 .. r-1 lost."""
+        G, per, rmax, H = len(bb), k + m, min(k, m), 16
+        n = G * per
+        stride = H + 12 + int(bb.max())
+        pay_stride = int(bb.max())
+        rng = np.random.default_rng(args.seed + 1)
+        lens = (np.repeat(bb, k) - 2 - rng.integers(0, 8, G * k)).astype(np.int32)
+        fbb, d_off, p_off, r_off, tot = fec.framed_layout(k, m, lens)
+        assert np.array_equal(fbb, bb)
+        pay = torch.empty((G * k, pay_stride), dtype=torch.uint8, device="cuda")
+        fec.synth_fill(pay, seed=args.seed)
+        lens_d = torch.from_numpy(lens).cuda()
+        data = torch.zeros(tot[0], dtype=torch.uint8, device="cuda")
+        par = {x: torch.zeros(tot[1], dtype=torch.uint8, device="cuda") for x in "fu"}
+        rec = {x: torch.zeros(tot[2], dtype=torch.uint8, device="cuda") for x in "fu"}
+        blocks = torch.zeros(tot[0], dtype=torch.uint8, device="cuda")
+        bb_d = torch.from_numpy(bb).cuda()
+        d_off_d, p_off_d, r_off_d = (torch.from_numpy(o).cuda() for o in (d_off, p_off, r_off))
+        hdr = torch.randint(0, 256, (n, H), dtype=torch.uint8, device="cuda")
+        pkt = {x: torch.zeros((n, stride), dtype=torch.uint8, device="cuda") for x in "fu"}
+        plen = {x: torch.zeros(n, dtype=torch.int32, device="cuda") for x in "fu"}
+        est = torch.zeros(G, dtype=torch.int32, device="cuda")
+        rows = torch.zeros((G, k), dtype=torch.uint8, device="cuda")
+        ol = torch.zeros(n, dtype=torch.int32, device="cuda")
+        rr = torch.zeros((G, rmax), dtype=torch.uint8, device="cuda")
+        st = torch.zeros(G, dtype=torch.int32, device="cuda")
+        rev = torch.zeros((G * rmax, pay_stride), dtype=torch.uint8, device="cuda")
+        rev_len = torch.zeros(G * rmax, dtype=torch.int32, device="cuda")
+        rev_pn = torch.zeros(G * rmax, dtype=torch.uint8, device="cuda")
+
+        def framed_seal():
+            eng.frame_encode_seal_ragged(k, m, bb_d, data, d_off_d, par["f"], p_off_d, hdr, H, pay,
+                                         lens_d, 1, pkt["f"], plen["f"], status=est)
+
+        def unframed_seal():
+            eng.seal_groups_ragged(k, m, bb_d, data, d_off_d, par["u"], p_off_d, hdr, H, None,
+                                   pkt["u"], plen["u"], encode=True, status=est)
+
+        framed_seal()
+        kern = {"framed_seal": fec.last_kernels()}
+        torch.cuda.synchronize()
+        assert int(est.abs().max()) == 0
+        unframed_seal()                                       # on the blocks the frame wrote
+        kern["unframed_seal"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        assert torch.equal(par["f"], par["u"]), "parity differs between the routes"
+        wl = {}
+        for x in "fu":
+            w = plen[x].clone().view(G, per)
+            w[:, :r] = -1
+            wl[x] = w.view(n)
+
+        def framed_open():
+            eng.open_decode_extract_ragged(k, m, bb_d, pkt["f"], wl["f"], H, 1, blocks, d_off_d,
+                                           rows, ol, rec["f"], r_off_d, rr, rev, rev_len,
+                                           rev_pn_len=rev_pn, status=st)
+
+        def unframed_open():
+            eng.open_decode_ragged(k, m, bb_d, pkt["u"], wl["u"], H, blocks, d_off_d, rows, ol,
+                                   rec["u"], r_off_d, rr, status=st)
+
+        framed_open()
+        kern["framed_open"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        assert int(st.abs().max()) == 0
+        lost = torch.arange(G, device="cuda")[:, None] * k + torch.arange(r, device="cuda")[None, :]
+        got = rev_len.view(G, rmax)[:, :r]
+        assert torch.equal(got, lens_d[lost]), "revived lengths are not the lost payloads'"
+        cols = torch.arange(pay_stride, device="cuda")[None, None, :]
+        mask = cols < got[:, :, None]
+        assert torch.equal(rev.view(G, rmax, pay_stride)[:, :r][mask], pay[lost][mask]), \
+            "revived payloads are not the lost ones"
+        unframed_open()
+        kern["unframed_open"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        assert int(st.abs().max()) == 0 and torch.equal(rec["f"], rec["u"])
+
+        names = ["framed_seal", "unframed_seal", "framed_open", "unframed_open"]
+        fns = dict(framed_seal=framed_seal, unframed_seal=unframed_seal, framed_open=framed_open,
+                   unframed_open=unframed_open)
+        ev = DeviceEvents(2 * len(names))
+        t = {x: [] for x in names}
+        for rep_i in range(args.warmup + args.reps):
+            order = names if rep_i % 2 == 0 else [names[1], names[0], names[3], names[2]]
+            for name in order:
+                timed(ev, names.index(name), fns[name])
+            torch.cuda.synchronize()
+            if rep_i >= args.warmup:
+                for i, name in enumerate(names):
+                    t[name].append(ev.elapsed_ms(2 * i, 2 * i + 1))
+        ev.close()
+        total = int(bb.astype(np.int64).sum())
+        frame_bytes = int(lens.astype(np.int64).sum()) + k * total
+        extract_bytes = 2 * r * total
+        line = dict(config=label, mode="framed", k=k, m=m, losses=r, groups=G, packets=n,
+                    reps=args.reps, kernels=kern,
+                    wire_bytes={"seal": per * (total + G * (H + 12)),
+                                "open": (per - r) * (total + G * (H + 12))},
+                    frame_kernel_bytes=frame_bytes, extract_kernel_bytes=extract_bytes)
+        for name in names:
+            med = statistics.median(t[name])
+            line[name] = dict(kernel_ms_median=round(med, 4), kernel_ms_min=round(min(t[name]), 4),
+                              kernel_ms_max=round(max(t[name]), 4))
+        for ph, extra in (("seal", frame_bytes), ("open", extract_bytes)):
+            f, u = line[f"framed_{ph}"]["kernel_ms_median"], line[f"unframed_{ph}"]["kernel_ms_median"]
+            line[f"{ph}_framing_ms"] = round(f - u, 4)
+            line[f"{ph}_framed_over_unframed"] = round(f / u, 3)
+            # what the extra bytes alone would cost at the unframed route's own byte rate
+            base = line["wire_bytes"][ph] * 2
+            line[f"{ph}_byte_ratio"] = round((base + extra) / base, 3)
+            line[f"{ph}_framing_GBps"] = round(extra / max(f - u, 1e-6) / 1e6, 1)
+        results.append(line)
+        print(json.dumps(line), flush=True)
+
     G = args.groups
     mixed = draw_sizes(G, args.seed)
     flat = np.full(G, 1352, np.int32)
     run = run_pp if args.pp else run_config
     for k, m, r in (tuple(int(v) for v in c.split(",")) for c in args.codes.split()):
+        if args.framed:
+            run_framed(k, m, r, mixed, f"mixed ({k},{m})")
+            continue
         run(k, m, r, mixed, f"mixed ({k},{m})")
         # the price of run-time shapes: every bb = 1352, one bucket = the compiled path (A / B)
         run(k, m, r, flat, f"all-1352 ({k},{m})")

@@ -4,7 +4,9 @@
 // Stand-alone (its own main, no GPU, no HIP): built from this file and
 // quic_amd/csrc/fec_host_plan.cpp with -fsanitize=address,undefined (`make ragged-check`).
 // It calls qfec_ragged_layout, qfec::ragged_pack and the planning functions of the host
-// pipeline (chunks, stage sizes, carve) on random sizes and checks offsets and bounds;
+// pipeline (chunks, stage sizes, carve) on random sizes and checks offsets and bounds, and the
+// two helpers of the framed calls (qfec_framed_layout, qfec_framed_rx_block_bytes) on hostile
+// inputs: zero groups, every packet absent, the largest length, offsets past 2^40;
 // out-of-bounds copies or overflowing arithmetic abort under the sanitizers.
 #include <climits>
 #include <cstdint>
@@ -272,6 +274,82 @@ static void check_plan_errors() {
     CHECK(qfec::uniform_chunk(241, 17550, 1, 1) == 59);            // 1048576 / 17550
 }
 
+// ---- the host helpers of the framed calls
+static void check_framed(std::mt19937& rng) {
+    long long tot[3] = {-1, -1, -1};
+    // zero groups: nothing is read
+    CHECK(qfec_framed_layout(5, 5, 0, nullptr, nullptr, nullptr, nullptr, nullptr, tot) == 0);
+    CHECK(tot[0] == 0 && tot[1] == 0 && tot[2] == 0);
+    CHECK(qfec_framed_rx_block_bytes(5, 5, 0, nullptr, nullptr, 0, nullptr) == 0);
+    CHECK(qfec_framed_layout(5, 5, 1, nullptr, nullptr, nullptr, nullptr, nullptr, tot) == -2);
+    CHECK(qfec_framed_layout(0, 5, 0, nullptr, nullptr, nullptr, nullptr, nullptr, tot) == -2);
+    CHECK(qfec_framed_rx_block_bytes(5, 0, 0, nullptr, nullptr, 0, nullptr) == -2);
+    CHECK(qfec_framed_rx_block_bytes(5, 5, -1, nullptr, nullptr, 0, nullptr) == -2);
+    // random groups in allocations of exactly their size; any offset array may be NULL
+    for (int rep = 0; rep < 50; ++rep) {
+        const int k = 1 + (int)(rng() % 40), m = 1 + (int)(rng() % 8);
+        const long long G = 1 + (long long)(rng() % 30);
+        std::vector<int> len((size_t)(G * k)), bb((size_t)G), want((size_t)G);
+        for (long long g = 0; g < G; ++g) {
+            int most = 0;
+            for (int i = 0; i < k; ++i) {
+                const int l = rng() % 7 == 0 ? 0x3fff : (int)(rng() % 1400);
+                len[(size_t)(g * k + i)] = l;
+                most = l > most ? l : most;
+            }
+            want[(size_t)g] = (most + 2 + 7) / 8 * 8;
+        }
+        std::vector<long long> d((size_t)G), r((size_t)G);
+        CHECK(qfec_framed_layout(k, m, G, len.data(), bb.data(), d.data(), nullptr, r.data(), tot) == 0);
+        CHECK(bb == want);
+        std::vector<long long> d2((size_t)G), r2((size_t)G);
+        long long tot2[3];
+        CHECK(qfec_ragged_layout(k, m, G, bb.data(), d2.data(), nullptr, r2.data(), tot2) == 0);
+        CHECK(d == d2 && r == r2 && tot[0] == tot2[0] && tot[1] == tot2[1] && tot[2] == tot2[2]);
+        const size_t bad = (size_t)(rng() % (unsigned)(G * k));
+        const int keep = len[bad];
+        for (int v : {0x4000, -1, INT_MAX, INT_MIN}) {
+            len[bad] = v;
+            CHECK(qfec_framed_layout(k, m, G, len.data(), bb.data(), nullptr, nullptr, nullptr, nullptr) == -2);
+        }
+        len[bad] = keep;
+        // the receiver's sizes: all absent, then a random receive set with hostile lengths
+        const long long per = k + m;
+        std::vector<int> pl((size_t)(G * per), -1), ad((size_t)(G * per), 16), rb((size_t)G, 7);
+        CHECK(qfec_framed_rx_block_bytes(k, m, G, pl.data(), ad.data(), 0, rb.data()) == 0);
+        for (int b : rb) CHECK(b == 0);
+        for (long long g = 0; g < G; ++g) {
+            long long most = 0;
+            for (long long i = 0; i < per; ++i) {
+                const size_t p = (size_t)(g * per + i);
+                const unsigned pick = rng() % 8;
+                ad[p] = pick == 0 ? -3 : (int)(rng() % 20);
+                pl[p] = pick == 1 ? -1 : pick == 2 ? INT_MAX : pick == 3 ? ad[p] + 11
+                                                    : ad[p] + 12 + (int)(rng() % 1400);
+                const long long pt = (long long)pl[p] - ad[p] - 12;
+                if (pl[p] >= 0 && ad[p] >= 0 && pt >= 0) {
+                    const long long st = pt + (i < k ? 2 : 0);
+                    most = st > most ? st : most;
+                }
+            }
+            want[(size_t)g] = (int)(most > INT_MAX ? INT_MAX : most);
+        }
+        CHECK(qfec_framed_rx_block_bytes(k, m, G, pl.data(), ad.data(), 0, rb.data()) == 0);
+        CHECK(rb == want);
+    }
+    // every length 0x3fff in groups of 255: the data offsets pass 2^40
+    {
+        const int k = 255, m = 1;
+        const long long G = 270000, per_group = ((long long)k * 16392 + 15) & ~15LL;
+        std::vector<int> len((size_t)(G * k), 0x3fff), bb((size_t)G);
+        std::vector<long long> d((size_t)G);
+        CHECK(qfec_framed_layout(k, m, G, len.data(), bb.data(), d.data(), nullptr, nullptr, tot) == 0);
+        CHECK(bb[0] == 16392 && bb[(size_t)G - 1] == 16392);
+        CHECK(d[(size_t)G - 1] == (G - 1) * per_group && d[(size_t)G - 1] > (1LL << 40));
+        CHECK(tot[0] == G * per_group && tot[1] == G * 16400 && tot[2] == G * 16400);
+    }
+}
+
 int main() {
     std::mt19937 rng(20240607);
     const int codes[][2] = {{10, 1}, {3, 2}, {5, 5}, {32, 4}, {10, 20}, {1, 3}, {250, 5}, {10, 10}};
@@ -288,6 +366,7 @@ int main() {
         }
     }
     check_plan_errors();
+    check_framed(rng);
     // errors: a size < 1, bad arguments, overflow of the running offset
     {
         const int bad[3] = {8, 0, 8};
