@@ -599,13 +599,14 @@ int qfec_null_seal_batch(qfec_ctx* c, long long n, const unsigned char* d_ad, lo
     if (n < 0 || ad_stride < 0 || pt_stride < 0 || out_stride < 0) return fail(-2, "bad n / stride");
     if (n && (!d_out || !d_out_len || (!d_ad && (d_ad_len || ad_len_all)) || (!d_pt && (d_pt_len || pt_len_all))))
         return fail(-2, "null buffer");
-    if ((((uintptr_t)d_out) | (uintptr_t)out_stride) & 3) return fail(-2, "out / out_stride not 4-byte aligned");
+    const RowsOut out = rows_out_of(d_out, out_stride, d_out_len);
+    if (!aligned4(out)) return fail(-2, "out / out_stride not 4-byte aligned");
     std::lock_guard<std::mutex> lk(c->mu);
     int rc;
     if ((rc = set_device(c))) return rc;
     QF_HIP(qfec::launch_null_seal(n, rows_of(d_ad, ad_stride, d_ad_len, ad_len_all),
-                                  rows_of(d_pt, pt_stride, d_pt_len, pt_len_all),
-                                  rows_out_of(d_out, out_stride, d_out_len), pick(c, stream)));
+                                  rows_of(d_pt, pt_stride, d_pt_len, pt_len_all), out,
+                                  pick(c, stream)));
     return 0;
 }
 
@@ -616,13 +617,14 @@ int qfec_null_open_batch(qfec_ctx* c, long long n, const unsigned char* d_pkt, l
     if (!c) return fail(-2, "null context");
     if (n < 0 || pkt_stride < 0 || out_stride < 0) return fail(-2, "bad n / stride");
     if (n && (!d_pkt || !d_out || !d_out_len)) return fail(-2, "null buffer");
-    if ((((uintptr_t)d_out) | (uintptr_t)out_stride) & 3) return fail(-2, "out / out_stride not 4-byte aligned");
+    const RowsOut out = rows_out_of(d_out, out_stride, d_out_len);
+    if (!aligned4(out)) return fail(-2, "out / out_stride not 4-byte aligned");
     std::lock_guard<std::mutex> lk(c->mu);
     int rc;
     if ((rc = set_device(c))) return rc;
     QF_HIP(qfec::launch_null_open(n, rows_of(d_pkt, pkt_stride, d_pkt_len, pkt_len_all),
-                                  rows_of(nullptr, 0, d_ad_len, ad_len_all),
-                                  rows_out_of(d_out, out_stride, d_out_len), pick(c, stream)));
+                                  rows_of(nullptr, 0, d_ad_len, ad_len_all), out,
+                                  pick(c, stream)));
     return 0;
 }
 
@@ -636,7 +638,8 @@ int qfec_encode_seal_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
     if (groups && (!d_data || !d_parity || !d_pkt || !d_pkt_len || (!d_hdr && (d_hdr_len || hdr_len_all))))
         return fail(-2, "null buffer");
     if (hdr_stride < 0 || pkt_stride < 0) return fail(-2, "bad stride");
-    if ((((uintptr_t)d_pkt) | (uintptr_t)pkt_stride) & 3) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
+    const RowsOut pkt = rows_out_of(d_pkt, pkt_stride, d_pkt_len);
+    if (!aligned4(pkt)) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     const hipStream_t st = pick(c, stream);
@@ -644,8 +647,7 @@ int qfec_encode_seal_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
     // each sealed with its packet header as the associated data; packet (g, i) = g * m + i
     if ((rc = encode_impl(c, k, m, bb, groups, d_data, d_parity, st))) return rc;
     QF_HIP(qfec::launch_null_seal(groups * m, rows_of(d_hdr, hdr_stride, d_hdr_len, hdr_len_all),
-                                  Rows{d_parity, bb, nullptr, bb},
-                                  rows_out_of(d_pkt, pkt_stride, d_pkt_len), st));
+                                  Rows{d_parity, bb, nullptr, bb}, pkt, st));
     return 0;
 }
 
@@ -661,7 +663,7 @@ extern "C++" int qfec::seal_groups_args(qfec_ctx* c, int k, int m, int bb, long 
         return fail(-2, "null buffer");
     if (hdr.stride < 0 || pkt.stride < 0) return fail(-2, "bad stride");
     if (!pt_len && (pt_len_all < 0 || pt_len_all > bb)) return fail(-2, "pt_len_all outside 0..block_bytes");
-    if ((((uintptr_t)pkt.p) | (uintptr_t)pkt.stride) & 3) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
+    if (!aligned4(pkt)) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
     return 0;
 }
 
@@ -702,6 +704,16 @@ int qfec_encode_seal_groups_batch(qfec_ctx* c, int k, int m, int bb, long long g
                        rows_out_of(d_pkt, pkt_stride, d_pkt_len), stream);
 }
 
+extern "C++" int qfec::open_decode_args(int k, int m, bool packets,
+                                        std::initializer_list<const void*> required,
+                                        long long pkt_stride, const int* ad_len, int ad_len_all) {
+    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
+    if (packets && any_null(required)) return fail(-2, "null buffer");
+    if (packets && pkt_stride <= 0) return fail(-2, "bad pkt_stride");
+    if (!ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
+    return 0;
+}
+
 // Receiver: open every packet of each group (quic_framer.cc:657 decrypts before the group
 // sees a packet), place the data plaintexts, fill the holes with opened FEC packets, decode.
 int qfec_open_decode_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
@@ -711,11 +723,10 @@ int qfec_open_decode_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
                            unsigned char* d_rec_rows, int* d_status, void* stream) {
     int rc = check_common(c, k, m, bb, groups);
     if (rc) return rc;
-    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
-    if (groups && (!d_pkt || !d_pkt_len || !d_blocks || !d_rows || !d_open_len || !d_rec || !d_rec_rows))
-        return fail(-2, "null buffer");
-    if (pkt_stride <= 0 && groups) return fail(-2, "bad pkt_stride");
-    if (!d_ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
+    if ((rc = open_decode_args(k, m, groups != 0,
+                               {d_pkt, d_pkt_len, d_blocks, d_rows, d_open_len, d_rec, d_rec_rows},
+                               pkt_stride, d_ad_len, ad_len_all)))
+        return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     const hipStream_t st = pick(c, stream);
@@ -859,7 +870,7 @@ extern "C++" int qfec::seal_ragged_pkt_args(int k, int m, Rows hdr, RowsOut pkt)
     if (k + m > 256) return fail(-2, "k + m > 256");
     if (!pkt.p || !pkt.len || (!hdr.p && (hdr.len || hdr.len_all))) return fail(-2, "null buffer");
     if (hdr.stride < 0 || pkt.stride < 0) return fail(-2, "bad stride");
-    if ((((uintptr_t)pkt.p) | (uintptr_t)pkt.stride) & 3) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
+    if (!aligned4(pkt)) return fail(-2, "pkt / pkt_stride not 4-byte aligned");
     return 0;
 }
 
@@ -909,14 +920,21 @@ int qfec_encode_seal_groups_batch_ragged(qfec_ctx* c, int k, int m, long long gr
                               rows_out_of(d_pkt, pkt_stride, d_pkt_len), d_status, stream);
 }
 
-// open_decode_impl over the packed layout.  The caller holds the workspace bracket.
+// open_decode_impl over the packed layout: open (framed: a data packet's plaintext goes behind
+// its prefix) -> ragged recovered decode -> open_status.  The caller holds the workspace bracket.
 extern "C++" int qfec::open_decode_ragged_impl(qfec_ctx* c, int k, int m, long long groups,
-                                               RaggedView v, Rows pkt, Rows ad, uint8_t* d_blocks,
-                                               uint8_t* d_rows, int32_t* d_open_len, uint8_t* d_rec,
+                                               RaggedView v, Rows pkt, Rows ad, const PnLen* framed,
+                                               uint8_t* d_blocks, uint8_t* d_rows,
+                                               int32_t* d_open_len, uint8_t* d_rec,
                                                uint8_t* d_rec_rows, int32_t* d_status,
                                                hipStream_t st) {
-    QF_HIP(qfec::launch_open_groups_ragged(k, m, groups, v, pkt, ad, d_blocks, d_rows, d_open_len,
-                                           st));
+    if (framed)
+        QF_HIP(qfec::launch_open_groups_framed(k, m, groups, v, pkt, ad, framed->pn_len,
+                                               framed->pn_len_all, d_blocks, d_rows, d_open_len,
+                                               st));
+    else
+        QF_HIP(qfec::launch_open_groups_ragged(k, m, groups, v, pkt, ad, d_blocks, d_rows,
+                                               d_open_len, st));
     int rc = decode_ragged_impl(c, k, m, groups, v, d_blocks, d_rows, d_rec, d_rec_rows, d_status,
                                 st);
     if (rc) return rc;
@@ -933,10 +951,9 @@ int qfec_open_decode_batch_ragged(qfec_ctx* c, int k, int m, long long groups, c
                                   int* d_status, void* stream) {
     int rc = ragged_check(c, k, m, groups, d_bb, d_blocks, d_blocks_off, d_rec, d_rec_off);
     if (rc) return rc;
-    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
-    if (!d_pkt || !d_pkt_len || !d_rows || !d_open_len || !d_rec_rows) return fail(-2, "null buffer");
-    if (pkt_stride <= 0) return fail(-2, "bad pkt_stride");
-    if (!d_ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
+    if ((rc = open_decode_args(k, m, true, {d_pkt, d_pkt_len, d_rows, d_open_len, d_rec_rows},
+                               pkt_stride, d_ad_len, ad_len_all)))
+        return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     if (groups == 0) return 0;
@@ -945,23 +962,19 @@ int qfec_open_decode_batch_ragged(qfec_ctx* c, int k, int m, long long groups, c
         return open_decode_ragged_impl(c, k, m, groups,
                                        {(const int32_t*)d_bb, d_blocks_off, d_rec_off},
                                        rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
-                                       rows_of(nullptr, 0, d_ad_len, ad_len_all), d_blocks, d_rows,
-                                       (int32_t*)d_open_len, d_rec, d_rec_rows,
+                                       rows_of(nullptr, 0, d_ad_len, ad_len_all), nullptr, d_blocks,
+                                       d_rows, (int32_t*)d_open_len, d_rec, d_rec_rows,
                                        (int32_t*)d_status, st);
     });
 }
 
 // ---- framed groups: QuicFecGroup's wire format around the ragged protected paths (pp_null.hip's
 // framed kernels).  Payload rows and revived payloads stay dense by packet; blocks are packed.
-static int framed_pay_args(const unsigned char* d_pay, long long pay_stride, const int* d_pay_len) {
-    if (!d_pay || !d_pay_len) return fail(-2, "null buffer");
-    if (pay_stride < 0) return fail(-2, "bad pay_stride");
-    return 0;
-}
-
-static int framed_rev_args(const unsigned char* d_rev, long long rev_stride, const int* d_rev_len) {
-    if (!d_rev || !d_rev_len) return fail(-2, "null buffer");
-    if (rev_stride < 0) return fail(-2, "bad rev_stride");
+// the payload rows a framed sender reads, the revived rows a framed receiver writes
+static int framed_rows_args(const unsigned char* d_row, long long stride, const int* d_len,
+                            const char* bad_stride) {
+    if (!d_row || !d_len) return fail(-2, "null buffer");
+    if (stride < 0) return fail(-2, bad_stride);
     return 0;
 }
 
@@ -974,7 +987,7 @@ int qfec_frame_blocks_batch_ragged(qfec_ctx* c, int k, long long groups, const i
     if (rc) return rc;
     if (any_null({d_bb, d_data, d_data_off})) return fail(-2, "null buffer");
     if ((uintptr_t)d_data & 15) return fail(-2, "ragged base pointers must be 16-byte aligned");
-    if ((rc = framed_pay_args(d_pay, pay_stride, d_pay_len))) return rc;
+    if ((rc = framed_rows_args(d_pay, pay_stride, d_pay_len, "bad pay_stride"))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     QF_HIP(qfec::launch_frame_blocks_ragged(
@@ -992,7 +1005,7 @@ int qfec_extract_revived_batch_ragged(qfec_ctx* c, int k, int m, long long group
     int rc = ragged_preface(c, k, m, groups);
     if (rc) return rc;
     if (any_null({d_bb, d_rec, d_rec_off, d_rec_rows})) return fail(-2, "null buffer");
-    if ((rc = framed_rev_args(d_rev, rev_stride, d_rev_len))) return rc;
+    if ((rc = framed_rows_args(d_rev, rev_stride, d_rev_len, "bad rev_stride"))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     QF_HIP(qfec::launch_extract_revived(k, m, groups, {(const int32_t*)d_bb, nullptr, d_rec_off},
@@ -1017,7 +1030,7 @@ int qfec_frame_encode_seal_groups_batch_ragged(
     const Rows hdr = rows_of(d_hdr, hdr_stride, d_hdr_len, hdr_len_all);
     const RowsOut pkt = rows_out_of(d_pkt, pkt_stride, d_pkt_len);
     if ((rc = seal_ragged_pkt_args(k, m, hdr, pkt))) return rc;
-    if ((rc = framed_pay_args(d_pay, pay_stride, d_pay_len))) return rc;
+    if ((rc = framed_rows_args(d_pay, pay_stride, d_pay_len, "bad pay_stride"))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     if (groups == 0) return 0;
@@ -1049,27 +1062,23 @@ int qfec_open_decode_extract_batch_ragged(
     long long rev_stride, int* d_rev_len, unsigned char* d_rev_pn_len, void* stream) {
     int rc = ragged_check(c, k, m, groups, d_bb, d_blocks, d_blocks_off, d_rec, d_rec_off);
     if (rc) return rc;
-    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
-    if (!d_pkt || !d_pkt_len || !d_rows || !d_open_len || !d_rec_rows) return fail(-2, "null buffer");
-    if (pkt_stride <= 0) return fail(-2, "bad pkt_stride");
-    if (!d_ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
-    if ((rc = framed_rev_args(d_rev, rev_stride, d_rev_len))) return rc;
+    if ((rc = open_decode_args(k, m, true, {d_pkt, d_pkt_len, d_rows, d_open_len, d_rec_rows},
+                               pkt_stride, d_ad_len, ad_len_all)))
+        return rc;
+    if ((rc = framed_rows_args(d_rev, rev_stride, d_rev_len, "bad rev_stride"))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     if (groups == 0) return 0;
     const hipStream_t st = pick(c, stream);
     const RaggedView v{(const int32_t*)d_bb, d_blocks_off, d_rec_off};
+    const PnLen framed{d_pn_len, pn_len_all};
     return with_workspace(c, st, [&] {
-        QF_HIP(qfec::launch_open_groups_framed(k, m, groups, v,
-                                               rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
-                                               rows_of(nullptr, 0, d_ad_len, ad_len_all), d_pn_len,
-                                               pn_len_all, d_blocks, d_rows, (int32_t*)d_open_len,
-                                               st));
-        const int r = decode_ragged_impl(c, k, m, groups, v, d_blocks, d_rows, d_rec, d_rec_rows,
-                                         (int32_t*)d_status, st);
+        const int r = open_decode_ragged_impl(c, k, m, groups, v,
+                                              rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
+                                              rows_of(nullptr, 0, d_ad_len, ad_len_all), &framed,
+                                              d_blocks, d_rows, (int32_t*)d_open_len, d_rec,
+                                              d_rec_rows, (int32_t*)d_status, st);
         if (r) return r;
-        QF_HIP(qfec::launch_open_status(k, std::min(k, m), groups, d_rows, d_rec_rows,
-                                        (int32_t*)d_status, st));
         QF_HIP(qfec::launch_extract_revived(k, m, groups, v, d_rec, d_rec_rows,
                                             (const int32_t*)d_status,
                                             rows_out_of(d_rev, rev_stride, d_rev_len),
@@ -1187,7 +1196,7 @@ int qfec_reserve(qfec_ctx* c, int k, int m, int bb, long long groups) {
         const uint8_t* t;
         if ((rc = get_enc_table(c, k, m, stream_encode_rc(k, m, bb, true, c->tune), &t))) return rc;
         // the ragged encode's table (chunks of at most 4 outputs)
-        if ((rc = get_enc_table(c, k, m, std::min(encode_rc(m, c->tune), 4), &t))) return rc;
+        if ((rc = get_enc_table(c, k, m, ragged_rc(encode_rc(m, c->tune)), &t))) return rc;
     }
     if (p.cenc) {
         const uint8_t* t;

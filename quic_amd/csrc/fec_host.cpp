@@ -222,11 +222,11 @@ int qfec_open_decode_batch_host(qfec_ctx* c, int k, int m, int bb, long long gro
                                 int* h_open_len) {
     int rc = check_common(c, k, m, bb, groups);
     if (rc) return rc;
-    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
-    if (groups == 0) return 0;
-    if (!h_pkt || !h_pkt_len || !h_rec || !h_rec_rows) return fail(-2, "null buffer");
-    if (pkt_stride <= 0) return fail(-2, "bad pkt_stride");
-    if (!h_ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
+    // no group: k + m alone is checked, then there is nothing to do
+    if (groups == 0) return open_decode_args(k, m, false, {}, 0, nullptr, 0);
+    if ((rc = open_decode_args(k, m, true, {h_pkt, h_pkt_len, h_rec, h_rec_rows}, pkt_stride,
+                               h_ad_len, ad_len_all)))
+        return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     const size_t np = (size_t)(k + m);
@@ -407,12 +407,12 @@ int qfec_open_decode_batch_ragged_host(qfec_ctx* c, int k, int m, long long grou
                                        int* h_status, int* h_open_len) {
     int rc = ragged_preface(c, k, m, groups);
     if (rc) return rc;
-    if (k + m > 255) return fail(-2, "k + m > 255 (row tag 255 marks an unfilled slot)");
-    if (!h_bb || !h_pkt || !h_pkt_len || !h_rec || !h_rec_off || !h_rec_rows)
-        return fail(-2, "null buffer");
-    if (groups == 0) return 0;
-    if (pkt_stride <= 0) return fail(-2, "bad pkt_stride");
-    if (!h_ad_len && ad_len_all < 0) return fail(-2, "bad ad_len_all");
+    // no group: the arrays are still asked for, the stride and ad_len_all are not looked at
+    const bool none = groups == 0;
+    if ((rc = open_decode_args(k, m, true, {h_bb, h_pkt, h_pkt_len, h_rec, h_rec_off, h_rec_rows},
+                               none ? 1 : pkt_stride, h_ad_len, none ? 0 : ad_len_all)))
+        return rc;
+    if (none) return 0;
     std::vector<long long> blk_off;
     if ((rc = device_layout(k, m, groups, h_bb, 0, &blk_off))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -433,8 +433,8 @@ int qfec_open_decode_batch_ragged_host(qfec_ctx* c, int k, int m, long long grou
     return host_pipeline_ragged(c, L, groups, db, dre, rs, [&](long long n) {
         return open_decode_ragged_impl(c, k, m, n, rs.view(),
                                        {dk.dev, pkt_stride, dkl.as<int32_t>(), 0},
-                                       {nullptr, 0, dal.as<int32_t>(), ad_len_all}, db.dev, dr.dev,
-                                       dol.as<int32_t>(), dre.dev, drr.dev,
+                                       {nullptr, 0, dal.as<int32_t>(), ad_len_all}, nullptr, db.dev,
+                                       dr.dev, dol.as<int32_t>(), dre.dev, drr.dev,
                                        rs.status.as<int32_t>(), c->stream);
     });
 }

@@ -139,12 +139,19 @@ inline Rows rows_of(const unsigned char* p, long long stride, const int* len, in
 inline RowsOut rows_out_of(unsigned char* p, long long stride, int* len) {
     return {p, stride, (int32_t*)len};
 }
+// what the seal and open kernels ask of the rows they write (each call site has its message)
+inline bool aligned4(RowsOut r) { return ((((uintptr_t)r.p) | (uintptr_t)r.stride) & 3) == 0; }
 // qfec_[encode_]seal_groups_batch[_host]; `required`: the arrays this form cannot do without
 int seal_groups_args(qfec_ctx* c, int k, int m, int bb, long long groups,
                      std::initializer_list<const void*> required, Rows hdr, const int* pt_len,
                      int pt_len_all, RowsOut pkt);
 // the packet side of the ragged seals, after the form's own checks of the block arrays
 int seal_ragged_pkt_args(int k, int m, Rows hdr, RowsOut pkt);
+// The receiver's arguments, every form of open-decode, after the form's preface; `required`: the
+// arrays this form cannot do without.  `packets` false: k + m and ad_len_all alone, for a call
+// with no group whose form then takes null arrays and any stride.
+int open_decode_args(int k, int m, bool packets, std::initializer_list<const void*> required,
+                     long long pkt_stride, const int* ad_len, int ad_len_all);
 
 // ---- the dispatch: which kernels a call runs on `st` (fec_api.cpp)
 // Where a decode writes.  Slot layout (qfec_decode_batch): recovered blocks go back into their
@@ -178,10 +185,15 @@ int encode_ragged_impl(qfec_ctx* c, int k, int m, long long G, RaggedView v, con
 int decode_ragged_impl(qfec_ctx* c, int k, int m, long long G, RaggedView v,
                        const uint8_t* d_blocks, const uint8_t* d_rows_in, uint8_t* d_rec,
                        uint8_t* d_rec_rows, int32_t* d_status, hipStream_t st);
-// v: the blocks (in_off) and the recovered blocks (out_off)
+// The framing of a framed open: each packet's pn_len, or one value for all (pn_len null).
+struct PnLen {
+    const uint8_t* pn_len;
+    int pn_len_all;
+};
+// v: the blocks (in_off) and the recovered blocks (out_off); framed: null for the unframed open
 int open_decode_ragged_impl(qfec_ctx* c, int k, int m, long long groups, RaggedView v, Rows pkt,
-                            Rows ad, uint8_t* d_blocks, uint8_t* d_rows, int32_t* d_open_len,
-                            uint8_t* d_rec, uint8_t* d_rec_rows, int32_t* d_status,
-                            hipStream_t st);
+                            Rows ad, const PnLen* framed, uint8_t* d_blocks, uint8_t* d_rows,
+                            int32_t* d_open_len, uint8_t* d_rec, uint8_t* d_rec_rows,
+                            int32_t* d_status, hipStream_t st);
 
 }  // namespace qfec

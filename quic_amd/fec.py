@@ -35,6 +35,11 @@ def _as_u8(a):
     return a, a.ctypes.data_as(_u8p)
 
 
+def _vp(a):
+    """void* of a numpy array; None stays None (a null pointer)."""
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
 def cauchy_256_encode(k, m, data_ptrs, recovery_blocks, block_bytes):
     """cauchy_256.h:78.  data_ptrs: sequence of k uint8 arrays (block_bytes each);
     recovery_blocks: writable uint8 array of m*block_bytes bytes (filled in place).
@@ -44,8 +49,7 @@ def cauchy_256_encode(k, m, data_ptrs, recovery_blocks, block_bytes):
     if not (isinstance(recovery_blocks, np.ndarray) and recovery_blocks.dtype == np.uint8
             and recovery_blocks.flags.c_contiguous):
         raise TypeError("recovery_blocks must be a C-contiguous uint8 numpy array")
-    return load().cauchy_256_encode(k, m, arr, recovery_blocks.ctypes.data_as(ctypes.c_void_p),
-                                    block_bytes)
+    return load().cauchy_256_encode(k, m, arr, _vp(recovery_blocks), block_bytes)
 
 
 def make_blocks(arrays, rows):
@@ -68,25 +72,83 @@ def cauchy_256_decode(k, m, blocks, block_bytes):
 def cauchy_matrix(k, m):
     """Rows 1..m-1 of the Cauchy matrix the reference uses, (m-1) x k."""
     out = np.zeros((m - 1, k), np.uint8)
-    rc = load().qfec_cauchy_matrix(k, m, out.ctypes.data_as(ctypes.c_void_p))
+    rc = load().qfec_cauchy_matrix(k, m, _vp(out))
     if rc:
         raise ValueError(f"no Cauchy matrix for k={k} m={m}")
     return out
 
 
 # ------------------------------------------------------------------ batch engine
-def _dptr(t):
+# Every wrapper below checks all of its arguments (_check, then _ptr where a pointer is taken)
+# before the library is touched (_call).
+_HOST_KIND = "host buffers must be contiguous CPU tensors (pinned for full speed)"
+
+
+def _check(t, name, dtype, shape, host=False, rows=False, optional=False):
+    """One array argument: a tensor of `dtype` (a torch dtype's name) and exactly `shape`, None
+    in `shape` standing for any extent (of a host buffer: any extent > 0).  An int (one value
+    for every row) passes here and is refused where a pointer is taken of it (_ptr); so does
+    None for an `optional` host array and for any device array (the library answers for a
+    missing one).  The library copies whole rows into and out of a host buffer, so a short one
+    would be overrun and a wrong dtype misread: a host buffer must be a contiguous CPU tensor
+    (TypeError), and its dtype or shape is a ValueError.  A device tensor's kind, placement and
+    contiguity are checked where its pointer is taken; its dtype or shape is a TypeError, but
+    for the dense per-row arrays (`rows`: one entry or row per packet, payload or revived
+    block), whose row count is a ValueError."""
+    if isinstance(t, int) or (t is None and (optional or not host)):
+        return
+    import torch
+    if host and (not isinstance(t, torch.Tensor) or t.is_cuda or not t.is_contiguous()):
+        raise TypeError(f"{name}: {_HOST_KIND}")
+    dtype = getattr(torch, dtype)
+    if t.dtype != dtype:
+        raise (ValueError if host else TypeError)(f"{name}: dtype {t.dtype}, expected {dtype}")
+    if t.dim() != len(shape) or any(got != want if want is not None else host and got <= 0
+                                    for got, want in zip(t.shape, shape)):
+        raise (ValueError if host or rows else TypeError)(
+            f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+
+
+def _ptr(t, host=False):
+    """void* of a tensor argument on its side of the bus; None stays None."""
     if t is None:
         return None
     import torch
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("device buffers must be torch tensors")
-    if not t.is_cuda or t.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32,
-                                       torch.int64):
-        raise TypeError("device buffers must be integer tensors on a ROCm device")
-    if not t.is_contiguous():
-        raise ValueError("device buffers must be contiguous")
+    if host:
+        if not isinstance(t, torch.Tensor) or t.is_cuda or not t.is_contiguous():
+            raise TypeError(_HOST_KIND)
+    else:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("device buffers must be torch tensors")
+        if not t.is_cuda or t.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32,
+                                           torch.int64):
+            raise TypeError("device buffers must be integer tensors on a ROCm device")
+        if not t.is_contiguous():
+            raise ValueError("device buffers must be contiguous")
     return ctypes.c_void_p(t.data_ptr())
+
+
+def _ptr_or_all(v, host=False):
+    """(array pointer, scalar) of a per-row argument (a length, a pn_len): a tensor, or an int
+    meaning the same value for every row."""
+    if isinstance(v, int):
+        return None, v
+    return _ptr(v, host), 0
+
+
+def _stride(t):
+    """Row stride of an optional row array (0 without one)."""
+    return 0 if t is None else t.stride(0)
+
+
+def _call(name, engine, *args, reference_rc=False):
+    """Call the library's `name` on the engine's context.  Returns its code; a non-zero one
+    raises FecError, but for the encodes (`reference_rc`), which hand the reference's -1
+    (unsupported parameters) to the caller and raise below it."""
+    rc = getattr(engine.lib, name)(engine._h, *args)
+    if rc < -1 if reference_rc else rc:
+        raise FecError(rc, name)
+    return rc
 
 
 def _stream(stream, like):
@@ -94,6 +156,14 @@ def _stream(stream, like):
         return ctypes.c_void_p(int(stream))
     import torch
     return ctypes.c_void_p(torch.cuda.current_stream(like.device).cuda_stream)
+
+
+def _groups(bb, **offs):
+    """G of a ragged device call: bb int32 [G] and its offset arrays int64 [G]."""
+    _check(bb, "bb", "int32", (None,))
+    for name, off in offs.items():
+        _check(off, name, "int64", (bb.shape[0],))
+    return bb.shape[0]
 
 
 class FecEngine:
@@ -133,134 +203,85 @@ class FecEngine:
         return v.value
 
     def reserve(self, k, m, block_bytes, groups):
-        rc = self.lib.qfec_reserve(self._h, k, m, block_bytes, groups)
-        if rc:
-            raise FecError(rc, "qfec_reserve")
+        _call("qfec_reserve", self, k, m, block_bytes, groups)
 
     # device-resident batch calls (enqueue only)
     def encode(self, k, m, block_bytes, data, parity, stream=None):
         """data [G][k][bb] -> parity [G][m][bb] (torch uint8 on the device).  Returns
         0 or -1 (the reference's unsupported-parameter code)."""
-        G = data.shape[0]
-        rc = self.lib.qfec_encode_batch(self._h, k, m, block_bytes, G, _dptr(data),
-                                        _dptr(parity), _stream(stream, data))
-        if rc < -1:
-            raise FecError(rc, "qfec_encode_batch")
-        return rc
+        return _call("qfec_encode_batch", self, k, m, block_bytes, data.shape[0], _ptr(data),
+                     _ptr(parity), _stream(stream, data), reference_rc=True)
 
     def decode(self, k, m, block_bytes, blocks, rows_in, out=None, rows_out=None, status=None,
                stream=None):
         """blocks [G][k][bb], rows_in [G][k] uint8.  out defaults to blocks (in place),
         rows_out to rows_in.  status: optional int32 [G]."""
-        G = blocks.shape[0]
         out = blocks if out is None else out
         rows_out = rows_in if rows_out is None else rows_out
-        rc = self.lib.qfec_decode_batch(self._h, k, m, block_bytes, G, _dptr(blocks),
-                                        _dptr(rows_in), _dptr(out), _dptr(rows_out),
-                                        _dptr(status), _stream(stream, blocks))
-        if rc:
-            raise FecError(rc, "qfec_decode_batch")
-        return rc
+        return _call("qfec_decode_batch", self, k, m, block_bytes, blocks.shape[0], _ptr(blocks),
+                     _ptr(rows_in), _ptr(out), _ptr(rows_out), _ptr(status),
+                     _stream(stream, blocks))
 
     def decode_recovered(self, k, m, block_bytes, blocks, rows_in, rec, rec_rows, status=None,
                          stream=None):
         """Recovered-blocks layout: rec [G][min(k,m)][bb], rec_rows [G][min(k,m)] uint8
         (data row of each recovered block, ascending; 255 = unused).  blocks / rows_in are
         not modified."""
-        G = blocks.shape[0]
-        rc = self.lib.qfec_decode_batch_recovered(self._h, k, m, block_bytes, G, _dptr(blocks),
-                                                  _dptr(rows_in), _dptr(rec), _dptr(rec_rows),
-                                                  _dptr(status), _stream(stream, blocks))
-        if rc:
-            raise FecError(rc, "qfec_decode_batch_recovered")
-        return rc
+        return _call("qfec_decode_batch_recovered", self, k, m, block_bytes, blocks.shape[0],
+                     _ptr(blocks), _ptr(rows_in), _ptr(rec), _ptr(rec_rows), _ptr(status),
+                     _stream(stream, blocks))
 
     # ragged batches: one (k, m), a block size per group (packed layout, include/quic_fec.h)
-    @staticmethod
-    def _ragged_args(bb, *offs):
-        import torch
-        if bb.dtype != torch.int32 or bb.dim() != 1:
-            raise TypeError("bb must be an int32 [G] device tensor")
-        for o in offs:
-            if o.dtype != torch.int64 or o.shape != bb.shape:
-                raise TypeError("offsets must be int64 [G] device tensors")
-        return bb.shape[0]
-
     def encode_ragged(self, k, m, bb, data, data_off, parity, par_off, status=None, stream=None):
         """Group g: data + data_off[g] holds [k][bb[g]], parity + par_off[g] receives
         [m][bb[g]].  bb int32 [G], offsets int64 [G] (bytes, multiples of 16), data / parity
         flat uint8, all on the device; status: optional int32 [G] (per-group 0 / -1).  Returns
         0 or -1 (k + m > 256 with m > 1)."""
-        G = self._ragged_args(bb, data_off, par_off)
-        rc = self.lib.qfec_encode_batch_ragged(self._h, k, m, G, _dptr(bb), _dptr(data),
-                                               _dptr(data_off), _dptr(parity), _dptr(par_off),
-                                               _dptr(status), _stream(stream, data))
-        if rc < -1:
-            raise FecError(rc, "qfec_encode_batch_ragged")
-        return rc
+        G = _groups(bb, data_off=data_off, par_off=par_off)
+        return _call("qfec_encode_batch_ragged", self, k, m, G, _ptr(bb), _ptr(data),
+                     _ptr(data_off), _ptr(parity), _ptr(par_off), _ptr(status),
+                     _stream(stream, data), reference_rc=True)
 
     def decode_ragged_recovered(self, k, m, bb, blocks, blocks_off, rows_in, rec, rec_off,
                                 rec_rows, status=None, stream=None):
         """Recovered-blocks layout per group: rec + rec_off[g] receives up to
         [min(k,m)][bb[g]], rec_rows [G][min(k,m)] the restored data rows (255 = unused).
         blocks / rows_in [G][k] are not modified."""
-        G = self._ragged_args(bb, blocks_off, rec_off)
-        rc = self.lib.qfec_decode_batch_ragged_recovered(
-            self._h, k, m, G, _dptr(bb), _dptr(blocks), _dptr(blocks_off), _dptr(rows_in),
-            _dptr(rec), _dptr(rec_off), _dptr(rec_rows), _dptr(status), _stream(stream, blocks))
-        if rc:
-            raise FecError(rc, "qfec_decode_batch_ragged_recovered")
-        return rc
+        G = _groups(bb, blocks_off=blocks_off, rec_off=rec_off)
+        return _call("qfec_decode_batch_ragged_recovered", self, k, m, G, _ptr(bb), _ptr(blocks),
+                     _ptr(blocks_off), _ptr(rows_in), _ptr(rec), _ptr(rec_off), _ptr(rec_rows),
+                     _ptr(status), _stream(stream, blocks))
 
     # packet protection next to the codec (NullEncrypter / NullDecrypter, pp_null.hip)
-    @staticmethod
-    def _lens(lens):
-        """(array pointer, scalar) for a per-packet length argument: an int32 device
-        tensor, or an int meaning the same length for every packet."""
-        if isinstance(lens, int):
-            return None, lens
-        return _dptr(lens), 0
-
     def null_seal(self, ad, ad_len, pt, pt_len, out, out_len, stream=None):
         """NullEncrypter::EncryptPacket over n packets: ad [n][ad_stride], pt [n][pt_stride]
         -> out [n][out_stride] = AD || tag12 || PT; out_len int32 [n] (-1: does not fit).
         ad_len / pt_len: int32 [n] tensors or ints (null_encrypter.cc:23-43)."""
         n = out.shape[0]
-        a, a_all = self._lens(ad_len)
-        p, p_all = self._lens(pt_len)
-        rc = self.lib.qfec_null_seal_batch(self._h, n, _dptr(ad), ad.stride(0) if n else 0, a,
-                                           a_all, _dptr(pt), pt.stride(0) if n else 0, p, p_all,
-                                           _dptr(out), out.stride(0), _dptr(out_len),
-                                           _stream(stream, out))
-        if rc:
-            raise FecError(rc, "qfec_null_seal_batch")
+        a, a_all = _ptr_or_all(ad_len)
+        p, p_all = _ptr_or_all(pt_len)
+        _call("qfec_null_seal_batch", self, n, _ptr(ad), ad.stride(0) if n else 0, a, a_all,
+              _ptr(pt), pt.stride(0) if n else 0, p, p_all, _ptr(out), out.stride(0),
+              _ptr(out_len), _stream(stream, out))
 
     def null_open(self, pkt, pkt_len, ad_len, out, out_len, stream=None):
         """NullDecrypter::DecryptPacket over n wire packets pkt [n][pkt_stride] (first ad_len
         bytes = associated data) -> plaintext in out [n][out_stride], out_len int32 [n]
         (-1: rejected)."""
-        n = pkt.shape[0]
-        p, p_all = self._lens(pkt_len)
-        a, a_all = self._lens(ad_len)
-        rc = self.lib.qfec_null_open_batch(self._h, n, _dptr(pkt), pkt.stride(0), p, p_all, a,
-                                           a_all, _dptr(out), out.stride(0), _dptr(out_len),
-                                           _stream(stream, pkt))
-        if rc:
-            raise FecError(rc, "qfec_null_open_batch")
+        p, p_all = _ptr_or_all(pkt_len)
+        a, a_all = _ptr_or_all(ad_len)
+        _call("qfec_null_open_batch", self, pkt.shape[0], _ptr(pkt), pkt.stride(0), p, p_all, a,
+              a_all, _ptr(out), out.stride(0), _ptr(out_len), _stream(stream, pkt))
 
     def encode_seal(self, k, m, block_bytes, data, parity, hdr, hdr_len, pkt, pkt_len,
                     stream=None):
         """SerializeFec on the device: encode data [G][k][bb] into parity [G][m][bb], then
         seal FEC packet g*m+i = hdr[g*m+i][:hdr_len] || tag12 || parity[g][i] into
         pkt [G*m][pkt_stride]; pkt_len int32 [G*m]."""
-        G = data.shape[0]
-        h, h_all = self._lens(hdr_len)
-        rc = self.lib.qfec_encode_seal_batch(self._h, k, m, block_bytes, G, _dptr(data),
-                                             _dptr(parity), _dptr(hdr), hdr.stride(0), h, h_all,
-                                             _dptr(pkt), pkt.stride(0), _dptr(pkt_len),
-                                             _stream(stream, data))
-        if rc:
-            raise FecError(rc, "qfec_encode_seal_batch")
+        h, h_all = _ptr_or_all(hdr_len)
+        _call("qfec_encode_seal_batch", self, k, m, block_bytes, data.shape[0], _ptr(data),
+              _ptr(parity), _ptr(hdr), hdr.stride(0), h, h_all, _ptr(pkt), pkt.stride(0),
+              _ptr(pkt_len), _stream(stream, data))
 
     def seal_groups(self, k, m, block_bytes, data, parity, hdr, hdr_len, pt_len, pkt, pkt_len,
                     encode=False, stream=None):
@@ -268,50 +289,24 @@ class FecEngine:
         hdr[p][:hdr_len] || tag12 || (data[g][i] if i < k else parity[g][i-k])[:pt_len] into
         pkt [G*(k+m)][pkt_stride]; pkt_len int32 [G*(k+m)].  encode=True first encodes data
         into parity (qfec_encode_seal_groups_batch)."""
-        G = data.shape[0]
-        h, h_all = self._lens(hdr_len)
-        p, p_all = self._lens(pt_len)
-        fn = self.lib.qfec_encode_seal_groups_batch if encode else self.lib.qfec_seal_groups_batch
-        rc = fn(self._h, k, m, block_bytes, G, _dptr(data), _dptr(parity), _dptr(hdr),
-                hdr.stride(0), h, h_all, p, p_all, _dptr(pkt), pkt.stride(0), _dptr(pkt_len),
-                _stream(stream, data))
-        if rc:
-            raise FecError(rc, "qfec_encode_seal_groups_batch" if encode else "qfec_seal_groups_batch")
+        h, h_all = _ptr_or_all(hdr_len)
+        p, p_all = _ptr_or_all(pt_len)
+        _call("qfec_encode_seal_groups_batch" if encode else "qfec_seal_groups_batch", self, k, m,
+              block_bytes, data.shape[0], _ptr(data), _ptr(parity), _ptr(hdr), hdr.stride(0), h,
+              h_all, p, p_all, _ptr(pkt), pkt.stride(0), _ptr(pkt_len), _stream(stream, data))
 
     def open_decode(self, k, m, block_bytes, pkt, pkt_len, ad_len, blocks, rows, open_len, rec,
                     rec_rows, status=None, stream=None):
         """Receiver: open every wire packet pkt [G*(k+m)][stride] (pkt_len int32, < 0 = not
         received), place the plaintexts into blocks [G][k][bb] / rows [G][k], then the
         recovered-layout decode into rec / rec_rows / status.  open_len int32 [G*(k+m)]."""
-        G = blocks.shape[0]
-        a, a_all = self._lens(ad_len)
-        rc = self.lib.qfec_open_decode_batch(self._h, k, m, block_bytes, G, _dptr(pkt),
-                                             pkt.stride(0), _dptr(pkt_len), a, a_all,
-                                             _dptr(blocks), _dptr(rows), _dptr(open_len),
-                                             _dptr(rec), _dptr(rec_rows), _dptr(status),
-                                             _stream(stream, pkt))
-        if rc:
-            raise FecError(rc, "qfec_open_decode_batch")
+        a, a_all = _ptr_or_all(ad_len)
+        _call("qfec_open_decode_batch", self, k, m, block_bytes, blocks.shape[0], _ptr(pkt),
+              pkt.stride(0), _ptr(pkt_len), a, a_all, _ptr(blocks), _ptr(rows), _ptr(open_len),
+              _ptr(rec), _ptr(rec_rows), _ptr(status), _stream(stream, pkt))
 
     # ragged packet protection: the two calls above over the packed layout, a block size per
     # group (include/quic_fec.h, "Ragged packet protection")
-    @staticmethod
-    def _ragged_pp_args(k, m, bb, offs, packets):
-        """_ragged_args plus the dense per-packet arguments: `packets` maps a name to
-        (tensor or int or None, dtype, 1 for a [G*(k+m)] array / 2 for [G*(k+m)][stride]
-        rows).  Every array has exactly one entry or row per packet."""
-        G = FecEngine._ragged_args(bb, *offs)
-        n = G * (k + m)
-        for name, (t, dtype, dim) in packets.items():
-            if t is None or isinstance(t, int):
-                continue
-            if t.dtype != dtype:
-                raise TypeError(f"{name}: dtype {t.dtype}, expected {dtype}")
-            if t.dim() != dim or t.shape[0] != n:
-                raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {n} packets "
-                                 f"(G = {G}, k + m = {k + m})")
-        return G
-
     def seal_groups_ragged(self, k, m, bb, data, data_off, parity, par_off, hdr, hdr_len, pt_len,
                            pkt, pkt_len, encode=False, status=None, stream=None):
         """seal_groups with a block size per group: packet p = g*(k+m)+i takes its plaintext
@@ -320,93 +315,64 @@ class FecEngine:
         pkt_len dense by packet as in seal_groups; pt_len int32 [G*(k+m)] or None (whole
         blocks).  encode=True first encodes into parity (status: optional int32 [G], -1 for
         the groups the encode rejects, none of whose packets is sealed)."""
-        import torch
-        G = FecEngine._ragged_pp_args(k, m, bb, (data_off, par_off), {
-            "hdr": (hdr, torch.uint8, 2), "hdr_len": (hdr_len, torch.int32, 1),
-            "pt_len": (pt_len, torch.int32, 1), "pkt": (pkt, torch.uint8, 2),
-            "pkt_len": (pkt_len, torch.int32, 1)})
-        if status is not None and (status.dtype != torch.int32 or status.shape != (G,)):
-            raise TypeError("status must be an int32 [G] device tensor")
+        G = _groups(bb, data_off=data_off, par_off=par_off)
+        n = G * (k + m)
+        _check(hdr, "hdr", "uint8", (n, None), rows=True)
+        _check(hdr_len, "hdr_len", "int32", (n,), rows=True)
+        _check(pt_len, "pt_len", "int32", (n,), rows=True)
+        _check(pkt, "pkt", "uint8", (n, None), rows=True)
+        _check(pkt_len, "pkt_len", "int32", (n,), rows=True)
+        _check(status, "status", "int32", (G,))
         if isinstance(pt_len, int):
             raise TypeError("pt_len: an int32 [G*(k+m)] tensor, or None for whole blocks")
-        h, h_all = self._lens(hdr_len)
-        args = (self._h, k, m, G, _dptr(bb), _dptr(data), _dptr(data_off), _dptr(parity),
-                _dptr(par_off), _dptr(hdr), hdr.stride(0) if hdr is not None else 0, h, h_all,
-                _dptr(pt_len), _dptr(pkt), pkt.stride(0), _dptr(pkt_len))
+        h, h_all = _ptr_or_all(hdr_len)
+        args = (k, m, G, _ptr(bb), _ptr(data), _ptr(data_off), _ptr(parity), _ptr(par_off),
+                _ptr(hdr), _stride(hdr), h, h_all, _ptr(pt_len), _ptr(pkt), pkt.stride(0),
+                _ptr(pkt_len))
         if encode:
-            rc = self.lib.qfec_encode_seal_groups_batch_ragged(*args, _dptr(status),
-                                                               _stream(stream, data))
+            _call("qfec_encode_seal_groups_batch_ragged", self, *args, _ptr(status),
+                  _stream(stream, data))
         else:
             if status is not None:
                 raise ValueError("status is the encode's: pass it with encode=True")
-            rc = self.lib.qfec_seal_groups_batch_ragged(*args, _stream(stream, data))
-        if rc:
-            raise FecError(rc, "qfec_encode_seal_groups_batch_ragged" if encode
-                           else "qfec_seal_groups_batch_ragged")
+            _call("qfec_seal_groups_batch_ragged", self, *args, _stream(stream, data))
 
     def open_decode_ragged(self, k, m, bb, pkt, pkt_len, ad_len, blocks, blocks_off, rows,
                            open_len, rec, rec_off, rec_rows, status=None, stream=None):
         """open_decode with a block size per group: blocks + blocks_off[g] receives
         [k][bb[g]], rec + rec_off[g] up to [min(k,m)][bb[g]] (flat uint8, offsets int64 [G]);
         pkt, pkt_len, open_len dense by packet, rows [G][k], rec_rows [G][min(k,m)]."""
-        import torch
-        G = FecEngine._ragged_pp_args(k, m, bb, (blocks_off, rec_off), {
-            "pkt": (pkt, torch.uint8, 2), "pkt_len": (pkt_len, torch.int32, 1),
-            "ad_len": (ad_len, torch.int32, 1), "open_len": (open_len, torch.int32, 1)})
-        rmax = min(k, m)
-        for name, t, dtype, shape in (("rows", rows, torch.uint8, (G, k)),
-                                      ("rec_rows", rec_rows, torch.uint8, (G, rmax)),
-                                      ("status", status, torch.int32, (G,))):
-            if t is not None and (t.dtype != dtype or tuple(t.shape) != shape):
-                raise TypeError(f"{name} must be a {dtype} {shape} device tensor")
-        a, a_all = self._lens(ad_len)
-        rc = self.lib.qfec_open_decode_batch_ragged(
-            self._h, k, m, G, _dptr(bb), _dptr(pkt), pkt.stride(0), _dptr(pkt_len), a, a_all,
-            _dptr(blocks), _dptr(blocks_off), _dptr(rows), _dptr(open_len), _dptr(rec),
-            _dptr(rec_off), _dptr(rec_rows), _dptr(status), _stream(stream, pkt))
-        if rc:
-            raise FecError(rc, "qfec_open_decode_batch_ragged")
+        G = _groups(bb, blocks_off=blocks_off, rec_off=rec_off)
+        n = G * (k + m)
+        _check(pkt, "pkt", "uint8", (n, None), rows=True)
+        _check(pkt_len, "pkt_len", "int32", (n,), rows=True)
+        _check(ad_len, "ad_len", "int32", (n,), rows=True)
+        _check(open_len, "open_len", "int32", (n,), rows=True)
+        _check(rows, "rows", "uint8", (G, k))
+        _check(rec_rows, "rec_rows", "uint8", (G, min(k, m)))
+        _check(status, "status", "int32", (G,))
+        a, a_all = _ptr_or_all(ad_len)
+        _call("qfec_open_decode_batch_ragged", self, k, m, G, _ptr(bb), _ptr(pkt), pkt.stride(0),
+              _ptr(pkt_len), a, a_all, _ptr(blocks), _ptr(blocks_off), _ptr(rows), _ptr(open_len),
+              _ptr(rec), _ptr(rec_off), _ptr(rec_rows), _ptr(status), _stream(stream, pkt))
 
     # framed groups: QuicFecGroup's wire format around the ragged protected calls
     # (include/quic_fec.h, "Framed groups")
-    @staticmethod
-    def _framed_args(G, rows, arrays):
-        """Dense per-row arguments of a framed call: `arrays` maps a name to (tensor or int or
-        None, dtype, 1 for a [rows] array / 2 for [rows][stride] rows)."""
-        for name, (t, dtype, dim) in arrays.items():
-            if t is None or isinstance(t, int):
-                continue
-            if t.dtype != dtype:
-                raise TypeError(f"{name}: dtype {t.dtype}, expected {dtype}")
-            if t.dim() != dim or t.shape[0] != rows:
-                raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {rows} rows (G = {G})")
-
-    @staticmethod
-    def _pn(pn_len):
-        """(array pointer, scalar) of a pn_len argument: a uint8 device tensor or an int."""
-        if isinstance(pn_len, int):
-            return None, pn_len
-        return _dptr(pn_len), 0
-
     def frame_blocks_ragged(self, k, bb, pay, pay_len, pn_len, data, data_off, status=None,
                             stream=None):
         """Blocks from payload rows: block (g, i) at data + data_off[g] + i*bb[g] becomes
         prefix || pay[g*k+i][:pay_len] || zeros.  pay uint8 [G*k][stride], pay_len int32 [G*k],
         pn_len uint8 [G*k] or an int; status: optional int32 [G] (-3 for a rejected group, of
         which nothing is written)."""
-        import torch
-        G = FecEngine._ragged_args(bb, data_off)
-        FecEngine._framed_args(G, G * k, {"pay": (pay, torch.uint8, 2),
-                                     "pay_len": (pay_len, torch.int32, 1),
-                                     "pn_len": (pn_len, torch.uint8, 1)})
-        if status is not None and (status.dtype != torch.int32 or status.shape != (G,)):
-            raise TypeError("status must be an int32 [G] device tensor")
-        pn, pn_all = self._pn(pn_len)
-        rc = self.lib.qfec_frame_blocks_batch_ragged(
-            self._h, k, G, _dptr(bb), _dptr(pay), pay.stride(0), _dptr(pay_len), pn, pn_all,
-            _dptr(data), _dptr(data_off), _dptr(status), _stream(stream, data))
-        if rc:
-            raise FecError(rc, "qfec_frame_blocks_batch_ragged")
+        G = _groups(bb, data_off=data_off)
+        _check(pay, "pay", "uint8", (G * k, None), rows=True)
+        _check(pay_len, "pay_len", "int32", (G * k,), rows=True)
+        _check(pn_len, "pn_len", "uint8", (G * k,), rows=True)
+        _check(status, "status", "int32", (G,))
+        pn, pn_all = _ptr_or_all(pn_len)
+        _call("qfec_frame_blocks_batch_ragged", self, k, G, _ptr(bb), _ptr(pay), pay.stride(0),
+              _ptr(pay_len), pn, pn_all, _ptr(data), _ptr(data_off), _ptr(status),
+              _stream(stream, data))
 
     def extract_revived_ragged(self, k, m, bb, rec, rec_off, rec_rows, status, rev, rev_len,
                                rev_pn_len=None, stream=None):
@@ -414,22 +380,16 @@ class FecEngine:
         payload of recovered block j of group g, rev_len int32 [G*rmax] its length (-1: no such
         block, or longer than the row), rev_pn_len uint8 [G*rmax] the prefix's top two bits.
         status: int32 [G] or None (every group taken as decoded)."""
-        import torch
-        G = FecEngine._ragged_args(bb, rec_off)
+        G = _groups(bb, rec_off=rec_off)
         rmax = min(k, m)
-        FecEngine._framed_args(G, G * rmax, {"rev": (rev, torch.uint8, 2),
-                                        "rev_len": (rev_len, torch.int32, 1),
-                                        "rev_pn_len": (rev_pn_len, torch.uint8, 1)})
-        for name, t, dtype, shape in (("rec_rows", rec_rows, torch.uint8, (G, rmax)),
-                                      ("status", status, torch.int32, (G,))):
-            if t is not None and (t.dtype != dtype or tuple(t.shape) != shape):
-                raise TypeError(f"{name} must be a {dtype} {shape} device tensor")
-        rc = self.lib.qfec_extract_revived_batch_ragged(
-            self._h, k, m, G, _dptr(bb), _dptr(rec), _dptr(rec_off), _dptr(rec_rows),
-            _dptr(status), _dptr(rev), rev.stride(0), _dptr(rev_len), _dptr(rev_pn_len),
-            _stream(stream, rec))
-        if rc:
-            raise FecError(rc, "qfec_extract_revived_batch_ragged")
+        _check(rev, "rev", "uint8", (G * rmax, None), rows=True)
+        _check(rev_len, "rev_len", "int32", (G * rmax,), rows=True)
+        _check(rev_pn_len, "rev_pn_len", "uint8", (G * rmax,), rows=True)
+        _check(rec_rows, "rec_rows", "uint8", (G, rmax))
+        _check(status, "status", "int32", (G,))
+        _call("qfec_extract_revived_batch_ragged", self, k, m, G, _ptr(bb), _ptr(rec),
+              _ptr(rec_off), _ptr(rec_rows), _ptr(status), _ptr(rev), rev.stride(0),
+              _ptr(rev_len), _ptr(rev_pn_len), _stream(stream, rec))
 
     def frame_encode_seal_ragged(self, k, m, bb, data, data_off, parity, par_off, hdr, hdr_len,
                                  pay, pay_len, pn_len, pkt, pkt_len, status=None, stream=None):
@@ -439,24 +399,22 @@ class FecEngine:
         pay_len, pn_len as in frame_blocks_ragged; hdr, pkt, pkt_len dense by packet as in
         seal_groups_ragged; status: optional int32 [G] (0, -1 encode rejected, -3 framing
         rejected)."""
-        import torch
-        G = FecEngine._ragged_pp_args(k, m, bb, (data_off, par_off), {
-            "hdr": (hdr, torch.uint8, 2), "hdr_len": (hdr_len, torch.int32, 1),
-            "pkt": (pkt, torch.uint8, 2), "pkt_len": (pkt_len, torch.int32, 1)})
-        FecEngine._framed_args(G, G * k, {"pay": (pay, torch.uint8, 2),
-                                     "pay_len": (pay_len, torch.int32, 1),
-                                     "pn_len": (pn_len, torch.uint8, 1)})
-        if status is not None and (status.dtype != torch.int32 or status.shape != (G,)):
-            raise TypeError("status must be an int32 [G] device tensor")
-        h, h_all = self._lens(hdr_len)
-        pn, pn_all = self._pn(pn_len)
-        rc = self.lib.qfec_frame_encode_seal_groups_batch_ragged(
-            self._h, k, m, G, _dptr(bb), _dptr(data), _dptr(data_off), _dptr(parity),
-            _dptr(par_off), _dptr(hdr), hdr.stride(0) if hdr is not None else 0, h, h_all,
-            _dptr(pay), pay.stride(0), _dptr(pay_len), pn, pn_all, _dptr(pkt), pkt.stride(0),
-            _dptr(pkt_len), _dptr(status), _stream(stream, data))
-        if rc:
-            raise FecError(rc, "qfec_frame_encode_seal_groups_batch_ragged")
+        G = _groups(bb, data_off=data_off, par_off=par_off)
+        n = G * (k + m)
+        _check(hdr, "hdr", "uint8", (n, None), rows=True)
+        _check(hdr_len, "hdr_len", "int32", (n,), rows=True)
+        _check(pkt, "pkt", "uint8", (n, None), rows=True)
+        _check(pkt_len, "pkt_len", "int32", (n,), rows=True)
+        _check(pay, "pay", "uint8", (G * k, None), rows=True)
+        _check(pay_len, "pay_len", "int32", (G * k,), rows=True)
+        _check(pn_len, "pn_len", "uint8", (G * k,), rows=True)
+        _check(status, "status", "int32", (G,))
+        h, h_all = _ptr_or_all(hdr_len)
+        pn, pn_all = _ptr_or_all(pn_len)
+        _call("qfec_frame_encode_seal_groups_batch_ragged", self, k, m, G, _ptr(bb), _ptr(data),
+              _ptr(data_off), _ptr(parity), _ptr(par_off), _ptr(hdr), _stride(hdr), h, h_all,
+              _ptr(pay), pay.stride(0), _ptr(pay_len), pn, pn_all, _ptr(pkt), pkt.stride(0),
+              _ptr(pkt_len), _ptr(status), _stream(stream, data))
 
     def open_decode_extract_ragged(self, k, m, bb, pkt, pkt_len, ad_len, pn_len, blocks,
                                    blocks_off, rows, open_len, rec, rec_off, rec_rows, rev,
@@ -464,40 +422,33 @@ class FecEngine:
         """Receiver: wire packets in, revived payloads out.  open_decode_ragged with a data
         packet's plaintext placed behind its prefix (pn_len uint8 [G*(k+m)] or an int), then
         extract_revived_ragged into rev / rev_len / rev_pn_len."""
-        import torch
-        G = FecEngine._ragged_pp_args(k, m, bb, (blocks_off, rec_off), {
-            "pkt": (pkt, torch.uint8, 2), "pkt_len": (pkt_len, torch.int32, 1),
-            "ad_len": (ad_len, torch.int32, 1), "open_len": (open_len, torch.int32, 1),
-            "pn_len": (pn_len, torch.uint8, 1)})
-        rmax = min(k, m)
-        FecEngine._framed_args(G, G * rmax, {"rev": (rev, torch.uint8, 2),
-                                        "rev_len": (rev_len, torch.int32, 1),
-                                        "rev_pn_len": (rev_pn_len, torch.uint8, 1)})
-        for name, t, dtype, shape in (("rows", rows, torch.uint8, (G, k)),
-                                      ("rec_rows", rec_rows, torch.uint8, (G, rmax)),
-                                      ("status", status, torch.int32, (G,))):
-            if t is not None and (t.dtype != dtype or tuple(t.shape) != shape):
-                raise TypeError(f"{name} must be a {dtype} {shape} device tensor")
-        a, a_all = self._lens(ad_len)
-        pn, pn_all = self._pn(pn_len)
-        rc = self.lib.qfec_open_decode_extract_batch_ragged(
-            self._h, k, m, G, _dptr(bb), _dptr(pkt), pkt.stride(0), _dptr(pkt_len), a, a_all, pn,
-            pn_all, _dptr(blocks), _dptr(blocks_off), _dptr(rows), _dptr(open_len), _dptr(rec),
-            _dptr(rec_off), _dptr(rec_rows), _dptr(status), _dptr(rev), rev.stride(0),
-            _dptr(rev_len), _dptr(rev_pn_len), _stream(stream, pkt))
-        if rc:
-            raise FecError(rc, "qfec_open_decode_extract_batch_ragged")
+        G = _groups(bb, blocks_off=blocks_off, rec_off=rec_off)
+        n, rmax = G * (k + m), min(k, m)
+        _check(pkt, "pkt", "uint8", (n, None), rows=True)
+        _check(pkt_len, "pkt_len", "int32", (n,), rows=True)
+        _check(ad_len, "ad_len", "int32", (n,), rows=True)
+        _check(open_len, "open_len", "int32", (n,), rows=True)
+        _check(pn_len, "pn_len", "uint8", (n,), rows=True)
+        _check(rev, "rev", "uint8", (G * rmax, None), rows=True)
+        _check(rev_len, "rev_len", "int32", (G * rmax,), rows=True)
+        _check(rev_pn_len, "rev_pn_len", "uint8", (G * rmax,), rows=True)
+        _check(rows, "rows", "uint8", (G, k))
+        _check(rec_rows, "rec_rows", "uint8", (G, rmax))
+        _check(status, "status", "int32", (G,))
+        a, a_all = _ptr_or_all(ad_len)
+        pn, pn_all = _ptr_or_all(pn_len)
+        _call("qfec_open_decode_extract_batch_ragged", self, k, m, G, _ptr(bb), _ptr(pkt),
+              pkt.stride(0), _ptr(pkt_len), a, a_all, pn, pn_all, _ptr(blocks), _ptr(blocks_off),
+              _ptr(rows), _ptr(open_len), _ptr(rec), _ptr(rec_off), _ptr(rec_rows), _ptr(status),
+              _ptr(rev), rev.stride(0), _ptr(rev_len), _ptr(rev_pn_len), _stream(stream, pkt))
 
     # host-pointer batch calls (synchronous; include H2D/D2H)
     def encode_host(self, k, m, block_bytes, data):
         data = np.ascontiguousarray(data, dtype=np.uint8)
         G = data.shape[0]
         parity = np.zeros((G, m, block_bytes), np.uint8)
-        rc = self.lib.qfec_encode_batch_host(self._h, k, m, block_bytes, G,
-                                             data.ctypes.data_as(ctypes.c_void_p),
-                                             parity.ctypes.data_as(ctypes.c_void_p))
-        if rc < -1:
-            raise FecError(rc, "qfec_encode_batch_host")
+        rc = _call("qfec_encode_batch_host", self, k, m, block_bytes, G, _vp(data), _vp(parity),
+                   reference_rc=True)
         return parity, rc
 
     def decode_host(self, k, m, block_bytes, blocks, rows):
@@ -505,12 +456,8 @@ class FecEngine:
         rows = np.array(rows, dtype=np.uint8, order="C", copy=True)
         G = blocks.shape[0]
         status = np.zeros(G, np.int32)
-        rc = self.lib.qfec_decode_batch_host(self._h, k, m, block_bytes, G,
-                                             blocks.ctypes.data_as(ctypes.c_void_p),
-                                             rows.ctypes.data_as(ctypes.c_void_p),
-                                             status.ctypes.data_as(ctypes.c_void_p))
-        if rc:
-            raise FecError(rc, "qfec_decode_batch_host")
+        _call("qfec_decode_batch_host", self, k, m, block_bytes, G, _vp(blocks), _vp(rows),
+              _vp(status))
         return blocks, rows, status
 
 
@@ -531,73 +478,25 @@ def last_grids():
     return out
 
 
-def _hptr(t):
-    import torch
-    if not isinstance(t, torch.Tensor) or t.is_cuda or not t.is_contiguous():
-        raise TypeError("host buffers must be contiguous CPU tensors (pinned for full speed)")
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _hcheck(t, name, dtype, shape):
-    """A host buffer argument: a contiguous CPU tensor of `dtype` and exactly `shape` (None in
-    `shape`: any extent, > 0).  The library copies whole rows into and out of it, so a short
-    buffer would be overrun and a wrong dtype misread: ValueError / TypeError instead."""
-    import torch
-    if not isinstance(t, torch.Tensor) or t.is_cuda or not t.is_contiguous():
-        raise TypeError(f"{name}: host buffers must be contiguous CPU tensors "
-                        "(pinned for full speed)")
-    if t.dtype != dtype:
-        raise ValueError(f"{name}: dtype {t.dtype}, expected {dtype}")
-    if t.dim() != len(shape) or any(want is not None and got != want
-                                    for got, want in zip(t.shape, shape)) \
-            or any(got <= 0 for got, want in zip(t.shape, shape) if want is None):
-        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-
-
-def _hcheck_lens(lens, name, n):
-    """A per-packet length argument: an int (the same for every packet) or int32 [n]."""
-    import torch
-    if not isinstance(lens, int):
-        _hcheck(lens, name, torch.int32, (n,))
-
-
 def encode_host_into(engine, k, m, block_bytes, data_h, parity_h):
     """Host-pointer encode on caller-owned CPU tensors (pinned memory recommended):
     H2D, kernels and D2H pipelined in chunks inside the library.  Returns 0 / -1."""
-    import torch
     G = data_h.shape[0]
-    _hcheck(data_h, "data", torch.uint8, (G, k, block_bytes))
-    _hcheck(parity_h, "parity", torch.uint8, (G, m, block_bytes))
-    rc = engine.lib.qfec_encode_batch_host(engine._h, k, m, block_bytes, data_h.shape[0],
-                                           _hptr(data_h), _hptr(parity_h))
-    if rc < -1:
-        raise FecError(rc, "qfec_encode_batch_host")
-    return rc
+    _check(data_h, "data", "uint8", (G, k, block_bytes), host=True)
+    _check(parity_h, "parity", "uint8", (G, m, block_bytes), host=True)
+    return _call("qfec_encode_batch_host", engine, k, m, block_bytes, G, _ptr(data_h, True),
+                 _ptr(parity_h, True), reference_rc=True)
 
 
 def decode_host_into(engine, k, m, block_bytes, blocks_h, rows_h, status_h=None):
     """Host-pointer in-place decode on caller-owned CPU tensors (cauchy_256_decode
     semantics per group)."""
-    import torch
     G = blocks_h.shape[0]
-    _hcheck(blocks_h, "blocks", torch.uint8, (G, k, block_bytes))
-    _hcheck(rows_h, "rows", torch.uint8, (G, k))
-    if status_h is not None:
-        _hcheck(status_h, "status", torch.int32, (G,))
-    rc = engine.lib.qfec_decode_batch_host(engine._h, k, m, block_bytes, blocks_h.shape[0],
-                                           _hptr(blocks_h), _hptr(rows_h),
-                                           None if status_h is None else _hptr(status_h))
-    if rc:
-        raise FecError(rc, "qfec_decode_batch_host")
-    return rc
-
-
-def _hlens(lens):
-    """(host array pointer, scalar) for a per-packet length argument of a host call: an int32
-    CPU tensor, or an int meaning the same length for every packet."""
-    if isinstance(lens, int):
-        return None, lens
-    return _hptr(lens), 0
+    _check(blocks_h, "blocks", "uint8", (G, k, block_bytes), host=True)
+    _check(rows_h, "rows", "uint8", (G, k), host=True)
+    _check(status_h, "status", "int32", (G,), host=True, optional=True)
+    return _call("qfec_decode_batch_host", engine, k, m, block_bytes, G, _ptr(blocks_h, True),
+                 _ptr(rows_h, True), _ptr(status_h, True))
 
 
 def encode_seal_groups_host_into(engine, k, m, block_bytes, data_h, hdr_h, hdr_len, pt_len,
@@ -605,25 +504,19 @@ def encode_seal_groups_host_into(engine, k, m, block_bytes, data_h, hdr_h, hdr_l
     """Sender, host to host (qfec_encode_seal_groups_batch_host): data [G][k][bb] and
     headers hdr [G*(k+m)][hdr_stride] (or None) -> every packet sealed into pkt
     [G*(k+m)][pkt_stride], pkt_len int32 [G*(k+m)].  Returns 0 / -1."""
-    import torch
     G = data_h.shape[0]
     n = G * (k + m)
-    _hcheck(data_h, "data", torch.uint8, (G, k, block_bytes))
-    if hdr_h is not None:
-        _hcheck(hdr_h, "hdr", torch.uint8, (n, None))
-    _hcheck_lens(hdr_len, "hdr_len", n)
-    _hcheck_lens(pt_len, "pt_len", n)
-    _hcheck(pkt_h, "pkt", torch.uint8, (n, None))
-    _hcheck(pkt_len_h, "pkt_len", torch.int32, (n,))
-    h, h_all = _hlens(hdr_len)
-    p, p_all = _hlens(pt_len)
-    rc = engine.lib.qfec_encode_seal_groups_batch_host(
-        engine._h, k, m, block_bytes, data_h.shape[0], _hptr(data_h),
-        None if hdr_h is None else _hptr(hdr_h), 0 if hdr_h is None else hdr_h.stride(0), h,
-        h_all, p, p_all, _hptr(pkt_h), pkt_h.stride(0), _hptr(pkt_len_h))
-    if rc < -1:
-        raise FecError(rc, "qfec_encode_seal_groups_batch_host")
-    return rc
+    _check(data_h, "data", "uint8", (G, k, block_bytes), host=True)
+    _check(hdr_h, "hdr", "uint8", (n, None), host=True, optional=True)
+    _check(hdr_len, "hdr_len", "int32", (n,), host=True)
+    _check(pt_len, "pt_len", "int32", (n,), host=True)
+    _check(pkt_h, "pkt", "uint8", (n, None), host=True)
+    _check(pkt_len_h, "pkt_len", "int32", (n,), host=True)
+    h, h_all = _ptr_or_all(hdr_len, True)
+    p, p_all = _ptr_or_all(pt_len, True)
+    return _call("qfec_encode_seal_groups_batch_host", engine, k, m, block_bytes, G,
+                 _ptr(data_h, True), _ptr(hdr_h, True), _stride(hdr_h), h, h_all, p, p_all,
+                 _ptr(pkt_h, True), pkt_h.stride(0), _ptr(pkt_len_h, True), reference_rc=True)
 
 
 def open_decode_host_into(engine, k, m, block_bytes, pkt_h, pkt_len_h, ad_len, rec_h,
@@ -631,46 +524,43 @@ def open_decode_host_into(engine, k, m, block_bytes, pkt_h, pkt_len_h, ad_len, r
     """Receiver, host to host (qfec_open_decode_batch_host): wire packets pkt
     [G*(k+m)][stride], pkt_len int32 (< 0: not received) -> rec [G][min(k,m)][bb],
     rec_rows, status [G], open_len [G*(k+m)]."""
-    import torch
     G = rec_h.shape[0]
     n, rmax = G * (k + m), min(k, m)
-    _hcheck(pkt_h, "pkt", torch.uint8, (n, None))
-    _hcheck(pkt_len_h, "pkt_len", torch.int32, (n,))
-    _hcheck_lens(ad_len, "ad_len", n)
-    _hcheck(rec_h, "rec", torch.uint8, (G, rmax, block_bytes))
-    _hcheck(rec_rows_h, "rec_rows", torch.uint8, (G, rmax))
-    if status_h is not None:
-        _hcheck(status_h, "status", torch.int32, (G,))
-    if open_len_h is not None:
-        _hcheck(open_len_h, "open_len", torch.int32, (n,))
-    a, a_all = _hlens(ad_len)
-    rc = engine.lib.qfec_open_decode_batch_host(
-        engine._h, k, m, block_bytes, rec_h.shape[0], _hptr(pkt_h), pkt_h.stride(0),
-        _hptr(pkt_len_h), a, a_all, _hptr(rec_h), _hptr(rec_rows_h),
-        None if status_h is None else _hptr(status_h),
-        None if open_len_h is None else _hptr(open_len_h))
-    if rc:
-        raise FecError(rc, "qfec_open_decode_batch_host")
-    return rc
+    _check(pkt_h, "pkt", "uint8", (n, None), host=True)
+    _check(pkt_len_h, "pkt_len", "int32", (n,), host=True)
+    _check(ad_len, "ad_len", "int32", (n,), host=True)
+    _check(rec_h, "rec", "uint8", (G, rmax, block_bytes), host=True)
+    _check(rec_rows_h, "rec_rows", "uint8", (G, rmax), host=True)
+    _check(status_h, "status", "int32", (G,), host=True, optional=True)
+    _check(open_len_h, "open_len", "int32", (n,), host=True, optional=True)
+    a, a_all = _ptr_or_all(ad_len, True)
+    return _call("qfec_open_decode_batch_host", engine, k, m, block_bytes, G, _ptr(pkt_h, True),
+                 pkt_h.stride(0), _ptr(pkt_len_h, True), a, a_all, _ptr(rec_h, True),
+                 _ptr(rec_rows_h, True), _ptr(status_h, True), _ptr(open_len_h, True))
 
 
 def decode_recovered_host_into(engine, k, m, block_bytes, blocks_h, rows_h, rec_h, rec_rows_h,
                                status_h=None):
     """Host-pointer decode returning only the recovered blocks (CPU tensors)."""
-    import torch
     G, rmax = blocks_h.shape[0], min(k, m)
-    _hcheck(blocks_h, "blocks", torch.uint8, (G, k, block_bytes))
-    _hcheck(rows_h, "rows", torch.uint8, (G, k))
-    _hcheck(rec_h, "rec", torch.uint8, (G, rmax, block_bytes))
-    _hcheck(rec_rows_h, "rec_rows", torch.uint8, (G, rmax))
-    if status_h is not None:
-        _hcheck(status_h, "status", torch.int32, (G,))
-    rc = engine.lib.qfec_decode_batch_recovered_host(
-        engine._h, k, m, block_bytes, blocks_h.shape[0], _hptr(blocks_h), _hptr(rows_h),
-        _hptr(rec_h), _hptr(rec_rows_h), None if status_h is None else _hptr(status_h))
-    if rc:
-        raise FecError(rc, "qfec_decode_batch_recovered_host")
-    return rc
+    _check(blocks_h, "blocks", "uint8", (G, k, block_bytes), host=True)
+    _check(rows_h, "rows", "uint8", (G, k), host=True)
+    _check(rec_h, "rec", "uint8", (G, rmax, block_bytes), host=True)
+    _check(rec_rows_h, "rec_rows", "uint8", (G, rmax), host=True)
+    _check(status_h, "status", "int32", (G,), host=True, optional=True)
+    return _call("qfec_decode_batch_recovered_host", engine, k, m, block_bytes, G,
+                 _ptr(blocks_h, True), _ptr(rows_h, True), _ptr(rec_h, True),
+                 _ptr(rec_rows_h, True), _ptr(status_h, True))
+
+
+def _layout(name, k, m, G, *arrays):
+    """One of the packed-layout calls (host only) over G groups: `arrays` are its numpy arrays
+    ahead of the three offset arrays int64 [G] and the three totals, which are returned behind
+    the call's code."""
+    offs = [np.zeros(G, np.int64) for _ in range(3)]
+    totals = np.zeros(3, np.int64)
+    rc = getattr(load(), name)(k, m, G, *[_vp(a) for a in arrays + tuple(offs)], _vp(totals))
+    return rc, offs, tuple(int(t) for t in totals)
 
 
 def ragged_layout(k, m, bb):
@@ -680,15 +570,10 @@ def ragged_layout(k, m, bb):
     bb = np.ascontiguousarray(bb, dtype=np.int32)
     if bb.ndim != 1:
         raise ValueError("bb must be one-dimensional")
-    G = bb.shape[0]
-    offs = [np.zeros(G, np.int64) for _ in range(3)]
-    totals = np.zeros(3, np.int64)
-    rc = load().qfec_ragged_layout(k, m, G, bb.ctypes.data_as(ctypes.c_void_p),
-                                   *[o.ctypes.data_as(ctypes.c_void_p) for o in offs],
-                                   totals.ctypes.data_as(ctypes.c_void_p))
+    rc, offs, totals = _layout("qfec_ragged_layout", k, m, bb.shape[0], bb)
     if rc:
         raise ValueError(f"qfec_ragged_layout: rc={rc} (k={k} m={m}, a size < 1 or overflow)")
-    return offs[0], offs[1], offs[2], tuple(int(t) for t in totals)
+    return offs[0], offs[1], offs[2], totals
 
 
 def framed_layout(k, m, pay_len):
@@ -701,16 +586,11 @@ def framed_layout(k, m, pay_len):
         raise ValueError("pay_len must hold k lengths per group")
     G = pay_len.size // k
     bb = np.zeros(G, np.int32)
-    offs = [np.zeros(G, np.int64) for _ in range(3)]
-    totals = np.zeros(3, np.int64)
-    rc = load().qfec_framed_layout(k, m, G, pay_len.ctypes.data_as(ctypes.c_void_p),
-                                   bb.ctypes.data_as(ctypes.c_void_p),
-                                   *[o.ctypes.data_as(ctypes.c_void_p) for o in offs],
-                                   totals.ctypes.data_as(ctypes.c_void_p))
+    rc, offs, totals = _layout("qfec_framed_layout", k, m, G, pay_len, bb)
     if rc:
         raise ValueError(f"qfec_framed_layout: rc={rc} (k={k} m={m}, a length outside "
                          "[0, 0x3fff] or overflow)")
-    return bb, offs[0], offs[1], offs[2], tuple(int(t) for t in totals)
+    return bb, offs[0], offs[1], offs[2], totals
 
 
 def framed_rx_block_bytes(k, m, pkt_len, ad_len):
@@ -723,15 +603,13 @@ def framed_rx_block_bytes(k, m, pkt_len, ad_len):
         raise ValueError("pkt_len must hold k + m lengths per group")
     G = pkt_len.size // (k + m)
     if isinstance(ad_len, (int, np.integer)):
-        a, a_all = None, int(ad_len)
+        ad_len, a_all = None, int(ad_len)
     else:
-        ad_len = np.ascontiguousarray(ad_len, dtype=np.int32).reshape(-1)
+        ad_len, a_all = np.ascontiguousarray(ad_len, dtype=np.int32).reshape(-1), 0
         if ad_len.size != pkt_len.size:
             raise ValueError("ad_len must hold one length per packet")
-        a, a_all = ad_len.ctypes.data_as(ctypes.c_void_p), 0
     bb = np.zeros(G, np.int32)
-    rc = load().qfec_framed_rx_block_bytes(k, m, G, pkt_len.ctypes.data_as(ctypes.c_void_p), a,
-                                           a_all, bb.ctypes.data_as(ctypes.c_void_p))
+    rc = load().qfec_framed_rx_block_bytes(k, m, G, _vp(pkt_len), _vp(ad_len), a_all, _vp(bb))
     if rc:
         raise ValueError(f"qfec_framed_rx_block_bytes: rc={rc} (k={k} m={m})")
     return bb
@@ -743,9 +621,9 @@ def _hcheck_ragged_one(n_blocks, bb_h, buf_h, off_h, name):
     name (n_blocks blocks each)."""
     import torch
     G = bb_h.shape[0] if isinstance(bb_h, torch.Tensor) and bb_h.dim() == 1 else None
-    _hcheck(bb_h, "bb", torch.int32, (G,))
-    _hcheck(off_h, f"{name}_off", torch.int64, (G,))
-    _hcheck(buf_h, name, torch.uint8, (None,))
+    _check(bb_h, "bb", "int32", (G,), host=True)
+    _check(off_h, f"{name}_off", "int64", (G,), host=True)
+    _check(buf_h, name, "uint8", (None,), host=True)
     if int(bb_h.min()) < 1:
         raise ValueError("bb: every block size must be >= 1")
     if int(off_h.min()) < 0 or int((off_h % 16).max()) != 0:
@@ -767,36 +645,26 @@ def encode_ragged_host_into(engine, k, m, bb_h, data_h, data_off_h, parity_h, pa
     """Host-pointer ragged encode on caller-owned CPU tensors (qfec_encode_batch_ragged_host):
     bb int32 [G], offsets int64 [G] (ascending, as ragged_layout gives them), data / parity flat
     uint8.  Returns 0 / -1."""
-    import torch
     G = _hcheck_ragged(k, m, bb_h, data_h, data_off_h, parity_h, par_off_h)
-    if status_h is not None:
-        _hcheck(status_h, "status", torch.int32, (G,))
-    rc = engine.lib.qfec_encode_batch_ragged_host(
-        engine._h, k, m, G, _hptr(bb_h), _hptr(data_h), _hptr(data_off_h), _hptr(parity_h),
-        _hptr(par_off_h), None if status_h is None else _hptr(status_h))
-    if rc < -1:
-        raise FecError(rc, "qfec_encode_batch_ragged_host")
-    return rc
+    _check(status_h, "status", "int32", (G,), host=True, optional=True)
+    return _call("qfec_encode_batch_ragged_host", engine, k, m, G, _ptr(bb_h, True),
+                 _ptr(data_h, True), _ptr(data_off_h, True), _ptr(parity_h, True),
+                 _ptr(par_off_h, True), _ptr(status_h, True), reference_rc=True)
 
 
 def decode_ragged_recovered_host_into(engine, k, m, bb_h, blocks_h, blocks_off_h, rows_h, rec_h,
                                       rec_off_h, rec_rows_h, status_h=None):
     """Host-pointer ragged decode returning only the recovered blocks
     (qfec_decode_batch_ragged_recovered_host); rows [G][k], rec_rows [G][min(k,m)]."""
-    import torch
     rmax = min(k, m)
     G = _hcheck_ragged(k, rmax, bb_h, blocks_h, blocks_off_h, rec_h, rec_off_h)
-    _hcheck(rows_h, "rows", torch.uint8, (G, k))
-    _hcheck(rec_rows_h, "rec_rows", torch.uint8, (G, rmax))
-    if status_h is not None:
-        _hcheck(status_h, "status", torch.int32, (G,))
-    rc = engine.lib.qfec_decode_batch_ragged_recovered_host(
-        engine._h, k, m, G, _hptr(bb_h), _hptr(blocks_h), _hptr(blocks_off_h), _hptr(rows_h),
-        _hptr(rec_h), _hptr(rec_off_h), _hptr(rec_rows_h),
-        None if status_h is None else _hptr(status_h))
-    if rc:
-        raise FecError(rc, "qfec_decode_batch_ragged_recovered_host")
-    return rc
+    _check(rows_h, "rows", "uint8", (G, k), host=True)
+    _check(rec_rows_h, "rec_rows", "uint8", (G, rmax), host=True)
+    _check(status_h, "status", "int32", (G,), host=True, optional=True)
+    return _call("qfec_decode_batch_ragged_recovered_host", engine, k, m, G, _ptr(bb_h, True),
+                 _ptr(blocks_h, True), _ptr(blocks_off_h, True), _ptr(rows_h, True),
+                 _ptr(rec_h, True), _ptr(rec_off_h, True), _ptr(rec_rows_h, True),
+                 _ptr(status_h, True))
 
 
 def encode_seal_groups_ragged_host_into(engine, k, m, bb_h, data_h, data_off_h, hdr_h, hdr_len,
@@ -805,27 +673,19 @@ def encode_seal_groups_ragged_host_into(engine, k, m, bb_h, data_h, data_off_h, 
     bb int32 [G], data flat uint8 with offsets int64 [G] (ascending, as ragged_layout gives
     them); hdr [G*(k+m)][hdr_stride] (or None), pkt [G*(k+m)][pkt_stride], pkt_len int32
     [G*(k+m)], pt_len int32 [G*(k+m)] or None (whole blocks); status: optional int32 [G]."""
-    import torch
     G = _hcheck_ragged_one(k, bb_h, data_h, data_off_h, "data")
     n = G * (k + m)
-    if hdr_h is not None:
-        _hcheck(hdr_h, "hdr", torch.uint8, (n, None))
-    _hcheck_lens(hdr_len, "hdr_len", n)
-    if pt_len is not None:
-        _hcheck(pt_len, "pt_len", torch.int32, (n,))
-    _hcheck(pkt_h, "pkt", torch.uint8, (n, None))
-    _hcheck(pkt_len_h, "pkt_len", torch.int32, (n,))
-    if status_h is not None:
-        _hcheck(status_h, "status", torch.int32, (G,))
-    h, h_all = _hlens(hdr_len)
-    rc = engine.lib.qfec_encode_seal_groups_batch_ragged_host(
-        engine._h, k, m, G, _hptr(bb_h), _hptr(data_h), _hptr(data_off_h),
-        None if hdr_h is None else _hptr(hdr_h), 0 if hdr_h is None else hdr_h.stride(0), h,
-        h_all, None if pt_len is None else _hptr(pt_len), _hptr(pkt_h), pkt_h.stride(0),
-        _hptr(pkt_len_h), None if status_h is None else _hptr(status_h))
-    if rc:
-        raise FecError(rc, "qfec_encode_seal_groups_batch_ragged_host")
-    return rc
+    _check(hdr_h, "hdr", "uint8", (n, None), host=True, optional=True)
+    _check(hdr_len, "hdr_len", "int32", (n,), host=True)
+    _check(pt_len, "pt_len", "int32", (n,), host=True, optional=True)
+    _check(pkt_h, "pkt", "uint8", (n, None), host=True)
+    _check(pkt_len_h, "pkt_len", "int32", (n,), host=True)
+    _check(status_h, "status", "int32", (G,), host=True, optional=True)
+    h, h_all = _ptr_or_all(hdr_len, True)
+    return _call("qfec_encode_seal_groups_batch_ragged_host", engine, k, m, G, _ptr(bb_h, True),
+                 _ptr(data_h, True), _ptr(data_off_h, True), _ptr(hdr_h, True), _stride(hdr_h), h,
+                 h_all, _ptr(pt_len, True), _ptr(pkt_h, True), pkt_h.stride(0),
+                 _ptr(pkt_len_h, True), _ptr(status_h, True))
 
 
 def open_decode_ragged_host_into(engine, k, m, bb_h, pkt_h, pkt_len_h, ad_len, rec_h, rec_off_h,
@@ -834,32 +694,25 @@ def open_decode_ragged_host_into(engine, k, m, bb_h, pkt_h, pkt_len_h, ad_len, r
     wire packets pkt [G*(k+m)][stride], pkt_len int32 (< 0: not received) -> rec (flat uint8,
     group g's up to [min(k,m)][bb[g]] at rec_off[g]; bytes not written keep their values),
     rec_rows [G][min(k,m)], status [G], open_len [G*(k+m)]."""
-    import torch
     rmax = min(k, m)
     G = _hcheck_ragged_one(rmax, bb_h, rec_h, rec_off_h, "rec")
     n = G * (k + m)
-    _hcheck(pkt_h, "pkt", torch.uint8, (n, None))
-    _hcheck(pkt_len_h, "pkt_len", torch.int32, (n,))
-    _hcheck_lens(ad_len, "ad_len", n)
-    _hcheck(rec_rows_h, "rec_rows", torch.uint8, (G, rmax))
-    if status_h is not None:
-        _hcheck(status_h, "status", torch.int32, (G,))
-    if open_len_h is not None:
-        _hcheck(open_len_h, "open_len", torch.int32, (n,))
-    a, a_all = _hlens(ad_len)
-    rc = engine.lib.qfec_open_decode_batch_ragged_host(
-        engine._h, k, m, G, _hptr(bb_h), _hptr(pkt_h), pkt_h.stride(0), _hptr(pkt_len_h), a,
-        a_all, _hptr(rec_h), _hptr(rec_off_h), _hptr(rec_rows_h),
-        None if status_h is None else _hptr(status_h),
-        None if open_len_h is None else _hptr(open_len_h))
-    if rc:
-        raise FecError(rc, "qfec_open_decode_batch_ragged_host")
-    return rc
+    _check(pkt_h, "pkt", "uint8", (n, None), host=True)
+    _check(pkt_len_h, "pkt_len", "int32", (n,), host=True)
+    _check(ad_len, "ad_len", "int32", (n,), host=True)
+    _check(rec_rows_h, "rec_rows", "uint8", (G, rmax), host=True)
+    _check(status_h, "status", "int32", (G,), host=True, optional=True)
+    _check(open_len_h, "open_len", "int32", (n,), host=True, optional=True)
+    a, a_all = _ptr_or_all(ad_len, True)
+    return _call("qfec_open_decode_batch_ragged_host", engine, k, m, G, _ptr(bb_h, True),
+                 _ptr(pkt_h, True), pkt_h.stride(0), _ptr(pkt_len_h, True), a, a_all,
+                 _ptr(rec_h, True), _ptr(rec_off_h, True), _ptr(rec_rows_h, True),
+                 _ptr(status_h, True), _ptr(open_len_h, True))
 
 
 def synth_fill(t, seed, byte_offset=0, stream=None):
     """Fill a device tensor with the seeded splitmix64 stream (quic_amd.synth)."""
-    rc = load().qfec_synth_fill(_dptr(t), t.numel() * t.element_size(), seed, byte_offset,
+    rc = load().qfec_synth_fill(_ptr(t), t.numel() * t.element_size(), seed, byte_offset,
                                 _stream(stream, t))
     if rc:
         raise FecError(rc, "qfec_synth_fill")
@@ -867,7 +720,7 @@ def synth_fill(t, seed, byte_offset=0, stream=None):
 
 def synth_gather(data, parity, src, blocks, k, m, block_bytes, stream=None):
     """blocks[g][i] = sent block src[g][i] of group g (device-side receive-set build)."""
-    rc = load().qfec_synth_gather(_dptr(data), _dptr(parity), _dptr(src), _dptr(blocks), k, m,
+    rc = load().qfec_synth_gather(_ptr(data), _ptr(parity), _ptr(src), _ptr(blocks), k, m,
                                   block_bytes, data.shape[0], _stream(stream, data))
     if rc:
         raise FecError(rc, "qfec_synth_gather")

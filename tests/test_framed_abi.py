@@ -132,6 +132,9 @@ def test_wrappers_check_arrays_before_the_call():
     k, m, G = 10, 1, 3
     n, rmax = G * (k + m), 1
     u8, i32, i64 = torch.uint8, torch.int32, torch.int64
+    # a wrong dtype or a wrong exact shape is a TypeError, a dense per-row array with another
+    # number of rows a ValueError
+    TE, VE = TypeError, ValueError
     bb = torch.full((G,), 1352, dtype=i32)
     off = torch.arange(G, dtype=i64) * 16000
     buf = torch.zeros(G * 16000, dtype=u8)
@@ -140,44 +143,50 @@ def test_wrappers_check_arrays_before_the_call():
     pay, pn = torch.zeros((G * k, 1351), dtype=u8), torch.ones(G * k, dtype=u8)
     good = dict(bb=bb, off=off, hdr=hdr, hdr_len=lens, pay=pay, pay_len=plens, pn=pn, pkt=pkt,
                 pkt_len=lens, st=torch.zeros(G, dtype=i32))
-    bad = [dict(bb=bb.to(i64)), dict(off=off[:-1]), dict(pay=pay[:-1]), dict(pay=pay.to(torch.int8)),
-           dict(pay_len=plens[:-1]), dict(pay_len=plens.to(i64)), dict(pn=pn[:-1]),
-           dict(pn=pn.to(i32)), dict(pkt=pkt[:-1]), dict(pkt_len=lens.to(i64)),
-           dict(hdr_len=lens[:-1]), dict(st=torch.zeros(G + 1, dtype=i32))]
-    for b in bad:
+    bad = [(dict(bb=bb.to(i64)), TE), (dict(off=off[:-1]), TE), (dict(pay=pay[:-1]), VE),
+           (dict(pay=pay.to(torch.int8)), TE), (dict(pay_len=plens[:-1]), VE),
+           (dict(pay_len=plens.to(i64)), TE), (dict(pn=pn[:-1]), VE), (dict(pn=pn.to(i32)), TE),
+           (dict(pkt=pkt[:-1]), VE), (dict(pkt_len=lens.to(i64)), TE),
+           (dict(hdr_len=lens[:-1]), VE), (dict(st=torch.zeros(G + 1, dtype=i32)), TE)]
+    for b, exc in bad:
         a = dict(good)
         a.update(b)
-        with pytest.raises((TypeError, ValueError)):
+        with pytest.raises(exc) as e:
             fec.FecEngine.frame_encode_seal_ragged(None, k, m, a["bb"], buf, a["off"], buf,
                                                    a["off"], a["hdr"], a["hdr_len"], a["pay"],
                                                    a["pay_len"], a["pn"], a["pkt"], a["pkt_len"],
                                                    status=a["st"])
+        assert e.type is exc, b
         if not set(b) & {"hdr_len", "pkt", "pkt_len"}:
-            with pytest.raises((TypeError, ValueError)):
+            with pytest.raises(exc) as e:
                 fec.FecEngine.frame_blocks_ragged(None, k, a["bb"], a["pay"], a["pay_len"],
                                                   a["pn"], buf, a["off"], status=a["st"])
+            assert e.type is exc, b
     rev, rl = torch.zeros((G * rmax, 1351), dtype=u8), torch.zeros(G * rmax, dtype=i32)
     rpn = torch.zeros(G * rmax, dtype=u8)
     good = dict(bb=bb, pkt=pkt, pkt_len=lens, ad_len=16, pn=torch.ones(n, dtype=u8), off=off,
                 rows=torch.zeros((G, k), dtype=u8), ol=lens, rr=torch.zeros((G, rmax), dtype=u8),
                 rev=rev, rl=rl, rpn=rpn, st=torch.zeros(G, dtype=i32))
-    bad = [dict(bb=bb[:-1]), dict(off=off.to(i32)), dict(pkt=pkt[:-1]), dict(pn=pn),
-           dict(pn=torch.ones(n, dtype=i32)), dict(ol=lens[:-1]), dict(rev=rev[:-1]),
-           dict(rev=rev.to(torch.int8)), dict(rl=rl.to(i64)), dict(rl=torch.zeros(G + 1, dtype=i32)),
-           dict(rpn=rpn.to(i32)), dict(rr=torch.zeros((G, rmax + 1), dtype=u8)),
-           dict(st=torch.zeros(G, dtype=i64))]
-    for b in bad:
+    bad = [(dict(bb=bb[:-1]), TE), (dict(off=off.to(i32)), TE), (dict(pkt=pkt[:-1]), VE),
+           (dict(pn=pn), VE), (dict(pn=torch.ones(n, dtype=i32)), TE), (dict(ol=lens[:-1]), VE),
+           (dict(rev=rev[:-1]), VE), (dict(rev=rev.to(torch.int8)), TE), (dict(rl=rl.to(i64)), TE),
+           (dict(rl=torch.zeros(G + 1, dtype=i32)), VE), (dict(rpn=rpn.to(i32)), TE),
+           (dict(rr=torch.zeros((G, rmax + 1), dtype=u8)), TE),
+           (dict(st=torch.zeros(G, dtype=i64)), TE)]
+    for b, exc in bad:
         a = dict(good)
         a.update(b)
-        with pytest.raises((TypeError, ValueError)):
+        with pytest.raises(exc) as e:
             fec.FecEngine.open_decode_extract_ragged(
                 None, k, m, a["bb"], a["pkt"], a["pkt_len"], a["ad_len"], a["pn"], buf, a["off"],
                 a["rows"], a["ol"], buf, a["off"], a["rr"], a["rev"], a["rl"],
                 rev_pn_len=a["rpn"], status=a["st"])
+        assert e.type is exc, b
         if set(b) & {"bb", "off", "rev", "rl", "rpn", "rr", "st"}:
-            with pytest.raises((TypeError, ValueError)):
+            with pytest.raises(exc) as e:
                 fec.FecEngine.extract_revived_ragged(None, k, m, a["bb"], buf, a["off"], a["rr"],
                                                      a["st"], a["rev"], a["rl"], a["rpn"])
+            assert e.type is exc, b
 
 
 @pytest.mark.parametrize("k,m", sorted(T.SHAPES))

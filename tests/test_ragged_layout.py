@@ -1,9 +1,15 @@
 """Ragged batches, host side (no GPU): the packed layout of qfec_ragged_layout and the argument
-checks of the Python host wrappers."""
+checks of the Python host wrappers, and what the host wrappers hand to the library."""
+import ctypes
+import os
+import re
+
 import numpy as np
 import pytest
 
 from quic_amd import fec
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def up16(v):
@@ -164,30 +170,155 @@ def _dec(a, **kw):
 
 def test_host_wrappers_reject_bad_buffers():
     """Non-contiguous, mis-typed or short host arrays are refused before the library is called
-    (engine None: a call that got through would fail differently)."""
+    (engine None: a call that got through would fail differently).  A buffer of the wrong kind
+    (not a tensor, not contiguous) is a TypeError, a wrong dtype, shape or value a ValueError."""
     import torch
     a = _host_args(4, 2, [8, 24, 1352])
     bad = [
-        dict(bb=a["bb"].to(torch.int64)),                       # sizes must be int32
-        dict(bb=torch.tensor([8, 0, 1352], dtype=torch.int32)),  # a size < 1
-        dict(data_off=a["data_off"].to(torch.int32)),           # offsets must be int64
-        dict(data_off=a["data_off"] + 8),                       # not a multiple of 16
-        dict(data_off=a["data_off"][:2]),                       # one offset per group
-        dict(data=a["data"][:-16]),                             # too short for the last group
-        dict(data=torch.zeros(2 * a["data"].numel(), dtype=torch.uint8)[::2]),  # non-contiguous
-        dict(data=a["data"].to(torch.int8)),                    # wrong dtype
-        dict(data=a["data"].numpy()),                           # not a tensor
-        dict(status=a["status"].to(torch.int64)),
+        (dict(bb=a["bb"].to(torch.int64)), ValueError),                  # sizes must be int32
+        (dict(bb=torch.tensor([8, 0, 1352], dtype=torch.int32)), ValueError),   # a size < 1
+        (dict(data_off=a["data_off"].to(torch.int32)), ValueError),      # offsets must be int64
+        (dict(data_off=a["data_off"] + 8), ValueError),                  # not a multiple of 16
+        (dict(data_off=a["data_off"][:2]), ValueError),                  # one offset per group
+        (dict(data=a["data"][:-16]), ValueError),             # too short for the last group
+        (dict(data=torch.zeros(2 * a["data"].numel(), dtype=torch.uint8)[::2]),
+         TypeError),                                                     # non-contiguous
+        (dict(data=a["data"].to(torch.int8)), ValueError),               # wrong dtype
+        (dict(data=a["data"].numpy()), TypeError),                       # not a tensor
+        (dict(status=a["status"].to(torch.int64)), ValueError),
     ]
-    for kw in bad:
-        with pytest.raises((TypeError, ValueError)):
+    for kw, exc in bad:
+        with pytest.raises(exc) as e:
             _enc(a, **kw)
-        with pytest.raises((TypeError, ValueError)):
+        assert e.type is exc, kw
+        with pytest.raises(exc) as e:
             _dec(a, **kw)
-    for kw in (dict(par=a["par"][:-1]), dict(par_off=a["par_off"].flip(0)[::1] * 0 - 16)):
-        with pytest.raises((TypeError, ValueError)):
+        assert e.type is exc, kw
+    for kw, exc in ((dict(par=a["par"][:-1]), ValueError),
+                    (dict(par_off=a["par_off"].flip(0)[::1] * 0 - 16), ValueError)):
+        with pytest.raises(exc) as e:
             _enc(a, **kw)
-    for kw in (dict(rec=a["rec"][:-1]), dict(rows=a["rows"][:, :3]),
-               dict(rows=a["rows"].t().contiguous().t()), dict(rec_rows=a["rec_rows"][:2])):
-        with pytest.raises((TypeError, ValueError)):
+        assert e.type is exc, kw
+    for kw, exc in ((dict(rec=a["rec"][:-1]), ValueError), (dict(rows=a["rows"][:, :3]), TypeError),
+                    (dict(rows=a["rows"].t().contiguous().t()), TypeError),
+                    (dict(rec_rows=a["rec_rows"][:2]), ValueError)):
+        with pytest.raises(exc) as e:
             _dec(a, **kw)
+        assert e.type is exc, kw
+
+
+# ---- what a wrapper hands to the library: a stand-in engine records the call
+class RecordingLib:
+    """Stands in for the loaded library: every symbol records (name, args) and returns 0."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def call(*args):
+            self.calls.append((name, args))
+            return 0
+        return call
+
+
+CTX = 0x5eed0
+
+
+def recording_engine():
+    """A FecEngine that was never created: its library records, its context is CTX."""
+    eng = fec.FecEngine.__new__(fec.FecEngine)
+    eng.lib, eng._h = RecordingLib(), ctypes.c_void_p(CTX)
+    return eng
+
+
+def header_params(symbol):
+    """The parameter names of `symbol`, in the order include/quic_fec.h declares them."""
+    with open(os.path.join(ROOT, "include", "quic_fec.h")) as f:
+        text = f.read()
+    decl = re.search(r"^QFEC_API\s+int\s+%s\s*\(([^;]*)\)\s*;" % re.escape(symbol), text, re.M)
+    assert decl, symbol
+    return [re.search(r"(\w+)\s*(\[\d*\])?\s*$", p).group(1) for p in decl.group(1).split(",")]
+
+
+def assert_call(eng, symbol, **expected):
+    """The one call `eng` recorded is `symbol`, and its arguments are `expected` (by the header's
+    parameter names: a tensor stands for its data_ptr(), None for a null pointer) in the header's
+    order."""
+    calls = [c for c in eng.lib.calls if c[0] != "qfec_ctx_destroy"]
+    assert [c[0] for c in calls] == [symbol]
+    del eng.lib.calls[:]
+    names = header_params(symbol)
+    assert sorted(names) == sorted(expected), symbol
+    got = [a.value if isinstance(a, ctypes.c_void_p) else a for a in calls[0][1]]
+    want = [expected[n].data_ptr() if hasattr(expected[n], "data_ptr") else expected[n]
+            for n in names]
+    assert got == want, (symbol, list(zip(names, got, want)))
+
+
+def test_host_wrappers_marshal_in_header_order():
+    """The uniform and the ragged codec host wrappers: every pointer, stride and scalar is in the
+    place include/quic_fec.h gives it, and an absent optional array is a null pointer."""
+    import torch
+    k, m, bb, G = 2, 1, 8, 2
+    n, rmax = G * (k + m), 1
+    u8, i32 = torch.uint8, torch.int32
+    eng = recording_engine()
+    data, par = torch.zeros((G, k, bb), dtype=u8), torch.zeros((G, m, bb), dtype=u8)
+    rows, st = torch.zeros((G, k), dtype=u8), torch.zeros(G, dtype=i32)
+    rec, rr = torch.zeros((G, rmax, bb), dtype=u8), torch.zeros((G, rmax), dtype=u8)
+    hdr, pkt = torch.zeros((n, 20), dtype=u8), torch.zeros((n, 48), dtype=u8)
+    hl, pl, kl, ol = (torch.zeros(n, dtype=i32) for _ in range(4))
+    uni = dict(ctx=CTX, k=k, m=m, block_bytes=bb, groups=G)
+
+    assert fec.encode_host_into(eng, k, m, bb, data, par) == 0
+    assert_call(eng, "qfec_encode_batch_host", **uni, h_data=data, h_parity=par)
+    assert fec.decode_host_into(eng, k, m, bb, data, rows) == 0
+    assert_call(eng, "qfec_decode_batch_host", **uni, h_blocks=data, h_rows=rows, h_status=None)
+    fec.decode_host_into(eng, k, m, bb, data, rows, st)
+    assert_call(eng, "qfec_decode_batch_host", **uni, h_blocks=data, h_rows=rows, h_status=st)
+    assert fec.decode_recovered_host_into(eng, k, m, bb, data, rows, rec, rr) == 0
+    assert_call(eng, "qfec_decode_batch_recovered_host", **uni, h_blocks=data, h_rows=rows,
+                h_rec=rec, h_rec_rows=rr, h_status=None)
+    fec.decode_recovered_host_into(eng, k, m, bb, data, rows, rec, rr, st)
+    assert_call(eng, "qfec_decode_batch_recovered_host", **uni, h_blocks=data, h_rows=rows,
+                h_rec=rec, h_rec_rows=rr, h_status=st)
+
+    assert fec.encode_seal_groups_host_into(eng, k, m, bb, data, hdr, hl, pl, pkt, kl) == 0
+    assert_call(eng, "qfec_encode_seal_groups_batch_host", **uni, h_data=data, h_hdr=hdr,
+                hdr_stride=20, h_hdr_len=hl, hdr_len_all=0, h_pt_len=pl, pt_len_all=0, h_pkt=pkt,
+                pkt_stride=48, h_pkt_len=kl)
+    fec.encode_seal_groups_host_into(eng, k, m, bb, data, None, 0, 7, pkt, kl)
+    assert_call(eng, "qfec_encode_seal_groups_batch_host", **uni, h_data=data, h_hdr=None,
+                hdr_stride=0, h_hdr_len=None, hdr_len_all=0, h_pt_len=None, pt_len_all=7,
+                h_pkt=pkt, pkt_stride=48, h_pkt_len=kl)
+    assert fec.open_decode_host_into(eng, k, m, bb, pkt, kl, 13, rec, rr) == 0
+    assert_call(eng, "qfec_open_decode_batch_host", **uni, h_pkt=pkt, pkt_stride=48, h_pkt_len=kl,
+                h_ad_len=None, ad_len_all=13, h_rec=rec, h_rec_rows=rr, h_status=None,
+                h_open_len=None)
+    fec.open_decode_host_into(eng, k, m, bb, pkt, kl, hl, rec, rr, st, ol)
+    assert_call(eng, "qfec_open_decode_batch_host", **uni, h_pkt=pkt, pkt_stride=48, h_pkt_len=kl,
+                h_ad_len=hl, ad_len_all=0, h_rec=rec, h_rec_rows=rr, h_status=st, h_open_len=ol)
+
+    a = _host_args(k, m, [8, 24])
+    rag = dict(ctx=CTX, k=k, m=m, groups=G, h_bb=a["bb"])
+    assert fec.encode_ragged_host_into(eng, k, m, a["bb"], a["data"], a["data_off"], a["par"],
+                                       a["par_off"]) == 0
+    assert_call(eng, "qfec_encode_batch_ragged_host", **rag, h_data=a["data"],
+                h_data_off=a["data_off"], h_parity=a["par"], h_par_off=a["par_off"],
+                h_status=None)
+    fec.encode_ragged_host_into(eng, k, m, a["bb"], a["data"], a["data_off"], a["par"],
+                                a["par_off"], a["status"])
+    assert_call(eng, "qfec_encode_batch_ragged_host", **rag, h_data=a["data"],
+                h_data_off=a["data_off"], h_parity=a["par"], h_par_off=a["par_off"],
+                h_status=a["status"])
+    assert fec.decode_ragged_recovered_host_into(eng, k, m, a["bb"], a["data"], a["data_off"],
+                                                 a["rows"], a["rec"], a["rec_off"],
+                                                 a["rec_rows"]) == 0
+    assert_call(eng, "qfec_decode_batch_ragged_recovered_host", **rag, h_blocks=a["data"],
+                h_blocks_off=a["data_off"], h_rows=a["rows"], h_rec=a["rec"],
+                h_rec_off=a["rec_off"], h_rec_rows=a["rec_rows"], h_status=None)
+    fec.decode_ragged_recovered_host_into(eng, k, m, a["bb"], a["data"], a["data_off"], a["rows"],
+                                          a["rec"], a["rec_off"], a["rec_rows"], a["status"])
+    assert_call(eng, "qfec_decode_batch_ragged_recovered_host", **rag, h_blocks=a["data"],
+                h_blocks_off=a["data_off"], h_rows=a["rows"], h_rec=a["rec"],
+                h_rec_off=a["rec_off"], h_rec_rows=a["rec_rows"], h_status=a["status"])
