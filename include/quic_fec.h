@@ -102,7 +102,8 @@ QFEC_API void qfec_ctx_destroy(qfec_ctx *ctx);
  * "host_chunk_mb" 1..4096, "host_min_groups" 1.., "ring_split" 0/1 ((10, 20) encode in two
  * units), and the grid shares "ring_wg", "bsyn_wg", "stream_wg" (-1 = the measured choice),
  * "psyn_wg", "dcol_wg", "xor_wg" (groups per wave of an oversubscribed grid; 0 = the resident
- * persistent grid).  get also reads "cus" (compute units of the device).  -2 for an unknown name or a value out of range (also for the measured-and-removed
+ * persistent grid), "arr_optimistic" 0/1 (the arrival-order receiver's data
+ * write during its open pass).  get also reads "cus" (compute units of the device).  -2 for an unknown name or a value out of range (also for the measured-and-removed
  * variants of earlier versions).  No environment variable changes what the library launches. */
 QFEC_API int qfec_ctx_set_option(qfec_ctx *ctx, const char *name, int value);
 QFEC_API int qfec_ctx_get_option(qfec_ctx *ctx, const char *name, int *value);
@@ -543,6 +544,84 @@ QFEC_API int qfec_open_decode_extract_batch_ragged(
     long long rev_stride, int *d_rev_len, unsigned char *d_rev_pn_len, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * Arrival-order receiver: the framed receiver over packets as the socket left them.
+ *
+ * qfec_open_decode_extract_batch_ragged wants packet p = g*(k+m)+i at row p of d_pkt.  A
+ * receiver's ring holds its datagrams in arrival order instead: connections and groups
+ * interleaved, with duplicates, packets of groups that already hold k, and packets of no FEC
+ * group.  Which of them a group takes depends on which of them decrypt (quic_framer.cc:657, then
+ * quic_fec_group.cc:167-169 and :210-213), so the caller cannot sort them beforehand.  The call
+ * here reads the ring as it is: n packets, a (group, index) tag per packet, a block size per
+ * group.
+ *
+ * Inputs: arrival a (0 <= a < n) is the wire packet at d_pkt + a*pkt_stride, d_pkt_len[a] bytes,
+ * its first d_ad_len[a] (or ad_len_all) bytes the associated data, its packet-number length
+ * d_pn_len[a] (or pn_len_all): these three arrays are per arrival here, not per slot.
+ * d_arr_group[a] (int32) is the group's index in this batch (which (connection, fec_group) pair a
+ * batch index stands for is the caller's bookkeeping); d_arr_index[a] (u8) is packet_number -
+ * fec_group, the byte the private header carries (qfec_wire_read_private): below k data packet i,
+ * from k to k+m-1 FEC packet i-k.
+ *
+ * Acceptance, defined sequentially over a = 0 .. n-1 (the device result equals it):
+ *   1. group tag outside [0, groups) or index >= k+m: QFEC_ARR_IGNORED.
+ *   2. the packet fails the framed open's length checks (d_pkt_len[a] in [0, pkt_stride], the AD
+ *      length >= 0, at least 12 bytes behind the AD, a plaintext of at most bb[g]-2 bytes for a
+ *      data packet and bb[g] for an FEC packet; none passes where bb[g] < 1) or its tag does not
+ *      match: QFEC_ARR_REJECTED.  Such a packet never reaches its group.
+ *   3. an earlier arrival with the same (g, i) opened: QFEC_ARR_DUPLICATE.  A rejected first
+ *      copy does not stand in the way of a later good one.
+ *   4. k distinct indices of group g opened earlier: QFEC_ARR_LATE.
+ *   5. otherwise the arrival is accepted: d_arr_state[a] = its plaintext length (>= 0).
+ * d_arr_state [n] (int32) may be NULL.
+ *
+ * Rule for everything else: per group, the call is qfec_open_decode_extract_batch_ragged on the
+ * accepted packets placed at p = g*(k+m)+i: d_open_len[p] (the accepted packet's plaintext
+ * length, else -1), the placed d_blocks slots with their prefixes, d_rows (the holes take the
+ * accepted FEC packets, ascending), d_rec, d_rec_rows, d_status (-3 for a group with fewer than k
+ * accepted, -1 for bb[g] % 8 != 0 with a recovery block), d_rev, d_rev_len, d_rev_pn_len.  A data
+ * packet that arrives after the group's k-th is late and comes back revived, with the bytes it
+ * was sent with.  The bytes that call leaves unspecified stay unspecified.
+ * d_arr_at [groups*(k+m)] (int32, output): the arrival accepted for slot p, -1 without one; it
+ * maps a slot back to its ring entry.  It and d_open_len are the call's only tables (no
+ * workspace beyond the decode's).
+ * bb[g] is the caller's; qfec_arrivals_rx_block_bytes gives the reference's value.
+ *
+ * Call-level limits, -2 before anything is enqueued: those of
+ * qfec_open_decode_extract_batch_ragged; n < 0; n or groups*(k+m) above INT32_MAX (arrival
+ * indices live in int32 tables); a NULL d_arr_group, d_arr_index or d_arr_at.  n == 0 is valid:
+ * every group gets status -3, and the per-arrival arrays (d_pkt, d_pkt_len, d_arr_group,
+ * d_arr_index), of which nothing is read then, may be NULL.
+ * Streams, graphs: the call only enqueues work, reads no device array back and sets its table up
+ * again inside every call, so a captured call can be replayed over new ring contents.  It runs in
+ * the decode-workspace bracket like every decode; qfec_reserve(ctx, k, m, largest bb, groups)
+ * covers a capture.
+ * Launches: five (four without d_arr_state), the ragged decode's, two.
+ * ------------------------------------------------------------------------------- */
+#define QFEC_ARR_REJECTED (-1)
+#define QFEC_ARR_IGNORED (-2)
+#define QFEC_ARR_DUPLICATE (-3)
+#define QFEC_ARR_LATE (-4)
+/* Host helper, no GPU: bb[g] = the largest stored size (plaintext + 2 for a data packet, the
+ * plaintext for an FEC packet, quic_fec_group.cc:264-265) among group g's first k distinct
+ * arrivals; 0 where nothing arrived.  By lengths alone, like qfec_framed_rx_block_bytes: an
+ * arrival counts with at least 12 bytes behind its associated data, only the first copy of an
+ * index counts, and tags outside the batch are skipped.  ad_len may be NULL (ad_len_all).
+ * -2: k + m > 255, n < 0, groups < 0, a NULL array. */
+QFEC_API int qfec_arrivals_rx_block_bytes(int k, int m, long long groups, long long n,
+                                          const int *arr_group, const unsigned char *arr_index,
+                                          const int *pkt_len, const int *ad_len, int ad_len_all,
+                                          int *bb);
+/* Receiver over arrivals: open -> bind -> qfec_decode_batch_ragged_recovered -> extraction. */
+QFEC_API int qfec_open_decode_extract_arrivals_ragged(
+    qfec_ctx *ctx, int k, int m, long long groups, const int *d_bb, long long n,
+    const unsigned char *d_pkt, long long pkt_stride, const int *d_pkt_len, const int *d_ad_len,
+    int ad_len_all, const unsigned char *d_pn_len, int pn_len_all, const int *d_arr_group,
+    const unsigned char *d_arr_index, int *d_arr_state, int *d_arr_at, unsigned char *d_blocks,
+    const long long *d_blocks_off, unsigned char *d_rows, int *d_open_len, unsigned char *d_rec,
+    const long long *d_rec_off, unsigned char *d_rec_rows, int *d_status, unsigned char *d_rev,
+    long long rev_stride, int *d_rev_len, unsigned char *d_rev_pn_len, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Support: the coefficient tables, a seeded synthetic workload, diagnostics.
  * ------------------------------------------------------------------------------- */
 /* Rows 1..m-1 of the Cauchy matrix the reference selects (cauchy_256.cpp:422-480),
@@ -566,7 +645,10 @@ QFEC_API const char *qfec_last_error(void);
  * "open_group_kernel<ragged> + open_assemble_kernel<ragged>" (the uniform grouped calls name
  * "null_seal_kernel<groups>" and "open_group_kernel + open_assemble_kernel"); the framed calls
  * name "frame_blocks_kernel", "null_seal_kernel<framed>", "open_group_kernel<framed> +
- * open_assemble_kernel<framed>" and "extract_revived_kernel". */
+ * open_assemble_kernel<framed>" and "extract_revived_kernel"; the arrivals call names
+ * "arrivals_init_kernel", "arrivals_pre_kernel", "open_arrivals_kernel",
+ * "arrivals_assemble_kernel" and (with d_arr_state) "arrivals_state_kernel" ahead of the decode's
+ * and "extract_revived_kernel". */
 QFEC_API const char *qfec_last_kernels(void);
 /* Grids of the persistent kernels the last call on this thread launched, as space-separated
  * "kernel=workgroups" entries (e.g. "gf_psyn_kernel=1024"); diagnostics and tests.  The general

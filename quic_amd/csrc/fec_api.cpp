@@ -452,6 +452,7 @@ const Opt kOptions[] = {
     {"ring_wg", &Tu::ring_wg, -1, 1 << 20},    {"bsyn_wg", &Tu::bsyn_wg, -1, 1 << 20},
     {"psyn_wg", &Tu::psyn_wg, 0, 1 << 20},     {"dcol_wg", &Tu::dcol_wg, 0, 1 << 20},
     {"stream_wg", &Tu::stream_wg, -1, 1 << 20}, {"xor_wg", &Tu::xor_wg, 0, 1 << 20},
+    {"arr_optimistic", &Tu::arr_optimistic, 0, 1},
 };
 
 const Opt* find_option(const char* name) {
@@ -1079,6 +1080,53 @@ int qfec_open_decode_extract_batch_ragged(
                                               d_blocks, d_rows, (int32_t*)d_open_len, d_rec,
                                               d_rec_rows, (int32_t*)d_status, st);
         if (r) return r;
+        QF_HIP(qfec::launch_extract_revived(k, m, groups, v, d_rec, d_rec_rows,
+                                            (const int32_t*)d_status,
+                                            rows_out_of(d_rev, rev_stride, d_rev_len),
+                                            d_rev_pn_len, st));
+        return 0;
+    });
+}
+
+// arrivals open (init -> open -> assemble -> state) -> ragged recovered decode -> open_status ->
+// extract: the framed receiver over packets in arrival order.  d_arr_at is the binding table, so
+// the call needs no workspace beyond the decode's.
+int qfec_open_decode_extract_arrivals_ragged(
+    qfec_ctx* c, int k, int m, long long groups, const int* d_bb, long long n,
+    const unsigned char* d_pkt, long long pkt_stride, const int* d_pkt_len, const int* d_ad_len,
+    int ad_len_all, const unsigned char* d_pn_len, int pn_len_all, const int* d_arr_group,
+    const unsigned char* d_arr_index, int* d_arr_state, int* d_arr_at, unsigned char* d_blocks,
+    const long long* d_blocks_off, unsigned char* d_rows, int* d_open_len, unsigned char* d_rec,
+    const long long* d_rec_off, unsigned char* d_rec_rows, int* d_status, unsigned char* d_rev,
+    long long rev_stride, int* d_rev_len, unsigned char* d_rev_pn_len, void* stream) {
+    int rc = ragged_check(c, k, m, groups, d_bb, d_blocks, d_blocks_off, d_rec, d_rec_off);
+    if (rc) return rc;
+    if ((rc = open_decode_args(k, m, true, {d_rows, d_open_len, d_rec_rows, d_arr_at}, pkt_stride,
+                               d_ad_len, ad_len_all)))
+        return rc;
+    if ((rc = framed_rows_args(d_rev, rev_stride, d_rev_len, "bad rev_stride"))) return rc;
+    if (n < 0) return fail(-2, "n < 0");
+    // arrival indices and slots live in int32 tables
+    if (n > INT32_MAX || groups > INT32_MAX / (k + m))
+        return fail(-2, "n or groups * (k + m) above INT32_MAX");
+    // the per-arrival arrays: nothing of them is read when nothing arrived
+    if (n > 0 && any_null({d_pkt, d_pkt_len, d_arr_group, d_arr_index}))
+        return fail(-2, "null buffer");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const hipStream_t st = pick(c, stream);
+    const RaggedView v{(const int32_t*)d_bb, d_blocks_off, d_rec_off};
+    return with_workspace(c, st, [&] {
+        QF_HIP(qfec::launch_open_arrivals_framed(
+            k, m, groups, v, n, rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
+            rows_of(nullptr, 0, d_ad_len, ad_len_all), d_pn_len, pn_len_all,
+            (const int32_t*)d_arr_group, d_arr_index, (int32_t*)d_arr_state, (int32_t*)d_arr_at,
+            d_blocks, d_rows, (int32_t*)d_open_len, c->tune.arr_optimistic != 0, st));
+        const int r = decode_ragged_impl(c, k, m, groups, v, d_blocks, d_rows, d_rec, d_rec_rows,
+                                         (int32_t*)d_status, st);
+        if (r) return r;
+        QF_HIP(qfec::launch_open_status(k, std::min(k, m), groups, d_rows, d_rec_rows,
+                                        (int32_t*)d_status, st));
         QF_HIP(qfec::launch_extract_revived(k, m, groups, v, d_rec, d_rec_rows,
                                             (const int32_t*)d_status,
                                             rows_out_of(d_rev, rev_stride, d_rev_len),

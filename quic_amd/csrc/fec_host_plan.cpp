@@ -5,6 +5,8 @@
 
 #include <algorithm>
 #include <cstring>
+#include <new>
+#include <vector>
 
 #include "../../include/quic_fec.h"
 
@@ -87,6 +89,43 @@ extern "C" int qfec_framed_rx_block_bytes(int k, int m, long long groups, const 
             most = std::max(most, tl - al - 12 + (i < k ? 2 : 0));
         }
         bb[g] = (int)std::min<long long>(most, 0x7fffffffLL);
+    }
+    return 0;
+}
+
+// The same size for packets that lie in arrival order: QuicFecGroup stores the first copy of an
+// index (quic_fec_group.cc:167-169) until it holds k packets (:210-213), so only a group's first
+// k distinct arrivals count.  By lengths alone, as above: whether a packet opens is the device's.
+extern "C" int qfec_arrivals_rx_block_bytes(int k, int m, long long groups, long long n,
+                                            const int* arr_group, const unsigned char* arr_index,
+                                            const int* pkt_len, const int* ad_len, int ad_len_all,
+                                            int* bb) {
+    if (k < 1 || m < 1 || k + m > 255 || groups < 0 || n < 0 || (groups && !bb) ||
+        (n && (!arr_group || !arr_index || !pkt_len)))
+        return -2;
+    const long long per = (long long)k + m;
+    long long slots;
+    if (__builtin_mul_overflow(groups, per, &slots)) return -2;
+    std::vector<unsigned char> seen;
+    std::vector<int> held;
+    try {
+        seen.assign((size_t)slots, 0);
+        held.assign((size_t)groups, 0);
+    } catch (const std::bad_alloc&) {
+        return -2;
+    }
+    for (long long g = 0; g < groups; ++g) bb[g] = 0;
+    for (long long a = 0; a < n; ++a) {
+        const long long g = arr_group[a];
+        const int i = arr_index[a];
+        if (g < 0 || g >= groups || i >= per) continue;   // no packet of this batch
+        const long long tl = pkt_len[a], al = ad_len ? ad_len[a] : ad_len_all;
+        if (tl < 0 || al < 0 || tl - al < 12) continue;    // no packet
+        if (seen[(size_t)(g * per + i)] || held[(size_t)g] >= k) continue;   // duplicate, late
+        seen[(size_t)(g * per + i)] = 1;
+        ++held[(size_t)g];
+        const long long size = tl - al - 12 + (i < k ? 2 : 0);
+        bb[g] = (int)std::max<long long>(bb[g], std::min<long long>(size, 0x7fffffffLL));
     }
     return 0;
 }

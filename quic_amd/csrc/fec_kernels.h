@@ -58,6 +58,8 @@ struct Tune {
     int dcol_wg = 4;          // gf_dcol encode / decode (units = column tiles; D 1909 -> 2000 GiB/s
                               //   over three alternating pairs on a power-limited box)
     int xor_wg = 0;           // xor_dma (m = 1)
+    int arr_optimistic = 1;   // arrivals receiver: first-candidate data packets are placed by the
+                              //   open pass (0: the assemble reads every accepted packet again)
     int host_chunk_mb = 64;   // host-pointer batches: chunk size
     int host_min_groups = 512;  // host-pointer batches: at least this many groups per chunk
                                 //   (capped at 2 GiB of staging per buffer)

@@ -68,6 +68,26 @@ hipError_t launch_null_seal_framed(int k, int m, long long groups, RaggedView v,
 hipError_t launch_open_groups_framed(int k, int m, long long groups, RaggedView v, Rows pkt,
                                      Rows ad, const uint8_t* pn_len, int pn_all, uint8_t* blocks,
                                      uint8_t* rows, int32_t* open_len, hipStream_t st);
+// The framed open over n packets in arrival order: arrival a is pkt row a,
+// tagged (arr_group[a], arr_index[a]); pn_len is per arrival.  Per group the first copy of each
+// index that opens is a candidate, the k earliest candidates are accepted, and blocks, rows and
+// open_len [G * (k + m)] come out as launch_open_groups_framed writes them for the accepted
+// packets placed by slot.  arr_at [G * (k + m)]: the arrival accepted for each slot, -1 without
+// one (the call's only table, set up again by every call); arr_state [n] (may be null): the
+// plaintext length of an accepted arrival, -1 rejected, -2 ignored tag, -3 duplicate, -4 late.
+// optimistic: a data arrival that is its slot's first candidate by the length checks alone (a
+// pre-pass finds it; its table lives in open_len until the assemble writes open_len) streams its
+// plaintext into the slot during the open pass, so an in-order ring is read once; without it the
+// assemble reads every accepted packet a second time.  The outputs are the same either way but
+// for the bytes of a slot whose row is 255.
+// Five launches (init, pre, open, assemble, state); no pre without optimistic, no state without
+// arr_state.
+hipError_t launch_open_arrivals_framed(int k, int m, long long groups, RaggedView v, long long n,
+                                       Rows pkt, Rows ad, const uint8_t* pn_len, int pn_all,
+                                       const int32_t* arr_group, const uint8_t* arr_index,
+                                       int32_t* arr_state, int32_t* arr_at, uint8_t* blocks,
+                                       uint8_t* rows, int32_t* open_len, bool optimistic,
+                                       hipStream_t st);
 // After the decode: recovered block (g, j) at rec + v.out_off[g] + j * bb[g] with
 // rec_rows[g * rmax + j] != 255 and status[g] == 0 (status null: every group) -> its payload at
 // rev row g * rmax + j, rev.len its length (clamped to bb[g] - 2), rev_pn_len (may be null) the

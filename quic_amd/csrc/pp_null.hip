@@ -1042,6 +1042,247 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void extract_revived_k
                 smem);
 }
 
+// ------------------------------------------------------------------ arrival-order receiver
+// The framed receiver over packets that lie in arrival order: arrival a
+// carries the tag (arr_group[a], arr_index[a]) = (the group's index in the batch, packet number -
+// fec_group).  The binding table arr_at [G * (k + m)] is the call's state: arrivals_init_kernel
+// sets it to INT32_MAX, every arrival that opens takes the minimum of its slot with its own
+// index (open_arrivals_kernel), and one wave per group keeps the k earliest of the group's
+// candidates, -1 elsewhere (arrivals_assemble_kernel).  A minimum does not depend on the order
+// the lanes run in, and a table is only read by the kernel after the one that writes it.
+// The optimistic data write: a second table of the same shape, kept in the open_len output
+// until the assemble overwrites it, takes the same minimum over the length checks alone
+// (arrivals_pre_kernel), so that a data slot's first candidate is known before any byte is
+// hashed.  That arrival streams its plaintext into the slot while it is hashed, as
+// open_group_kernel does; the assemble places only what is not in place already, so an
+// in-order ring is read once.
+constexpr int kArrIgnored = -2, kArrRejected = -1, kArrDuplicate = -3, kArrLate = -4;
+constexpr int32_t kArrNone = 0x7fffffff;
+
+// pre_at: null without the optimistic write
+__global__ __launch_bounds__(kPPThreads) void arrivals_init_kernel(long long slots,
+                                                                   int32_t* arr_at,
+                                                                   int32_t* pre_at) {
+    const long long p = (long long)blockIdx.x * kPPThreads + threadIdx.x;
+    if (p >= slots) return;
+    arr_at[p] = kArrNone;
+    if (pre_at) pre_at[p] = kArrNone;
+}
+
+// One lane per arrival: a data arrival with a tag of this batch that passes the length checks
+// takes the minimum of pre_at[g * (k + m) + i] with its own index.
+__global__ __launch_bounds__(kPPThreads) void arrivals_pre_kernel(
+    int k, int m, FramedSlots sl, long long n, long long pkt_stride,
+    const int32_t* __restrict__ pkt_len, const int32_t* __restrict__ ad_len, int ad_all,
+    const int32_t* __restrict__ arr_group, const uint8_t* __restrict__ arr_index,
+    int32_t* pre_at) {
+    const long long a = (long long)blockIdx.x * kPPThreads + threadIdx.x;
+    if (a >= n) return;
+    const long long g = arr_group[a];
+    const int i = arr_index[a];
+    if (g < 0 || g >= sl.r.groups || i >= k) return;
+    if (open_len_ok(pkt_len, ad_len, ad_all, a, sl.limit(sl.size(g), true), pkt_stride))
+        atomicMin(pre_at + g * (k + m) + i, (int32_t)a);
+}
+
+// One lane per arrival, 64 per wave: the length checks of the framed open against the tagged
+// group's bb (open_len_ok with FramedSlots' limits), AD || plaintext hashed through the wave's
+// tile, and where the tag matches atomicMin(arr_at[g * (k + m) + i], a).  arr_state (may be
+// null) receives the plaintext length of an arrival that opened, kArrRejected or kArrIgnored;
+// the two kernels below turn an opened arrival that is not kept into kArrLate / kArrDuplicate.
+// pre_at (null: no optimistic write): the data arrival that is its slot's first candidate by
+// the length checks writes prefix || plaintext || zeros into the slot, before its tag is known;
+// the assemble overwrites the slot where another packet is accepted for it.
+template <class H>
+__global__ __launch_bounds__(64) void open_arrivals_kernel(
+    int k, int m, FramedSlots sl, long long n, const uint8_t* __restrict__ pkt,
+    long long pkt_stride, const int32_t* __restrict__ pkt_len,
+    const int32_t* __restrict__ ad_len, int ad_all, const int32_t* __restrict__ arr_group,
+    const uint8_t* __restrict__ arr_index, int32_t* arr_state, int32_t* arr_at,
+    const int32_t* __restrict__ pre_at, uint8_t* blocks) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const long long a = (long long)blockIdx.x * 64 + threadIdx.x;
+    const int per = k + m;
+    bool tagged = false, ok = false, place = false;
+    long long g = 0;
+    int i = 0, al = 0, cl = 0, bb = -1;
+    if (a < n) {
+        g = arr_group[a];
+        i = arr_index[a];
+        tagged = g >= 0 && g < sl.r.groups && i < per;
+        if (tagged) {
+            bb = sl.size(g);
+            al = len_of(ad_len, ad_all, a);
+            cl = pkt_len[a] - al;
+            ok = open_len_ok(pkt_len, ad_len, ad_all, a, sl.limit(bb, i < k), pkt_stride);
+            place = ok && i < k && pre_at && pre_at[g * per + i] == (int32_t)a;
+        }
+    }
+    const uint8_t* pp = pkt + (ok ? a : 0) * pkt_stride;
+    const uint8_t* c = pp + al;
+    H h;
+    h.init();
+    Sink s;
+    if (ok) span<true, false, 1>(h, s, pp, al);
+    tile_stream(h, ok ? c + 12 : nullptr, ok ? cl - 12 : 0,
+                place ? sl.slot(blocks, g, k, i, bb) + 2 : nullptr, place ? bb - 2 : 0, smem);
+    if (a >= n) return;
+    if (place) sl.prefix(blocks, g, k, i, bb, cl - 12, a);
+    bool opened = false;
+    if (ok) {
+        uint32_t t0, t1, t2;
+        h.tag(t0, t1, t2);
+        opened = tag_matches(c, t0, t1, t2);
+    }
+    if (opened) atomicMin(arr_at + g * per + i, (int32_t)a);
+    if (arr_state) arr_state[a] = !tagged ? kArrIgnored : opened ? cl - 12 : kArrRejected;
+}
+
+// Block slot dst[0 .. bb) = lead || src[0 .. pl) || zeros, by the whole wave: lead is the two
+// prefix bytes `pre` of a data packet's slot (nlead 2) or nothing (nlead 0).  Dword stores where
+// the slot and bb allow them; the dwords read then hold at least one byte of lead || src, and
+// the bytes in front of src are the packet's own (its tag).
+__device__ void wave_place(uint8_t* dst, const uint8_t* src, int pl, int bb, int nlead,
+                           uint32_t pre, int lane) {
+    const int end = nlead + pl;   // bytes of the slot that are not padding
+    if ((((uintptr_t)dst) | (uint32_t)bb) & 3u) {
+        for (int o = lane; o < bb; o += 64)
+            dst[o] = o < nlead ? (uint8_t)(pre >> (8 * o)) : o < end ? src[o - nlead] : 0;
+        return;
+    }
+    const uint8_t* v0 = src - nlead;   // the slot's byte o is v0[o] for nlead <= o < end
+    const uint32_t sh = (uint32_t)(uintptr_t)v0 & 3u;
+    const uint32_t* s4 = (const uint32_t*)(v0 - sh);
+    for (int u = lane; u < (bb >> 2); u += 64) {
+        const int o = 4 * u;
+        uint32_t v = 0;
+        if (o < end) {
+            const uint32_t w0 = s4[u];
+            const uint32_t w1 = (sh && o + 4 - (int)sh < end) ? s4[u + 1] : 0u;
+            v = sh ? __builtin_amdgcn_alignbyte(w1, w0, sh) : w0;
+            if (end - o < 4) v &= (1u << (8 * (end - o))) - 1u;
+            if (u == 0 && nlead) v = (v & 0xffff0000u) | (pre & 0xffffu);
+        }
+        ((uint32_t*)dst)[u] = v;
+    }
+}
+
+// One wave per group, after the open pass: the group's candidates are the slots whose arr_at
+// holds an arrival (the first copy of that index that opened).  Ranked by arrival index, the
+// first k are accepted (QuicFecGroup takes no packet once it holds k, quic_fec_group.cc:
+// 210-213); the others are late: arr_at -1 and, where arr_state is kept, kArrLate.  Then what
+// open_assemble_kernel writes for the accepted packets placed by slot: open_len, rows (the
+// holes, ascending, take the accepted FEC packets, ascending; 255 where none is left), and every
+// accepted packet's plaintext in its slot, a data packet's behind its prefix.  optimistic: on
+// entry open_len holds arrivals_pre_kernel's table, and a data slot whose accepted arrival is
+// the one named there was written by the open pass.
+__global__ __launch_bounds__(kAsmWaves * 64) void arrivals_assemble_kernel(
+    int k, int m, FramedSlots sl, const uint8_t* __restrict__ pkt, long long pkt_stride,
+    const int32_t* __restrict__ pkt_len, const int32_t* __restrict__ ad_len, int ad_all,
+    int32_t* arr_state, int32_t* arr_at, int32_t* open_len, bool optimistic, uint8_t* blocks,
+    uint8_t* rows) {
+    __shared__ int32_t cand[kAsmWaves][256];   // the slot's candidate, then its accepted arrival
+    __shared__ uint8_t lavail[kAsmWaves][256], lhole[kAsmWaves][256];
+    __shared__ uint8_t inplace[kAsmWaves][256];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long g = (long long)blockIdx.x * kAsmWaves + w;
+    if (g >= sl.r.groups) return;   // uniform over the wave; no workgroup barrier below
+    const int bb = sl.size(g);
+    const int per = k + m;
+    int32_t* at = arr_at + g * per;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int s = lane; s < per; s += 64) cand[w][s] = at[s];
+    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes are visible
+    __builtin_amdgcn_wave_barrier();
+    // rank of each candidate among the group's; every lane runs the whole loop
+    int32_t keep[4] = {-1, -1, -1, -1};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (64 * q >= per) break;   // uniform: no slot of the group is left
+        const int s = lane + 64 * q;
+        const int32_t a = s < per ? cand[w][s] : kArrNone;
+        int rank = 0;
+        for (int t = 0; t < per; ++t) rank += cand[w][t] < a ? 1 : 0;
+        const bool is = a != kArrNone;
+        keep[q] = is && rank < k ? a : -1;
+        if (is && rank >= k && arr_state) arr_state[a] = kArrLate;
+    }
+    __builtin_amdgcn_wave_barrier();   // every rank is formed before the table changes
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int s = lane + 64 * q;
+        if (s < per) {
+            const int32_t a = keep[q];
+            cand[w][s] = a;
+            at[s] = a;
+            inplace[w][s] = optimistic && a >= 0 && open_len[g * per + s] == a;
+            open_len[g * per + s] = a < 0 ? -1 : pkt_len[a] - len_of(ad_len, ad_all, a) - 12;
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+    // rows, as open_assemble_kernel forms them
+    int na = 0;
+    for (int b0 = 0; b0 < m; b0 += 64) {
+        const int j = b0 + lane;
+        const bool v = j < m && cand[w][k + j] >= 0;
+        const unsigned long long bal = __ballot(v);
+        if (v) lavail[w][na + __popcll(bal & below)] = (uint8_t)j;
+        na += __popcll(bal);
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+    int nh = 0;
+    for (int b0 = 0; b0 < k; b0 += 64) {
+        const int i = b0 + lane;
+        const bool miss = i < k && cand[w][i] < 0;
+        const unsigned long long bal = __ballot(miss);
+        const int r = nh + __popcll(bal & below);
+        if (i < k) {
+            int row = i;
+            if (miss) {
+                row = r < na ? k + lavail[w][r] : 255;
+                if (r < na) lhole[w][r] = (uint8_t)i;
+            }
+            rows[g * k + i] = (uint8_t)row;
+        }
+        nh += __popcll(bal);
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+    // the accepted data packets into their own slots, the accepted FEC packets into the holes
+    for (int i = 0; i < k; ++i) {
+        const int32_t a = __builtin_amdgcn_readfirstlane(cand[w][i]);   // the same in every lane
+        if (a < 0 || __builtin_amdgcn_readfirstlane((int)inplace[w][i])) continue;
+        const int al = len_of(ad_len, ad_all, a);
+        const int pl = pkt_len[a] - al - 12;
+        const uint32_t pre = (uint32_t)pl | ((uint32_t)(sl.pn_len ? sl.pn_len[a] : sl.pn_all) << 14);
+        wave_place(sl.slot(blocks, g, k, i, bb), pkt + a * pkt_stride + al + 12, pl, bb, 2, pre,
+                   lane);
+    }
+    const int nfill = min(nh, na);
+    for (int h = 0; h < nfill; ++h) {
+        const int32_t a = __builtin_amdgcn_readfirstlane(cand[w][k + lavail[w][h]]);
+        const int al = len_of(ad_len, ad_all, a);
+        wave_place(sl.slot(blocks, g, k, lhole[w][h], bb), pkt + a * pkt_stride + al + 12,
+                   pkt_len[a] - al - 12, bb, 0, 0u, lane);
+    }
+}
+
+// One lane per arrival, after the assemble: an arrival that opened (arr_state >= 0) and is not
+// the one its slot kept was not the first copy of its index: kArrDuplicate.  (The first copy
+// of a slot that was not kept already carries kArrLate.)
+__global__ __launch_bounds__(kPPThreads) void arrivals_state_kernel(
+    int per, long long n, const int32_t* __restrict__ arr_group,
+    const uint8_t* __restrict__ arr_index, const int32_t* __restrict__ arr_at,
+    int32_t* arr_state) {
+    const long long a = (long long)blockIdx.x * kPPThreads + threadIdx.x;
+    if (a >= n) return;
+    if (arr_state[a] < 0) return;
+    if (arr_at[(long long)arr_group[a] * per + arr_index[a]] != (int32_t)a)
+        arr_state[a] = kArrDuplicate;
+}
+
 unsigned pp_grid(long long n) {
     return (unsigned)((n + kPPThreads - 1) / kPPThreads);
 }
@@ -1156,6 +1397,45 @@ hipError_t launch_open_groups_framed(int k, int m, long long groups, RaggedView 
     return open_go("open_group_kernel<framed> + open_assemble_kernel<framed>", k, m, groups,
                    FramedSlots{RaggedSlots{v.bb, v.in_off, groups}, pn_len, pn_all}, pkt, ad,
                    blocks, rows, open_len, st);
+}
+
+hipError_t launch_open_arrivals_framed(int k, int m, long long groups, RaggedView v, long long n,
+                                       Rows pkt, Rows ad, const uint8_t* pn_len, int pn_all,
+                                       const int32_t* arr_group, const uint8_t* arr_index,
+                                       int32_t* arr_state, int32_t* arr_at, uint8_t* blocks,
+                                       uint8_t* rows, int32_t* open_len, bool optimistic,
+                                       hipStream_t st) {
+    const long long slots = groups * (k + m);
+    if (k + m > 255 || n > 0x7fffffffLL || slots > 0x7fffffffLL) return hipErrorInvalidValue;
+    const FramedSlots sl{RaggedSlots{v.bb, v.in_off, groups}, pn_len, pn_all};
+    if (slots > 0) {
+        note_kernel("arrivals_init_kernel");
+        qlaunch(arrivals_init_kernel, dim3(pp_grid(slots)), dim3(kPPThreads), 0, st, slots, arr_at,
+                optimistic ? open_len : nullptr);
+    }
+    if (n > 0 && slots > 0 && optimistic) {
+        note_kernel("arrivals_pre_kernel");
+        qlaunch(arrivals_pre_kernel, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, k, m, sl, n,
+                pkt.stride, pkt.len, ad.len, ad.len_all, arr_group, arr_index, open_len);
+    }
+    if (n > 0) {
+        note_kernel("open_arrivals_kernel");
+        qlaunch(open_arrivals_kernel<Fnv>, dim3(tile_grid(n)), dim3(64), kTileBytes, st, k, m, sl, n,
+                pkt.p, pkt.stride, pkt.len, ad.len, ad.len_all, arr_group, arr_index, arr_state,
+                arr_at, slots > 0 && optimistic ? open_len : nullptr, blocks);
+    }
+    if (slots > 0) {
+        note_kernel("arrivals_assemble_kernel");
+        qlaunch(arrivals_assemble_kernel, dim3((unsigned)((groups + kAsmWaves - 1) / kAsmWaves)),
+                dim3(kAsmWaves * 64), 0, st, k, m, sl, pkt.p, pkt.stride, pkt.len, ad.len,
+                ad.len_all, arr_state, arr_at, open_len, optimistic, blocks, rows);
+    }
+    if (n > 0 && slots > 0 && arr_state) {
+        note_kernel("arrivals_state_kernel");
+        qlaunch(arrivals_state_kernel, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, k + m, n,
+                arr_group, arr_index, arr_at, arr_state);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_extract_revived(int k, int m, long long groups, RaggedView v, const uint8_t* rec,

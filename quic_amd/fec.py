@@ -442,6 +442,44 @@ class FecEngine:
               _ptr(rows), _ptr(open_len), _ptr(rec), _ptr(rec_off), _ptr(rec_rows), _ptr(status),
               _ptr(rev), rev.stride(0), _ptr(rev_len), _ptr(rev_pn_len), _stream(stream, pkt))
 
+    def open_decode_extract_arrivals_ragged(self, k, m, bb, pkt, pkt_len, ad_len, pn_len,
+                                            arr_group, arr_index, arr_state, arr_at, blocks,
+                                            blocks_off, rows, open_len, rec, rec_off, rec_rows,
+                                            rev, rev_len, rev_pn_len=None, status=None,
+                                            stream=None):
+        """Receiver over packets in arrival order (include/quic_fec.h, "Arrival-order
+        receiver"): pkt uint8 [n][stride], pkt_len int32 [n], ad_len int32 [n] or an int, pn_len
+        uint8 [n] or an int are per arrival; arr_group int32 [n] and arr_index uint8 [n] tag each
+        arrival with its group in this batch and packet_number - fec_group.  arr_state int32 [n]
+        or None receives each arrival's fate (its plaintext length, or ARR_REJECTED /
+        ARR_IGNORED / ARR_DUPLICATE / ARR_LATE), arr_at int32 [G*(k+m)] the arrival accepted for
+        each slot (-1: none).  Everything else is open_decode_extract_ragged's on the accepted
+        packets placed by slot."""
+        G = _groups(bb, blocks_off=blocks_off, rec_off=rec_off)
+        _check(pkt, "pkt", "uint8", (None, None), rows=True)
+        n, slots, rmax = pkt.shape[0], G * (k + m), min(k, m)
+        _check(pkt_len, "pkt_len", "int32", (n,), rows=True)
+        _check(ad_len, "ad_len", "int32", (n,), rows=True)
+        _check(pn_len, "pn_len", "uint8", (n,), rows=True)
+        _check(arr_group, "arr_group", "int32", (n,), rows=True)
+        _check(arr_index, "arr_index", "uint8", (n,), rows=True)
+        _check(arr_state, "arr_state", "int32", (n,), rows=True)
+        _check(arr_at, "arr_at", "int32", (slots,), rows=True)
+        _check(open_len, "open_len", "int32", (slots,), rows=True)
+        _check(rev, "rev", "uint8", (G * rmax, None), rows=True)
+        _check(rev_len, "rev_len", "int32", (G * rmax,), rows=True)
+        _check(rev_pn_len, "rev_pn_len", "uint8", (G * rmax,), rows=True)
+        _check(rows, "rows", "uint8", (G, k))
+        _check(rec_rows, "rec_rows", "uint8", (G, rmax))
+        _check(status, "status", "int32", (G,))
+        a, a_all = _ptr_or_all(ad_len)
+        pn, pn_all = _ptr_or_all(pn_len)
+        _call("qfec_open_decode_extract_arrivals_ragged", self, k, m, G, _ptr(bb), n, _ptr(pkt),
+              pkt.stride(0), _ptr(pkt_len), a, a_all, pn, pn_all, _ptr(arr_group),
+              _ptr(arr_index), _ptr(arr_state), _ptr(arr_at), _ptr(blocks), _ptr(blocks_off),
+              _ptr(rows), _ptr(open_len), _ptr(rec), _ptr(rec_off), _ptr(rec_rows), _ptr(status),
+              _ptr(rev), rev.stride(0), _ptr(rev_len), _ptr(rev_pn_len), _stream(stream, pkt))
+
     # host-pointer batch calls (synchronous; include H2D/D2H)
     def encode_host(self, k, m, block_bytes, data):
         data = np.ascontiguousarray(data, dtype=np.uint8)
@@ -612,6 +650,35 @@ def framed_rx_block_bytes(k, m, pkt_len, ad_len):
     rc = load().qfec_framed_rx_block_bytes(k, m, G, _vp(pkt_len), _vp(ad_len), a_all, _vp(bb))
     if rc:
         raise ValueError(f"qfec_framed_rx_block_bytes: rc={rc} (k={k} m={m})")
+    return bb
+
+
+# what open_decode_extract_arrivals_ragged's arr_state says of an arrival that was not accepted
+ARR_REJECTED, ARR_IGNORED, ARR_DUPLICATE, ARR_LATE = -1, -2, -3, -4
+
+
+def arrivals_rx_block_bytes(k, m, groups, arr_group, arr_index, pkt_len, ad_len):
+    """framed_rx_block_bytes for packets in arrival order (qfec_arrivals_rx_block_bytes; host
+    only): arr_group int32 [n], arr_index uint8 [n], pkt_len int32 [n], ad_len an int32 array [n]
+    or an int -> bb int32 [groups], the largest stored packet among each group's first k distinct
+    arrivals, 0 for a group of which nothing arrived.  Tags outside the batch are skipped."""
+    arr_group = np.ascontiguousarray(arr_group, dtype=np.int32).reshape(-1)
+    arr_index = np.ascontiguousarray(arr_index, dtype=np.uint8).reshape(-1)
+    pkt_len = np.ascontiguousarray(pkt_len, dtype=np.int32).reshape(-1)
+    n = pkt_len.size
+    if arr_group.size != n or arr_index.size != n:
+        raise ValueError("arr_group, arr_index and pkt_len must hold one entry per arrival")
+    if isinstance(ad_len, (int, np.integer)):
+        ad_len, a_all = None, int(ad_len)
+    else:
+        ad_len, a_all = np.ascontiguousarray(ad_len, dtype=np.int32).reshape(-1), 0
+        if ad_len.size != n:
+            raise ValueError("ad_len must hold one length per arrival")
+    bb = np.zeros(groups, np.int32)
+    rc = load().qfec_arrivals_rx_block_bytes(k, m, groups, n, _vp(arr_group), _vp(arr_index),
+                                             _vp(pkt_len), _vp(ad_len), a_all, _vp(bb))
+    if rc:
+        raise ValueError(f"qfec_arrivals_rx_block_bytes: rc={rc} (k={k} m={m} groups={groups})")
     return bb
 
 

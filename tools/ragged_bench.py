@@ -30,9 +30,20 @@ The parity of the two routes is compared byte for byte first (the wire data pack
 purpose: the framed ones carry no prefix).  The difference is set against the bytes the frame and
 extract kernels move.
 
+--arrivals: the arrival-order receiver on the --framed workload:
+  slot      qfec_open_decode_extract_batch_ragged, every received packet at its slot
+  arrivals  qfec_open_decode_extract_arrivals_ragged on the same packets as an in-order,
+            duplicate-free ring (gathered once, not timed) with a (group, index) tag each
+  two_read  the same call with the option arr_optimistic = 0: no data packet is placed by the
+            open pass, the assemble reads every accepted packet a second time
+  shuffled  the arrivals call on the same ring shuffled, with 5 % of its packets twice
+The outputs of slot and arrivals are compared byte for byte first; the shuffled ring must revive
+every lost payload.  The time ratio is set against the ratio of the bytes the two routes move.
+
   python tools/ragged_bench.py --out profiles/ragged/ragged_bench.json
   python tools/ragged_bench.py --pp --out profiles/ragged/ragged_pp_bench.json
   python tools/ragged_bench.py --framed --out profiles/ragged/framed_bench.json
+  python tools/ragged_bench.py --arrivals --out profiles/ragged/arrivals_bench.json
 """
 import argparse
 import json
@@ -74,6 +85,11 @@ def main():
                          "one uniform protected call per distinct bb")
     ap.add_argument("--framed", action="store_true",
                     help="the framed protected paths against the unframed ragged ones")
+    ap.add_argument("--arrivals", action="store_true",
+                    help="the arrival-order receiver against the slot-order framed receiver")
+    ap.add_argument("--variants", default=None,
+                    help="--arrivals: comma-separated subset of slot,arrivals,two_read,shuffled "
+                         "to time (for a kernel trace of one route)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.reps < 20:
@@ -482,13 +498,196 @@ def main():
         results.append(line)
         print(json.dumps(line), flush=True)
 
+    def run_arrivals(k, m, r, bb, label):
+        """--arrivals: the framed receiver by slot against the arrivals call on the same received
+        packets as a ring, data packets 0 .. r-1 of every group lost."""
+        G, per, rmax, H = len(bb), k + m, min(k, m), 16
+        n = G * per
+        stride = H + 12 + int(bb.max())
+        pay_stride = int(bb.max())
+        rng = np.random.default_rng(args.seed + 1)
+        lens = (np.repeat(bb, k) - 2 - rng.integers(0, 8, G * k)).astype(np.int32)
+        fbb, d_off, p_off, r_off, tot = fec.framed_layout(k, m, lens)
+        assert np.array_equal(fbb, bb)
+        pay = torch.empty((G * k, pay_stride), dtype=torch.uint8, device="cuda")
+        fec.synth_fill(pay, seed=args.seed)
+        lens_d = torch.from_numpy(lens).cuda()
+        data = torch.zeros(tot[0], dtype=torch.uint8, device="cuda")
+        par = torch.zeros(tot[1], dtype=torch.uint8, device="cuda")
+        bb_d = torch.from_numpy(bb).cuda()
+        d_off_d, p_off_d, r_off_d = (torch.from_numpy(o).cuda() for o in (d_off, p_off, r_off))
+        hdr = torch.randint(0, 256, (n, H), dtype=torch.uint8, device="cuda")
+        pkt = torch.zeros((n, stride), dtype=torch.uint8, device="cuda")
+        plen = torch.zeros(n, dtype=torch.int32, device="cuda")
+        est = torch.zeros(G, dtype=torch.int32, device="cuda")
+        eng.frame_encode_seal_ragged(k, m, bb_d, data, d_off_d, par, p_off_d, hdr, H, pay, lens_d,
+                                     1, pkt, plen, status=est)
+        torch.cuda.synchronize()
+        assert int(est.abs().max()) == 0
+        del data, par, hdr
+        wl = plen.clone().view(G, per)
+        wl[:, :r] = -1
+        wl = wl.view(n)
+
+        def outputs():
+            return dict(blocks=torch.zeros(tot[0], dtype=torch.uint8, device="cuda"),
+                        rec=torch.zeros(tot[2], dtype=torch.uint8, device="cuda"),
+                        rows=torch.zeros((G, k), dtype=torch.uint8, device="cuda"),
+                        ol=torch.zeros(n, dtype=torch.int32, device="cuda"),
+                        rr=torch.zeros((G, rmax), dtype=torch.uint8, device="cuda"),
+                        st=torch.zeros(G, dtype=torch.int32, device="cuda"),
+                        rev=torch.zeros((G * rmax, pay_stride), dtype=torch.uint8, device="cuda"),
+                        rev_len=torch.zeros(G * rmax, dtype=torch.int32, device="cuda"),
+                        rev_pn=torch.zeros(G * rmax, dtype=torch.uint8, device="cuda"))
+
+        # the rings (gathered once, not timed): the received packets in slot order, and the same
+        # packets shuffled with 5 % of them twice
+        recv = torch.nonzero(wl >= 0).view(-1)
+        dup = recv[torch.from_numpy(rng.choice(recv.numel(), recv.numel() // 20,
+                                               replace=False)).cuda()]
+        mixed_src = torch.cat([recv, dup])[torch.from_numpy(
+            rng.permutation(recv.numel() + dup.numel())).cuda()]
+
+        def ring_of(src):
+            return dict(n=src.numel(), pkt=pkt[src].contiguous(), len=plen[src].contiguous(),
+                        grp=(src // per).to(torch.int32), idx=(src % per).to(torch.uint8),
+                        state=torch.zeros(src.numel(), dtype=torch.int32, device="cuda"),
+                        at=torch.zeros(n, dtype=torch.int32, device="cuda"))
+
+        rings = dict(arrivals=ring_of(recv), shuffled=ring_of(mixed_src))
+        out = dict(slot=outputs(), arrivals=outputs())
+        out["shuffled"] = out["arrivals"]
+
+        def slot():
+            o = out["slot"]
+            eng.open_decode_extract_ragged(k, m, bb_d, pkt, wl, H, 1, o["blocks"], d_off_d,
+                                           o["rows"], o["ol"], o["rec"], r_off_d, o["rr"], o["rev"],
+                                           o["rev_len"], rev_pn_len=o["rev_pn"], status=o["st"])
+
+        def arrivals_call(name, optimistic=1):
+            R, o = rings[name], out[name]
+            eng.set_option("arr_optimistic", optimistic)
+            eng.open_decode_extract_arrivals_ragged(
+                k, m, bb_d, R["pkt"], R["len"], H, 1, R["grp"], R["idx"], R["state"], R["at"],
+                o["blocks"], d_off_d, o["rows"], o["ol"], o["rec"], r_off_d, o["rr"], o["rev"],
+                o["rev_len"], rev_pn_len=o["rev_pn"], status=o["st"])
+            eng.set_option("arr_optimistic", 1)
+
+        def revives_lost(o):
+            lost = torch.arange(G, device="cuda")[:, None] * k + \
+                torch.arange(r, device="cuda")[None, :]
+            got = o["rev_len"].view(G, rmax)[:, :r]
+            cols = torch.arange(pay_stride, device="cuda")[None, None, :]
+            mask = cols < got[:, :, None]
+            return int(o["st"].abs().max()) == 0 and torch.equal(got, lens_d[lost]) and \
+                torch.equal(o["rev"].view(G, rmax, pay_stride)[:, :r][mask], pay[lost][mask])
+
+        kern = {}
+        slot()
+        kern["slot"] = fec.last_kernels()
+        arrivals_call("arrivals")
+        kern["arrivals"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        assert revives_lost(out["slot"]), "the slot route does not revive the lost payloads"
+        a, b = out["slot"], out["arrivals"]
+
+        def same_as_slot():
+            for name in ("blocks", "rec", "rows", "rr", "st", "rev", "rev_len", "rev_pn"):
+                assert torch.equal(a[name], b[name]), f"{name} differs between the routes"
+            # open_len: the arrivals route marks the FEC packets behind the k-th as late
+            taken = rings["arrivals"]["at"] >= 0
+            assert torch.equal(a["ol"][taken], b["ol"][taken]) and int(b["ol"][~taken].max()) == -1
+
+        same_as_slot()
+        states = rings["arrivals"]["state"]
+        accepted = int((states >= 0).sum())
+        assert accepted == G * k and int((states == -4).sum()) == recv.numel() - G * k
+        # plaintext bytes the assemble reads: every accepted packet's, or (optimistic) those of
+        # the accepted FEC packets alone
+        second_read2 = int(states[states >= 0].sum())
+        second_read = int(states[(states >= 0) & (rings["arrivals"]["idx"] >= k)].sum())
+        for o in b.values():
+            o.zero_()
+        arrivals_call("arrivals", 0)
+        kern["two_read"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        same_as_slot()
+        arrivals_call("shuffled")
+        torch.cuda.synchronize()
+        assert revives_lost(out["shuffled"]), "the shuffled ring does not revive the lost payloads"
+        sh = rings["shuffled"]["state"]
+        shuffled = dict(arrivals=rings["shuffled"]["n"], accepted=int((sh >= 0).sum()),
+                        duplicate=int((sh == -3).sum()), late=int((sh == -4).sum()),
+                        revived=int((out["shuffled"]["rev_len"] >= 0).sum()),
+                        accepted_plaintext_bytes=int(sh[sh >= 0].sum()))
+
+        names = ["slot", "arrivals", "two_read", "shuffled"]
+        timed_names = args.variants.split(",") if args.variants else names
+        assert set(timed_names) <= set(names)
+        fns = dict(slot=slot, arrivals=lambda: arrivals_call("arrivals"),
+                   two_read=lambda: arrivals_call("arrivals", 0),
+                   shuffled=lambda: arrivals_call("shuffled"))
+        ev = DeviceEvents(2 * len(names))
+        t = {x: [] for x in names}
+        for rep_i in range(args.warmup + args.reps):
+            order = names if rep_i % 2 == 0 else [names[2], names[1], names[0], names[3]]
+            for name in order:
+                if name in timed_names:
+                    timed(ev, names.index(name), fns[name])
+            torch.cuda.synchronize()
+            if rep_i >= args.warmup:
+                for i, name in enumerate(names):
+                    t[name].append(ev.elapsed_ms(2 * i, 2 * i + 1) if name in timed_names else 0.0)
+        ev.close()
+        # bytes each route moves, from the shapes: T = the blocks' bytes of one block per group
+        T = int(bb.astype(np.int64).sum())
+        wire = int(plen[recv].to(torch.int64).sum())
+        after_open = (k + r) * T + 2 * r * T                  # decode in + out, extract in + out
+        slot_bytes = wire + k * T + after_open                # every received packet read, k placed
+        nr = rings["arrivals"]["n"]
+        tags = 5 * nr
+        # arr_at: init, read and write per slot, one atomic per opened arrival; arr_state written,
+        # read and looked up per arrival
+        tables2 = 12 * n + 8 * nr + 12 * nr
+        # the pre-pass: its table initialised and read per slot, lengths and tags read per
+        # arrival, one atomic per data arrival, one look-up per data arrival in the open pass
+        tables = tables2 + 8 * n + 13 * nr + 12 * (k - r) * G
+        arr_bytes = wire + tags + tables + second_read + k * T + after_open
+        arr2_bytes = wire + tags + tables2 + second_read2 + k * T + after_open
+        line = dict(config=label, mode="arrivals", k=k, m=m, losses=r, groups=G, packets=n,
+                    reps=args.reps, kernels=kern, ring_packets=nr,
+                    bytes_moved=dict(slot=slot_bytes, arrivals=arr_bytes, two_read=arr2_bytes,
+                                     tag_bytes=tags, table_bytes=tables,
+                                     table_bytes_two_read=tables2,
+                                     second_read_bytes=second_read,
+                                     second_read_bytes_two_read=second_read2),
+                    shuffled_ring=shuffled)
+        for name in names:
+            med = statistics.median(t[name])
+            line[name] = dict(kernel_ms_median=round(med, 4), kernel_ms_min=round(min(t[name]), 4),
+                              kernel_ms_max=round(max(t[name]), 4))
+        if args.variants:                                     # a trace run: no ratios
+            results.append(line)
+            print(json.dumps(line), flush=True)
+            return
+        line["arrivals_over_slot"] = round(line["arrivals"]["kernel_ms_median"] /
+                                           line["slot"]["kernel_ms_median"], 3)
+        line["byte_ratio"] = round(arr_bytes / slot_bytes, 3)
+        line["two_read_over_slot"] = round(line["two_read"]["kernel_ms_median"] /
+                                           line["slot"]["kernel_ms_median"], 3)
+        line["two_read_byte_ratio"] = round(arr2_bytes / slot_bytes, 3)
+        line["shuffled_over_arrivals"] = round(line["shuffled"]["kernel_ms_median"] /
+                                               line["arrivals"]["kernel_ms_median"], 3)
+        results.append(line)
+        print(json.dumps(line), flush=True)
+
     G = args.groups
     mixed = draw_sizes(G, args.seed)
     flat = np.full(G, 1352, np.int32)
     run = run_pp if args.pp else run_config
     for k, m, r in (tuple(int(v) for v in c.split(",")) for c in args.codes.split()):
-        if args.framed:
-            run_framed(k, m, r, mixed, f"mixed ({k},{m})")
+        if args.framed or args.arrivals:
+            (run_framed if args.framed else run_arrivals)(k, m, r, mixed, f"mixed ({k},{m})")
             continue
         run(k, m, r, mixed, f"mixed ({k},{m})")
         # the price of run-time shapes: every bb = 1352, one bucket = the compiled path (A / B)

@@ -6,8 +6,11 @@
 // It calls qfec_ragged_layout, qfec::ragged_pack and the planning functions of the host
 // pipeline (chunks, stage sizes, carve) on random sizes and checks offsets and bounds, and the
 // two helpers of the framed calls (qfec_framed_layout, qfec_framed_rx_block_bytes) on hostile
-// inputs: zero groups, every packet absent, the largest length, offsets past 2^40;
+// inputs: zero groups, every packet absent, the largest length, offsets past 2^40, and the helper
+// of the arrival-order receiver (qfec_arrivals_rx_block_bytes): duplicates, more than k arrivals,
+// tags outside the batch, no arrival, a tag at the last group;
 // out-of-bounds copies or overflowing arithmetic abort under the sanitizers.
+#include <algorithm>
 #include <climits>
 #include <cstdint>
 #include <cstdio>
@@ -350,6 +353,79 @@ static void check_framed(std::mt19937& rng) {
     }
 }
 
+// ---- the host helper of the arrival-order receiver, in arrays of exactly n entries
+static void check_arrivals(std::mt19937& rng) {
+    // n = 0: no array is read, every size is 0; no groups: nothing is written
+    {
+        std::vector<int> bb(3, 7);
+        CHECK(qfec_arrivals_rx_block_bytes(5, 5, 3, 0, nullptr, nullptr, nullptr, nullptr, 0, bb.data()) == 0);
+        CHECK(bb == std::vector<int>(3, 0));
+        CHECK(qfec_arrivals_rx_block_bytes(5, 5, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr) == 0);
+        const int grp[1] = {0}, len[1] = {40};
+        const unsigned char idx[1] = {0};
+        CHECK(qfec_arrivals_rx_block_bytes(5, 5, 0, 1, grp, idx, len, nullptr, 16, nullptr) == 0);
+        CHECK(qfec_arrivals_rx_block_bytes(5, 5, 1, -1, grp, idx, len, nullptr, 16, bb.data()) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes(5, 5, -1, 1, grp, idx, len, nullptr, 16, bb.data()) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes(0, 5, 1, 1, grp, idx, len, nullptr, 16, bb.data()) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes(250, 6, 1, 1, grp, idx, len, nullptr, 16, bb.data()) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes(5, 5, 1, 1, nullptr, idx, len, nullptr, 16, bb.data()) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes(5, 5, 1, 1, grp, nullptr, len, nullptr, 16, bb.data()) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes(5, 5, 1, 1, grp, idx, nullptr, nullptr, 16, bb.data()) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes(5, 5, 1, 1, grp, idx, len, nullptr, 16, nullptr) == -2);
+    }
+    // duplicates, more than k arrivals, a tag at the last group, ignored tags: k = 2, m = 2
+    {
+        //                 dup of (0,0)   late in g0  last group   ignored: g = -1, g = G, i = k+m, 255
+        const int grp[] = {0, 0, 0, 0,    0,          2, 2,        -1, 3, 1, 1};
+        const unsigned char idx[] = {0, 0, 3, 1,  2,  3, 3,        0, 0, 4, 255};
+        const int len[] = {16 + 12 + 10, 16 + 12 + 900, 16 + 12 + 16, 16 + 12 + 500,
+                           16 + 12 + 1000, 16 + 12 + 24, 16 + 12 + 999,
+                           2000, 2000, 2000, 2000};
+        int bb[3] = {7, 7, 7};
+        CHECK(qfec_arrivals_rx_block_bytes(2, 2, 3, 11, grp, idx, len, nullptr, 16, bb) == 0);
+        // g0: (0, 10 + 2) and FEC (3, 16) are its first k = 2; the duplicate's 900 bytes, data
+        // packet 1 and FEC packet 2 come too late.  g1: only ignored tags.  g2: the first copy.
+        CHECK(bb[0] == 16 && bb[1] == 0 && bb[2] == 24);
+        // a first copy with fewer than 12 bytes behind its AD does not count, its second copy does
+        const int grp2[] = {0, 0}, len2[] = {16 + 11, 16 + 12 + 30};
+        const unsigned char idx2[] = {1, 1};
+        int one[1] = {7};
+        CHECK(qfec_arrivals_rx_block_bytes(2, 2, 1, 2, grp2, idx2, len2, nullptr, 16, one) == 0);
+        CHECK(one[0] == 32);
+    }
+    // random streams with hostile tags and lengths against the sequential rule
+    for (int rep = 0; rep < 50; ++rep) {
+        const int k = 1 + (int)(rng() % 40), m = 1 + (int)(rng() % 8), per = k + m;
+        const long long G = 1 + (long long)(rng() % 12);
+        const size_t n = rng() % 600;
+        std::vector<int> grp(n), len(n), ad(n), bb((size_t)G, 7), want((size_t)G, 0);
+        std::vector<unsigned char> idx(n);
+        std::vector<std::vector<bool>> seen((size_t)G, std::vector<bool>((size_t)per, false));
+        std::vector<int> held((size_t)G, 0);
+        for (size_t a = 0; a < n; ++a) {
+            const unsigned pick = rng() % 16;
+            grp[a] = pick == 0 ? -1 : pick == 1 ? (int)G : pick == 2 ? INT_MIN : pick == 3 ? INT_MAX
+                                                                          : (int)(rng() % G);
+            if (pick == 4) grp[a] = (int)G - 1;
+            idx[a] = (unsigned char)(pick == 5 ? per : pick == 6 ? 255 : rng() % per);
+            ad[a] = pick == 7 ? -3 : (int)(rng() % 20);
+            len[a] = pick == 8 ? -1 : pick == 9 ? INT_MAX : pick == 10 ? ad[a] + 11
+                                                          : ad[a] + 12 + (int)(rng() % 1400);
+            const long long g = grp[a], pt = (long long)len[a] - ad[a] - 12;
+            if (g < 0 || g >= G || idx[a] >= per) continue;
+            if (len[a] < 0 || ad[a] < 0 || pt < 0) continue;
+            if (seen[(size_t)g][idx[a]] || held[(size_t)g] >= k) continue;
+            seen[(size_t)g][idx[a]] = true;
+            ++held[(size_t)g];
+            const long long st = pt + (idx[a] < k ? 2 : 0);
+            want[(size_t)g] = std::max(want[(size_t)g], (int)std::min<long long>(st, INT_MAX));
+        }
+        CHECK(qfec_arrivals_rx_block_bytes(k, m, G, (long long)n, grp.data(), idx.data(), len.data(),
+                                           ad.data(), 0, bb.data()) == 0);
+        CHECK(bb == want);
+    }
+}
+
 int main() {
     std::mt19937 rng(20240607);
     const int codes[][2] = {{10, 1}, {3, 2}, {5, 5}, {32, 4}, {10, 20}, {1, 3}, {250, 5}, {10, 10}};
@@ -367,6 +443,7 @@ int main() {
     }
     check_plan_errors();
     check_framed(rng);
+    check_arrivals(rng);
     // errors: a size < 1, bad arguments, overflow of the running offset
     {
         const int bad[3] = {8, 0, 8};
