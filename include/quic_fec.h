@@ -228,6 +228,68 @@ QFEC_API int qfec_decode_batch_ragged_recovered_host(qfec_ctx *ctx, int k, int m
                                                      unsigned char *h_rec_rows, int *h_status);
 
 /* ---------------------------------------------------------------------------------
+ * Pointer-table batches: encode and decode blocks where they lie.  The batched form of the
+ * drop-in ABI's one pointer per block (cauchy_256_encode's data_ptrs[], cauchy_256_decode's
+ * Block{data,row}[]): the k blocks of a group may lie in k unrelated device buffers (mbufs of a
+ * device mempool, ring slots of different sizes, blocks shared between groups), and nothing is
+ * packed first.
+ *
+ * Tables: d_data_ptrs / d_block_ptrs [G*k], d_parity_ptrs [G*m] and d_rec_ptrs [G*min(k,m)] are
+ * device arrays of device addresses; entry g*k + pos names block pos of group g (the index is
+ * 64-bit).  d_bb [G] is the block size per group, or NULL: every group has bb_all.  rows
+ * [G][k], rec_rows [G][min(k,m)] and status [G] are dense as in the uniform calls.
+ *
+ * Per-group semantics are exactly those of qfec_encode_batch_ragged /
+ * qfec_decode_batch_ragged_recovered with block_bytes = bb[g]: k <= 1 copies; m == 1 is XOR
+ * with any bb >= 1; for m > 1 and bb[g] % 8 != 0 the status is -1 (the encode writes the XOR
+ * parity to the group's first parity block only); a malformed receive set has status -3;
+ * rec_rows is 255 past a group's erasure count; with m > 1 and k + m > 256 the encode writes
+ * every group's XOR parity to its first parity block and returns -1.
+ *
+ * Entries that are never dereferenced (a caller may leave anything in them): every entry of a
+ * group with bb[g] < 1; parity entries 1 .. m-1 of a group the encode rejects; d_rec_ptrs
+ * entries at or past the group's erasure count; every d_rec_ptrs entry of a group with a
+ * negative status.
+ *
+ * Every other entry must be a valid device address of bb[g] bytes.  The library cannot check
+ * this and does not try (as the pointer arrays of batched BLAS): a wrong entry is a wild read
+ * or write on the device, not an error code.
+ *
+ * Alignment: a block may start at any address; the result is the same bytes.  No byte outside
+ * [ptr, ptr + bb[g]) of any block is read or written.
+ *
+ * Overlap: input blocks may overlap or be shared between groups.  Output blocks must be
+ * distinct from each other and must not overlap any input block of the batch.  In-place decode
+ * is not offered (the apply works in output chunks that each re-read the inputs).
+ *
+ * Call-level -2, before anything is enqueued: the ragged calls' limits (k, m, groups < 0, a
+ * null context), a NULL table, d_bb == NULL with bb_all < 1, a null d_rows_in / d_rec_rows, and
+ * for m > 1 more than 2^31 - 1 (group, output chunk) units (chunks of at most 4 outputs).
+ *
+ * Streams, graphs: the calls only enqueue on `stream` and read no device array back.  The
+ * decode uses the decode workspace in the same bracket as every decode;
+ * qfec_reserve(ctx, k, m, any block_bytes, groups) covers a capture.  A captured call reads the
+ * tables when it runs: it may be replayed after the caller rewrote them in place.
+ * ------------------------------------------------------------------------------- */
+/* Parity block y of group g is written at d_parity_ptrs[g*m + y].  d_status [G] may be NULL. */
+QFEC_API int qfec_encode_batch_ptrs(qfec_ctx *ctx, int k, int m, long long groups,
+                                    const int *d_bb, int bb_all,
+                                    const unsigned char *const *d_data_ptrs,
+                                    unsigned char *const *d_parity_ptrs, int *d_status,
+                                    void *stream);
+
+/* Recovered-blocks layout: recovered block j of group g is written at
+ * d_rec_ptrs[g*min(k,m) + j], its data row to d_rec_rows[g*min(k,m) + j] (ascending; 255 past
+ * the count).  The blocks and d_rows_in [G][k] are left untouched.  d_status may be NULL. */
+QFEC_API int qfec_decode_batch_ptrs_recovered(qfec_ctx *ctx, int k, int m, long long groups,
+                                              const int *d_bb, int bb_all,
+                                              const unsigned char *const *d_block_ptrs,
+                                              const unsigned char *d_rows_in,
+                                              unsigned char *const *d_rec_ptrs,
+                                              unsigned char *d_rec_rows, int *d_status,
+                                              void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Packet protection next to the FEC path (SURVEY.md §8 f, rank 4).
  *
  * The reference encrypts every packet after serialisation -- the FEC packets right after
@@ -641,7 +703,9 @@ QFEC_API const char *qfec_last_error(void);
 /* Names of the kernels this thread's last engine call launched, " + "-separated, e.g.
  * "decode_prep_lane_kernel + gf_stream_kernel<decode>" (bench.py reports it).  The ragged
  * calls name "gf_ragged_kernel<encode>", "gf_ragged_kernel<decode>", "xor_ragged_kernel" and
- * "copy_ragged_kernel"; the ragged protected calls add "null_seal_kernel<ragged>" and
+ * "copy_ragged_kernel"; the pointer-table calls name "gf_ptrs_kernel<encode>",
+ * "gf_ptrs_kernel<decode>", "xor_ptrs_kernel" and "copy_ptrs_kernel" (and, without d_bb and with
+ * bb_all % 8 != 0, "ptrs_decode_status_kernel"); the ragged protected calls add "null_seal_kernel<ragged>" and
  * "open_group_kernel<ragged> + open_assemble_kernel<ragged>" (the uniform grouped calls name
  * "null_seal_kernel<groups>" and "open_group_kernel + open_assemble_kernel"); the framed calls
  * name "frame_blocks_kernel", "null_seal_kernel<framed>", "open_group_kernel<framed> +

@@ -79,6 +79,16 @@ SIGNATURES = {
                                                                ctypes.c_void_p, ctypes.c_void_p,
                                                                ctypes.c_void_p, ctypes.c_void_p,
                                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "qfec_encode_batch_ptrs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+    "qfec_decode_batch_ptrs_recovered": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int,
+                                                        ctypes.c_int, ctypes.c_longlong,
+                                                        ctypes.c_void_p, ctypes.c_int,
+                                                        ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p,
+                                                        ctypes.c_void_p, ctypes.c_void_p]),
     "qfec_null_seal_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
                                             ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                             ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p]),

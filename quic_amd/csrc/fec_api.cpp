@@ -12,6 +12,7 @@
 
 #include "fec_internal.h"
 #include "gf256.h"
+#include "gf_ptrs.h"
 #include "pp_null.h"
 
 using namespace qfec;
@@ -746,6 +747,19 @@ int qfec_open_decode_batch(qfec_ctx* c, int k, int m, int bb, long long groups,
 // against the (32, 4) encode's 0.86 ms for less data); more chunks re-read the group from L2.
 static int ragged_rc(int rc) { return std::min(rc, 4); }
 
+// The decode plan of the run-time-shape decodes (ragged and pointer-table).  The prep's tables
+// do not depend on the block size: plan and prep with the smallest valid one, the per-group
+// size only enters the apply and the status fix-up.
+static DecodePlan ragged_decode_plan(int k, int m) {
+    DecodePlan p = decode_plan(k, m, 8);
+    if (p.rc > ragged_rc(p.rc)) {   // smaller chunks never need more table bytes per group
+        p.rc = ragged_rc(p.rc);
+        p.nchunk = (p.rmax + p.rc - 1) / p.rc;
+        p.tab_gstride = (long long)p.nchunk * k * std::max(p.rc, 4);
+    }
+    return p;
+}
+
 extern "C++" int qfec::encode_ragged_impl(qfec_ctx* c, int k, int m, long long G, RaggedView v,
                                           const uint8_t* d_data, uint8_t* d_par, int32_t* d_status,
                                           hipStream_t st) {
@@ -779,14 +793,7 @@ extern "C++" int qfec::decode_ragged_impl(qfec_ctx* c, int k, int m, long long G
                                           uint8_t* d_rec, uint8_t* d_rec_rows, int32_t* d_status,
                                           hipStream_t st) {
     if (G == 0) return 0;
-    // the prep's tables do not depend on the block size: plan and prep with the smallest valid
-    // one, the per-group size only enters the apply and the status fix-up
-    DecodePlan p = decode_plan(k, m, 8);
-    if (p.rc > ragged_rc(p.rc)) {   // smaller chunks never need more table bytes per group
-        p.rc = ragged_rc(p.rc);
-        p.nchunk = (p.rmax + p.rc - 1) / p.rc;
-        p.tab_gstride = (long long)p.nchunk * k * std::max(p.rc, 4);
-    }
+    const DecodePlan p = ragged_decode_plan(k, m);
     if (k <= 1) {   // cauchy_256.cpp:1257-1261
         QF_HIP(qfec::launch_copy_ragged(d_blocks, d_rec, v, d_rows_in, d_rec_rows, d_status, m, G,
                                         true, st, c->tune));
@@ -861,6 +868,118 @@ int qfec_decode_batch_ragged_recovered(qfec_ctx* c, int k, int m, long long grou
     return with_workspace(c, st, [&] {
         return decode_ragged_impl(c, k, m, groups, {(const int32_t*)d_bb, d_blocks_off, d_rec_off},
                                   d_blocks, d_rows_in, d_rec, d_rec_rows, (int32_t*)d_status, st);
+    });
+}
+
+// ---- pointer-table batches: the ragged batches with every block at an address of its own
+// (gf_ptrs.hip).  The same order of cases and the same tables as encode_ragged_impl /
+// decode_ragged_impl; the tables' entries cannot be checked and are not read here.
+// The m > 1 kernels count (group, chunk) units in 32 bits.
+static int ptrs_units_check(long long G, int nchunk) {
+    if (G > 0x7fffffffLL / nchunk) return fail(-2, "groups x output chunks exceed 2^31 - 1 units");
+    return 0;
+}
+
+static int encode_ptrs_impl(qfec_ctx* c, int k, int m, long long G, qfec::PtrsView v,
+                            int32_t* d_status, hipStream_t st) {
+    if (G == 0) return 0;
+    if (k <= 1) {   // cauchy_256.cpp:1508-1516
+        QF_HIP(qfec::launch_copy_ptrs(v, nullptr, nullptr, d_status, k, m, G, false, st, c->tune));
+        return 0;
+    }
+    if (m == 1 || k + m > 256) {   // :1519-1534, as encode_impl: P0 only
+        QF_HIP(qfec::launch_xor_ptrs(v, nullptr, d_status, k, m, G, false, m == 1 ? 0 : 1, st,
+                                     c->tune));
+        return m == 1 ? 0 : fail(-1, "unsupported (k + m > 256)");
+    }
+    const int rc = ragged_rc(encode_rc(m, c->tune));
+    int r = ptrs_units_check(G, (m + rc - 1) / rc);
+    if (r) return r;
+    const uint8_t* tab = nullptr;
+    if ((r = get_enc_table(c, k, m, rc, &tab))) return r;
+    // the groups with bb % 8 != 0: P0 and status -1; every other group: the GF encode
+    QF_HIP(qfec::launch_xor_ptrs(v, nullptr, d_status, k, m, G, false, 2, st, c->tune));
+    const qfec::Apply a{nullptr, nullptr, tab, nullptr, nullptr, nullptr, k, m, 0, G, rc, 0, 0, 0,
+                        st, &c->tune};
+    QF_HIP(qfec::launch_gf_ptrs(a, v, (m + rc - 1) / rc, false));
+    return 0;
+}
+
+// The caller holds the workspace bracket (with_workspace).
+static int decode_ptrs_impl(qfec_ctx* c, int k, int m, long long G, qfec::PtrsView v,
+                            const uint8_t* d_rows_in, uint8_t* d_rec_rows, int32_t* d_status,
+                            hipStream_t st) {
+    if (G == 0) return 0;
+    const DecodePlan p = ragged_decode_plan(k, m);
+    if (k <= 1) {   // cauchy_256.cpp:1257-1261
+        QF_HIP(qfec::launch_copy_ptrs(v, d_rows_in, d_rec_rows, d_status, k, m, G, true, st,
+                                      c->tune));
+        return 0;
+    }
+    int r = m == 1 ? 0 : ptrs_units_check(G, p.nchunk);
+    if (r) return r;
+    Workspace& W = ws_for(c, st);
+    if ((r = reserve_workspace(W, p, G, false))) return r;
+    if (m == 1) {   // :1264-1267
+        QF_HIP(qfec::launch_m1_prep(d_rows_in, d_rec_rows, d_status, (uint8_t*)W.dslots.p, k, G,
+                                    true, st));
+        QF_HIP(qfec::launch_xor_ptrs(v, (const uint8_t*)W.dslots.p, nullptr, k, 1, G, true, 0, st,
+                                     c->tune));
+        return 0;
+    }
+    const uint8_t* cenc = nullptr;
+    if ((r = get_cenc(c, k, m, &cenc))) return r;
+    qfec::DecodeWork w{(uint8_t*)W.dcoef.p, (uint8_t*)W.dslots.p, (int32_t*)W.dnout.p};
+    const qfec::PrepIO io{d_rows_in, nullptr, d_rec_rows, d_status, w};
+    QF_HIP(qfec::launch_decode_prep(io, cenc, k, m, 8, p.rc, p.rmax, G, st, c->tune));
+    if (k + m > 256) return 0;   // every group is a no-op or status -1
+    QF_HIP(qfec::launch_ptrs_decode_status(v, d_rows_in, d_rec_rows, d_status, w.nout, k, p.rmax,
+                                           G, st));
+    const qfec::Apply a{nullptr, nullptr, w.coef, cenc, nullptr, w.nout, k, m, 0, G, p.rc, p.rmax,
+                        p.tab_gstride, 0, st, &c->tune};
+    QF_HIP(qfec::launch_gf_ptrs(a, v, p.nchunk, true));
+    return 0;
+}
+
+static int ptrs_check(qfec_ctx* c, int k, int m, long long groups, const void* bb, int bb_all,
+                      const void* in_ptrs, const void* out_ptrs) {
+    int rc = ragged_preface(c, k, m, groups);
+    if (rc) return rc;
+    if (any_null({in_ptrs, out_ptrs})) return fail(-2, "null pointer table");
+    if (!bb && bb_all < 1) return fail(-2, "bb_all < 1 without d_bb");
+    return 0;
+}
+
+int qfec_encode_batch_ptrs(qfec_ctx* c, int k, int m, long long groups, const int* d_bb,
+                           int bb_all, const unsigned char* const* d_data_ptrs,
+                           unsigned char* const* d_parity_ptrs, int* d_status, void* stream) {
+    int rc = ptrs_check(c, k, m, groups, d_bb, bb_all, d_data_ptrs, d_parity_ptrs);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    return encode_ptrs_impl(c, k, m, groups,
+                            {(const unsigned long long*)d_data_ptrs,
+                             (const unsigned long long*)d_parity_ptrs, (const int32_t*)d_bb, bb_all},
+                            (int32_t*)d_status, pick(c, stream));
+}
+
+int qfec_decode_batch_ptrs_recovered(qfec_ctx* c, int k, int m, long long groups, const int* d_bb,
+                                     int bb_all, const unsigned char* const* d_block_ptrs,
+                                     const unsigned char* d_rows_in,
+                                     unsigned char* const* d_rec_ptrs, unsigned char* d_rec_rows,
+                                     int* d_status, void* stream) {
+    int rc = ptrs_check(c, k, m, groups, d_bb, bb_all, d_block_ptrs, d_rec_ptrs);
+    if (rc) return rc;
+    if (!d_rows_in || !d_rec_rows) return fail(-2, "null buffer");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    if (groups == 0) return 0;
+    const hipStream_t st = pick(c, stream);
+    return with_workspace(c, st, [&] {
+        return decode_ptrs_impl(c, k, m, groups,
+                                {(const unsigned long long*)d_block_ptrs,
+                                 (const unsigned long long*)d_rec_ptrs, (const int32_t*)d_bb, bb_all},
+                                d_rows_in, d_rec_rows, (int32_t*)d_status, st);
     });
 }
 

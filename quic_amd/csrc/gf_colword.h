@@ -1,5 +1,5 @@
 // gf_colword.h — column-word access of the bit-sliced apply kernels (gf_apply_kernel in
-// fec_kernels.hip, gf_ragged_kernel in gf_ragged.hip).
+// fec_kernels.hip, the ragged and pointer-table unit in gf_ragged_unit.h).
 //
 // Word c of sub-row t covers bytes [t*s + 4c, +4); the last word of a sub-row may be partial
 // (s % 4 != 0).  Loads of the last word are shifted back inside the sub-row (never past the

@@ -16,105 +16,9 @@
 // All of a unit's shape (bb, offsets, counts) is wave-uniform.  No MFMA: byte XORs only.
 #include <algorithm>
 
-#include "fec_kernels.h"
-#include "gf256.h"
-#include "gf_bitslice.h"
-#include "gf_colword.h"
+#include "gf_ragged_unit.h"
 
 namespace qfec {
-
-// Logical workgroup of hardware block b: consecutive logical workgroups run on one XCD (the
-// bijection of gf_apply_kernel), so the chunks of one group share an L2.
-__device__ __forceinline__ unsigned xcd_logical_block() {
-    const unsigned nbk = gridDim.x, b = blockIdx.x, xcd = b & 7u, q8 = nbk >> 3, r8 = nbk & 7u;
-    return xcd * q8 + (xcd < r8 ? xcd : r8) + (b >> 3);
-}
-
-// A wave-uniform 64-bit value the compiler may not see as uniform (loaded per group): keep
-// it in scalar registers.
-__device__ __forceinline__ long long uniform64(long long v) {
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((unsigned long long)v >> 32));
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
-// One (group, chunk) unit: n <= RC outputs over every column tile of the group.
-//   cw: the unit's coefficient words, [k][RCP] bytes (RCP = max(4, RC))
-//   outputs j < n go to gout + j * bb
-template <int RC, bool TINY>
-__device__ __forceinline__ void ragged_unit(const uint8_t* gin, uint8_t* gout,
-                                            const uint32_t* cw, int k, int bb, int n,
-                                            int lane) {
-    constexpr int RCP = RC < 4 ? 4 : RC;
-    constexpr int NCW = RCP / 4;
-    constexpr int PD = 2;
-    const int s = bb >> 3;
-    const int nw = (s + 3) >> 2;
-    const int ntiles = (nw + 63) >> 6;
-#pragma unroll 1
-    for (int tile = 0; tile < ntiles; ++tile) {
-        const int c = tile * 64 + lane;
-        const ColAccess ca = col_access<TINY>(c, nw, s);
-        uint32_t acc[RC][8];
-#pragma unroll
-        for (int j = 0; j < RC; ++j)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) acc[j][r] = 0;
-        // two blocks in flight while one is combined, as gf_apply_kernel (PD = 2)
-        uint32_t raw[PD][8];
-#pragma unroll
-        for (int u = 0; u < PD; ++u) {
-            const uint8_t* p = gin + (long long)min(u, k - 1) * bb;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) raw[u][t] = load_raw<TINY>(p + t * s, ca, s);
-        }
-#pragma unroll 1
-        for (int pos0 = 0; pos0 < k; pos0 += PD) {
-#pragma unroll
-            for (int u = 0; u < PD; ++u) {
-                const int pos = pos0 + u;
-                if (pos < k) {
-                    WZ v;
-#pragma unroll
-                    for (int t = 0; t < 8; ++t)
-                        v.W[t] = TINY ? raw[u][t] : (raw[u][t] >> ca.shift);
-                    const uint8_t* p = gin + (long long)min(pos + PD, k - 1) * bb;
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) raw[u][t] = load_raw<TINY>(p + t * s, ca, s);
-                    uint32_t cwv[NCW];
-#pragma unroll
-                    for (int q = 0; q < NCW; ++q) cwv[q] = cw[pos * NCW + q];
-                    expand_wz(v);
-#pragma unroll
-                    for (int j = 0; j < RC; ++j) {
-                        if (j < n) {
-                            const uint32_t a = (cwv[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-                            apply_nibble<0>(acc[j], a & 15u, v);
-                            apply_nibble<4>(acc[j], a >> 4, v);
-                        }
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < RC; ++j) {
-            if (j < n) {
-                uint8_t* dst = gout + (long long)j * bb;
-#pragma unroll
-                for (int r = 0; r < 8; ++r) store_word(dst + r * s, c, ca, acc[j][r]);
-            }
-        }
-    }
-}
-
-// Register bound (the kernel is launched with 256 threads; the bound only caps VGPRs at
-// 512 / ceil(waves / 4) = 168, three waves per SIMD).  The loops around the unit cost registers
-// that gf_apply_kernel's straight-line body does not need: at gf_apply's bound for RC 4
-// (128 VGPRs) the kernel spilled 232 bytes per lane; at 168 it needs no scratch.  Measured on
-// one box, alternating: (32, 4) encode 1.10 -> 0.87 ms, decode 1.01 -> 0.75 ms.  RC 8 does
-// not fit under any bound (256 VGPRs and 404 bytes of scratch at two waves), so the ragged
-// paths use chunks of at most 4 outputs.
-constexpr int kRaggedBound = 640;
 
 //   coef:   encode: the shared [nchunk][k][RCP] table; decode: + g * coef_gstride
 //   encode: outputs o = chunk*RC + j < m go to out + out_off[g] + o*bb[g]
@@ -150,14 +54,14 @@ __global__ __launch_bounds__(kRaggedBound) void gf_ragged_kernel(
         uint8_t* gout = out + uniform64(out_off[g]) + (long long)chunk * RC * bb;
         const uint32_t* cw = (const uint32_t*)(coef + (DECODE ? g * coef_gstride : 0) +
                                                (long long)chunk * k * RCP);
-        if (bb >= 32) ragged_unit<RC, false>(gin, gout, cw, k, bb, n, lane);
-        else ragged_unit<RC, true>(gin, gout, cw, k, bb, n, lane);
+        const PackedIn bin{gin, bb};
+        const PackedOut bout{gout, bb};
+        if (bb >= 32) ragged_unit<RC, false>(bin, bout, cw, k, bb, n, lane);
+        else ragged_unit<RC, true>(bin, bout, cw, k, bb, n, lane);
     }
 }
 
 // ------------------------------------------------------------------ XOR (m == 1)
-typedef uint32_t rg_u32x4a8 __attribute__((ext_vector_type(4), aligned(8)));
-
 // out block of group g = XOR of its k blocks.  16-byte units where bb % 8 == 0 (every block
 // then starts 8-byte aligned), unaligned 4-byte units otherwise, and a byte tail.  Every byte
 // is touched once: non-temporal, as xor_flat_kernel.
@@ -267,11 +171,6 @@ __global__ __launch_bounds__(256) void ragged_decode_status_kernel(
 }
 
 // ---------------------------------------------------------------------- launchers
-// ragged_grid (fec_kernels.h) against the workgroups of `kern` the device holds
-static unsigned ragged_grid_of(const void* kern, long long units, const Tune& t) {
-    return ragged_grid(units, (long long)t.cus * resident_blocks(kern, 256, 0));
-}
-
 hipError_t launch_gf_ragged(const Apply& a, RaggedView v, int nchunk, bool decode) {
     const long long units = a.groups * nchunk;
     if (units <= 0) return hipSuccess;

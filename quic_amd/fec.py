@@ -166,6 +166,33 @@ def _groups(bb, **offs):
     return bb.shape[0]
 
 
+def _ptr_tables(bb, status, **tables):
+    """G of a pointer-table call: every table (tensor, n) is int64 [G][n]; bb is an int or
+    int32 [G], status None or int32 [G]."""
+    import torch
+    G = None
+    for name, (t, n) in tables.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: a pointer table must be an int64 device tensor")
+        G = t.shape[0] if G is None and t.dim() else G
+        _check(t, name, "int64", (G, n))
+    if isinstance(bb, bool) or not isinstance(bb, int):
+        if not isinstance(bb, torch.Tensor):
+            raise TypeError("bb: an int or an int32 device tensor")
+        _check(bb, "bb", "int32", (G,))
+    _check(status, "status", "int32", (G,))
+    return G
+
+
+def block_ptrs(tensor, byte_offsets):
+    """The int64 device tensor tensor.data_ptr() + byte_offsets: the addresses of blocks that
+    start `byte_offsets` (any integer array or tensor, any shape) bytes into `tensor`, as the
+    pointer-table calls take them.  The caller keeps `tensor` alive while they are used."""
+    import torch
+    off = torch.as_tensor(byte_offsets, dtype=torch.int64)
+    return (off + tensor.data_ptr()).to(tensor.device)
+
+
 class FecEngine:
     """One per GPU: owns a qfec_ctx (coefficient tables, decode workspace, staging)."""
 
@@ -251,6 +278,33 @@ class FecEngine:
         return _call("qfec_decode_batch_ragged_recovered", self, k, m, G, _ptr(bb), _ptr(blocks),
                      _ptr(blocks_off), _ptr(rows_in), _ptr(rec), _ptr(rec_off), _ptr(rec_rows),
                      _ptr(status), _stream(stream, blocks))
+
+    # pointer-table batches: every block at a device address of its own (include/quic_fec.h)
+    def encode_ptrs(self, k, m, bb, data_ptrs, parity_ptrs, status=None, stream=None):
+        """Group g: its data blocks lie at the addresses data_ptrs[g] (int64 [G][k]), parity
+        block y is written at parity_ptrs[g][y] (int64 [G][m]); see block_ptrs().  bb: int32 [G]
+        device tensor, or an int for every group; status: optional int32 [G].  The library cannot
+        check the addresses.  Returns 0 or -1 (k + m > 256 with m > 1)."""
+        G = _ptr_tables(bb, status, data_ptrs=(data_ptrs, k), parity_ptrs=(parity_ptrs, m))
+        d_bb, bb_all = _ptr_or_all(bb)
+        return _call("qfec_encode_batch_ptrs", self, k, m, G, d_bb, bb_all, _ptr(data_ptrs),
+                     _ptr(parity_ptrs), _ptr(status), _stream(stream, data_ptrs),
+                     reference_rc=True)
+
+    def decode_ptrs_recovered(self, k, m, bb, block_ptrs, rows_in, rec_ptrs, rec_rows,
+                              status=None, stream=None):
+        """Recovered-blocks layout over addresses: the received blocks lie at block_ptrs[g]
+        (int64 [G][k]), recovered block j is written at rec_ptrs[g][j] (int64 [G][min(k,m)]) and
+        its data row to rec_rows [G][min(k,m)] (255 = unused; such rec_ptrs entries are never
+        dereferenced).  rows_in uint8 [G][k]; bb and status as in encode_ptrs."""
+        rmax = min(k, m)
+        G = _ptr_tables(bb, status, block_ptrs=(block_ptrs, k), rec_ptrs=(rec_ptrs, rmax))
+        _check(rows_in, "rows_in", "uint8", (G, k))
+        _check(rec_rows, "rec_rows", "uint8", (G, rmax))
+        d_bb, bb_all = _ptr_or_all(bb)
+        return _call("qfec_decode_batch_ptrs_recovered", self, k, m, G, d_bb, bb_all,
+                     _ptr(block_ptrs), _ptr(rows_in), _ptr(rec_ptrs), _ptr(rec_rows),
+                     _ptr(status), _stream(stream, block_ptrs))
 
     # packet protection next to the codec (NullEncrypter / NullDecrypter, pp_null.hip)
     def null_seal(self, ad, ad_len, pt, pt_len, out, out_len, stream=None):

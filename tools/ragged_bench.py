@@ -40,7 +40,19 @@ extract kernels move.
 The outputs of slot and arrivals are compared byte for byte first; the shuffled ring must revive
 every lost payload.  The time ratio is set against the ratio of the bytes the two routes move.
 
+--ptrs: the pointer-table batches against the packed ragged calls, the
+same groups, data rows 0 .. r-1 lost:
+  packed     qfec_encode_batch_ragged / qfec_decode_batch_ragged_recovered
+  identity   qfec_encode_batch_ptrs / qfec_decode_batch_ptrs_recovered with tables that point into
+             the same packed buffers
+  scattered  the pointer form with every block placed on its own in a seeded random order, at
+             16-byte aligned addresses (the receive set names the surviving data blocks and the
+             parity blocks where they lie)
+  unaligned  the same at addresses of every residue mod 16
+The outputs of all four are compared byte for byte first.
+
   python tools/ragged_bench.py --out profiles/ragged/ragged_bench.json
+  python tools/ragged_bench.py --ptrs --out profiles/ragged/ptrs_bench.json
   python tools/ragged_bench.py --pp --out profiles/ragged/ragged_pp_bench.json
   python tools/ragged_bench.py --framed --out profiles/ragged/framed_bench.json
   python tools/ragged_bench.py --arrivals --out profiles/ragged/arrivals_bench.json
@@ -78,8 +90,9 @@ def main():
     ap.add_argument("--reps", type=int, default=21)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=2025)
-    ap.add_argument("--codes", default="32,4,2 10,1,1",
-                    help="space-separated k,m,losses triples (default: the two measured codes)")
+    ap.add_argument("--codes", default=None,
+                    help="space-separated k,m,losses triples (default: 32,4,2 10,1,1; with "
+                         "--ptrs also 10,10,5)")
     ap.add_argument("--pp", action="store_true",
                     help="the protected paths: ragged encode + seal and open -> decode against "
                          "one uniform protected call per distinct bb")
@@ -87,6 +100,8 @@ def main():
                     help="the framed protected paths against the unframed ragged ones")
     ap.add_argument("--arrivals", action="store_true",
                     help="the arrival-order receiver against the slot-order framed receiver")
+    ap.add_argument("--ptrs", action="store_true",
+                    help="the pointer-table batches against the packed ragged calls")
     ap.add_argument("--variants", default=None,
                     help="--arrivals: comma-separated subset of slot,arrivals,two_read,shuffled "
                          "to time (for a kernel trace of one route)")
@@ -94,6 +109,8 @@ def main():
     args = ap.parse_args()
     if args.reps < 20:
         ap.error("--reps must be at least 20")
+    if args.codes is None:
+        args.codes = "32,4,2 10,1,1" + (" 10,10,5" if args.ptrs else "")
 
     import torch
     from bench import DeviceEvents
@@ -681,11 +698,161 @@ def main():
         results.append(line)
         print(json.dumps(line), flush=True)
 
+    def run_ptrs(k, m, r, bb, label):
+        """--ptrs: the packed ragged calls against the pointer form over identity tables and over
+        individually placed blocks, data rows 0 .. r-1 of every group lost."""
+        G, rmax = len(bb), min(k, m)
+        bb64 = bb.astype(np.int64)
+        d_off, p_off, r_off, tot = fec.ragged_layout(k, m, bb)
+        data = torch.empty(tot[0], dtype=torch.uint8, device="cuda")
+        fec.synth_fill(data, seed=args.seed)
+        bb_d = torch.from_numpy(bb).cuda()
+        d_off_d, p_off_d, r_off_d = (torch.from_numpy(o).cuda() for o in (d_off, p_off, r_off))
+        rows_np = np.tile(np.arange(k, dtype=np.uint8), (G, 1))
+        rows_np[:, :r] = k + np.arange(r, dtype=np.uint8)
+        rows = torch.from_numpy(rows_np).cuda()
+
+        def step(n):
+            return bb64[:, None] * np.arange(n, dtype=np.int64)[None, :]
+
+        def outputs():
+            return dict(par=torch.zeros(tot[1], dtype=torch.uint8, device="cuda"),
+                        rec=torch.zeros(tot[2], dtype=torch.uint8, device="cuda"),
+                        rr=torch.zeros((G, rmax), dtype=torch.uint8, device="cuda"),
+                        est=torch.zeros(G, dtype=torch.int32, device="cuda"),
+                        st=torch.zeros(G, dtype=torch.int32, device="cuda"))
+
+        def copy_blocks(src_ptrs, dst_ptrs, sizes):
+            # one block per "group": the pointer form's k = 1 encode is a block copy
+            n = src_ptrs.numel()
+            assert eng.encode_ptrs(1, 1, sizes, src_ptrs.view(n, 1), dst_ptrs.view(n, 1)) == 0
+
+        def placed(n_per_group, seed, residues):
+            """Offsets [G][n] of G * n blocks in a seeded random order, every block in a slot of
+            its own (its size rounded up to 16, plus 16 when it starts off a 16-byte boundary)."""
+            rng = np.random.default_rng(seed)
+            sizes = np.repeat(bb64, n_per_group)
+            order = rng.permutation(sizes.size)
+            res = (np.arange(sizes.size) % 16) if residues else np.zeros(sizes.size, np.int64)
+            slot = ((sizes[order] + 15) & ~15) + (16 if residues else 0)
+            start = np.concatenate([[0], np.cumsum(slot)[:-1]]) + res
+            off = np.empty(sizes.size, np.int64)
+            off[order] = start
+            return off.reshape(G, n_per_group), int(slot.sum())
+
+        # packed: the baseline and the buffers the identity tables point into
+        P = outputs()
+        assert eng.encode_ragged(k, m, bb_d, data, d_off_d, P["par"], p_off_d, status=P["est"]) == 0
+        kern = {"packed_encode": fec.last_kernels()}
+        blocks = data.clone()
+        copy_blocks(fec.block_ptrs(P["par"], p_off[:, None] + step(r)),
+                    fec.block_ptrs(blocks, d_off[:, None] + step(r)),
+                    torch.from_numpy(np.repeat(bb, r)).cuda())
+        eng.decode_ragged_recovered(k, m, bb_d, blocks, d_off_d, rows, P["rec"], r_off_d, P["rr"],
+                                    status=P["st"])
+        kern["packed_decode"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        assert int(P["est"].abs().max()) == 0 and int(P["st"].abs().max()) == 0
+
+        routes = {"packed": dict(out=P)}
+        I = outputs()
+        routes["identity"] = dict(
+            out=I, data=fec.block_ptrs(data, d_off[:, None] + step(k)),
+            recv=fec.block_ptrs(blocks, d_off[:, None] + step(k)),
+            par=fec.block_ptrs(I["par"], p_off[:, None] + step(m)),
+            rec=fec.block_ptrs(I["rec"], r_off[:, None] + step(rmax)))
+        sizes_k = torch.from_numpy(np.repeat(bb, k)).cuda()
+        for name, residues in (("scattered", False), ("unaligned", True)):
+            o = outputs()
+            offs = {x: placed(n, args.seed + i, residues)
+                    for i, (x, n) in enumerate((("data", k), ("par", m), ("rec", rmax)))}
+            arena = {x: torch.zeros(offs[x][1] + 32, dtype=torch.uint8, device="cuda") for x in offs}
+            tab = {x: fec.block_ptrs(arena[x], offs[x][0]) for x in offs}
+            copy_blocks(routes["identity"]["data"], tab["data"], sizes_k)
+            recv = tab["data"].clone()
+            recv[:, :r] = tab["par"][:, :r]          # the received parity blocks, where they lie
+            routes[name] = dict(out=o, data=tab["data"], recv=recv, par=tab["par"], rec=tab["rec"],
+                                arena=arena, residues=sorted(set((offs["data"][0] % 16).ravel()
+                                                                 .tolist())))
+
+        def encode(name):
+            R, o = routes[name], routes[name]["out"]
+            if name == "packed":
+                eng.encode_ragged(k, m, bb_d, data, d_off_d, o["par"], p_off_d, status=o["est"])
+            else:
+                eng.encode_ptrs(k, m, bb_d, R["data"], R["par"], status=o["est"])
+
+        def decode(name):
+            R, o = routes[name], routes[name]["out"]
+            if name == "packed":
+                eng.decode_ragged_recovered(k, m, bb_d, blocks, d_off_d, rows, o["rec"], r_off_d,
+                                            o["rr"], status=o["st"])
+            else:
+                eng.decode_ptrs_recovered(k, m, bb_d, R["recv"], rows, R["rec"], o["rr"],
+                                          status=o["st"])
+
+        # the same bytes from every route, at the timed size
+        names = list(routes)
+        for name in names[1:]:
+            R, o = routes[name], routes[name]["out"]
+            encode(name)
+            kern[name + "_encode"] = fec.last_kernels()
+            decode(name)
+            kern[name + "_decode"] = fec.last_kernels()
+            if "arena" in R:                          # gather the placed outputs into the packed form
+                copy_blocks(R["par"], fec.block_ptrs(o["par"], p_off[:, None] + step(m)),
+                            torch.from_numpy(np.repeat(bb, m)).cuda())
+                copy_blocks(R["rec"][:, :r].contiguous(),
+                            fec.block_ptrs(o["rec"], r_off[:, None] + step(r)),
+                            torch.from_numpy(np.repeat(bb, r)).cuda())
+            torch.cuda.synchronize()
+            assert torch.equal(o["par"], P["par"]), f"{name}: parity differs from the packed call's"
+            assert torch.equal(o["rec"], P["rec"]), f"{name}: recovered blocks differ"
+            assert torch.equal(o["rr"], P["rr"]) and torch.equal(o["st"], P["st"]) and \
+                torch.equal(o["est"], P["est"]), f"{name}: rows or statuses differ"
+
+        phases = [(ph, name) for ph in ("encode", "decode") for name in names]
+        ev = DeviceEvents(2 * len(phases))
+        t = {x: [] for x in phases}
+        for rep_i in range(args.warmup + args.reps):
+            for ph, fn in (("encode", encode), ("decode", decode)):
+                rot = rep_i % len(names)               # the routes alternate inside a repetition
+                for name in names[rot:] + names[:rot]:
+                    timed(ev, phases.index((ph, name)), lambda: fn(name))
+            torch.cuda.synchronize()
+            if rep_i >= args.warmup:
+                for i, x in enumerate(phases):
+                    t[x].append(ev.elapsed_ms(2 * i, 2 * i + 1))
+        ev.close()
+        total = int(bb64.sum())
+        nbytes = {"encode": (k + m) * total, "decode": (k + r) * total}
+        line = dict(config=label, mode="ptrs", k=k, m=m, losses=r, groups=G,
+                    distinct_bb=len(set(bb.tolist())), reps=args.reps, kernels=kern,
+                    bytes_moved=nbytes, table_bytes={"encode": 8 * (k + m) * G,
+                                                     "decode": 8 * (k + rmax) * G},
+                    residues={n: routes[n]["residues"] for n in ("scattered", "unaligned")})
+        for ph, name in phases:
+            v = t[(ph, name)]
+            med = statistics.median(v)
+            line[f"{name}_{ph}"] = dict(kernel_ms_median=round(med, 4), kernel_ms_min=round(min(v), 4),
+                                        kernel_ms_max=round(max(v), 4),
+                                        GBps=round(nbytes[ph] / (med * 1e-3) / 1e9, 1))
+        for ph in ("encode", "decode"):
+            base = line[f"packed_{ph}"]["kernel_ms_median"]
+            for name in names[1:]:
+                line[f"{name}_{ph}_over_packed"] = round(
+                    line[f"{name}_{ph}"]["kernel_ms_median"] / base, 3)
+        results.append(line)
+        print(json.dumps(line), flush=True)
+
     G = args.groups
     mixed = draw_sizes(G, args.seed)
     flat = np.full(G, 1352, np.int32)
     run = run_pp if args.pp else run_config
     for k, m, r in (tuple(int(v) for v in c.split(",")) for c in args.codes.split()):
+        if args.ptrs:
+            run_ptrs(k, m, r, mixed, f"mixed ({k},{m})")
+            continue
         if args.framed or args.arrivals:
             (run_framed if args.framed else run_arrivals)(k, m, r, mixed, f"mixed ({k},{m})")
             continue
