@@ -20,11 +20,11 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden \
 DCOLK := e63 e83 d62 d82
 # preset syndrome-decode instantiations, one object per code (gf_psyn.h)
 PSYNK := 1010 1015 1020 1515 55
-SRCS := $(CSRC)/fec_kernels.hip $(CSRC)/decode_prep.hip $(CSRC)/xor_dma.hip $(CSRC)/gf_stream.hip $(CSRC)/gf_bsyn.hip $(CSRC)/gf_psyn.hip $(PSYNK:%=$(CSRC)/gf_psyn_%.hip) $(CSRC)/gf_dcol.hip $(DCOLK:%=$(CSRC)/gf_dcol_%.hip) $(CSRC)/gf_ragged.hip $(CSRC)/gf_ptrs.hip $(CSRC)/pp_null.hip $(CSRC)/fec_api.cpp $(CSRC)/fec_host.cpp $(CSRC)/fec_host_plan.cpp $(CSRC)/fec_group.cpp $(CSRC)/fec_wire.cpp
+SRCS := $(CSRC)/fec_kernels.hip $(CSRC)/decode_prep.hip $(CSRC)/xor_dma.hip $(CSRC)/gf_stream.hip $(CSRC)/gf_bsyn.hip $(CSRC)/gf_psyn.hip $(PSYNK:%=$(CSRC)/gf_psyn_%.hip) $(CSRC)/gf_dcol.hip $(DCOLK:%=$(CSRC)/gf_dcol_%.hip) $(CSRC)/gf_ragged.hip $(CSRC)/gf_ptrs.hip $(CSRC)/gf_mixed.hip $(CSRC)/pp_null.hip $(CSRC)/fec_api.cpp $(CSRC)/fec_host.cpp $(CSRC)/fec_host_plan.cpp $(CSRC)/fec_group.cpp $(CSRC)/fec_wire.cpp
 # the headers every object depends on; the rest (include/*.h, pp_null.h, ...) are tracked per
 # object by -MMD below, so a public-header edit rebuilds only the host files that include it
 HDRS := $(CSRC)/fec_kernels.h $(CSRC)/gf256.h $(CSRC)/gf_bitslice.h
-OBJS := $(ROOT)build/fec_kernels.o $(ROOT)build/decode_prep.o $(ROOT)build/xor_dma.o $(ROOT)build/gf_stream.o $(ROOT)build/gf_bsyn.o $(ROOT)build/gf_psyn.o $(PSYNK:%=$(ROOT)build/gf_psyn_%.o) $(ROOT)build/gf_dcol.o $(DCOLK:%=$(ROOT)build/gf_dcol_%.o) $(ROOT)build/gf_ragged.o $(ROOT)build/gf_ptrs.o $(ROOT)build/pp_null.o $(ROOT)build/fec_api.o $(ROOT)build/fec_host.o $(ROOT)build/fec_host_plan.o $(ROOT)build/fec_group.o $(ROOT)build/fec_wire.o
+OBJS := $(ROOT)build/fec_kernels.o $(ROOT)build/decode_prep.o $(ROOT)build/xor_dma.o $(ROOT)build/gf_stream.o $(ROOT)build/gf_bsyn.o $(ROOT)build/gf_psyn.o $(PSYNK:%=$(ROOT)build/gf_psyn_%.o) $(ROOT)build/gf_dcol.o $(DCOLK:%=$(ROOT)build/gf_dcol_%.o) $(ROOT)build/gf_ragged.o $(ROOT)build/gf_ptrs.o $(ROOT)build/gf_mixed.o $(ROOT)build/pp_null.o $(ROOT)build/fec_api.o $(ROOT)build/fec_host.o $(ROOT)build/fec_host_plan.o $(ROOT)build/fec_group.o $(ROOT)build/fec_wire.o
 
 # Build guard (tools/check_stubs.py): every kernel stub a host pass registers has device code
 # in the same object.  Run after each HIP compile (the object is deleted on a mismatch) and on
@@ -78,7 +78,7 @@ $(ROOT)build/fec_kernels.o: $(CSRC)/fec_kernels.hip $(CSRC)/gf_colword.h $(HDRS)
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
 
 # the prep kernels of every m > 1 decode
-$(ROOT)build/decode_prep.o: $(CSRC)/decode_prep.hip $(HDRS)
+$(ROOT)build/decode_prep.o: $(CSRC)/decode_prep.hip $(CSRC)/gf_mixed.h $(HDRS)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
@@ -145,6 +145,12 @@ $(ROOT)build/gf_ragged.o: $(CSRC)/gf_ragged.hip $(CSRC)/gf_ragged_unit.h $(CSRC)
 
 # the same kernels over pointer tables (every block at an address of its own)
 $(ROOT)build/gf_ptrs.o: $(CSRC)/gf_ptrs.hip $(CSRC)/gf_ptrs.h $(CSRC)/gf_ragged_unit.h $(CSRC)/gf_colword.h $(HDRS)
+	@mkdir -p $(ROOT)build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }
+
+# the same unit over mixed-code batches (a (k, m) per group through a code set)
+$(ROOT)build/gf_mixed.o: $(CSRC)/gf_mixed.hip $(CSRC)/gf_mixed.h $(CSRC)/gf_ragged_unit.h $(CSRC)/gf_colword.h $(HDRS)
 	@mkdir -p $(ROOT)build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 	@$(STUBCHECK) $@ || { rm -f $@; exit 1; }

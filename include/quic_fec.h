@@ -228,6 +228,109 @@ QFEC_API int qfec_decode_batch_ragged_recovered_host(qfec_ctx *ctx, int k, int m
                                                      unsigned char *h_rec_rows, int *h_status);
 
 /* ---------------------------------------------------------------------------------
+ * Mixed-code batches: one launch over groups that each carry their own (k, m) as well as
+ * their own block_bytes.  The reference gives every FEC group a configuration of its own
+ * (quic_fec_group.cc:84-96) and an adaptive sender changes it with the measured loss
+ * (quic_connection.cc:822-966), so one connection produces groups of several codes back to
+ * back and a server holds all presets at once.
+ *
+ * Code set: qfec_codeset_create builds, once, what the kernels need per code (encode table,
+ * encode matrix, chunk counts) for up to 32 codes (the wire has five configuration bits).
+ * Each (k, m) is whatever qfec_encode_batch_ragged accepts at call level, k <= 1, m == 1 and
+ * k + m > 256 included; duplicates are allowed; anything else (ncodes outside 1..32, a NULL
+ * array, k < 1, k > 255, m < 1) is -2.  A set belongs to its context and is immutable, so a
+ * captured call stays valid; destroy it before the context.  qfec_codeset_dims gives
+ * kmax = max k, mmax = max m and rmax = max over codes of min(k, m).
+ *
+ * Layout: code [G] is a u8 device array, the group's index into the set.  bb [G] and the
+ * packed layout are those of the ragged calls with the group's own counts: group g's k_g
+ * blocks are [k_g][bb[g]] at base + off[g]; its outputs are [m_g][bb[g]] (parity) or
+ * [min(k_g, m_g)][bb[g]] (recovered blocks).  Offsets are multiples of 16, the base pointers
+ * are 16-byte aligned, gaps are never written.  rows is [G][kmax]: only the first k_g tags of
+ * a row are read.  rec_rows is [G][rmax]: every entry at or past the group's erasure count
+ * is 255, up to the set's rmax, so a caller scans it uniformly.  status is [G], may be NULL.
+ *
+ * Per-group semantics are exactly those of qfec_encode_batch_ragged /
+ * qfec_decode_batch_ragged_recovered with that group's (k, m) and bb: k <= 1 copies; m == 1
+ * is XOR with any bb >= 1; for m > 1 with bb[g] % 8 != 0 or k + m > 256 the encode gives
+ * status -1 with the XOR parity in the first parity block and nothing else written, and the
+ * decode follows cauchy_256.cpp:1287-1294 (status 0 without a recovery block, else -1); a
+ * malformed receive set has status -3 and is left as it was; a group with bb[g] < 1 is
+ * skipped.  A group whose code[g] >= ncodes has status -2 and none of its blocks, rows or
+ * outputs is read or written (its rec_rows entries are 255).  Because rejection is per
+ * group, the call itself returns 0 in all these cases.
+ *
+ * Call-level -2, before anything is enqueued: a NULL context, set or array (status excepted),
+ * a set of another context, groups < 0, a base pointer that is not 16-byte aligned, and more
+ * than 2^31 - 1 (group, output chunk) units (groups x the largest chunk count of a code, in
+ * chunks of at most 4 outputs).
+ *
+ * Enqueue only: the device calls never read code, bb or the offsets back; the kernels read
+ * the arrays when they run.  A captured call may therefore be replayed after code, bb,
+ * offsets, rows and data were rewritten in place.  The decode uses the decode workspace in
+ * the same bracket as every decode; qfec_codeset_reserve(cs, groups) sizes both workspaces,
+ * eager and graph, for `groups` groups of the set, so a capture then allocates nothing.
+ *
+ * Bucket or mix: bucket by (k, m) whenever a bucket fills the device
+ * (thousands of groups per code): the per-code calls are then faster in kernel time.  Mix when
+ * the traffic spreads a flush of about a thousand groups or fewer over several codes.
+ * ------------------------------------------------------------------------------- */
+typedef struct qfec_codeset qfec_codeset;
+QFEC_API int qfec_codeset_create(qfec_ctx *ctx, int ncodes, const int *k, const int *m,
+                                 qfec_codeset **out);
+QFEC_API void qfec_codeset_destroy(qfec_codeset *cs);
+/* rmax = max over codes of min(k, m); any of the three may be NULL */
+QFEC_API int qfec_codeset_dims(const qfec_codeset *cs, int *kmax, int *mmax, int *rmax);
+QFEC_API int qfec_codeset_reserve(qfec_codeset *cs, long long groups);
+
+/* Host helper, no GPU: qfec_ragged_layout with the block counts of code[g]: k_g, m_g and
+ * min(k_g, m_g) blocks of bb[g] bytes per group, every group rounded up to 16 bytes.  Any of
+ * the offset arrays and totals may be NULL.  -2 on code[g] >= ncodes, bb[g] < 1, ncodes
+ * outside 1..32, a bad k / m / groups or overflow. */
+QFEC_API int qfec_mixed_layout(int ncodes, const int *k, const int *m, long long groups,
+                               const unsigned char *code, const int *bb, long long *data_off,
+                               long long *par_off, long long *rec_off, long long totals[3]);
+
+/* d_parity + d_par_off[g] receives [m_g][bb[g]].  d_status [G] may be NULL. */
+QFEC_API int qfec_encode_batch_mixed(qfec_ctx *ctx, const qfec_codeset *cs, long long groups,
+                                     const unsigned char *d_code, const int *d_bb,
+                                     const unsigned char *d_data, const long long *d_data_off,
+                                     unsigned char *d_parity, const long long *d_par_off,
+                                     int *d_status, void *stream);
+
+/* As qfec_decode_batch_ragged_recovered: d_blocks and d_rows_in [G][kmax] are left untouched;
+ * recovered block j of group g goes to d_rec + d_rec_off[g] + j * bb[g] and its data row to
+ * d_rec_rows[g * rmax + j] (ascending; 255 past the count). */
+QFEC_API int qfec_decode_batch_mixed_recovered(qfec_ctx *ctx, const qfec_codeset *cs,
+                                               long long groups, const unsigned char *d_code,
+                                               const int *d_bb, const unsigned char *d_blocks,
+                                               const long long *d_blocks_off,
+                                               const unsigned char *d_rows_in,
+                                               unsigned char *d_rec, const long long *d_rec_off,
+                                               unsigned char *d_rec_rows, int *d_status,
+                                               void *stream);
+
+/* Host-pointer variants: the same arguments in host memory; synchronous; chunked and pipelined
+ * like qfec_*_batch_ragged*_host, with the block count of each group's own code.  Chunks are cut
+ * on group boundaries by bytes ("host_chunk_mb").  The same offset checks apply: ascending,
+ * non-overlapping, multiples of 16 (-2 otherwise, and for bb[g] < 1); qfec_mixed_layout
+ * produces such offsets.  A group whose code[g] >= ncodes stages nothing and has status -2.
+ * Bytes of the output buffer the call does not write keep the caller's values. */
+QFEC_API int qfec_encode_batch_mixed_host(qfec_ctx *ctx, const qfec_codeset *cs, long long groups,
+                                          const unsigned char *h_code, const int *h_bb,
+                                          const unsigned char *h_data,
+                                          const long long *h_data_off, unsigned char *h_parity,
+                                          const long long *h_par_off, int *h_status);
+QFEC_API int qfec_decode_batch_mixed_recovered_host(qfec_ctx *ctx, const qfec_codeset *cs,
+                                                    long long groups, const unsigned char *h_code,
+                                                    const int *h_bb, const unsigned char *h_blocks,
+                                                    const long long *h_blocks_off,
+                                                    const unsigned char *h_rows,
+                                                    unsigned char *h_rec,
+                                                    const long long *h_rec_off,
+                                                    unsigned char *h_rec_rows, int *h_status);
+
+/* ---------------------------------------------------------------------------------
  * Pointer-table batches: encode and decode blocks where they lie.  The batched form of the
  * drop-in ABI's one pointer per block (cauchy_256_encode's data_ptrs[], cauchy_256_decode's
  * Block{data,row}[]): the k blocks of a group may lie in k unrelated device buffers (mbufs of a
@@ -705,7 +808,10 @@ QFEC_API const char *qfec_last_error(void);
  * calls name "gf_ragged_kernel<encode>", "gf_ragged_kernel<decode>", "xor_ragged_kernel" and
  * "copy_ragged_kernel"; the pointer-table calls name "gf_ptrs_kernel<encode>",
  * "gf_ptrs_kernel<decode>", "xor_ptrs_kernel" and "copy_ptrs_kernel" (and, without d_bb and with
- * bb_all % 8 != 0, "ptrs_decode_status_kernel"); the ragged protected calls add "null_seal_kernel<ragged>" and
+ * bb_all % 8 != 0, "ptrs_decode_status_kernel"); the mixed-code calls name
+ * "xor_copy_mixed_kernel<encode>" / "<decode>", "gf_mixed_kernel<encode>" / "<decode>" and
+ * "decode_prep_mixed_kernel" ("decode_prep_mixed_kernel<cached>" when the set's encode matrices
+ * do not fit in LDS); the ragged protected calls add "null_seal_kernel<ragged>" and
  * "open_group_kernel<ragged> + open_assemble_kernel<ragged>" (the uniform grouped calls name
  * "null_seal_kernel<groups>" and "open_group_kernel + open_assemble_kernel"); the framed calls
  * name "frame_blocks_kernel", "null_seal_kernel<framed>", "open_group_kernel<framed> +

@@ -102,6 +102,14 @@ QFEC_API void qfec_batch_free(qfec_batch *b);
  * writes, small packets), where the uniform buckets turn into many launches of a few groups
  * each.  Returns -2 while groups are queued (flush first). */
 QFEC_API int qfec_batch_set_ragged(qfec_batch *b, int on);
+/* Mixed buckets (off by default; they take precedence over ragged ones).  on != 0: one bucket
+ * per direction, every queued group keeps its own (k, m) and block_bytes, max_groups counts
+ * across codes, and a flush packs the bucket (qfec_mixed_layout) and runs ONE mixed-code host
+ * call (qfec_*_batch_mixed*_host, include/quic_fec.h).  The queue keeps one code set and
+ * rebuilds it when a group of a new code arrives.  For adaptive traffic, where the per-code
+ * buckets would each wait for max_groups or the timeout and leave as small launches.  Returns
+ * -2 while groups are queued (flush first). */
+QFEC_API int qfec_batch_set_mixed(qfec_batch *b, int on);
 QFEC_API int qfec_batch_add_encode(qfec_batch *b, qfec_group *g);   /* group must stay alive */
 QFEC_API int qfec_batch_add_decode(qfec_batch *b, qfec_group *g);
 QFEC_API int qfec_batch_poll(qfec_batch *b);    /* flushes if the timeout expired; >= 0 = groups done */

@@ -79,6 +79,40 @@ SIGNATURES = {
                                                                ctypes.c_void_p, ctypes.c_void_p,
                                                                ctypes.c_void_p, ctypes.c_void_p,
                                                                ctypes.c_void_p, ctypes.c_void_p]),
+    "qfec_codeset_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "qfec_codeset_destroy": (None, [ctypes.c_void_p]),
+    "qfec_codeset_dims": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(ctypes.c_int)]),
+    "qfec_codeset_reserve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong]),
+    "qfec_mixed_layout": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
+    "qfec_encode_batch_mixed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_longlong, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
+    "qfec_decode_batch_mixed_recovered": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_longlong, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p]),
+    "qfec_encode_batch_mixed_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_longlong, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p]),
+    "qfec_decode_batch_mixed_recovered_host": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_longlong, ctypes.c_void_p,
+                                                              ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_void_p, ctypes.c_void_p,
+                                                              ctypes.c_void_p, ctypes.c_void_p]),
     "qfec_encode_batch_ptrs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

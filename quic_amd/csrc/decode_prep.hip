@@ -28,6 +28,7 @@
 #include "fec_kernels.h"
 #include "gf256.h"
 #include "gf_bitslice.h"
+#include "gf_mixed.h"
 
 namespace qfec {
 
@@ -80,24 +81,41 @@ struct PrepOut {
     int32_t* nout;
     int32_t* status;
     int k, rmax;
+    // Strides of the per-group arrays, in entries per group: rows at g * kstride(), rec_rows
+    // and slots at g * rstride(), the prep's table at coef + table_at().  A call of one code
+    // strides by its own k and rmax; a mixed batch (PrepOutMixed) carries the set's as members.
+    __device__ __forceinline__ int kstride() const { return k; }
+    __device__ __forceinline__ int rstride() const { return rmax; }
+    __device__ __forceinline__ long long table_at(long long g, int nchunk, int k_, int rcp) const {
+        return g * (long long)nchunk * k_ * rcp;
+    }
+};
+struct PrepOutMixed : PrepOut {
+    int ks, rs;                 // the set's kmax and rmax
+    long long tab_gstride;      // the set's table bytes per group
+    __device__ __forceinline__ int kstride() const { return ks; }
+    __device__ __forceinline__ int rstride() const { return rs; }
+    __device__ __forceinline__ long long table_at(long long g, int, int, int) const {
+        return g * tab_gstride;
+    }
 };
 
 // The epilogue of group g, run by the nl lanes that share it (lane = 0 .. nl - 1; nl = 1:
 // one lane writes everything).  rg: the group's tags as read; recpos(j) / era(j): the slot
 // of recovery block j and the erased row it receives, j < n.  n = 0 leaves the group
 // unchanged with status st.
-template <class RecPos, class Era>
-__device__ __forceinline__ void finish_group(const PrepOut& o, long long g, int lane, int nl,
+template <class Out, class RecPos, class Era>
+__device__ __forceinline__ void finish_group(const Out& o, long long g, int lane, int nl,
                                              const uint8_t* rg, int n, int st, RecPos recpos,
                                              Era era) {
-    const uint8_t* rgg = o.rows_in + g * o.k;
-    uint8_t* ro = o.rows_out ? o.rows_out + g * o.k : nullptr;
-    uint8_t* rec = o.rec_rows ? o.rec_rows + g * o.rmax : nullptr;
+    const uint8_t* rgg = o.rows_in + g * o.kstride();
+    uint8_t* ro = o.rows_out ? o.rows_out + g * o.kstride() : nullptr;
+    uint8_t* rec = o.rec_rows ? o.rec_rows + g * o.rstride() : nullptr;
     if (ro && ro != rgg)
         for (int i = lane; i < o.k; i += nl) ro[i] = rg[i];
     if (nl > 1) wave_sync();
     for (int j = lane; j < n; j += nl) {
-        o.slots[g * o.rmax + j] = (uint8_t)recpos(j);
+        o.slots[g * o.rstride() + j] = (uint8_t)recpos(j);
         if (ro) ro[recpos(j)] = (uint8_t)era(j);        // :791
     }
     if (rec)
@@ -214,8 +232,9 @@ __device__ __forceinline__ void write_syn_table(uint8_t* tb, int lane, const Pre
     }
 }
 
+template <class Out>
 __device__ __forceinline__ void prep_group(long long g, int lane, const GfLds& gf,
-                                           const PrepScratch& sc, const PrepOut& o,
+                                           const PrepScratch& sc, const Out& o,
                                            const uint8_t* cenc, uint8_t* __restrict__ coef, int m,
                                            int bb, int rc, int nchunk, bool syndrome) {
     uint8_t* rowl = sc.rowl;
@@ -230,7 +249,7 @@ __device__ __forceinline__ void prep_group(long long g, int lane, const GfLds& g
         present[i] = 0;
         recidx[i] = 255;
     }
-    const uint8_t* rg = o.rows_in + g * k;
+    const uint8_t* rg = o.rows_in + g * o.kstride();
     for (int i = lane; i < k; i += 64) rowl[i] = rg[i];
     wave_sync();
     // present[x] != 0: data row x received; syndrome mode keeps one of its slots + 1
@@ -282,7 +301,7 @@ __device__ __forceinline__ void prep_group(long long g, int lane, const GfLds& g
             n = 0;
         }
     }
-    uint8_t* tb = coef + g * (long long)nchunk * k * rcp;   // the group's table
+    uint8_t* tb = coef + o.table_at(g, nchunk, k, rcp);   // the group's table
     if (syndrome) {
         if (n) write_syn_table(tb, lane, sc, k, n);
         else write_syn_unchanged(tb, lane, k);
@@ -330,6 +349,60 @@ __global__ __launch_bounds__(256) void decode_prep_kernel(
     for (long long g = (long long)blockIdx.x * nwv + w; g < groups;
          g += (long long)gridDim.x * nwv)
         prep_group(g, lane, gf, sc, o, lcenc, coef, m, bb, rc, nchunk, syndrome != 0);
+}
+
+// The same prep over a mixed batch (gf_mixed.h): group g's code is codes[code[g]], its k, m and
+// encode matrix are read per group, its rows lie at g * kmax, its rec_rows / slots at g * rmax
+// (the set's largest) and its table at coef + g * coef_gstride.  Groups whose code has m == 1
+// or k <= 1, or names no code of the set, are xor_copy_mixed_kernel's.  The group's own bb
+// enters classify, so the status -1 of bb % 8 != 0 needs no fix-up pass.
+// LDS: exp / log, the offsets of the codes' matrices, then (stage_cenc) every decodable code's
+// m x k matrix, then the per-wave scratch; without stage_cenc (the matrices do not fit beside
+// one wave's scratch) cenc is read from memory through the cache.
+__global__ __launch_bounds__(256) void decode_prep_mixed_kernel(
+    const uint8_t* __restrict__ rows_in, int32_t* __restrict__ status,
+    const MixedCode* __restrict__ codes, int ncodes, const uint8_t* __restrict__ code,
+    const int32_t* __restrict__ bbs, uint8_t* __restrict__ coef, uint8_t* __restrict__ slots,
+    int32_t* __restrict__ nout, uint8_t* __restrict__ rec_rows, long long groups, int kmax,
+    int rmax, int rc, long long coef_gstride, int scratch_bytes, int stage_cenc, int cenc_bytes) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint8_t* gexp = smem;                       // 512
+    uint8_t* glog = gexp + 512;                 // 256
+    int32_t* loff = (int32_t*)(glog + 256);     // kMixedMaxCodes offsets into lcenc
+    uint8_t* lcenc = (uint8_t*)(loff + kMixedMaxCodes);
+    for (int i = threadIdx.x; i < 512; i += blockDim.x) gexp[i] = c_gf.exp[i];
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) glog[i] = c_gf.log[i];
+    if (stage_cenc) {
+        int at = 0;   // the same running offset in every thread
+        for (int c = 0; c < ncodes; ++c) {
+            const int mk = codes[c].cenc ? codes[c].m * codes[c].k : 0;
+            if (threadIdx.x == 0) loff[c] = at;
+            for (int i = threadIdx.x; i < mk; i += blockDim.x) lcenc[at + i] = codes[c].cenc[i];
+            at += (mk + 15) & ~15;
+        }
+    }
+    __syncthreads();
+    const int nwv = blockDim.x >> 6;
+    const int w = wave_id(), lane = threadIdx.x & 63;
+    uint8_t* base = lcenc + (stage_cenc ? cenc_bytes : 0) + (size_t)w * scratch_bytes;
+    const PrepScratch sc{base, base + 256, base + 512, base + 768, base + 1024, base + 1280};
+    const GfLds gf{gexp, glog};
+    for (long long g = (long long)blockIdx.x * nwv + w; g < groups;
+         g += (long long)gridDim.x * nwv) {
+        const int ci = __builtin_amdgcn_readfirstlane((int)code[g]);
+        if (ci >= ncodes) continue;
+        const int k = __builtin_amdgcn_readfirstlane(codes[ci].k);
+        const int m = __builtin_amdgcn_readfirstlane(codes[ci].m);
+        if (k <= 1 || m <= 1) continue;
+        const int bb = __builtin_amdgcn_readfirstlane(bbs[g]);
+        const int rg = min(k, m);
+        // a code with k + m > 256 has no matrix: classify answers before one is read
+        const uint8_t* cenc = stage_cenc ? lcenc + loff[ci] : codes[ci].cenc;
+        const PrepOutMixed o{{rows_in, nullptr, rec_rows, slots, nout, status, k, rg}, kmax, rmax,
+                             coef_gstride};
+        prep_group(g, lane, gf, sc, o, cenc, coef, m, bb, rc, 0, false);
+        for (int j = rg + lane; j < rmax; j += 64) rec_rows[g * rmax + j] = 255;
+    }
 }
 
 // ------------------------------------------------------------- 16 lanes per group
@@ -1005,6 +1078,29 @@ hipError_t launch_decode_prep(const PrepIO& io, const uint8_t* cenc, int k, int 
     qlaunch((decode_prep_kernel), dim3(nb), dim3(nwv * 64), lds, st, io.rows_in, io.rows_out,
             io.status, cenc, w.coef, w.slots, w.nout, io.rec_rows, groups, k, m, bb, rc, rmax,
             nchunk, scratch, syndrome ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode_prep_mixed(const MixedSet& s, MixedView v, const PrepIO& io,
+                                    long long groups, hipStream_t st, const Tune& t) {
+    if (groups <= 0) return hipSuccess;
+    const DecodeWork& w = io.w;
+    const int scratch = (int)((1280 + (size_t)s.solve_rmax * 2 * s.solve_rmax + 15) & ~(size_t)15);
+    const size_t head = 768 + kMixedMaxCodes * sizeof(int32_t);
+    // the codes' matrices beside at least one wave's scratch, or read through the cache
+    const bool stage = head + (size_t)s.cenc_bytes + scratch <= 64 * 1024;
+    const size_t fixed = head + (stage ? (size_t)s.cenc_bytes : 0);
+    int nwv = 4;
+    while (nwv > 1 && fixed + (size_t)nwv * scratch > 64 * 1024) nwv >>= 1;
+    const size_t lds = fixed + (size_t)nwv * scratch;
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    const unsigned nb = persistent_grid(groups, nwv, (long long)t.cus * 16, 0, 0);
+    if (!nb) return hipErrorInvalidValue;
+    note_kernel(stage ? "decode_prep_mixed_kernel" : "decode_prep_mixed_kernel<cached>");
+    note_grid("decode_prep_mixed_kernel", nb);
+    qlaunch((decode_prep_mixed_kernel), dim3(nb), dim3(nwv * 64), lds, st, io.rows_in, io.status,
+            s.codes, s.ncodes, v.code, v.bb, w.coef, w.slots, w.nout, io.rec_rows, groups, s.kmax,
+            s.rmax, s.dec_rc, s.coef_gstride, scratch, stage ? 1 : 0, s.cenc_bytes);
     return hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 
 #include "fec_internal.h"
 #include "gf256.h"
+#include "gf_mixed.h"
 #include "gf_ptrs.h"
 #include "pp_null.h"
 
@@ -868,6 +869,187 @@ int qfec_decode_batch_ragged_recovered(qfec_ctx* c, int k, int m, long long grou
     return with_workspace(c, st, [&] {
         return decode_ragged_impl(c, k, m, groups, {(const int32_t*)d_bb, d_blocks_off, d_rec_off},
                                   d_blocks, d_rows_in, d_rec, d_rec_rows, (int32_t*)d_status, st);
+    });
+}
+
+// ---- mixed-code batches: a (k, m) per group through an index into a code set (gf_mixed.hip,
+// decode_prep_mixed_kernel).  Every per-group decision, the rejection of a code index
+// included, is the kernels': nothing here reads d_code, d_bb or the offsets back.
+int qfec_codeset_create(qfec_ctx* c, int ncodes, const int* k, const int* m, qfec_codeset** out) {
+    if (!c || !out) return fail(-2, "null context or output");
+    if (!blob_ok()) return fail(-2, "embedded Cauchy tables have the wrong size");
+    if (ncodes < 1 || ncodes > qfec::kMixedMaxCodes || !k || !m)
+        return fail(-2, "a code set holds 1 to 32 codes");
+    for (int i = 0; i < ncodes; ++i)
+        if (k[i] < 1 || k[i] > 255 || m[i] < 1) return fail(-2, "bad (k, m) in a code set");
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = set_device(c);
+    if (rc) return rc;
+    auto cs = std::make_unique<qfec_codeset>();
+    cs->ctx = c;
+    cs->k.assign(k, k + ncodes);
+    cs->m.assign(m, m + ncodes);
+    qfec::MixedSet& s = cs->s;
+    s.ncodes = ncodes;
+    // One chunk size per direction for the whole set, the largest a code asks for (2 or 4):
+    // one GF launch per call, and a code with m = 2 in a set with larger codes runs with two
+    // of four accumulator rows idle.
+    s.enc_rc = s.dec_rc = 2;
+    const auto decodable = [&](int i) { return qfec::mixed_is_gf(k[i], m[i]) && m[i] <= 256 - k[i]; };
+    for (int i = 0; i < ncodes; ++i) {
+        s.kmax = std::max(s.kmax, k[i]);
+        cs->mmax = std::max(cs->mmax, m[i]);
+        s.rmax = std::max(s.rmax, std::min(k[i], m[i]));
+        cs->any_gf |= qfec::mixed_is_gf(k[i], m[i]);
+        if (!decodable(i)) continue;
+        s.enc_rc = std::max(s.enc_rc, ragged_rc(encode_rc(m[i], c->tune)));
+        s.dec_rc = std::max(s.dec_rc, ragged_decode_plan(k[i], m[i]).rc);
+    }
+    std::vector<qfec::MixedCode> rec((size_t)ncodes);
+    std::vector<const uint8_t*> tabs((size_t)ncodes, nullptr);
+    long long enc_bytes = 0;
+    for (int i = 0; i < ncodes; ++i) {
+        qfec::MixedCode& d = rec[(size_t)i];
+        d = {k[i], m[i], 0, 0, 0, nullptr};
+        if (!decodable(i)) continue;
+        const int rmax = std::min(k[i], m[i]);
+        d.enc_nchunk = (m[i] + s.enc_rc - 1) / s.enc_rc;
+        d.dec_nchunk = (rmax + s.dec_rc - 1) / s.dec_rc;
+        if ((rc = get_enc_table(c, k[i], m[i], s.enc_rc, &tabs[(size_t)i]))) return rc;
+        if ((rc = get_cenc(c, k[i], m[i], &d.cenc))) return rc;
+        d.enc_off = enc_bytes;
+        enc_bytes += (long long)d.enc_nchunk * k[i] * std::max(s.enc_rc, 4);
+        s.enc_nchunk = std::max(s.enc_nchunk, d.enc_nchunk);
+        s.dec_nchunk = std::max(s.dec_nchunk, d.dec_nchunk);
+        s.coef_gstride = std::max(s.coef_gstride,
+                                  (long long)d.dec_nchunk * k[i] * std::max(s.dec_rc, 4));
+        s.cenc_bytes += (m[i] * k[i] + 15) & ~15;
+        s.solve_rmax = std::max(s.solve_rmax, rmax);
+    }
+    // the tables get_enc_table built, side by side in one buffer of the set
+    QF_HIP(cs->enc.ensure((size_t)enc_bytes));
+    for (int i = 0; i < ncodes; ++i)
+        if (tabs[(size_t)i])
+            QF_HIP(hipMemcpy((uint8_t*)cs->enc.p + rec[(size_t)i].enc_off, tabs[(size_t)i],
+                             (size_t)rec[(size_t)i].enc_nchunk * k[i] * std::max(s.enc_rc, 4),
+                             hipMemcpyDeviceToDevice));
+    s.enc_tabs = (const uint8_t*)cs->enc.p;
+    QF_HIP(cs->codes.ensure(rec.size() * sizeof(qfec::MixedCode)));
+    QF_HIP(hipMemcpy(cs->codes.p, rec.data(), rec.size() * sizeof(qfec::MixedCode),
+                     hipMemcpyHostToDevice));
+    s.codes = (const qfec::MixedCode*)cs->codes.p;
+    *out = cs.release();
+    return 0;
+}
+
+void qfec_codeset_destroy(qfec_codeset* cs) {
+    if (!cs) return;
+    if (cs->ctx) (void)hipSetDevice(cs->ctx->device);
+    delete cs;
+}
+
+int qfec_codeset_dims(const qfec_codeset* cs, int* kmax, int* mmax, int* rmax) {
+    if (!cs) return fail(-2, "null code set");
+    if (kmax) *kmax = cs->s.kmax;
+    if (mmax) *mmax = cs->mmax;
+    if (rmax) *rmax = cs->s.rmax;
+    return 0;
+}
+
+// the decode workspace of `groups` groups of the set
+static int mixed_reserve(Workspace& W, const qfec::MixedSet& s, long long groups) {
+    QF_HIP(W.ensure(W.dcoef, (size_t)groups * (size_t)s.coef_gstride));
+    QF_HIP(W.ensure(W.dslots, (size_t)groups * (size_t)s.rmax));
+    QF_HIP(W.ensure(W.dnout, (size_t)groups * sizeof(int32_t)));
+    return 0;
+}
+
+int qfec_codeset_reserve(qfec_codeset* cs, long long groups) {
+    if (!cs || groups < 0) return fail(-2, "null code set or groups < 0");
+    qfec_ctx* c = cs->ctx;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = set_device(c);
+    if (rc) return rc;
+    for (Workspace* W : {&c->ws, &c->ws_graph})
+        if ((rc = mixed_reserve(*W, cs->s, groups))) return rc;
+    return 0;
+}
+
+extern "C++" int qfec::encode_mixed_impl(qfec_ctx* c, const qfec_codeset* cs, long long G,
+                                         MixedView v, const uint8_t* d_data, uint8_t* d_par,
+                                         int32_t* d_status, hipStream_t st) {
+    if (G == 0) return 0;
+    QF_HIP(qfec::launch_xor_copy_mixed(cs->s, v, d_data, d_par, nullptr, nullptr, d_status, G,
+                                       false, st, c->tune));
+    QF_HIP(qfec::launch_gf_mixed(cs->s, v, d_data, d_par, nullptr, nullptr, G, false, st, c->tune));
+    return 0;
+}
+
+// The caller holds the workspace bracket (with_workspace).
+extern "C++" int qfec::decode_mixed_impl(qfec_ctx* c, const qfec_codeset* cs, long long G,
+                                         MixedView v, const uint8_t* d_blocks,
+                                         const uint8_t* d_rows_in, uint8_t* d_rec,
+                                         uint8_t* d_rec_rows, int32_t* d_status, hipStream_t st) {
+    if (G == 0) return 0;
+    const qfec::MixedSet& s = cs->s;
+    QF_HIP(qfec::launch_xor_copy_mixed(s, v, d_blocks, d_rec, d_rows_in, d_rec_rows, d_status, G,
+                                       true, st, c->tune));
+    if (!cs->any_gf) return 0;
+    Workspace& W = ws_for(c, st);
+    int r = mixed_reserve(W, s, G);
+    if (r) return r;
+    qfec::DecodeWork w{(uint8_t*)W.dcoef.p, (uint8_t*)W.dslots.p, (int32_t*)W.dnout.p};
+    const qfec::PrepIO io{d_rows_in, nullptr, d_rec_rows, d_status, w};
+    QF_HIP(qfec::launch_decode_prep_mixed(s, v, io, G, st, c->tune));
+    QF_HIP(qfec::launch_gf_mixed(s, v, d_blocks, d_rec, w.coef, w.nout, G, true, st, c->tune));
+    return 0;
+}
+
+static int mixed_check(qfec_ctx* c, const qfec_codeset* cs, long long groups, int nchunk,
+                       std::initializer_list<const void*> arrays, const void* a, const void* b) {
+    if (!c) return fail(-2, "null context");
+    if (!cs || cs->ctx != c) return fail(-2, "no code set of this context");
+    if (groups < 0) return fail(-2, "groups < 0");
+    if (any_null(arrays) || !a || !b) return fail(-2, "null buffer");
+    if ((((uintptr_t)a) | (uintptr_t)b) & 15) return fail(-2, "mixed base pointers must be 16-byte aligned");
+    if (nchunk > 0 && groups > 0x7fffffffLL / nchunk)
+        return fail(-2, "groups x output chunks exceed 2^31 - 1 units");
+    return 0;
+}
+
+int qfec_encode_batch_mixed(qfec_ctx* c, const qfec_codeset* cs, long long groups,
+                            const unsigned char* d_code, const int* d_bb,
+                            const unsigned char* d_data, const long long* d_data_off,
+                            unsigned char* d_parity, const long long* d_par_off, int* d_status,
+                            void* stream) {
+    int rc = mixed_check(c, cs, groups, cs ? cs->s.enc_nchunk : 0,
+                         {d_code, d_bb, d_data_off, d_par_off}, d_data, d_parity);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    return encode_mixed_impl(c, cs, groups, {d_code, (const int32_t*)d_bb, d_data_off, d_par_off},
+                             d_data, d_parity, (int32_t*)d_status, pick(c, stream));
+}
+
+int qfec_decode_batch_mixed_recovered(qfec_ctx* c, const qfec_codeset* cs, long long groups,
+                                      const unsigned char* d_code, const int* d_bb,
+                                      const unsigned char* d_blocks,
+                                      const long long* d_blocks_off,
+                                      const unsigned char* d_rows_in, unsigned char* d_rec,
+                                      const long long* d_rec_off, unsigned char* d_rec_rows,
+                                      int* d_status, void* stream) {
+    int rc = mixed_check(c, cs, groups, cs ? cs->s.dec_nchunk : 0,
+                         {d_code, d_bb, d_blocks_off, d_rec_off, d_rows_in, d_rec_rows}, d_blocks,
+                         d_rec);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    if (groups == 0) return 0;
+    const hipStream_t st = pick(c, stream);
+    return with_workspace(c, st, [&] {
+        return decode_mixed_impl(c, cs, groups,
+                                 {d_code, (const int32_t*)d_bb, d_blocks_off, d_rec_off}, d_blocks,
+                                 d_rows_in, d_rec, d_rec_rows, (int32_t*)d_status, st);
     });
 }
 

@@ -282,6 +282,11 @@ struct qfec_batch {
     size_t max_groups;
     unsigned max_delay_us;
     bool ragged = false;   // buckets keyed by (k, m) only (key bb = 0), one ragged call each
+    bool mixed = false;    // one bucket per direction (key (0, 0, -1)), one mixed-code call each
+    // mixed: the one code set, rebuilt when a group of a new code arrives
+    std::vector<int> set_k, set_m;
+    qfec_codeset* cs = nullptr;
+    ~qfec_batch() { qfec_codeset_destroy(cs); }
     struct Enc {
         qfec_group* g;
         int bb;
@@ -300,6 +305,7 @@ struct qfec_batch {
     std::vector<unsigned char> hbuf, hrows;
     std::vector<int> hstatus;
     qfec::RaggedPack pack;
+    std::vector<unsigned char> hcode;
 };
 
 namespace {
@@ -354,10 +360,106 @@ int flush_dec_ragged(qfec_batch* b, std::vector<qfec_batch::Dec>& v, int k, int 
     return rc ? rc : (int)G;
 }
 
+// The mixed bucket (key bb = -1): the groups keep their own (k, m) and block size.  Their codes
+// are looked up in the queue's one code set, which is rebuilt when a new code arrives (and
+// started afresh from this flush's codes once it would pass 32); then qfec_mixed_layout, the
+// packing, and one mixed host call.
+template <class V>
+int mixed_codes(qfec_batch* b, const V& v) {
+    const size_t G = v.size();
+    b->hcode.resize(G);
+    for (int pass = 0; pass < 2; ++pass) {
+        bool grew = false;
+        for (size_t i = 0; i < G; ++i) {
+            const int k = (int)v[i].g->g.k(), m = (int)v[i].g->g.m();
+            size_t c = 0;
+            while (c < b->set_k.size() && (b->set_k[c] != k || b->set_m[c] != m)) ++c;
+            if (c == b->set_k.size()) {
+                b->set_k.push_back(k);
+                b->set_m.push_back(m);
+                grew = true;
+            }
+            b->hcode[i] = (unsigned char)(c < 256 ? c : 255);
+        }
+        if (b->set_k.size() <= 32) {
+            if (!grew && b->cs) return 0;
+            qfec_codeset_destroy(b->cs);
+            b->cs = nullptr;
+            return qfec_codeset_create(b->ctx, (int)b->set_k.size(), b->set_k.data(),
+                                       b->set_m.data(), &b->cs);
+        }
+        b->set_k.clear();   // too many codes over time: keep those of this flush
+        b->set_m.clear();
+    }
+    return -2;              // more than 32 codes in one flush
+}
+
+template <class V>
+int mixed_pack(qfec_batch* b, const V& v, bool decode) {
+    const size_t G = v.size();
+    qfec::RaggedPack& p = b->pack;
+    p.bb.resize(G);
+    for (size_t i = 0; i < G; ++i) p.bb[i] = v[i].bb;
+    p.in_off.assign(G, 0);
+    p.out_off.assign(G, 0);
+    long long totals[3] = {0, 0, 0};
+    const int rc = qfec_mixed_layout((int)b->set_k.size(), b->set_k.data(), b->set_m.data(),
+                                     (long long)G, b->hcode.data(), p.bb.data(), p.in_off.data(),
+                                     decode ? nullptr : p.out_off.data(),
+                                     decode ? p.out_off.data() : nullptr, totals);
+    if (rc) return rc;
+    p.in.resize((size_t)totals[0]);
+    p.out.assign((size_t)totals[decode ? 2 : 1], 0);
+    for (size_t i = 0; i < G; ++i)
+        memcpy(p.in.data() + p.in_off[i], v[i].blocks.data(), v[i].blocks.size());
+    return 0;
+}
+
+int flush_enc_mixed(qfec_batch* b, std::vector<qfec_batch::Enc>& v) {
+    const size_t G = v.size();
+    int rc = mixed_codes(b, v);
+    if (rc || (rc = mixed_pack(b, v, false))) return rc;
+    qfec::RaggedPack& p = b->pack;
+    b->hstatus.assign(G, 0);
+    rc = qfec_encode_batch_mixed_host(b->ctx, b->cs, (long long)G, b->hcode.data(), p.bb.data(),
+                                      p.in.data(), p.in_off.data(), p.out.data(),
+                                      p.out_off.data(), b->hstatus.data());
+    for (size_t i = 0; i < G; ++i)
+        v[i].g->g.SetRedundancy(p.out.data() + p.out_off[i], p.bb[i], rc ? rc : b->hstatus[i]);
+    v.clear();
+    return rc ? rc : (int)G;
+}
+
+int flush_dec_mixed(qfec_batch* b, std::vector<qfec_batch::Dec>& v) {
+    const size_t G = v.size();
+    int rc = mixed_codes(b, v);
+    if (rc || (rc = mixed_pack(b, v, true))) return rc;
+    int kmax = 0, rmax = 0;
+    qfec_codeset_dims(b->cs, &kmax, nullptr, &rmax);
+    b->hrows.assign(G * ((size_t)kmax + (size_t)rmax), 255);
+    unsigned char* rows = b->hrows.data();
+    unsigned char* rec_rows = rows + G * (size_t)kmax;
+    for (size_t i = 0; i < G; ++i)
+        memcpy(rows + i * (size_t)kmax, v[i].rows.data(), v[i].rows.size());
+    qfec::RaggedPack& p = b->pack;
+    b->hstatus.assign(G, 0);
+    rc = qfec_decode_batch_mixed_recovered_host(b->ctx, b->cs, (long long)G, b->hcode.data(),
+                                                p.bb.data(), p.in.data(), p.in_off.data(), rows,
+                                                p.out.data(), p.out_off.data(), rec_rows,
+                                                b->hstatus.data());
+    for (size_t i = 0; i < G; ++i)
+        v[i].g->g.SetRevived(v[i].missing, p.out.data() + p.out_off[i], rec_rows + i * (size_t)rmax,
+                             p.bb[i], rc ? rc : b->hstatus[i],
+                             std::min(v[i].g->g.k(), v[i].g->g.m()));
+    v.clear();
+    return rc ? rc : (int)G;
+}
+
 int flush_enc(qfec_batch* b, const std::tuple<int, int, int>& key) {
     auto& v = b->enc[key];
     if (v.empty()) return 0;
     const int k = std::get<0>(key), m = std::get<1>(key), bb = std::get<2>(key);
+    if (bb < 0) return flush_enc_mixed(b, v);
     if (bb == 0) return flush_enc_ragged(b, v, k, m);
     const size_t G = v.size();
     b->hbuf.resize(G * (size_t)(k + m) * bb);
@@ -375,6 +477,7 @@ int flush_dec(qfec_batch* b, const std::tuple<int, int, int>& key) {
     auto& v = b->dec[key];
     if (v.empty()) return 0;
     const int k = std::get<0>(key), m = std::get<1>(key), bb = std::get<2>(key);
+    if (bb < 0) return flush_dec_mixed(b, v);
     if (bb == 0) return flush_dec_ragged(b, v, k, m);
     const size_t G = v.size();
     const size_t rmax = (size_t)std::min(k, m);
@@ -491,6 +594,19 @@ int qfec_batch_set_ragged(qfec_batch* b, int on) {
     return 0;
 }
 
+int qfec_batch_set_mixed(qfec_batch* b, int on) {
+    if (!b) return -2;
+    if (qfec_batch_pending(b)) return -2;   // queued groups sit in buckets of the other kind
+    b->mixed = on != 0;
+    return 0;
+}
+
+// The bucket of a group: (k, m, bb), (k, m, 0) with ragged buckets, one for all with mixed ones.
+static std::tuple<int, int, int> bucket_key(const qfec_batch* b, const qfec_group* g, int bb) {
+    if (b->mixed) return std::make_tuple(0, 0, -1);
+    return std::make_tuple((int)g->g.k(), (int)g->g.m(), b->ragged ? 0 : bb);
+}
+
 int qfec_batch_add_encode(qfec_batch* b, qfec_group* g) {
     qfec_batch::Enc e;
     int bb = 0;
@@ -498,7 +614,7 @@ int qfec_batch_add_encode(qfec_batch* b, qfec_group* g) {
     e.g = g;
     e.bb = bb;
     e.t = std::chrono::steady_clock::now();
-    auto key = std::make_tuple((int)g->g.k(), (int)g->g.m(), b->ragged ? 0 : bb);
+    const auto key = bucket_key(b, g, bb);
     auto& v = b->enc[key];
     v.push_back(std::move(e));
     return v.size() >= b->max_groups ? flush_enc(b, key) : 0;
@@ -511,7 +627,7 @@ int qfec_batch_add_decode(qfec_batch* b, qfec_group* g) {
     d.g = g;
     d.bb = bb;
     d.t = std::chrono::steady_clock::now();
-    auto key = std::make_tuple((int)g->g.k(), (int)g->g.m(), b->ragged ? 0 : bb);
+    const auto key = bucket_key(b, g, bb);
     auto& v = b->dec[key];
     v.push_back(std::move(d));
     return v.size() >= b->max_groups ? flush_dec(b, key) : 0;

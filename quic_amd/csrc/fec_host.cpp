@@ -344,6 +344,86 @@ int qfec_decode_batch_ragged_recovered_host(qfec_ctx* c, int k, int m, long long
     });
 }
 
+// ---- mixed-code batches: the ragged host forms with a block count per group, taken from the
+// group's code (a group whose code index names no code of the set stages nothing: the device
+// gives it status -2)
+namespace {
+struct MixedCounts {
+    std::vector<int> in, par, rec;
+    MixedCounts(const qfec_codeset* cs, const unsigned char* code, long long G)
+        : in((size_t)G, 0), par((size_t)G, 0), rec((size_t)G, 0) {
+        for (long long g = 0; g < G; ++g) {
+            if (code[g] >= cs->s.ncodes) continue;
+            const int k = cs->k[code[g]], m = cs->m[code[g]];
+            in[(size_t)g] = k;
+            par[(size_t)g] = m;
+            rec[(size_t)g] = std::min(k, m);
+        }
+    }
+};
+int mixed_host_preface(qfec_ctx* c, const qfec_codeset* cs, long long groups) {
+    if (!c) return fail(-2, "null context");
+    if (!cs || cs->ctx != c) return fail(-2, "no code set of this context");
+    if (groups < 0) return fail(-2, "groups < 0");
+    return 0;
+}
+}  // namespace
+
+int qfec_encode_batch_mixed_host(qfec_ctx* c, const qfec_codeset* cs, long long groups,
+                                 const unsigned char* h_code, const int* h_bb,
+                                 const unsigned char* h_data, const long long* h_data_off,
+                                 unsigned char* h_parity, const long long* h_par_off,
+                                 int* h_status) {
+    int rc = mixed_host_preface(c, cs, groups);
+    if (rc) return rc;
+    if (!h_code || !h_bb || !h_data || !h_data_off || !h_parity || !h_par_off)
+        return fail(-2, "null buffer");
+    if (groups == 0) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const MixedCounts n(cs, h_code, groups);
+    StageList L{h_bb};
+    Stage& dd = L.packed(h_data_off, n.in.data()).in(h_data);
+    Stage& dp = L.packed(h_par_off, n.par.data()).in(h_parity).out(h_parity);
+    RaggedStages rs(L, h_bb, h_status);
+    Stage& dc = L.dense(1).in(h_code);
+    return host_pipeline_ragged(c, L, groups, dd, dp, rs, [&](long long g) {
+        const RaggedView v = rs.view();
+        return encode_mixed_impl(c, cs, g, {dc.dev, v.bb, v.in_off, v.out_off}, dd.dev, dp.dev,
+                                 rs.status.as<int32_t>(), c->stream);
+    });
+}
+
+int qfec_decode_batch_mixed_recovered_host(qfec_ctx* c, const qfec_codeset* cs, long long groups,
+                                           const unsigned char* h_code, const int* h_bb,
+                                           const unsigned char* h_blocks,
+                                           const long long* h_blocks_off,
+                                           const unsigned char* h_rows, unsigned char* h_rec,
+                                           const long long* h_rec_off, unsigned char* h_rec_rows,
+                                           int* h_status) {
+    int rc = mixed_host_preface(c, cs, groups);
+    if (rc) return rc;
+    if (!h_code || !h_bb || !h_blocks || !h_blocks_off || !h_rows || !h_rec || !h_rec_off ||
+        !h_rec_rows)
+        return fail(-2, "null buffer");
+    if (groups == 0) return 0;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const MixedCounts n(cs, h_code, groups);
+    StageList L{h_bb};
+    Stage& db = L.packed(h_blocks_off, n.in.data()).in(h_blocks);
+    Stage& dre = L.packed(h_rec_off, n.rec.data()).in(h_rec).out(h_rec);
+    RaggedStages rs(L, h_bb, h_status);
+    Stage& dc = L.dense(1).in(h_code);
+    Stage& dr = L.dense(cs->s.kmax).in(h_rows);
+    Stage& drr = L.dense(cs->s.rmax).out(h_rec_rows);
+    return host_pipeline_ragged(c, L, groups, db, dre, rs, [&](long long g) {
+        const RaggedView v = rs.view();
+        return decode_mixed_impl(c, cs, g, {dc.dev, v.bb, v.in_off, v.out_off}, db.dev, dr.dev,
+                                 dre.dev, drr.dev, rs.status.as<int32_t>(), c->stream);
+    });
+}
+
 // Sender, host to host, ragged: qfec_encode_seal_groups_batch_host with a block size per group.
 // The parity is laid out on the device and never leaves it.
 int qfec_encode_seal_groups_batch_ragged_host(qfec_ctx* c, int k, int m, long long groups,

@@ -32,7 +32,7 @@ size_t one_stage_bytes(const qfec::StageList& L, const qfec::Stage& s, long long
     if (!s.present) return 0;
     if (!s.off) return (size_t)n * s.per_group;
     const long long last = g0 + n - 1;
-    return (size_t)(s.off[last] + (long long)s.nblk * L.bb[last] - s.off[g0]);
+    return (size_t)(s.off[last] + s.blocks(last) * L.bb[last] - s.off[g0]);
 }
 
 }  // namespace
@@ -46,6 +46,30 @@ extern "C" int qfec_ragged_layout(int k, int m, long long groups, const int* bb,
     long long run[3] = {0, 0, 0};
     for (long long g = 0; g < groups; ++g) {
         if (bb[g] < 1) return -2;
+        for (int a = 0; a < 3; ++a) {
+            if (off[a]) off[a][g] = run[a];
+            if (!advance(&run[a], nblk[a], bb[g])) return -2;
+        }
+    }
+    if (totals)
+        for (int a = 0; a < 3; ++a) totals[a] = run[a];
+    return 0;
+}
+
+// qfec_ragged_layout with the block counts of each group's own code.
+extern "C" int qfec_mixed_layout(int ncodes, const int* k, const int* m, long long groups,
+                                 const unsigned char* code, const int* bb, long long* data_off,
+                                 long long* par_off, long long* rec_off, long long totals[3]) {
+    if (ncodes < 1 || ncodes > 32 || !k || !m || groups < 0 || (groups && (!code || !bb)))
+        return -2;
+    for (int c = 0; c < ncodes; ++c)
+        if (k[c] < 1 || k[c] > 255 || m[c] < 1) return -2;
+    long long* const off[3] = {data_off, par_off, rec_off};
+    long long run[3] = {0, 0, 0};
+    for (long long g = 0; g < groups; ++g) {
+        if (code[g] >= ncodes || bb[g] < 1) return -2;
+        const int kg = k[code[g]], mg = m[code[g]];
+        const long long nblk[3] = {kg, mg, kg < mg ? kg : mg};
         for (int a = 0; a < 3; ++a) {
             if (off[a]) off[a][g] = run[a];
             if (!advance(&run[a], nblk[a], bb[g])) return -2;
@@ -197,8 +221,8 @@ int ragged_chunks(const StageList& L, const Stage& in, const Stage& out, long lo
         if (in.off[g] < 0 || out.off[g] < 0 || ((in.off[g] | out.off[g]) & 15))
             return *msg = "ragged offsets must be non-negative multiples of 16", -2;
         if ((g && (in.off[g] < in_end || out.off[g] < out_end)) ||
-            !block_end(in.off[g], in.nblk, bb[g], &in_end) ||
-            !block_end(out.off[g], out.nblk, bb[g], &out_end))
+            !block_end(in.off[g], in.blocks(g), bb[g], &in_end) ||
+            !block_end(out.off[g], out.blocks(g), bb[g], &out_end))
             return *msg = "host ragged batches need ascending, non-overlapping offsets", -2;
     }
     ch->groups = G;

@@ -27,7 +27,8 @@ int ragged_pack(int k, int m, bool decode, const std::vector<const unsigned char
 
 // One array a host-pointer batch stages on the device, stated once.  Its bytes for the groups
 // [g0, g0 + n) of a chunk: dense, n * per_group; or packed, the span from group g0's offset to
-// the end of the chunk's last group (nblk blocks of bb[g] bytes at off[g]).  `src` is the host
+// the end of the chunk's last group (nblk blocks of bb[g] bytes at off[g]; nblk_g: a count per
+// group instead, the mixed-code batches').  `src` is the host
 // array copied in before the kernels, `dst` the one copied out after them (both: the caller's
 // bytes are staged in, so what the kernels leave unwritten returns as it was; neither: the
 // array lives on the device only).  An absent stage is a null device pointer and zero bytes.
@@ -36,6 +37,7 @@ struct Stage {
     size_t per_group = 0;              // dense
     const long long* off = nullptr;    // packed: [G], ascending
     int nblk = 0;
+    const int* nblk_g = nullptr;       // packed: [G] blocks per group, instead of nblk
     const void* src = nullptr;
     void* dst = nullptr;
     size_t row_pitch = 0, row_width = 0;   // copy out only row_width bytes of every row_pitch
@@ -47,6 +49,7 @@ struct Stage {
     Stage& out(void* h) { dst = h; return *this; }
     Stage& rows(size_t pitch, size_t width) { row_pitch = pitch; row_width = width; return *this; }
     template <class T> T* as() const { return (T*)dev; }
+    long long blocks(long long g) const { return nblk_g ? nblk_g[g] : nblk; }
     // where the chunk that starts at group g0 begins in a host array of this stage
     size_t host_at(long long g0) const { return off ? (size_t)off[g0] : (size_t)g0 * per_group; }
 };
@@ -66,6 +69,12 @@ struct StageList {
         Stage& st = add();
         st.off = off;
         st.nblk = nblk;
+        return st;
+    }
+    Stage& packed(const long long* off, const int* nblk_g) {
+        Stage& st = add();
+        st.off = off;
+        st.nblk_g = nblk_g;
         return st;
     }
     Stage& add() {

@@ -14,6 +14,7 @@
 
 #include "../../include/quic_fec.h"
 #include "fec_kernels.h"
+#include "gf_mixed.h"
 
 namespace qfec {
 
@@ -103,6 +104,17 @@ struct qfec_ctx {
     std::mutex mu;   // one caller at a time per context (the reference is single-threaded)
 };
 
+// A code set (qfec_codeset_create): the codes of a mixed-code batch.
+struct qfec_codeset {
+    qfec_ctx* ctx = nullptr;
+    int mmax = 0;
+    bool any_gf = false;      // a code with k > 1 and m > 1: the decode runs the prep
+    std::vector<int> k, m;    // the codes, for the host forms' block counts
+    qfec::MixedSet s{};
+    qfec::DevBuf codes;       // MixedCode [ncodes]; the matrices it names are the context's
+    qfec::DevBuf enc;         // the codes' encode tables, copies of the context's
+};
+
 namespace qfec {
 
 int set_device(qfec_ctx* c);
@@ -185,6 +197,13 @@ int encode_ragged_impl(qfec_ctx* c, int k, int m, long long G, RaggedView v, con
 int decode_ragged_impl(qfec_ctx* c, int k, int m, long long G, RaggedView v,
                        const uint8_t* d_blocks, const uint8_t* d_rows_in, uint8_t* d_rec,
                        uint8_t* d_rec_rows, int32_t* d_status, hipStream_t st);
+// Mixed-code batches (gf_mixed.h): what the device and the host forms enqueue on `st`.  The
+// decode's caller holds the workspace bracket.
+int encode_mixed_impl(qfec_ctx* c, const qfec_codeset* cs, long long G, MixedView v,
+                      const uint8_t* d_data, uint8_t* d_par, int32_t* d_status, hipStream_t st);
+int decode_mixed_impl(qfec_ctx* c, const qfec_codeset* cs, long long G, MixedView v,
+                      const uint8_t* d_blocks, const uint8_t* d_rows_in, uint8_t* d_rec,
+                      uint8_t* d_rec_rows, int32_t* d_status, hipStream_t st);
 // The framing of a framed open: each packet's pn_len, or one value for all (pn_len null).
 struct PnLen {
     const uint8_t* pn_len;

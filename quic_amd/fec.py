@@ -166,6 +166,63 @@ def _groups(bb, **offs):
     return bb.shape[0]
 
 
+def _mixed_groups(code, bb, status, **offs):
+    """G of a mixed-code device call: code uint8 [G], then bb, the offsets and status as in the
+    ragged calls."""
+    import torch
+    if not isinstance(code, torch.Tensor):
+        raise TypeError("code: a uint8 device tensor [G]")
+    _check(code, "code", "uint8", (None,))
+    G = code.shape[0]
+    _check(bb, "bb", "int32", (G,))
+    for name, off in offs.items():
+        _check(off, name, "int64", (G,))
+    _check(status, "status", "int32", (G,))
+    return G
+
+
+def _codes(codes):
+    """(k, m) pairs -> the two int32 arrays the library takes."""
+    pairs = [(int(k), int(m)) for k, m in codes]
+    return (pairs, np.array([k for k, _ in pairs], np.int32),
+            np.array([m for _, m in pairs], np.int32))
+
+
+class CodeSet:
+    """The codes of a mixed-code batch (qfec_codeset): built once per engine, immutable.
+    codes[i] = (k, m); kmax, mmax and rmax (the largest min(k, m)) size the row arrays."""
+
+    def __init__(self, engine, codes):
+        self.codes, k, m = _codes(codes)
+        self.engine = engine
+        h = ctypes.c_void_p()
+        rc = engine.lib.qfec_codeset_create(engine._h, len(self.codes), _vp(k), _vp(m),
+                                            ctypes.byref(h))
+        if rc:
+            raise FecError(rc, "qfec_codeset_create")
+        self._h = h
+        d = [ctypes.c_int() for _ in range(3)]
+        engine.lib.qfec_codeset_dims(h, *[ctypes.byref(x) for x in d])
+        self.kmax, self.mmax, self.rmax = (x.value for x in d)
+
+    def reserve(self, groups):
+        """Size both decode workspaces for `groups` groups (qfec_codeset_reserve)."""
+        rc = self.engine.lib.qfec_codeset_reserve(self._h, groups)
+        if rc:
+            raise FecError(rc, "qfec_codeset_reserve")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.engine.lib.qfec_codeset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _ptr_tables(bb, status, **tables):
     """G of a pointer-table call: every table (tensor, n) is int64 [G][n]; bb is an int or
     int32 [G], status None or int32 [G]."""
@@ -278,6 +335,37 @@ class FecEngine:
         return _call("qfec_decode_batch_ragged_recovered", self, k, m, G, _ptr(bb), _ptr(blocks),
                      _ptr(blocks_off), _ptr(rows_in), _ptr(rec), _ptr(rec_off), _ptr(rec_rows),
                      _ptr(status), _stream(stream, blocks))
+
+    # mixed-code batches: a (k, m) per group through a code set (include/quic_fec.h)
+    def codeset(self, codes):
+        """A CodeSet of this engine for `codes`, a sequence of 1 to 32 (k, m) pairs; a group
+        names its code by its index in the sequence.  Close it before the engine."""
+        return CodeSet(self, codes)
+
+    def encode_mixed(self, cs, code, bb, data, data_off, parity, par_off, status=None,
+                     stream=None):
+        """Group g has code cs.codes[code[g]] = (k_g, m_g): data + data_off[g] holds
+        [k_g][bb[g]], parity + par_off[g] receives [m_g][bb[g]].  code uint8 [G], bb int32 [G],
+        offsets int64 [G] (bytes, multiples of 16), data / parity flat uint8, all on the device;
+        status: optional int32 [G] (per group 0, -1, or -2 for a code index outside the set).
+        Returns 0: every rejection is per group."""
+        G = _mixed_groups(code, bb, status, data_off=data_off, par_off=par_off)
+        return _call("qfec_encode_batch_mixed", self, cs._h, G, _ptr(code), _ptr(bb), _ptr(data),
+                     _ptr(data_off), _ptr(parity), _ptr(par_off), _ptr(status),
+                     _stream(stream, data))
+
+    def decode_mixed_recovered(self, cs, code, bb, blocks, blocks_off, rows_in, rec, rec_off,
+                               rec_rows, status=None, stream=None):
+        """Recovered-blocks layout per group: rec + rec_off[g] receives up to
+        [min(k_g, m_g)][bb[g]].  rows_in is uint8 [G][cs.kmax] (the first k_g tags of a row are
+        read), rec_rows uint8 [G][cs.rmax] (255 = unused, up to the set's rmax).  blocks /
+        rows_in are not modified."""
+        G = _mixed_groups(code, bb, status, blocks_off=blocks_off, rec_off=rec_off)
+        _check(rows_in, "rows_in", "uint8", (G, cs.kmax))
+        _check(rec_rows, "rec_rows", "uint8", (G, cs.rmax))
+        return _call("qfec_decode_batch_mixed_recovered", self, cs._h, G, _ptr(code), _ptr(bb),
+                     _ptr(blocks), _ptr(blocks_off), _ptr(rows_in), _ptr(rec), _ptr(rec_off),
+                     _ptr(rec_rows), _ptr(status), _stream(stream, blocks))
 
     # pointer-table batches: every block at a device address of its own (include/quic_fec.h)
     def encode_ptrs(self, k, m, bb, data_ptrs, parity_ptrs, status=None, stream=None):
@@ -668,6 +756,27 @@ def ragged_layout(k, m, bb):
     return offs[0], offs[1], offs[2], totals
 
 
+def mixed_layout(codes, code, bb):
+    """The packed layout of a mixed-code batch (qfec_mixed_layout; host only): group g has
+    codes[code[g]] = (k_g, m_g) and block size bb[g].  Returns (data_off, par_off, rec_off,
+    totals) as ragged_layout.  ValueError for a code index outside `codes`, a size < 1, a bad
+    set or an overflow."""
+    pairs, k, m = _codes(codes)
+    code = np.ascontiguousarray(code, dtype=np.uint8)
+    bb = np.ascontiguousarray(bb, dtype=np.int32)
+    if code.ndim != 1 or bb.shape != code.shape:
+        raise ValueError("code and bb must be one-dimensional and of one length")
+    G = code.shape[0]
+    offs = [np.zeros(G, np.int64) for _ in range(3)]
+    totals = np.zeros(3, np.int64)
+    rc = load().qfec_mixed_layout(len(pairs), _vp(k), _vp(m), G, _vp(code), _vp(bb),
+                                  *[_vp(o) for o in offs], _vp(totals))
+    if rc:
+        raise ValueError(f"qfec_mixed_layout: rc={rc} (a code index outside the set, a size < 1, "
+                         "a bad set or overflow)")
+    return offs[0], offs[1], offs[2], tuple(int(t) for t in totals)
+
+
 def framed_layout(k, m, pay_len):
     """The block sizes and the packed layout of framed groups (qfec_framed_layout; host only):
     pay_len int32 [G*k] -> (bb, data_off, par_off, rec_off, totals) with
@@ -786,6 +895,56 @@ def decode_ragged_recovered_host_into(engine, k, m, bb_h, blocks_h, blocks_off_h
                  _ptr(blocks_h, True), _ptr(blocks_off_h, True), _ptr(rows_h, True),
                  _ptr(rec_h, True), _ptr(rec_off_h, True), _ptr(rec_rows_h, True),
                  _ptr(status_h, True))
+
+
+def _hcheck_mixed(cs, code_h, bb_h, bufs):
+    """Host arguments of a mixed-code call: code uint8 [G], bb int32 [G] (every size >= 1), and
+    per packed buffer (name, tensor, offsets, blocks per code): offsets int64 [G], non-negative
+    multiples of 16, inside the flat uint8 buffer.  A group whose code index names no code of
+    the set holds no blocks."""
+    import torch
+    G = code_h.shape[0] if isinstance(code_h, torch.Tensor) and code_h.dim() == 1 else None
+    _check(code_h, "code", "uint8", (G,), host=True)
+    _check(bb_h, "bb", "int32", (G,), host=True)
+    if int(bb_h.min()) < 1:
+        raise ValueError("bb: every block size must be >= 1")
+    for name, buf_h, off_h, per_code in bufs:
+        _check(off_h, f"{name}_off", "int64", (G,), host=True)
+        _check(buf_h, name, "uint8", (None,), host=True)
+        if int(off_h.min()) < 0 or int((off_h % 16).max()) != 0:
+            raise ValueError(f"{name}_off: offsets must be non-negative multiples of 16")
+        counts = torch.tensor(list(per_code) + [0] * (256 - len(per_code)), dtype=torch.int64)
+        if int((off_h + counts[code_h.long()] * bb_h.to(torch.int64)).max()) > buf_h.numel():
+            raise ValueError(f"{name}: buffer of {buf_h.numel()} bytes is too short for its groups")
+    return G
+
+
+def encode_mixed_host_into(engine, cs, code_h, bb_h, data_h, data_off_h, parity_h, par_off_h,
+                           status_h=None):
+    """Host-pointer mixed-code encode on caller-owned CPU tensors (qfec_encode_batch_mixed_host):
+    code uint8 [G], bb int32 [G], offsets int64 [G] (ascending, as mixed_layout gives them),
+    data / parity flat uint8.  Returns 0: every rejection is per group."""
+    G = _hcheck_mixed(cs, code_h, bb_h, [("data", data_h, data_off_h, [k for k, _ in cs.codes]),
+                                         ("parity", parity_h, par_off_h, [m for _, m in cs.codes])])
+    _check(status_h, "status", "int32", (G,), host=True, optional=True)
+    return _call("qfec_encode_batch_mixed_host", engine, cs._h, G, _ptr(code_h, True),
+                 _ptr(bb_h, True), _ptr(data_h, True), _ptr(data_off_h, True),
+                 _ptr(parity_h, True), _ptr(par_off_h, True), _ptr(status_h, True))
+
+
+def decode_mixed_recovered_host_into(engine, cs, code_h, bb_h, blocks_h, blocks_off_h, rows_h,
+                                     rec_h, rec_off_h, rec_rows_h, status_h=None):
+    """Host-pointer mixed-code decode returning only the recovered blocks
+    (qfec_decode_batch_mixed_recovered_host); rows [G][cs.kmax], rec_rows [G][cs.rmax]."""
+    G = _hcheck_mixed(cs, code_h, bb_h, [("blocks", blocks_h, blocks_off_h, [k for k, _ in cs.codes]),
+                                         ("rec", rec_h, rec_off_h, [min(c) for c in cs.codes])])
+    _check(rows_h, "rows", "uint8", (G, cs.kmax), host=True)
+    _check(rec_rows_h, "rec_rows", "uint8", (G, cs.rmax), host=True)
+    _check(status_h, "status", "int32", (G,), host=True, optional=True)
+    return _call("qfec_decode_batch_mixed_recovered_host", engine, cs._h, G, _ptr(code_h, True),
+                 _ptr(bb_h, True), _ptr(blocks_h, True), _ptr(blocks_off_h, True),
+                 _ptr(rows_h, True), _ptr(rec_h, True), _ptr(rec_off_h, True),
+                 _ptr(rec_rows_h, True), _ptr(status_h, True))
 
 
 def encode_seal_groups_ragged_host_into(engine, k, m, bb_h, data_h, data_off_h, hdr_h, hdr_len,

@@ -49,6 +49,7 @@ _SIG = {
     "qfec_batch_new": (_c.c_void_p, [_c.c_void_p, _c.c_size_t, _c.c_uint]),
     "qfec_batch_free": (None, [_c.c_void_p]),
     "qfec_batch_set_ragged": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "qfec_batch_set_mixed": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "qfec_batch_add_encode": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
     "qfec_batch_add_decode": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
     "qfec_batch_poll": (_c.c_int, [_c.c_void_p]),
@@ -202,6 +203,13 @@ class FecBatch:
         is queued."""
         if self._L.qfec_batch_set_ragged(self._h, 1 if on else 0):
             raise ValueError("set_ragged: flush the queued groups first")
+
+    def set_mixed(self, on):
+        """One bucket per direction and one mixed-code launch per flush, each group with its own
+        (k, m) and block_bytes; max_groups counts across codes (qfec_batch_set_mixed; off by
+        default).  Only while nothing is queued."""
+        if self._L.qfec_batch_set_mixed(self._h, 1 if on else 0):
+            raise ValueError("set_mixed: flush the queued groups first")
 
     def add_encode(self, group):
         self._keep.append(group)

@@ -51,7 +51,18 @@ same groups, data rows 0 .. r-1 lost:
   unaligned  the same at addresses of every residue mod 16
 The outputs of all four are compared byte for byte first.
 
+--mixed: the mixed-code batches against the ragged calls, two losses per
+group (data rows 0 and 1):
+  mixed   one qfec_encode_batch_mixed / qfec_decode_batch_mixed_recovered call over groups drawn
+          uniformly from the six presets (5,5) (10,10) (10,15) (10,20) (15,15) (250,5)
+  sorted  the same groups pre-sorted by code into one packed buffer per code (not timed) and one
+          qfec_encode_batch_ragged / qfec_decode_batch_ragged_recovered per code
+at --groups groups (a) and at 1,024, the queue's scale (b); and a set of the one code (32, 4)
+against the ragged call on identical input (c): the price of the per-group look-ups.  Outputs
+are compared byte for byte first.
+
   python tools/ragged_bench.py --out profiles/ragged/ragged_bench.json
+  python tools/ragged_bench.py --mixed --out profiles/ragged/mixed_bench.json
   python tools/ragged_bench.py --ptrs --out profiles/ragged/ptrs_bench.json
   python tools/ragged_bench.py --pp --out profiles/ragged/ragged_pp_bench.json
   python tools/ragged_bench.py --framed --out profiles/ragged/framed_bench.json
@@ -102,6 +113,8 @@ def main():
                     help="the arrival-order receiver against the slot-order framed receiver")
     ap.add_argument("--ptrs", action="store_true",
                     help="the pointer-table batches against the packed ragged calls")
+    ap.add_argument("--mixed", action="store_true",
+                    help="the mixed-code batches against one ragged call per code")
     ap.add_argument("--variants", default=None,
                     help="--arrivals: comma-separated subset of slot,arrivals,two_read,shuffled "
                          "to time (for a kernel trace of one route)")
@@ -845,7 +858,161 @@ def main():
         results.append(line)
         print(json.dumps(line), flush=True)
 
+    def run_mixed(codes, r, G, label):
+        """--mixed: one mixed call against one ragged call per code on the same groups, data rows
+        0 .. r-1 of every group lost."""
+        rng = np.random.default_rng(args.seed + 7)
+        nc = len(codes)
+        code = rng.integers(0, nc, G).astype(np.uint8)
+        bb = draw_sizes(G, args.seed)
+        bb64 = bb.astype(np.int64)
+        ks = np.array([k for k, _ in codes], np.int64)[code]
+        ms = np.array([m for _, m in codes], np.int64)[code]
+        cs = eng.codeset(codes)
+        kmax, rmax = cs.kmax, cs.rmax
+        d_off, p_off, r_off, tot = fec.mixed_layout(codes, code, bb)
+        data = torch.empty(tot[0], dtype=torch.uint8, device="cuda")
+        fec.synth_fill(data, seed=args.seed)
+        par = torch.zeros(tot[1], dtype=torch.uint8, device="cuda")
+        rec = torch.zeros(tot[2], dtype=torch.uint8, device="cuda")
+        code_d, bb_d = torch.from_numpy(code).cuda(), torch.from_numpy(bb).cuda()
+        d_off_d, p_off_d, r_off_d = (torch.from_numpy(o).cuda() for o in (d_off, p_off, r_off))
+        rows_np = np.tile(np.arange(kmax, dtype=np.int64), (G, 1))
+        rows_np[:, :r] = ks[:, None] + np.arange(r)[None, :]
+        rows = torch.from_numpy(rows_np.astype(np.uint8)).cuda()
+        rr = torch.zeros((G, rmax), dtype=torch.uint8, device="cuda")
+        est = torch.zeros(G, dtype=torch.int32, device="cuda")
+        st = torch.zeros(G, dtype=torch.int32, device="cuda")
+
+        def mixed_encode():
+            eng.encode_mixed(cs, code_d, bb_d, data, d_off_d, par, p_off_d, status=est)
+
+        mixed_encode()
+        kern = {"mixed_encode": fec.last_kernels()}
+        blocks = data.clone()
+        torch._foreach_copy_(views(blocks, d_off, r * bb64), views(par, p_off, r * bb64))
+
+        def mixed_decode():
+            eng.decode_mixed_recovered(cs, code_d, bb_d, blocks, d_off_d, rows, rec, r_off_d, rr,
+                                       status=st)
+
+        mixed_decode()
+        kern["mixed_decode"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        assert int(est.abs().max()) == 0 and int(st.abs().max()) == 0
+
+        # the parent's route: the groups sorted by code, one packed buffer per code (not timed)
+        def up16(v):
+            return (v + 15) & ~15
+
+        buckets = []
+        for c, (k, m) in enumerate(codes):
+            idx = np.nonzero(code == c)[0]
+            if not len(idx):
+                continue
+            bo = fec.ragged_layout(k, m, bb[idx])
+            ix = torch.from_numpy(idx).cuda()
+            buckets.append(dict(
+                k=k, m=m, idx=idx, bb=bb_d[ix].contiguous(),
+                off=[torch.from_numpy(o).cuda() for o in bo[:3]], tot=bo[3],
+                data=torch.cat(views(data, d_off[idx], up16(k * bb64[idx]))),
+                blocks=torch.cat(views(blocks, d_off[idx], up16(k * bb64[idx]))),
+                rows=rows[ix][:, :k].contiguous(),
+                par=torch.zeros(bo[3][1], dtype=torch.uint8, device="cuda"),
+                rec=torch.zeros(bo[3][2], dtype=torch.uint8, device="cuda"),
+                rr=torch.zeros((len(idx), min(k, m)), dtype=torch.uint8, device="cuda"),
+                st=torch.zeros(len(idx), dtype=torch.int32, device="cuda")))
+        nb = len(buckets)
+
+        def sorted_encode(ev=None, base=0):
+            for i, B in enumerate(buckets):
+                f = lambda: eng.encode_ragged(B["k"], B["m"], B["bb"], B["data"], B["off"][0],
+                                              B["par"], B["off"][1])
+                timed(ev, base + i, f) if ev else f()
+
+        def sorted_decode(ev=None, base=0):
+            for i, B in enumerate(buckets):
+                f = lambda: eng.decode_ragged_recovered(B["k"], B["m"], B["bb"], B["blocks"],
+                                                        B["off"][0], B["rows"], B["rec"],
+                                                        B["off"][2], B["rr"], status=B["st"])
+                timed(ev, base + i, f) if ev else f()
+
+        # the same bytes from both routes, at the timed size
+        sorted_encode()
+        kern["sorted_encode"] = fec.last_kernels()
+        sorted_decode()
+        kern["sorted_decode"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        for B in buckets:
+            idx, k, m = B["idx"], B["k"], B["m"]
+            assert torch.equal(torch.cat(views(par, p_off[idx], up16(m * bb64[idx]))), B["par"]), \
+                "parity differs between the routes"
+            got = torch.cat(views(rec, r_off[idx], r * bb64[idx]))
+            want = torch.cat(views(B["rec"], B["off"][2].cpu().numpy(), r * bb64[idx]))
+            assert torch.equal(got, want), "recovered blocks differ between the routes"
+            assert torch.equal(got, torch.cat(views(data, d_off[idx], r * bb64[idx]))), \
+                "recovered blocks are not the lost data"
+            assert torch.equal(rr[torch.from_numpy(idx).cuda()][:, :min(k, m)], B["rr"])
+
+        ev = DeviceEvents(2 * (2 + 2 * nb))
+        t = {x: [] for x in ("mixed_encode", "mixed_decode", "sorted_encode", "sorted_decode")}
+        wall = {x: [] for x in t}
+
+        def walled(name, fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            wall[name].append((time.perf_counter() - t0) * 1e3)
+
+        for rep_i in range(args.warmup + args.reps):
+            order = [("mixed_encode", lambda: timed(ev, 0, mixed_encode)),
+                     ("sorted_encode", lambda: sorted_encode(ev, 2)),
+                     ("mixed_decode", lambda: timed(ev, 1, mixed_decode)),
+                     ("sorted_decode", lambda: sorted_decode(ev, 2 + nb))]
+            if rep_i % 2:
+                order = [order[1], order[0], order[3], order[2]]
+            for name, fn in order:
+                walled(name, fn)
+            if rep_i < args.warmup:
+                for x in wall:
+                    wall[x].clear()
+                continue
+            t["mixed_encode"].append(ev.elapsed_ms(0, 1))
+            t["mixed_decode"].append(ev.elapsed_ms(2, 3))
+            t["sorted_encode"].append(sum(ev.elapsed_ms(2 * (2 + i), 2 * (2 + i) + 1)
+                                          for i in range(nb)))
+            t["sorted_decode"].append(sum(ev.elapsed_ms(2 * (2 + nb + i), 2 * (2 + nb + i) + 1)
+                                          for i in range(nb)))
+        ev.close()
+        nbytes = {"encode": int(((ks + ms) * bb64).sum()), "decode": int(((ks + r) * bb64).sum())}
+        line = dict(config=label, mode="mixed", codes=[list(c) for c in codes], losses=r, groups=G,
+                    groups_per_code=[int((code == c).sum()) for c in range(nc)],
+                    ragged_calls_per_phase=nb, reps=args.reps, kernels=kern, grids=fec.last_grids(),
+                    bytes_moved=nbytes)
+        for name, v in t.items():
+            med = statistics.median(v)
+            by = nbytes["encode" if name.endswith("encode") else "decode"]
+            line[name] = dict(kernel_ms_median=round(med, 4), kernel_ms_min=round(min(v), 4),
+                              kernel_ms_max=round(max(v), 4),
+                              wall_ms_median=round(statistics.median(wall[name]), 4),
+                              GBps=round(by / (med * 1e-3) / 1e9, 1))
+        for ph in ("encode", "decode"):
+            for what in ("kernel", "wall"):
+                line[f"{ph}_{what}_mixed_over_sorted"] = round(
+                    line[f"mixed_{ph}"][f"{what}_ms_median"] /
+                    line[f"sorted_{ph}"][f"{what}_ms_median"], 3)
+        cs.close()
+        results.append(line)
+        print(json.dumps(line), flush=True)
+
     G = args.groups
+    if args.mixed:
+        presets = [(5, 5), (10, 10), (10, 15), (10, 20), (15, 15), (250, 5)]
+        run_mixed(presets, 2, G, f"(a) six presets, {G} groups")
+        run_mixed(presets, 2, 1024, "(b) six presets, 1024 groups")
+        run_mixed([(32, 4)], 2, G, f"(c) one code (32,4), {G} groups")
+        args.codes = ""
     mixed = draw_sizes(G, args.seed)
     flat = np.full(G, 1352, np.int32)
     run = run_pp if args.pp else run_config

@@ -8,7 +8,8 @@
 // two helpers of the framed calls (qfec_framed_layout, qfec_framed_rx_block_bytes) on hostile
 // inputs: zero groups, every packet absent, the largest length, offsets past 2^40, and the helper
 // of the arrival-order receiver (qfec_arrivals_rx_block_bytes): duplicates, more than k arrivals,
-// tags outside the batch, no arrival, a tag at the last group;
+// tags outside the batch, no arrival, a tag at the last group; and the layout of the mixed-code
+// batches (qfec_mixed_layout): ragged counts per group, hostile code indices, G = 0;
 // out-of-bounds copies or overflowing arithmetic abort under the sanitizers.
 #include <algorithm>
 #include <climits>
@@ -86,6 +87,147 @@ static void check_pack(int k, int m, bool decode, const std::vector<int>& bb, st
     CHECK((long long)pk.in.size() == up16(in_end));
     CHECK((long long)pk.out.size() == up16(out_end));
     for (unsigned char b : pk.out) CHECK(b == 0);
+}
+
+namespace qfec { struct Chunks; struct Stage; struct StageList; }
+static void check_carve(qfec::StageList& L, const qfec::Chunks& ch);
+
+// ---- qfec_mixed_layout: the block counts of each group's own code, in arrays of exactly G
+// entries; hostile code indices, sizes and sets; G = 0
+static void check_mixed_layout(std::mt19937& rng) {
+    const int ks[] = {10, 1, 2, 3, 5, 32, 10, 250, 250}, ms[] = {1, 3, 2, 2, 5, 4, 20, 5, 7};
+    const int nc = 9;
+    for (int rep = 0; rep < 60; ++rep) {
+        const long long G = rep == 0 ? 0 : 1 + (long long)(rng() % 200);
+        std::vector<unsigned char> code((size_t)G);
+        std::vector<int> bb((size_t)G);
+        for (auto& c : code) c = (unsigned char)(rng() % nc);
+        for (auto& b : bb) b = 1 + (int)(rng() % 2100);
+        std::vector<long long> d((size_t)G), p((size_t)G), r((size_t)G);
+        long long tot[3] = {-1, -1, -1};
+        CHECK(qfec_mixed_layout(nc, ks, ms, G, code.data(), bb.data(), d.data(), p.data(), r.data(),
+                                tot) == 0);
+        long long run[3] = {0, 0, 0};
+        for (long long g = 0; g < G; ++g) {
+            const int k = ks[code[(size_t)g]], m = ms[code[(size_t)g]];
+            const int n[3] = {k, m, k < m ? k : m};
+            const long long got[3] = {d[(size_t)g], p[(size_t)g], r[(size_t)g]};
+            for (int a = 0; a < 3; ++a) {
+                CHECK(got[a] == run[a] && got[a] % 16 == 0);
+                run[a] = up16(run[a] + (long long)n[a] * bb[(size_t)g]);
+            }
+        }
+        CHECK(tot[0] == run[0] && tot[1] == run[1] && tot[2] == run[2]);
+        // any output may be NULL
+        CHECK(qfec_mixed_layout(nc, ks, ms, G, code.data(), bb.data(), nullptr, nullptr, nullptr,
+                                nullptr) == 0);
+        if (G == 0) {
+            CHECK(qfec_mixed_layout(nc, ks, ms, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                    tot) == 0);
+            CHECK(tot[0] == 0 && tot[1] == 0 && tot[2] == 0);
+            continue;
+        }
+        // the staging plan over these groups: a block count per group (0 for a group whose code
+        // index names no code), random gaps, chunks of a few groups and one group per chunk
+        {
+            std::vector<int> nin((size_t)G), nout((size_t)G);
+            std::vector<long long> in_off((size_t)G), out_off((size_t)G);
+            long long ri = 0, ro = 0;
+            for (long long g = 0; g < G; ++g) {
+                const bool none = rng() % 9 == 0;
+                nin[(size_t)g] = none ? 0 : ks[code[(size_t)g]];
+                nout[(size_t)g] = none ? 0 : ms[code[(size_t)g]];
+                in_off[(size_t)g] = ri += 16 * (rng() % 4);
+                out_off[(size_t)g] = ro += 16 * (rng() % 4);
+                ri = up16(ri + (long long)nin[(size_t)g] * bb[(size_t)g]);
+                ro = up16(ro + (long long)nout[(size_t)g] * bb[(size_t)g]);
+            }
+            for (long long target : {1LL << 20, 64LL << 10, 1LL}) {
+                qfec::StageList L{bb.data()};
+                qfec::Stage& in = L.packed(in_off.data(), nin.data());
+                qfec::Stage& out = L.packed(out_off.data(), nout.data());
+                for (size_t b : {4, 8, 8, 4, 1, 250, 10}) L.dense(b);   // bb .. status, code, rows
+                qfec::Chunks ch;
+                const char* msg = nullptr;
+                CHECK(qfec::ragged_chunks(L, in, out, G, target, &ch, &msg) == 0);
+                CHECK(ch.count() >= 1 && ch.begin(0) == 0 && ch.begin(ch.count()) == G);
+                if (target == 1) CHECK(ch.count() == G);                // one group per chunk
+                for (long long i = 0; i < ch.count(); ++i) {
+                    const long long g0 = ch.begin(i), n = ch.begin(i + 1) - g0;
+                    CHECK(n >= 1);
+                    if (n > 1) CHECK((long long)qfec::stage_bytes(L, g0, n) <= target);
+                    const long long last = g0 + n - 1;
+                    CHECK((long long)in.off[last] + (long long)nin[(size_t)last] * bb[(size_t)last] -
+                              in.off[g0] <= (long long)qfec::stage_bytes(L, g0, n));
+                }
+                check_carve(L, ch);
+            }
+            // overlapping by the group's own count: group 0 of 250 blocks, the next 16 bytes on
+            if (G >= 2) {
+                nin[0] = 250;
+                in_off[1] = in_off[0] + 16;
+                qfec::StageList L{bb.data()};
+                qfec::Stage& in = L.packed(in_off.data(), nin.data());
+                qfec::Stage& out = L.packed(out_off.data(), nout.data());
+                qfec::Chunks ch;
+                const char* msg = nullptr;
+                CHECK(qfec::ragged_chunks(L, in, out, G, 1 << 20, &ch, &msg) == -2);
+            }
+        }
+        // one hostile entry at a time; the offset arrays are exactly G long
+        const size_t at = (size_t)(rng() % (unsigned)G);
+        const unsigned char keep_c = code[at];
+        for (int v : {nc, nc + 1, 32, 255}) {
+            code[at] = (unsigned char)v;
+            CHECK(qfec_mixed_layout(nc, ks, ms, G, code.data(), bb.data(), d.data(), p.data(),
+                                    r.data(), tot) == -2);
+        }
+        code[at] = keep_c;
+        const int keep_b = bb[at];
+        for (int v : {0, -1, INT_MIN}) {
+            bb[at] = v;
+            CHECK(qfec_mixed_layout(nc, ks, ms, G, code.data(), bb.data(), d.data(), p.data(),
+                                    r.data(), tot) == -2);
+        }
+        bb[at] = keep_b;
+        // a one-code set is qfec_ragged_layout
+        std::vector<unsigned char> zero((size_t)G, 0);
+        std::vector<long long> d2((size_t)G), p2((size_t)G), r2((size_t)G);
+        long long tot2[3];
+        const int k1[1] = {ks[rep % nc]}, m1[1] = {ms[rep % nc]};
+        CHECK(qfec_mixed_layout(1, k1, m1, G, zero.data(), bb.data(), d.data(), p.data(), r.data(),
+                                tot) == 0);
+        CHECK(qfec_ragged_layout(k1[0], m1[0], G, bb.data(), d2.data(), p2.data(), r2.data(),
+                                 tot2) == 0);
+        CHECK(d == d2 && p == p2 && r == r2 && tot[0] == tot2[0] && tot[1] == tot2[1] &&
+              tot[2] == tot2[2]);
+    }
+    // bad sets and arguments
+    const unsigned char c0[3] = {0, 0, 0};
+    const int b8[3] = {8, 8, 8};
+    long long tot[3];
+    std::vector<int> k33(33, 5);
+    CHECK(qfec_mixed_layout(0, ks, ms, 1, c0, b8, nullptr, nullptr, nullptr, tot) == -2);
+    CHECK(qfec_mixed_layout(33, k33.data(), k33.data(), 1, c0, b8, nullptr, nullptr, nullptr, tot) == -2);
+    CHECK(qfec_mixed_layout(32, k33.data(), k33.data(), 1, c0, b8, nullptr, nullptr, nullptr, tot) == 0);
+    CHECK(qfec_mixed_layout(-1, ks, ms, 0, nullptr, nullptr, nullptr, nullptr, nullptr, tot) == -2);
+    CHECK(qfec_mixed_layout(nc, nullptr, ms, 1, c0, b8, nullptr, nullptr, nullptr, tot) == -2);
+    CHECK(qfec_mixed_layout(nc, ks, nullptr, 1, c0, b8, nullptr, nullptr, nullptr, tot) == -2);
+    CHECK(qfec_mixed_layout(nc, ks, ms, -1, c0, b8, nullptr, nullptr, nullptr, tot) == -2);
+    CHECK(qfec_mixed_layout(nc, ks, ms, 1, nullptr, b8, nullptr, nullptr, nullptr, tot) == -2);
+    CHECK(qfec_mixed_layout(nc, ks, ms, 1, c0, nullptr, nullptr, nullptr, nullptr, tot) == -2);
+    for (int v : {0, 256, -4, INT_MAX}) {
+        const int kb[2] = {5, v}, mb[2] = {5, 5};
+        CHECK(qfec_mixed_layout(2, kb, mb, 1, c0, b8, nullptr, nullptr, nullptr, tot) == -2);
+    }
+    for (int v : {0, -1, INT_MIN}) {
+        const int kb[2] = {5, 5}, mb[2] = {5, v};
+        CHECK(qfec_mixed_layout(2, kb, mb, 1, c0, b8, nullptr, nullptr, nullptr, tot) == -2);
+    }
+    // overflow of the running offset: 2^31 - 1 parity blocks of 2^31 - 1 bytes per group
+    const int kb[1] = {255}, mb[1] = {INT_MAX}, bmax[3] = {INT_MAX, INT_MAX, INT_MAX};
+    CHECK(qfec_mixed_layout(1, kb, mb, 1, c0, bmax, nullptr, nullptr, nullptr, tot) == 0);
+    CHECK(qfec_mixed_layout(1, kb, mb, 3, c0, bmax, nullptr, nullptr, nullptr, tot) == -2);
 }
 
 // ---- the staging plan of the host-pointer batches (fec_host.cpp declares these lists)
@@ -444,6 +586,7 @@ int main() {
     check_plan_errors();
     check_framed(rng);
     check_arrivals(rng);
+    check_mixed_layout(rng);
     // errors: a size < 1, bad arguments, overflow of the running offset
     {
         const int bad[3] = {8, 0, 8};
