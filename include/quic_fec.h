@@ -787,6 +787,103 @@ QFEC_API int qfec_open_decode_extract_arrivals_ragged(
     long long rev_stride, int *d_rev_len, unsigned char *d_rev_pn_len, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * Mixed-code wire path: the framed sender and the arrival-order receiver with a (k, m) per group.
+ *
+ * One adaptive connection produces groups of several codes back to back, and the configuration
+ * travels in every packet's private flags, so a receive ring holds arrivals of groups of
+ * different codes.  The two calls here take the codes through a set (qfec_codeset, d_code [G]) as
+ * the mixed codec does; no block crosses to the host on either side.
+ *
+ * Packet geometry: packet p no longer belongs to group p / (k + m).  Two prefix tables, device
+ * arrays the kernels read when they run (never read back, like d_code, d_bb and the offsets):
+ *   d_pkt_first [G+1] (int32): group g's wire packets and slots are d_pkt_first[g] ..
+ *     d_pkt_first[g] + k_g + m_g - 1; packet d_pkt_first[g] + i is data packet i for i < k_g,
+ *     else FEC packet i - k_g.
+ *   d_pay_first [G+1] (int32, sender only): group g's payload rows, d_pay_len and d_pn_len
+ *     entries are d_pay_first[g] .. d_pay_first[g] + k_g - 1.
+ * npkt and npay are the capacities of the per-packet and per-payload arrays: upper bounds the
+ * host sizes the grids by, so a captured call can be replayed after the tables were rewritten.
+ * qfec_mixed_packet_layout builds both tables.
+ *
+ * Rule, sender: per group the call is qfec_frame_encode_seal_groups_batch_ragged with that
+ * group's (k, m) and bb[g]: the same blocks, parity, packets and d_pkt_len, and the same status
+ * values (the -3 of a rejected frame and the -1 of bb % 8 != 0 included).  Headers, packets and
+ * d_pkt_len are dense by packet index [npkt]; payload rows, d_pay_len and d_pn_len dense by
+ * payload index [npay]; blocks and parity lie in qfec_mixed_layout's packed layout.
+ * Rule, receiver: the acceptance rule of the arrival-order receiver above, steps 1 - 5, with k
+ * and k + m read per group (an index >= k_g + m_g is ignored; late is "after k_g distinct opened
+ * indices"); everything else is, per group, qfec_open_decode_extract_arrivals_ragged with that
+ * group's (k, m, bb) on that group's arrivals in their order.  The slot of arrival a is
+ * d_pkt_first[g] + d_arr_index[a]; d_arr_at and d_open_len are [npkt]; d_rows is [G][kmax] (only
+ * the first k_g entries of a row are written); d_rec_rows is [G][rmax] over the set's rmax (255
+ * from the group's own min(k_g, m_g) on); d_rev, d_rev_len and d_rev_pn_len rows are g*rmax + j
+ * (d_rev_len -1 past the group's own count).
+ *
+ * A group is rejected with status -2 when d_code[g] >= ncodes, when its d_pkt_first span is not
+ * exactly k_g + m_g wide, starts below 0 or reaches past npkt, or (sender) when its d_pay_first
+ * span is not exactly k_g wide, starts below 0 or reaches past npay.  None of its blocks, parity,
+ * packets, rows, revived rows or payloads is read or written; its d_rec_rows are 255; arrivals
+ * tagged to it are QFEC_ARR_IGNORED.  Every packet index below npkt that lies in no valid
+ * group's span (the span of a rejected group clipped to npkt, a gap of the table, the capacity
+ * past the table's total; all of [0, npkt) when groups == 0) is set to d_pkt_len -1 on the
+ * sender, to d_arr_at -1 and d_open_len -1 on the receiver, with either value of
+ * arr_optimistic, and nothing else of it is written.  The tables need not be well formed for memory
+ * safety: entries are read at indices 0 .. G only and every (group, index) is checked before it
+ * is used; a table that is not ascending may give a packet any of the outcomes above.
+ *
+ * Call-level limits, -2 before anything is enqueued: those of the ragged call of the same
+ * direction (with npkt in place of groups*(k+m)) and of the mixed codec calls; a set that holds a
+ * code with k + m > 255; npkt or npay negative or above INT32_MAX.  n == 0 stays valid.
+ * Streams, graphs: enqueue only; qfec_codeset_reserve(cs, groups) covers a capture of either.
+ * Bucket or mix: the sender as the mixed codec (bucket by code when a
+ * bucket fills the device, mix a flush of about a thousand groups: a third of the per-code
+ * calls' time there, 12 % more at 65,536 groups); the receiver was no slower mixed at either
+ * scale, so a ring need not be split by code.
+ * ------------------------------------------------------------------------------- */
+/* Host helper, no GPU: the two prefix tables ([groups + 1] each, either may be NULL) of groups
+ * laid out one after the other.  A group with code[g] >= ncodes gets an empty span in both.
+ * -2 on the argument errors of qfec_mixed_layout and on a total above INT32_MAX. */
+QFEC_API int qfec_mixed_packet_layout(int ncodes, const int *k, const int *m, long long groups,
+                                      const unsigned char *code, int *pkt_first, int *pay_first);
+/* Host helper, no GPU: bb[g] = roundup8(max(pay_len + 2)) over the group's own k_g lengths at
+ * pay_first[g] (NULL: the dense table of qfec_mixed_packet_layout) in pay_len [npay], then
+ * qfec_mixed_layout's offsets and totals.  -2 on a length outside [0, 0x3fff], on a span outside
+ * [0, npay] and on qfec_mixed_layout's errors (code[g] >= ncodes among them). */
+QFEC_API int qfec_framed_layout_mixed(int ncodes, const int *k, const int *m, long long groups,
+                                      const unsigned char *code, const int *pay_first,
+                                      long long npay, const int *pay_len, int *bb,
+                                      long long *data_off, long long *par_off,
+                                      long long *rec_off, long long totals[3]);
+/* Host helper, no GPU: qfec_arrivals_rx_block_bytes with the k and k + m of the arrival's own
+ * group.  Arrivals tagged to a group without a code are skipped (its bb is 0).  -2 also for a
+ * set that holds a code with k + m > 255. */
+QFEC_API int qfec_arrivals_rx_block_bytes_mixed(int ncodes, const int *k, const int *m,
+                                                long long groups, const unsigned char *code,
+                                                long long n, const int *arr_group,
+                                                const unsigned char *arr_index,
+                                                const int *pkt_len, const int *ad_len,
+                                                int ad_len_all, int *bb);
+/* Sender: frame -> qfec_encode_batch_mixed -> seal of every packet. */
+QFEC_API int qfec_frame_encode_seal_groups_batch_mixed(
+    qfec_ctx *ctx, const qfec_codeset *cs, long long groups, const unsigned char *d_code,
+    const int *d_bb, const int *d_pkt_first, const int *d_pay_first, long long npkt,
+    long long npay, unsigned char *d_data, const long long *d_data_off, unsigned char *d_parity,
+    const long long *d_par_off, const unsigned char *d_hdr, long long hdr_stride,
+    const int *d_hdr_len, int hdr_len_all, const unsigned char *d_pay, long long pay_stride,
+    const int *d_pay_len, const unsigned char *d_pn_len, int pn_len_all, unsigned char *d_pkt,
+    long long pkt_stride, int *d_pkt_len, int *d_status, void *stream);
+/* Receiver over arrivals: open -> bind -> qfec_decode_batch_mixed_recovered -> extraction. */
+QFEC_API int qfec_open_decode_extract_arrivals_mixed(
+    qfec_ctx *ctx, const qfec_codeset *cs, long long groups, const unsigned char *d_code,
+    const int *d_bb, const int *d_pkt_first, long long npkt, long long n,
+    const unsigned char *d_pkt, long long pkt_stride, const int *d_pkt_len, const int *d_ad_len,
+    int ad_len_all, const unsigned char *d_pn_len, int pn_len_all, const int *d_arr_group,
+    const unsigned char *d_arr_index, int *d_arr_state, int *d_arr_at, unsigned char *d_blocks,
+    const long long *d_blocks_off, unsigned char *d_rows, int *d_open_len, unsigned char *d_rec,
+    const long long *d_rec_off, unsigned char *d_rec_rows, int *d_status, unsigned char *d_rev,
+    long long rev_stride, int *d_rev_len, unsigned char *d_rev_pn_len, void *stream);
+
+/* ---------------------------------------------------------------------------------
  * Support: the coefficient tables, a seeded synthetic workload, diagnostics.
  * ------------------------------------------------------------------------------- */
 /* Rows 1..m-1 of the Cauchy matrix the reference selects (cauchy_256.cpp:422-480),
@@ -818,7 +915,12 @@ QFEC_API const char *qfec_last_error(void);
  * open_assemble_kernel<framed>" and "extract_revived_kernel"; the arrivals call names
  * "arrivals_init_kernel", "arrivals_pre_kernel", "open_arrivals_kernel",
  * "arrivals_assemble_kernel" and (with d_arr_state) "arrivals_state_kernel" ahead of the decode's
- * and "extract_revived_kernel". */
+ * and "extract_revived_kernel"; the mixed-code wire calls name "mixed_wire_plan_kernel" first and
+ * carry a "<mixed>" suffix on the kernels that read the mixed geometry:
+ * "frame_blocks_kernel<mixed>", "null_seal_kernel<mixed>", "arrivals_pre_kernel<mixed>",
+ * "open_arrivals_kernel<mixed>", "arrivals_assemble_kernel<mixed>", "arrivals_unowned_kernel",
+ * "arrivals_state_kernel<mixed>",
+ * "open_status_kernel<mixed>" and "extract_revived_kernel<mixed>" (around the mixed codec's). */
 QFEC_API const char *qfec_last_kernels(void);
 /* Grids of the persistent kernels the last call on this thread launched, as space-separated
  * "kernel=workgroups" entries (e.g. "gf_psyn_kernel=1024"); diagnostics and tests.  The general

@@ -14,6 +14,7 @@
 #include "gf256.h"
 #include "gf_mixed.h"
 #include "gf_ptrs.h"
+#include "pp_mixed.h"
 #include "pp_null.h"
 
 using namespace qfec;
@@ -964,14 +965,24 @@ static int mixed_reserve(Workspace& W, const qfec::MixedSet& s, long long groups
     return 0;
 }
 
+// The two work arrays of a mixed wire call (pp_mixed.h: eff, ecode) in the workspace's scratch
+// buffer, which no mixed decode uses.
+static size_t mixed_wire_bytes(long long groups) { return (size_t)groups * (sizeof(int32_t) + 1); }
+static void mixed_wire_work(Workspace& W, long long groups, qfec::MixedWire* w) {
+    w->eff = (int32_t*)W.dscratch.p;
+    w->ecode = (uint8_t*)W.dscratch.p + (size_t)groups * sizeof(int32_t);
+}
+
 int qfec_codeset_reserve(qfec_codeset* cs, long long groups) {
     if (!cs || groups < 0) return fail(-2, "null code set or groups < 0");
     qfec_ctx* c = cs->ctx;
     std::lock_guard<std::mutex> lk(c->mu);
     int rc = set_device(c);
     if (rc) return rc;
-    for (Workspace* W : {&c->ws, &c->ws_graph})
+    for (Workspace* W : {&c->ws, &c->ws_graph}) {
         if ((rc = mixed_reserve(*W, cs->s, groups))) return rc;
+        QF_HIP(W->ensure(W->dscratch, mixed_wire_bytes(groups)));
+    }
     return 0;
 }
 
@@ -1432,6 +1443,115 @@ int qfec_open_decode_extract_arrivals_ragged(
                                             (const int32_t*)d_status,
                                             rows_out_of(d_rev, rev_stride, d_rev_len),
                                             d_rev_pn_len, st));
+        return 0;
+    });
+}
+
+// ---- mixed-code wire path: the two calls above with a (k, m) per group (pp_mixed.h).  Nothing
+// here reads d_code, d_bb, the offsets or the prefix tables back: the plan kernel decides every
+// group, and npkt / npay size the grids.
+// The limits both directions add to mixed_check's.  The k + m limit of the set stands here; the
+// shared packet-argument helpers below (seal_ragged_pkt_args, open_decode_args) are therefore
+// called with the smallest code, (1, 1), which passes their own k + m check, for the rest of
+// what they check: the packet arrays, strides and lengths.
+static int mixed_wire_check(const qfec_codeset* cs, long long npkt, long long npay) {
+    for (size_t i = 0; i < cs->k.size(); ++i)
+        if (cs->k[i] + cs->m[i] > 255)
+            return fail(-2, "a code of the set has k + m > 255 (the wire's group-offset byte)");
+    if (npkt < 0 || npkt > INT32_MAX || npay < 0 || npay > INT32_MAX)
+        return fail(-2, "npkt or npay outside [0, INT32_MAX]");
+    return 0;
+}
+
+// plan -> frame -> mixed encode with the plan's codes and sizes -> framed seal
+int qfec_frame_encode_seal_groups_batch_mixed(
+    qfec_ctx* c, const qfec_codeset* cs, long long groups, const unsigned char* d_code,
+    const int* d_bb, const int* d_pkt_first, const int* d_pay_first, long long npkt,
+    long long npay, unsigned char* d_data, const long long* d_data_off, unsigned char* d_parity,
+    const long long* d_par_off, const unsigned char* d_hdr, long long hdr_stride,
+    const int* d_hdr_len, int hdr_len_all, const unsigned char* d_pay, long long pay_stride,
+    const int* d_pay_len, const unsigned char* d_pn_len, int pn_len_all, unsigned char* d_pkt,
+    long long pkt_stride, int* d_pkt_len, int* d_status, void* stream) {
+    int rc = mixed_check(c, cs, groups, cs ? cs->s.enc_nchunk : 0,
+                         {d_code, d_bb, d_data_off, d_par_off, d_pkt_first, d_pay_first}, d_data,
+                         d_parity);
+    if (rc) return rc;
+    if ((rc = mixed_wire_check(cs, npkt, npay))) return rc;
+    const Rows hdr = rows_of(d_hdr, hdr_stride, d_hdr_len, hdr_len_all);
+    const RowsOut pkt = rows_out_of(d_pkt, pkt_stride, d_pkt_len);
+    if ((rc = seal_ragged_pkt_args(1, 1, hdr, pkt))) return rc;
+    if ((rc = framed_rows_args(d_pay, pay_stride, d_pay_len, "bad pay_stride"))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const hipStream_t st = pick(c, stream);
+    const Rows pay = rows_of(d_pay, pay_stride, d_pay_len, 0);
+    return with_workspace(c, st, [&] {
+        Workspace& W = ws_for(c, st);
+        QF_HIP(W.ensure(W.dscratch, mixed_wire_bytes(groups)));
+        qfec::MixedWire w{d_code, (const int32_t*)d_bb, (const int32_t*)d_pkt_first,
+                          (const int32_t*)d_pay_first, npkt, npay, nullptr, nullptr};
+        mixed_wire_work(W, groups, &w);
+        QF_HIP(qfec::launch_mixed_wire_plan(cs->s, groups, w, &pay, st));
+        QF_HIP(qfec::launch_frame_blocks_mixed(cs->s, groups, w, pay, d_pn_len, pn_len_all, d_data,
+                                               d_data_off, st));
+        const int r = encode_mixed_impl(c, cs, groups, {w.ecode, w.eff, d_data_off, d_par_off},
+                                        d_data, d_parity, (int32_t*)d_status, st);
+        if (r) return r;
+        QF_HIP(qfec::launch_null_seal_mixed(cs->s, groups, w, pay, d_parity, d_par_off, hdr, pkt,
+                                            (int32_t*)d_status, st));
+        return 0;
+    });
+}
+
+// plan -> arrivals open (init -> pre -> open -> assemble -> state) -> mixed recovered decode with
+// the plan's codes and sizes -> open_status -> extract
+int qfec_open_decode_extract_arrivals_mixed(
+    qfec_ctx* c, const qfec_codeset* cs, long long groups, const unsigned char* d_code,
+    const int* d_bb, const int* d_pkt_first, long long npkt, long long n,
+    const unsigned char* d_pkt, long long pkt_stride, const int* d_pkt_len, const int* d_ad_len,
+    int ad_len_all, const unsigned char* d_pn_len, int pn_len_all, const int* d_arr_group,
+    const unsigned char* d_arr_index, int* d_arr_state, int* d_arr_at, unsigned char* d_blocks,
+    const long long* d_blocks_off, unsigned char* d_rows, int* d_open_len, unsigned char* d_rec,
+    const long long* d_rec_off, unsigned char* d_rec_rows, int* d_status, unsigned char* d_rev,
+    long long rev_stride, int* d_rev_len, unsigned char* d_rev_pn_len, void* stream) {
+    int rc = mixed_check(c, cs, groups, cs ? cs->s.dec_nchunk : 0,
+                         {d_code, d_bb, d_blocks_off, d_rec_off, d_pkt_first}, d_blocks, d_rec);
+    if (rc) return rc;
+    if ((rc = mixed_wire_check(cs, npkt, 0))) return rc;
+    if ((rc = open_decode_args(1, 1, true, {d_rows, d_open_len, d_rec_rows, d_arr_at}, pkt_stride,
+                               d_ad_len, ad_len_all)))
+        return rc;
+    if ((rc = framed_rows_args(d_rev, rev_stride, d_rev_len, "bad rev_stride"))) return rc;
+    if (n < 0 || n > INT32_MAX) return fail(-2, "n outside [0, INT32_MAX]");
+    // the per-arrival arrays: nothing of them is read when nothing arrived
+    if (n > 0 && any_null({d_pkt, d_pkt_len, d_arr_group, d_arr_index}))
+        return fail(-2, "null buffer");
+    if (groups > 0x7fffffffLL / cs->s.rmax) return fail(-2, "groups * rmax above INT32_MAX");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const hipStream_t st = pick(c, stream);
+    return with_workspace(c, st, [&] {
+        Workspace& W = ws_for(c, st);
+        QF_HIP(W.ensure(W.dscratch, mixed_wire_bytes(groups)));
+        qfec::MixedWire w{d_code, (const int32_t*)d_bb, (const int32_t*)d_pkt_first, nullptr, npkt,
+                          0, nullptr, nullptr};
+        mixed_wire_work(W, groups, &w);
+        QF_HIP(qfec::launch_mixed_wire_plan(cs->s, groups, w, nullptr, st));
+        QF_HIP(qfec::launch_open_arrivals_mixed(
+            cs->s, groups, w, d_blocks_off, n, rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
+            rows_of(nullptr, 0, d_ad_len, ad_len_all), d_pn_len, pn_len_all,
+            (const int32_t*)d_arr_group, d_arr_index, (int32_t*)d_arr_state, (int32_t*)d_arr_at,
+            d_blocks, d_rows, (int32_t*)d_open_len, c->tune.arr_optimistic != 0, st));
+        const int r = decode_mixed_impl(c, cs, groups, {w.ecode, w.eff, d_blocks_off, d_rec_off},
+                                        d_blocks, d_rows, d_rec, d_rec_rows, (int32_t*)d_status,
+                                        st);
+        if (r) return r;
+        QF_HIP(qfec::launch_open_status_mixed(cs->s, groups, w, d_rows, d_rec_rows,
+                                              (int32_t*)d_status, st));
+        QF_HIP(qfec::launch_extract_revived_mixed(cs->s, groups, w, d_rec, d_rec_off, d_rec_rows,
+                                                  (const int32_t*)d_status,
+                                                  rows_out_of(d_rev, rev_stride, d_rev_len),
+                                                  d_rev_pn_len, st));
         return 0;
     });
 }

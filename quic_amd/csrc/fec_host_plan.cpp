@@ -154,6 +154,101 @@ extern "C" int qfec_arrivals_rx_block_bytes(int k, int m, long long groups, long
     return 0;
 }
 
+// ---- the packet geometry of a mixed-code batch: with a code per group, packet p no longer
+// belongs to group p / (k + m), so the wire calls take two prefix tables.
+static bool mixed_codes_ok(int ncodes, const int* k, const int* m) {
+    if (ncodes < 1 || ncodes > 32 || !k || !m) return false;
+    for (int c = 0; c < ncodes; ++c)
+        if (k[c] < 1 || k[c] > 255 || m[c] < 1) return false;
+    return true;
+}
+
+extern "C" int qfec_mixed_packet_layout(int ncodes, const int* k, const int* m, long long groups,
+                                        const unsigned char* code, int* pkt_first,
+                                        int* pay_first) {
+    if (!mixed_codes_ok(ncodes, k, m) || groups < 0 || (groups && !code)) return -2;
+    long long pkt = 0, pay = 0;
+    for (long long g = 0; g < groups; ++g) {
+        if (pkt_first) pkt_first[g] = (int)pkt;
+        if (pay_first) pay_first[g] = (int)pay;
+        if (code[g] >= ncodes) continue;   // no code: an empty span in both tables
+        pkt += (long long)k[code[g]] + m[code[g]];
+        pay += k[code[g]];
+        if (pkt > 0x7fffffffLL) return -2;   // pay <= pkt
+    }
+    if (pkt_first) pkt_first[groups] = (int)pkt;
+    if (pay_first) pay_first[groups] = (int)pay;
+    return 0;
+}
+
+// qfec_framed_layout with each group's own k lengths, at pay_first[g] (null: the dense table
+// qfec_mixed_packet_layout gives); then qfec_mixed_layout's offsets.
+extern "C" int qfec_framed_layout_mixed(int ncodes, const int* k, const int* m, long long groups,
+                                        const unsigned char* code, const int* pay_first,
+                                        long long npay, const int* pay_len, int* bb,
+                                        long long* data_off, long long* par_off,
+                                        long long* rec_off, long long totals[3]) {
+    if (!mixed_codes_ok(ncodes, k, m) || groups < 0 || npay < 0 ||
+        (groups && (!code || !bb || !pay_len)))
+        return -2;
+    long long run = 0;
+    for (long long g = 0; g < groups; ++g) {
+        if (code[g] >= ncodes) return -2;
+        const int kg = k[code[g]];
+        const long long at = pay_first ? pay_first[g] : run;
+        if (at < 0 || at > npay - kg) return -2;   // the group's lengths lie outside pay_len
+        run = at + kg;
+        int most = 0;
+        for (int i = 0; i < kg; ++i) {
+            const int len = pay_len[at + i];
+            if (len < 0 || len > 0x3fff) return -2;
+            most = std::max(most, len);
+        }
+        bb[g] = (most + 2 + 7) & ~7;
+    }
+    return qfec_mixed_layout(ncodes, k, m, groups, code, bb, data_off, par_off, rec_off, totals);
+}
+
+// qfec_arrivals_rx_block_bytes with k and k + m of the arrival's own group.
+extern "C" int qfec_arrivals_rx_block_bytes_mixed(int ncodes, const int* k, const int* m,
+                                                  long long groups, const unsigned char* code,
+                                                  long long n, const int* arr_group,
+                                                  const unsigned char* arr_index,
+                                                  const int* pkt_len, const int* ad_len,
+                                                  int ad_len_all, int* bb) {
+    if (!mixed_codes_ok(ncodes, k, m) || groups < 0 || n < 0 || (groups && (!bb || !code)) ||
+        (n && (!arr_group || !arr_index || !pkt_len)))
+        return -2;
+    for (int c = 0; c < ncodes; ++c)
+        if (k[c] + (long long)m[c] > 255) return -2;
+    // an index is a byte: 256 slots per group hold every tag
+    std::vector<unsigned char> seen;
+    std::vector<int> held;
+    try {
+        if (groups > 0x7fffffffLL) return -2;
+        seen.assign((size_t)groups * 256, 0);
+        held.assign((size_t)groups, 0);
+    } catch (const std::bad_alloc&) {
+        return -2;
+    }
+    for (long long g = 0; g < groups; ++g) bb[g] = 0;
+    for (long long a = 0; a < n; ++a) {
+        const long long g = arr_group[a];
+        const int i = arr_index[a];
+        if (g < 0 || g >= groups || code[g] >= ncodes) continue;   // no group, or one without a code
+        const int kg = k[code[g]], per = kg + m[code[g]];
+        if (i >= per) continue;                                     // no packet of this group
+        const long long tl = pkt_len[a], al = ad_len ? ad_len[a] : ad_len_all;
+        if (tl < 0 || al < 0 || tl - al < 12) continue;             // no packet
+        if (seen[(size_t)(g * 256 + i)] || held[(size_t)g] >= kg) continue;   // duplicate, late
+        seen[(size_t)(g * 256 + i)] = 1;
+        ++held[(size_t)g];
+        const long long size = tl - al - 12 + (i < kg ? 2 : 0);
+        bb[g] = (int)std::max<long long>(bb[g], std::min<long long>(size, 0x7fffffffLL));
+    }
+    return 0;
+}
+
 namespace qfec {
 
 int ragged_pack(int k, int m, bool decode, const std::vector<const unsigned char*>& blocks,

@@ -43,8 +43,15 @@
 // data plaintext two bytes into its slot and writes the prefix), plus the two kernels that only
 // move bytes through tile_stream: frame_blocks_kernel (payload rows -> blocks) and
 // extract_revived_kernel (recovered blocks -> payload rows).
+//
+// Mixed forms (a (k, m) per group through a code set; pp_mixed.h): the
+// framed sender and the arrival-order receiver over a geometry of two prefix tables.  The
+// per-arrival and per-group kernels are one body over a geometry type (UniGeo, MixedGeo); the
+// seal takes MixedRows, whose packets find their group by a search of the table
+// (mixed_group_of); mixed_wire_plan_kernel decides every group once for all of them.
 #include "fec_kernels.h"
 #include "pp_null.h"
+#include "pp_mixed.h"
 
 namespace qfec {
 
@@ -612,9 +619,185 @@ __device__ __forceinline__ void pt_status(const FramedRows& r, long long p) {
     if (r.status && p == g * per && framed_rejects(r, g)) r.status[g] = -3;
 }
 
+// Where a packet lies among the rows: the three lookups above find the group of packet p by a
+// division, so their place is p itself.
+__device__ __forceinline__ long long pt_where(const PtRows&, long long p) { return p; }
+__device__ __forceinline__ long long pt_where(const RaggedRows&, long long p) { return p; }
+__device__ __forceinline__ long long pt_where(const FramedRows&, long long p) { return p; }
+
+// ------------------------------------------------------------------ mixed geometry
+// With a code per group (a code set, gf_mixed.h) packet p no longer belongs to group
+// p / (k + m): the groups' spans are a prefix table first [G + 1], and a group's k and m are
+// the MixedCode record of its code.  The plan kernel below decides once which groups a call
+// runs (ecode[g] = code[g], or 255 for a rejected group) and with which size (eff[g]); every
+// other kernel reads those two arrays, so no two of them can disagree about a group.
+// The geometry a per-arrival or per-group kernel asks.  find(g, &l) says whether the call runs
+// group g and fills the lane's record l; k(l), m(l) and first(l, g), the group's first packet /
+// slot, read it; find_wave is find for a group that is the same in every lane of the wave;
+// rows(g) is the group's row of the rows array.  Uniform: constants, and an empty record.
+struct UniGeo {
+    int kk, mm, pp;   // pp = k + m
+    // what a kernel takes in its arguments to build the geometry from (two scalars here, so
+    // that the uniform kernels keep the argument block they had)
+    typedef int A0;
+    typedef int A1;
+    __device__ __forceinline__ UniGeo(int k, int m) : kk(k), mm(m), pp(k + m) {}
+    struct Lane {};
+    __device__ __forceinline__ bool find(long long, Lane*) const { return true; }
+    __device__ __forceinline__ bool find_wave(long long, Lane*) const { return true; }
+    __device__ __forceinline__ int k(const Lane&) const { return kk; }
+    __device__ __forceinline__ int m(const Lane&) const { return mm; }
+    __device__ __forceinline__ int per(const Lane&) const { return pp; }
+    __device__ __forceinline__ long long first(const Lane&, long long g) const { return g * pp; }
+    __device__ __forceinline__ long long rows(long long g) const { return g * kk; }
+};
+// Mixed: the MixedCode record of ecode[g] (255: no group of this call) and first[g].  The loads
+// are per lane; the table of records is at most 1 KiB and stays in cache.
+struct MixedTabs {
+    const MixedCode* codes;
+    const uint8_t* ecode;
+    const int32_t* pkt_first;
+};
+struct MixedGeo {
+    const MixedCode* codes;
+    const uint8_t* ecode;
+    const int32_t* pkt_first;
+    int kmax;
+    typedef MixedTabs A0;
+    typedef int A1;
+    __host__ __device__ __forceinline__ MixedGeo(const MixedTabs& t, int kmax_)
+        : codes(t.codes), ecode(t.ecode), pkt_first(t.pkt_first), kmax(kmax_) {}
+    struct Lane {
+        int k, m;
+        long long first;
+    };
+    __device__ __forceinline__ bool find(long long g, Lane* l) const {
+        const uint32_t ci = ecode[g];
+        if (ci == 255) return false;
+        *l = {codes[ci].k, codes[ci].m, (long long)pkt_first[g]};
+        return true;
+    }
+    __device__ __forceinline__ bool find_wave(long long g, Lane* l) const {
+        const uint32_t ci = (uint32_t)__builtin_amdgcn_readfirstlane((int)ecode[g]);
+        if (ci == 255) return false;
+        *l = {__builtin_amdgcn_readfirstlane(codes[ci].k),
+              __builtin_amdgcn_readfirstlane(codes[ci].m),
+              (long long)__builtin_amdgcn_readfirstlane(pkt_first[g])};
+        return true;
+    }
+    __device__ __forceinline__ int k(const Lane& l) const { return l.k; }
+    __device__ __forceinline__ int m(const Lane& l) const { return l.m; }
+    __device__ __forceinline__ int per(const Lane& l) const { return l.k + l.m; }
+    __device__ __forceinline__ long long first(const Lane& l, long long) const { return l.first; }
+    __device__ __forceinline__ long long rows(long long g) const { return g * kmax; }
+};
+
+// One lane per group: the verdict on group g (pp_mixed.h, launch_mixed_wire_plan).
+__global__ __launch_bounds__(kPPThreads) void mixed_wire_plan_kernel(
+    long long groups, const MixedCode* __restrict__ codes, int ncodes,
+    const uint8_t* __restrict__ code, const int32_t* __restrict__ bbs,
+    const int32_t* __restrict__ pkt_first, long long npkt, const int32_t* __restrict__ pay_first,
+    long long npay, const int32_t* __restrict__ pay_len, long long pay_stride, int32_t* eff,
+    uint8_t* ecode) {
+    const long long g = (long long)blockIdx.x * kPPThreads + threadIdx.x;
+    if (g >= groups) return;
+    const uint32_t ci = code[g];
+    bool ok = ci < (uint32_t)ncodes;
+    int k = 0, bb = 0;
+    long long p0 = 0;
+    if (ok) {
+        k = codes[ci].k;
+        const long long per = (long long)k + codes[ci].m;
+        const long long f0 = pkt_first[g], f1 = pkt_first[g + 1];
+        ok = f0 >= 0 && f1 - f0 == per && f0 + per <= npkt;
+        if (pay_first) {
+            p0 = pay_first[g];
+            ok = ok && p0 >= 0 && (long long)pay_first[g + 1] - p0 == k && p0 + k <= npay;
+        }
+    }
+    if (ok) {
+        bb = bbs[g];
+        if (pay_first && framed_group_rejects(pay_len + p0, k, pay_stride, bb)) bb = 0;
+    }
+    ecode[g] = ok ? (uint8_t)ci : (uint8_t)255;
+    eff[g] = bb;
+}
+
+// The group whose span of `first` holds x, for the lanes of one wave whose x are x0 .. x0 + 63
+// (x0 from the workgroup index, so that the compiler sees it and the two bounds as uniform):
+// the last g in [0, G) with first[g] <= x (empty spans in front of it are passed over).  Two
+// searches with wave-uniform indices for x0 and x0 + 63, then each lane's own search between
+// the two answers.  Every loop's trip count depends on G and the two uniform answers alone, so
+// the lanes never leave a loop apart; every index read lies in [0, G).  A table that is not
+// ascending gives some group of the batch; the caller checks x against that group's span.
+__device__ __forceinline__ long long mixed_group_of(const int32_t* first, long long G,
+                                                    long long x, long long x0) {
+    long long b0 = 0, b1 = 0;
+    for (long long len = G; len > 1;) {
+        const long long half = len >> 1;
+        const long long v0 = __builtin_amdgcn_readfirstlane(first[b0 + half]);
+        const long long v1 = __builtin_amdgcn_readfirstlane(first[b1 + half]);
+        b0 = v0 <= x0 ? b0 + half : b0;
+        b1 = v1 <= x0 + 63 ? b1 + half : b1;
+        len -= half;
+    }
+    long long b = b0;
+    for (long long len = b1 - b0 + 1; len > 1;) {   // b1 < b0 (a hostile table): no step
+        const long long half = len >> 1;
+        b = (long long)first[b + half] <= x ? b + half : b;
+        len -= half;
+    }
+    return b;
+}
+
+// Rows of the mixed framed sender: FramedRows with the packet's place found by the tables.
+struct MixedRows {
+    Rows pay;
+    const uint8_t* par;
+    const long long* par_off;
+    const int32_t* eff;
+    const uint8_t* ecode;
+    const MixedCode* codes;
+    const int32_t* pkt_first;
+    const int32_t* pay_first;
+    long long groups, npkt;
+    int32_t* status;
+};
+// g < 0: the packet lies in no group the call runs
+struct MixedAt {
+    long long g, pay;   // pay: the payload row of a data packet
+    int i, k, m, bb;
+};
+__device__ __forceinline__ MixedAt pt_where(const MixedRows& r, long long p) {
+    MixedAt w{-1, 0, 0, 0, 0, 0};
+    if (r.groups <= 0) return w;   // uniform
+    const long long g = mixed_group_of(r.pkt_first, r.groups, p, (long long)blockIdx.x * 64);
+    const uint32_t ci = r.ecode[g];
+    if (ci == 255 || p >= r.npkt) return w;
+    const int k = r.codes[ci].k, m = r.codes[ci].m;
+    const long long d = p - r.pkt_first[g];
+    if (d < 0 || d >= k + m) return w;
+    return {g, d < k ? r.pay_first[g] + d : 0, (int)d, k, m, r.eff[g]};
+}
+__device__ __forceinline__ const uint8_t* pt_row(const MixedRows& r, const MixedAt& w) {
+    return w.i < w.k ? r.pay.p + w.pay * r.pay.stride
+                     : r.par + r.par_off[w.g] + (w.i - w.k) * (long long)w.bb;
+}
+__device__ __forceinline__ int pt_len_of(const MixedRows& r, const int32_t*, int,
+                                         const MixedAt& w) {
+    return w.g < 0 ? -1 : w.i < w.k ? r.pay.len[w.pay] : w.bb;
+}
+__device__ __forceinline__ bool pt_fits(const MixedRows&, const MixedAt& w, int) {
+    return w.g >= 0 && w.bb > 0 && !ragged_encode_rejects(w.k, w.m, w.bb);
+}
+// eff 0 in a group the plan kept: the frame's rejection
+__device__ __forceinline__ void pt_status(const MixedRows& r, const MixedAt& w) {
+    if (r.status && w.g >= 0 && w.i == 0 && w.bb == 0) r.status[w.g] = -3;
+}
+
 // One wave seals 64 packets (one per lane): the AD through the lane's own streamer (a few
 // bytes), the plaintext through the wave's LDS tile (tile_stream), then the tag.  R: where the
-// plaintext rows are (PtRows, RaggedRows, FramedRows).
+// plaintext rows are (PtRows, RaggedRows, FramedRows, MixedRows).
 template <class H, class R>
 __global__ __launch_bounds__(64) void null_seal_kernel(
     long long n, const uint8_t* __restrict__ ad, long long ad_stride,
@@ -622,17 +805,18 @@ __global__ __launch_bounds__(64) void null_seal_kernel(
     int pt_all, uint8_t* out, long long out_stride, int32_t* out_len) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+    const auto at = pt_where(pr, i);   // asked by every lane of the wave (MixedRows searches)
     bool ok = false;
     int al = 0, pl = 0;
     if (i < n) {
         al = len_of(ad_len, ad_all, i);
-        pl = pt_len_of(pr, pt_len, pt_all, i);
+        pl = pt_len_of(pr, pt_len, pt_all, at);
         // a row longer than its stride would read the next packet's bytes (or past the buffer
         // for the last one): rejected like a packet that does not fit
         ok = al >= 0 && pl >= 0 && (ad_stride == 0 || al <= ad_stride) &&
-             pt_fits(pr, i, pl) && (long long)al + 12 + pl <= out_stride;
+             pt_fits(pr, at, pl) && (long long)al + 12 + pl <= out_stride;
         out_len[i] = ok ? al + 12 + pl : -1;
-        pt_status(pr, i);
+        pt_status(pr, at);
     }
     uint8_t* o = out + (ok ? i : 0) * out_stride;
     H h;
@@ -641,7 +825,7 @@ __global__ __launch_bounds__(64) void null_seal_kernel(
     s.begin(o);
     if (ok) span<true, true, 1>(h, s, ad + i * ad_stride, al);   // a few bytes: 16-byte pieces
     t = s;   // AD's unstored tail bytes; the tag follows them once it is known
-    tile_stream(h, ok ? pt_row(pr, i) : nullptr, ok ? pl : 0, o + al + 12, ok ? pl : 0, smem);
+    tile_stream(h, ok ? pt_row(pr, at) : nullptr, ok ? pl : 0, o + al + 12, ok ? pl : 0, smem);
     if (!ok) return;
     uint32_t t0, t1, t2;
     h.tag(t0, t1, t2);
@@ -948,15 +1132,28 @@ __global__ __launch_bounds__(kAsmWaves * 64) void open_assemble_kernel(
 
 // After the decode: a group with an unfilled slot (row 255) is malformed whatever path
 // decoded it (the m = 1 XOR decode takes any row >= k as its parity block): status -3 and no
-// recovered rows.
-__global__ __launch_bounds__(kPPThreads) void open_status_kernel(long long groups, int k,
+// recovered rows.  K: the group's k and its rows (UniRowsK; MixedGeo, where a rejected group
+// keeps the status -2 the decode gave it).
+struct UniRowsK {
+    int kk;
+    struct Lane {};
+    __device__ __forceinline__ bool find(long long, Lane*) const { return true; }
+    __device__ __forceinline__ int k(const Lane&) const { return kk; }
+    __device__ __forceinline__ long long rows(long long g) const { return g * kk; }
+};
+
+template <class K>
+__global__ __launch_bounds__(kPPThreads) void open_status_kernel(long long groups, K ge,
                                                                  int rmax,
                                                                  const uint8_t* __restrict__ rows,
                                                                  uint8_t* rec_rows,
                                                                  int32_t* status) {
     const long long g = (long long)blockIdx.x * kPPThreads + threadIdx.x;
     if (g >= groups) return;
-    const uint8_t* r = rows + g * k;
+    typename K::Lane gl{};
+    if (!ge.find(g, &gl)) return;
+    const int k = ge.k(gl);
+    const uint8_t* r = rows + ge.rows(g);
     bool unfilled = false;
     for (int i = 0; i < k; ++i) unfilled |= r[i] == 255;
     if (!unfilled) return;
@@ -994,6 +1191,41 @@ __global__ __launch_bounds__(64) __attribute__((flatten)) void frame_blocks_kern
         if (i == 0) {
             if (eff) eff[g] = ok ? bb : 0;
             if (status) status[g] = ok ? 0 : -3;
+        }
+        if (ok) len = pay_len[q];
+    }
+    uint8_t* blk = ok ? data + data_off[g] + i * (long long)bb : nullptr;
+    NoHash h;
+    tile_stream(h, ok ? pay + q * pay_stride : nullptr, len, ok ? blk + 2 : nullptr,
+                ok ? bb - 2 : 0, smem);
+    if (!ok) return;
+    const uint32_t v = (uint32_t)len | ((uint32_t)(pn_len ? pn_len[q] : pn_all) << 14);
+    gst8(blk, v);
+    gst8(blk + 1, v >> 8);
+}
+
+// The same over the mixed geometry: one lane per payload row q of [npay], its group found by
+// the pay_first table (mixed_group_of), its place checked against the group's span.  The plan
+// kernel has asked framed_group_rejects for every group already: eff[g] is bb[g], or 0 for a
+// group that is not framed, so the lanes read the verdict where frame_blocks_kernel forms it.
+__global__ __launch_bounds__(64) __attribute__((flatten)) void frame_blocks_mixed_kernel(
+    long long groups, long long npay, const MixedCode* __restrict__ codes,
+    const uint8_t* __restrict__ ecode, const int32_t* __restrict__ eff,
+    const int32_t* __restrict__ pay_first, const uint8_t* __restrict__ pay, long long pay_stride,
+    const int32_t* __restrict__ pay_len, const uint8_t* __restrict__ pn_len, int pn_all,
+    uint8_t* data, const long long* __restrict__ data_off) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const long long q = (long long)blockIdx.x * 64 + threadIdx.x;
+    const long long g = mixed_group_of(pay_first, groups, q, (long long)blockIdx.x * 64);
+    bool ok = false;
+    int len = 0, bb = 0;
+    long long i = 0;
+    if (q < npay) {
+        const uint32_t ci = ecode[g];
+        if (ci != 255) {
+            i = q - pay_first[g];
+            bb = eff[g];
+            ok = i >= 0 && i < codes[ci].k && bb > 0;
         }
         if (ok) len = pay_len[q];
     }
@@ -1070,19 +1302,23 @@ __global__ __launch_bounds__(kPPThreads) void arrivals_init_kernel(long long slo
 }
 
 // One lane per arrival: a data arrival with a tag of this batch that passes the length checks
-// takes the minimum of pre_at[g * (k + m) + i] with its own index.
+// takes the minimum of pre_at[g * (k + m) + i] with its own index.  Ge: the groups' geometry
+// (UniGeo, MixedGeo), here and in the kernels below.
+template <class Ge>
 __global__ __launch_bounds__(kPPThreads) void arrivals_pre_kernel(
-    int k, int m, FramedSlots sl, long long n, long long pkt_stride,
+    typename Ge::A0 g0, typename Ge::A1 g1, FramedSlots sl, long long n, long long pkt_stride,
     const int32_t* __restrict__ pkt_len, const int32_t* __restrict__ ad_len, int ad_all,
     const int32_t* __restrict__ arr_group, const uint8_t* __restrict__ arr_index,
     int32_t* pre_at) {
+    const Ge ge(g0, g1);
     const long long a = (long long)blockIdx.x * kPPThreads + threadIdx.x;
     if (a >= n) return;
     const long long g = arr_group[a];
     const int i = arr_index[a];
-    if (g < 0 || g >= sl.r.groups || i >= k) return;
+    typename Ge::Lane gl{};
+    if (g < 0 || g >= sl.r.groups || !ge.find(g, &gl) || i >= ge.k(gl)) return;
     if (open_len_ok(pkt_len, ad_len, ad_all, a, sl.limit(sl.size(g), true), pkt_stride))
-        atomicMin(pre_at + g * (k + m) + i, (int32_t)a);
+        atomicMin(pre_at + ge.first(gl, g) + i, (int32_t)a);
 }
 
 // One lane per arrival, 64 per wave: the length checks of the framed open against the tagged
@@ -1093,31 +1329,33 @@ __global__ __launch_bounds__(kPPThreads) void arrivals_pre_kernel(
 // pre_at (null: no optimistic write): the data arrival that is its slot's first candidate by
 // the length checks writes prefix || plaintext || zeros into the slot, before its tag is known;
 // the assemble overwrites the slot where another packet is accepted for it.
-template <class H>
+template <class H, class Ge>
 __global__ __launch_bounds__(64) void open_arrivals_kernel(
-    int k, int m, FramedSlots sl, long long n, const uint8_t* __restrict__ pkt,
-    long long pkt_stride, const int32_t* __restrict__ pkt_len,
+    typename Ge::A0 g0, typename Ge::A1 g1, FramedSlots sl, long long n,
+    const uint8_t* __restrict__ pkt, long long pkt_stride, const int32_t* __restrict__ pkt_len,
     const int32_t* __restrict__ ad_len, int ad_all, const int32_t* __restrict__ arr_group,
     const uint8_t* __restrict__ arr_index, int32_t* arr_state, int32_t* arr_at,
     const int32_t* __restrict__ pre_at, uint8_t* blocks) {
+    const Ge ge(g0, g1);
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const long long a = (long long)blockIdx.x * 64 + threadIdx.x;
-    const int per = k + m;
     bool tagged = false, ok = false, place = false;
     long long g = 0;
+    typename Ge::Lane gl{};
     int i = 0, al = 0, cl = 0, bb = -1;
     if (a < n) {
         g = arr_group[a];
         i = arr_index[a];
-        tagged = g >= 0 && g < sl.r.groups && i < per;
+        tagged = g >= 0 && g < sl.r.groups && ge.find(g, &gl) && i < ge.per(gl);
         if (tagged) {
             bb = sl.size(g);
             al = len_of(ad_len, ad_all, a);
             cl = pkt_len[a] - al;
-            ok = open_len_ok(pkt_len, ad_len, ad_all, a, sl.limit(bb, i < k), pkt_stride);
-            place = ok && i < k && pre_at && pre_at[g * per + i] == (int32_t)a;
+            ok = open_len_ok(pkt_len, ad_len, ad_all, a, sl.limit(bb, i < ge.k(gl)), pkt_stride);
+            place = ok && i < ge.k(gl) && pre_at && pre_at[ge.first(gl, g) + i] == (int32_t)a;
         }
     }
+    const int k = ge.k(gl);
     const uint8_t* pp = pkt + (ok ? a : 0) * pkt_stride;
     const uint8_t* c = pp + al;
     H h;
@@ -1134,7 +1372,7 @@ __global__ __launch_bounds__(64) void open_arrivals_kernel(
         h.tag(t0, t1, t2);
         opened = tag_matches(c, t0, t1, t2);
     }
-    if (opened) atomicMin(arr_at + g * per + i, (int32_t)a);
+    if (opened) atomicMin(arr_at + ge.first(gl, g) + i, (int32_t)a);
     if (arr_state) arr_state[a] = !tagged ? kArrIgnored : opened ? cl - 12 : kArrRejected;
 }
 
@@ -1176,20 +1414,26 @@ __device__ void wave_place(uint8_t* dst, const uint8_t* src, int pl, int bb, int
 // accepted packet's plaintext in its slot, a data packet's behind its prefix.  optimistic: on
 // entry open_len holds arrivals_pre_kernel's table, and a data slot whose accepted arrival is
 // the one named there was written by the open pass.
+template <class Ge>
 __global__ __launch_bounds__(kAsmWaves * 64) void arrivals_assemble_kernel(
-    int k, int m, FramedSlots sl, const uint8_t* __restrict__ pkt, long long pkt_stride,
-    const int32_t* __restrict__ pkt_len, const int32_t* __restrict__ ad_len, int ad_all,
-    int32_t* arr_state, int32_t* arr_at, int32_t* open_len, bool optimistic, uint8_t* blocks,
-    uint8_t* rows) {
+    typename Ge::A0 g0, typename Ge::A1 g1, FramedSlots sl, const uint8_t* __restrict__ pkt,
+    long long pkt_stride, const int32_t* __restrict__ pkt_len,
+    const int32_t* __restrict__ ad_len, int ad_all, int32_t* arr_state, int32_t* arr_at,
+    int32_t* open_len, bool optimistic, uint8_t* blocks, uint8_t* rows) {
+    const Ge ge(g0, g1);
     __shared__ int32_t cand[kAsmWaves][256];   // the slot's candidate, then its accepted arrival
     __shared__ uint8_t lavail[kAsmWaves][256], lhole[kAsmWaves][256];
     __shared__ uint8_t inplace[kAsmWaves][256];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long long g = (long long)blockIdx.x * kAsmWaves + w;
     if (g >= sl.r.groups) return;   // uniform over the wave; no workgroup barrier below
+    typename Ge::Lane gl{};
+    if (!ge.find_wave(g, &gl)) return;   // the same: one group per wave
+    const int k = ge.k(gl), m = ge.m(gl);
     const int bb = sl.size(g);
-    const int per = k + m;
-    int32_t* at = arr_at + g * per;
+    const int per = ge.per(gl);
+    const long long first = ge.first(gl, g);
+    int32_t* at = arr_at + first;
     const unsigned long long below = (1ull << lane) - 1ull;
     for (int s = lane; s < per; s += 64) cand[w][s] = at[s];
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes are visible
@@ -1215,8 +1459,8 @@ __global__ __launch_bounds__(kAsmWaves * 64) void arrivals_assemble_kernel(
             const int32_t a = keep[q];
             cand[w][s] = a;
             at[s] = a;
-            inplace[w][s] = optimistic && a >= 0 && open_len[g * per + s] == a;
-            open_len[g * per + s] = a < 0 ? -1 : pkt_len[a] - len_of(ad_len, ad_all, a) - 12;
+            inplace[w][s] = optimistic && a >= 0 && open_len[first + s] == a;
+            open_len[first + s] = a < 0 ? -1 : pkt_len[a] - len_of(ad_len, ad_all, a) - 12;
         }
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -1244,7 +1488,7 @@ __global__ __launch_bounds__(kAsmWaves * 64) void arrivals_assemble_kernel(
                 row = r < na ? k + lavail[w][r] : 255;
                 if (r < na) lhole[w][r] = (uint8_t)i;
             }
-            rows[g * k + i] = (uint8_t)row;
+            rows[ge.rows(g) + i] = (uint8_t)row;
         }
         nh += __popcll(bal);
     }
@@ -1272,14 +1516,40 @@ __global__ __launch_bounds__(kAsmWaves * 64) void arrivals_assemble_kernel(
 // One lane per arrival, after the assemble: an arrival that opened (arr_state >= 0) and is not
 // the one its slot kept was not the first copy of its index: kArrDuplicate.  (The first copy
 // of a slot that was not kept already carries kArrLate.)
+// Mixed geometry only, one lane per slot, after the assemble: a slot below npkt that no group of
+// the call owns (the clipped span of a rejected group, a gap of the table, the capacity past the
+// table's total) still holds the init pass's kArrNone, which no arrival index can equal; it and
+// its open_len become -1, as a slot without an accepted arrival has them.  (With the uniform
+// geometry every slot belongs to a group and the assemble writes it.)
+__global__ __launch_bounds__(kPPThreads) void arrivals_unowned_kernel(long long slots,
+                                                                      int32_t* arr_at,
+                                                                      int32_t* open_len) {
+    const long long p = (long long)blockIdx.x * kPPThreads + threadIdx.x;
+    if (p >= slots) return;
+    if (arr_at[p] != kArrNone) return;
+    arr_at[p] = -1;
+    open_len[p] = -1;
+}
+
+// F: a group's first slot (UniFirst, MixedFirst); only an arrival tagged to a group the call
+// runs has a state >= 0.
+struct UniFirst {
+    int per;
+    __device__ __forceinline__ long long operator()(long long g) const { return g * per; }
+};
+struct MixedFirst {
+    const int32_t* first;
+    __device__ __forceinline__ long long operator()(long long g) const { return first[g]; }
+};
+template <class F>
 __global__ __launch_bounds__(kPPThreads) void arrivals_state_kernel(
-    int per, long long n, const int32_t* __restrict__ arr_group,
+    F first, long long n, const int32_t* __restrict__ arr_group,
     const uint8_t* __restrict__ arr_index, const int32_t* __restrict__ arr_at,
     int32_t* arr_state) {
     const long long a = (long long)blockIdx.x * kPPThreads + threadIdx.x;
     if (a >= n) return;
     if (arr_state[a] < 0) return;
-    if (arr_at[(long long)arr_group[a] * per + arr_index[a]] != (int32_t)a)
+    if (arr_at[first((long long)arr_group[a]) + arr_index[a]] != (int32_t)a)
         arr_state[a] = kArrDuplicate;
 }
 
@@ -1399,43 +1669,64 @@ hipError_t launch_open_groups_framed(int k, int m, long long groups, RaggedView 
                    blocks, rows, open_len, st);
 }
 
+// The arrival-order open over the geometry ge (UniGeo, MixedGeo): slots = the length of arr_at
+// and open_len; mixed: the kernels' names carry "<mixed>".
+template <class Ge, class F>
+static hipError_t arrivals_go(bool mixed, typename Ge::A0 g0, typename Ge::A1 g1, F first, long long groups, long long slots,
+                              FramedSlots sl, long long n, Rows pkt, Rows ad,
+                              const int32_t* arr_group, const uint8_t* arr_index,
+                              int32_t* arr_state, int32_t* arr_at, uint8_t* blocks, uint8_t* rows,
+                              int32_t* open_len, bool optimistic, hipStream_t st) {
+    if (n > 0x7fffffffLL || slots > 0x7fffffffLL) return hipErrorInvalidValue;
+    if ((groups + kAsmWaves - 1) / kAsmWaves > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (slots > 0) {
+        note_kernel("arrivals_init_kernel");
+        qlaunch(arrivals_init_kernel, dim3(pp_grid(slots)), dim3(kPPThreads), 0, st, slots, arr_at,
+                optimistic ? open_len : nullptr);
+    }
+    if (n > 0 && slots > 0 && groups > 0 && optimistic) {
+        note_kernel(mixed ? "arrivals_pre_kernel<mixed>" : "arrivals_pre_kernel");
+        qlaunch(arrivals_pre_kernel<Ge>, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, g0, g1, sl, n,
+                pkt.stride, pkt.len, ad.len, ad.len_all, arr_group, arr_index, open_len);
+    }
+    if (n > 0) {
+        note_kernel(mixed ? "open_arrivals_kernel<mixed>" : "open_arrivals_kernel");
+        qlaunch((open_arrivals_kernel<Fnv, Ge>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, g0,
+                g1, sl, n, pkt.p, pkt.stride, pkt.len, ad.len, ad.len_all, arr_group, arr_index,
+                arr_state, arr_at, slots > 0 && groups > 0 && optimistic ? open_len : nullptr,
+                blocks);
+    }
+    if (slots > 0 && groups > 0) {
+        note_kernel(mixed ? "arrivals_assemble_kernel<mixed>" : "arrivals_assemble_kernel");
+        qlaunch(arrivals_assemble_kernel<Ge>,
+                dim3((unsigned)((groups + kAsmWaves - 1) / kAsmWaves)), dim3(kAsmWaves * 64), 0, st,
+                g0, g1, sl, pkt.p, pkt.stride, pkt.len, ad.len, ad.len_all, arr_state, arr_at, open_len,
+                optimistic, blocks, rows);
+    }
+    if (mixed && slots > 0) {
+        note_kernel("arrivals_unowned_kernel");
+        qlaunch(arrivals_unowned_kernel, dim3(pp_grid(slots)), dim3(kPPThreads), 0, st, slots,
+                arr_at, open_len);
+    }
+    if (n > 0 && slots > 0 && groups > 0 && arr_state) {
+        note_kernel(mixed ? "arrivals_state_kernel<mixed>" : "arrivals_state_kernel");
+        qlaunch(arrivals_state_kernel<F>, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, first, n,
+                arr_group, arr_index, arr_at, arr_state);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_open_arrivals_framed(int k, int m, long long groups, RaggedView v, long long n,
                                        Rows pkt, Rows ad, const uint8_t* pn_len, int pn_all,
                                        const int32_t* arr_group, const uint8_t* arr_index,
                                        int32_t* arr_state, int32_t* arr_at, uint8_t* blocks,
                                        uint8_t* rows, int32_t* open_len, bool optimistic,
                                        hipStream_t st) {
-    const long long slots = groups * (k + m);
-    if (k + m > 255 || n > 0x7fffffffLL || slots > 0x7fffffffLL) return hipErrorInvalidValue;
-    const FramedSlots sl{RaggedSlots{v.bb, v.in_off, groups}, pn_len, pn_all};
-    if (slots > 0) {
-        note_kernel("arrivals_init_kernel");
-        qlaunch(arrivals_init_kernel, dim3(pp_grid(slots)), dim3(kPPThreads), 0, st, slots, arr_at,
-                optimistic ? open_len : nullptr);
-    }
-    if (n > 0 && slots > 0 && optimistic) {
-        note_kernel("arrivals_pre_kernel");
-        qlaunch(arrivals_pre_kernel, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, k, m, sl, n,
-                pkt.stride, pkt.len, ad.len, ad.len_all, arr_group, arr_index, open_len);
-    }
-    if (n > 0) {
-        note_kernel("open_arrivals_kernel");
-        qlaunch(open_arrivals_kernel<Fnv>, dim3(tile_grid(n)), dim3(64), kTileBytes, st, k, m, sl, n,
-                pkt.p, pkt.stride, pkt.len, ad.len, ad.len_all, arr_group, arr_index, arr_state,
-                arr_at, slots > 0 && optimistic ? open_len : nullptr, blocks);
-    }
-    if (slots > 0) {
-        note_kernel("arrivals_assemble_kernel");
-        qlaunch(arrivals_assemble_kernel, dim3((unsigned)((groups + kAsmWaves - 1) / kAsmWaves)),
-                dim3(kAsmWaves * 64), 0, st, k, m, sl, pkt.p, pkt.stride, pkt.len, ad.len,
-                ad.len_all, arr_state, arr_at, open_len, optimistic, blocks, rows);
-    }
-    if (n > 0 && slots > 0 && arr_state) {
-        note_kernel("arrivals_state_kernel");
-        qlaunch(arrivals_state_kernel, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, k + m, n,
-                arr_group, arr_index, arr_at, arr_state);
-    }
-    return hipGetLastError();
+    if (k + m > 255) return hipErrorInvalidValue;
+    return arrivals_go<UniGeo>(false, k, m, UniFirst{k + m}, groups, groups * (k + m),
+                       FramedSlots{RaggedSlots{v.bb, v.in_off, groups}, pn_len, pn_all}, n, pkt,
+                       ad, arr_group, arr_index, arr_state, arr_at, blocks, rows, open_len,
+                       optimistic, st);
 }
 
 hipError_t launch_extract_revived(int k, int m, long long groups, RaggedView v, const uint8_t* rec,
@@ -1455,8 +1746,81 @@ hipError_t launch_open_status(int k, int rmax, long long groups, const uint8_t* 
                               uint8_t* rec_rows, int32_t* status, hipStream_t st) {
     if (groups <= 0) return hipSuccess;
     if (!pp_grid_ok(groups)) return hipErrorInvalidValue;
-    qlaunch(open_status_kernel, dim3(pp_grid(groups)), dim3(kPPThreads), 0, st, groups, k, rmax,
-            rows, rec_rows, status);
+    qlaunch(open_status_kernel<UniRowsK>, dim3(pp_grid(groups)), dim3(kPPThreads), 0, st, groups,
+            UniRowsK{k}, rmax, rows, rec_rows, status);
+    return hipGetLastError();
+}
+
+// ---- the mixed-code wire path (pp_mixed.h)
+hipError_t launch_mixed_wire_plan(const MixedSet& s, long long groups, MixedWire w,
+                                  const Rows* pay, hipStream_t st) {
+    if (groups <= 0) return hipSuccess;
+    if (!pp_grid_ok(groups)) return hipErrorInvalidValue;
+    note_kernel("mixed_wire_plan_kernel");
+    qlaunch(mixed_wire_plan_kernel, dim3(pp_grid(groups)), dim3(kPPThreads), 0, st, groups,
+            s.codes, s.ncodes, w.code, w.bb, w.pkt_first, w.npkt, pay ? w.pay_first : nullptr,
+            w.npay, pay ? pay->len : nullptr, pay ? pay->stride : 0LL, w.eff, w.ecode);
+    return hipGetLastError();
+}
+
+hipError_t launch_frame_blocks_mixed(const MixedSet& s, long long groups, MixedWire w, Rows pay,
+                                     const uint8_t* pn_len, int pn_all, uint8_t* data,
+                                     const long long* data_off, hipStream_t st) {
+    if (groups <= 0 || w.npay <= 0) return hipSuccess;
+    if (!pp_grid_ok(w.npay)) return hipErrorInvalidValue;
+    note_kernel("frame_blocks_kernel<mixed>");
+    qlaunch(frame_blocks_mixed_kernel, dim3(tile_grid(w.npay)), dim3(64), kTileBytes, st, groups,
+            w.npay, s.codes, (const uint8_t*)w.ecode, (const int32_t*)w.eff, w.pay_first, pay.p,
+            pay.stride, pay.len, pn_len, pn_all, data, data_off);
+    return hipGetLastError();
+}
+
+hipError_t launch_null_seal_mixed(const MixedSet& s, long long groups, MixedWire w, Rows pay,
+                                  const uint8_t* parity, const long long* par_off, Rows hdr,
+                                  RowsOut out, int32_t* status, hipStream_t st) {
+    return seal_go("null_seal_kernel<mixed>", w.npkt, hdr,
+                   MixedRows{pay, parity, par_off, w.eff, w.ecode, s.codes, w.pkt_first,
+                             w.pay_first, groups, w.npkt, status},
+                   nullptr, 0, out, st);
+}
+
+hipError_t launch_open_arrivals_mixed(const MixedSet& s, long long groups, MixedWire w,
+                                      const long long* blocks_off, long long n, Rows pkt, Rows ad,
+                                      const uint8_t* pn_len, int pn_all, const int32_t* arr_group,
+                                      const uint8_t* arr_index, int32_t* arr_state,
+                                      int32_t* arr_at, uint8_t* blocks, uint8_t* rows,
+                                      int32_t* open_len, bool optimistic, hipStream_t st) {
+    return arrivals_go<MixedGeo>(true, MixedTabs{s.codes, w.ecode, w.pkt_first}, s.kmax,
+                       MixedFirst{w.pkt_first}, groups, w.npkt,
+                       FramedSlots{RaggedSlots{w.eff, blocks_off, groups}, pn_len, pn_all}, n, pkt,
+                       ad, arr_group, arr_index, arr_state, arr_at, blocks, rows, open_len,
+                       optimistic, st);
+}
+
+hipError_t launch_open_status_mixed(const MixedSet& s, long long groups, MixedWire w,
+                                    const uint8_t* rows, uint8_t* rec_rows, int32_t* status,
+                                    hipStream_t st) {
+    if (groups <= 0) return hipSuccess;
+    if (!pp_grid_ok(groups)) return hipErrorInvalidValue;
+    note_kernel("open_status_kernel<mixed>");
+    qlaunch(open_status_kernel<MixedGeo>, dim3(pp_grid(groups)), dim3(kPPThreads), 0, st, groups,
+            MixedGeo(MixedTabs{s.codes, w.ecode, w.pkt_first}, s.kmax), s.rmax, rows, rec_rows, status);
+    return hipGetLastError();
+}
+
+// extract_revived_kernel reads no k or m: the set's rmax is its row stride, and rec_rows is 255
+// from a group's own count on
+hipError_t launch_extract_revived_mixed(const MixedSet& s, long long groups, MixedWire w,
+                                        const uint8_t* rec, const long long* rec_off,
+                                        const uint8_t* rec_rows, const int32_t* status,
+                                        RowsOut rev, uint8_t* rev_pn_len, hipStream_t st) {
+    const long long n = groups * s.rmax;
+    if (n <= 0) return hipSuccess;
+    if (!pp_grid_ok(n)) return hipErrorInvalidValue;
+    note_kernel("extract_revived_kernel<mixed>");
+    qlaunch(extract_revived_kernel, dim3(tile_grid(n)), dim3(64), kTileBytes, st, s.rmax, n, rec,
+            rec_off, (const int32_t*)w.eff, rec_rows, status, rev.p, rev.stride, rev.len,
+            rev_pn_len);
     return hipGetLastError();
 }
 

@@ -622,6 +622,73 @@ class FecEngine:
               _ptr(rows), _ptr(open_len), _ptr(rec), _ptr(rec_off), _ptr(rec_rows), _ptr(status),
               _ptr(rev), rev.stride(0), _ptr(rev_len), _ptr(rev_pn_len), _stream(stream, pkt))
 
+    # mixed-code wire path (include/quic_fec.h, "Mixed-code wire path")
+    def frame_encode_seal_mixed(self, cs, code, bb, pkt_first, pay_first, data, data_off, parity,
+                                par_off, hdr, hdr_len, pay, pay_len, pn_len, pkt, pkt_len,
+                                status=None, stream=None):
+        """frame_encode_seal_ragged with a code per group: group g has cs.codes[code[g]], its
+        packets are rows pkt_first[g] .. of hdr / pkt / pkt_len (npkt rows), its payloads rows
+        pay_first[g] .. of pay / pay_len / pn_len (npay rows); pkt_first, pay_first int32 [G+1]
+        device tensors (mixed_packet_layout).  status: optional int32 [G] (0, -1, -3, or -2 for a
+        group without a code or with a span that does not fit)."""
+        G = _mixed_groups(code, bb, status, data_off=data_off, par_off=par_off)
+        _check(pkt_first, "pkt_first", "int32", (G + 1,))
+        _check(pay_first, "pay_first", "int32", (G + 1,))
+        _check(pkt, "pkt", "uint8", (None, None), rows=True)
+        _check(pay, "pay", "uint8", (None, None), rows=True)
+        npkt, npay = pkt.shape[0], pay.shape[0]
+        _check(hdr, "hdr", "uint8", (npkt, None), rows=True)
+        _check(hdr_len, "hdr_len", "int32", (npkt,), rows=True)
+        _check(pkt_len, "pkt_len", "int32", (npkt,), rows=True)
+        _check(pay_len, "pay_len", "int32", (npay,), rows=True)
+        _check(pn_len, "pn_len", "uint8", (npay,), rows=True)
+        h, h_all = _ptr_or_all(hdr_len)
+        pn, pn_all = _ptr_or_all(pn_len)
+        _call("qfec_frame_encode_seal_groups_batch_mixed", self, cs._h, G, _ptr(code), _ptr(bb),
+              _ptr(pkt_first), _ptr(pay_first), npkt, npay, _ptr(data), _ptr(data_off),
+              _ptr(parity), _ptr(par_off), _ptr(hdr), _stride(hdr), h, h_all, _ptr(pay),
+              pay.stride(0), _ptr(pay_len), pn, pn_all, _ptr(pkt), pkt.stride(0), _ptr(pkt_len),
+              _ptr(status), _stream(stream, data))
+
+    def open_decode_extract_arrivals_mixed(self, cs, code, bb, pkt_first, pkt, pkt_len, ad_len,
+                                           pn_len, arr_group, arr_index, arr_state, arr_at,
+                                           blocks, blocks_off, rows, open_len, rec, rec_off,
+                                           rec_rows, rev, rev_len, rev_pn_len=None, status=None,
+                                           stream=None):
+        """open_decode_extract_arrivals_ragged with a code per group: the slot of arrival a is
+        pkt_first[g] + arr_index[a] (pkt_first int32 [G+1]); arr_at and open_len are int32 [npkt]
+        (npkt = arr_at's length), rows uint8 [G][cs.kmax], rec_rows uint8 [G][cs.rmax], rev /
+        rev_len / rev_pn_len hold G * cs.rmax rows.  Arrivals of a group without a code or with
+        a span that does not fit are ARR_IGNORED and the group's status is -2."""
+        G = _mixed_groups(code, bb, status, blocks_off=blocks_off, rec_off=rec_off)
+        _check(pkt_first, "pkt_first", "int32", (G + 1,))
+        import torch
+        if not isinstance(arr_at, torch.Tensor) or not isinstance(pkt, torch.Tensor):
+            raise TypeError("pkt and arr_at: device tensors (their lengths are n and npkt)")
+        _check(pkt, "pkt", "uint8", (None, None), rows=True)
+        _check(arr_at, "arr_at", "int32", (None,), rows=True)
+        n, npkt, rmax = pkt.shape[0], arr_at.shape[0], cs.rmax
+        _check(pkt_len, "pkt_len", "int32", (n,), rows=True)
+        _check(ad_len, "ad_len", "int32", (n,), rows=True)
+        _check(pn_len, "pn_len", "uint8", (n,), rows=True)
+        _check(arr_group, "arr_group", "int32", (n,), rows=True)
+        _check(arr_index, "arr_index", "uint8", (n,), rows=True)
+        _check(arr_state, "arr_state", "int32", (n,), rows=True)
+        _check(open_len, "open_len", "int32", (npkt,), rows=True)
+        _check(rev, "rev", "uint8", (G * rmax, None), rows=True)
+        _check(rev_len, "rev_len", "int32", (G * rmax,), rows=True)
+        _check(rev_pn_len, "rev_pn_len", "uint8", (G * rmax,), rows=True)
+        _check(rows, "rows", "uint8", (G, cs.kmax))
+        _check(rec_rows, "rec_rows", "uint8", (G, rmax))
+        a, a_all = _ptr_or_all(ad_len)
+        pn, pn_all = _ptr_or_all(pn_len)
+        _call("qfec_open_decode_extract_arrivals_mixed", self, cs._h, G, _ptr(code), _ptr(bb),
+              _ptr(pkt_first), npkt, n, _ptr(pkt), pkt.stride(0), _ptr(pkt_len), a, a_all, pn,
+              pn_all, _ptr(arr_group), _ptr(arr_index), _ptr(arr_state), _ptr(arr_at),
+              _ptr(blocks), _ptr(blocks_off), _ptr(rows), _ptr(open_len), _ptr(rec),
+              _ptr(rec_off), _ptr(rec_rows), _ptr(status), _ptr(rev), rev.stride(0),
+              _ptr(rev_len), _ptr(rev_pn_len), _stream(stream, pkt))
+
     # host-pointer batch calls (synchronous; include H2D/D2H)
     def encode_host(self, k, m, block_bytes, data):
         data = np.ascontiguousarray(data, dtype=np.uint8)
@@ -842,6 +909,84 @@ def arrivals_rx_block_bytes(k, m, groups, arr_group, arr_index, pkt_len, ad_len)
                                              _vp(pkt_len), _vp(ad_len), a_all, _vp(bb))
     if rc:
         raise ValueError(f"qfec_arrivals_rx_block_bytes: rc={rc} (k={k} m={m} groups={groups})")
+    return bb
+
+
+def mixed_packet_layout(codes, code):
+    """The packet geometry of a mixed-code batch (qfec_mixed_packet_layout; host only): code
+    uint8 [G] -> (pkt_first, pay_first), int32 [G+1] prefix tables: group g's wire packets and
+    slots are pkt_first[g] .. pkt_first[g] + k_g + m_g - 1, its payload rows pay_first[g] ..
+    pay_first[g] + k_g - 1.  A group with code[g] >= len(codes) gets an empty span in both.
+    ValueError for a bad set or a total above INT32_MAX."""
+    pairs, k, m = _codes(codes)
+    code = np.ascontiguousarray(code, dtype=np.uint8)
+    if code.ndim != 1:
+        raise ValueError("code must be one-dimensional")
+    G = code.shape[0]
+    pkt_first, pay_first = np.zeros(G + 1, np.int32), np.zeros(G + 1, np.int32)
+    rc = load().qfec_mixed_packet_layout(len(pairs), _vp(k), _vp(m), G, _vp(code),
+                                         _vp(pkt_first), _vp(pay_first))
+    if rc:
+        raise ValueError(f"qfec_mixed_packet_layout: rc={rc} (a bad set, or more than INT32_MAX "
+                         "packets)")
+    return pkt_first, pay_first
+
+
+def framed_layout_mixed(codes, code, pay_len, pay_first=None):
+    """framed_layout with a code per group (qfec_framed_layout_mixed; host only): pay_len int32
+    [npay] holds group g's k_g lengths at pay_first[g] (None: the dense table of
+    mixed_packet_layout) -> (bb, data_off, par_off, rec_off, totals) with bb[g] =
+    roundup8(max(the group's lengths) + 2) and mixed_layout's offsets.  ValueError for a length
+    outside [0, 0x3fff], a span outside pay_len, or a code index outside the set."""
+    pairs, k, m = _codes(codes)
+    code = np.ascontiguousarray(code, dtype=np.uint8)
+    pay_len = np.ascontiguousarray(pay_len, dtype=np.int32).reshape(-1)
+    if code.ndim != 1:
+        raise ValueError("code must be one-dimensional")
+    G = code.shape[0]
+    if pay_first is not None:
+        pay_first = np.ascontiguousarray(pay_first, dtype=np.int32)
+        if pay_first.shape != (G + 1,):
+            raise ValueError("pay_first must hold G + 1 entries")
+    bb = np.zeros(G, np.int32)
+    offs = [np.zeros(G, np.int64) for _ in range(3)]
+    totals = np.zeros(3, np.int64)
+    rc = load().qfec_framed_layout_mixed(len(pairs), _vp(k), _vp(m), G, _vp(code), _vp(pay_first),
+                                         pay_len.size, _vp(pay_len), _vp(bb),
+                                         *[_vp(o) for o in offs], _vp(totals))
+    if rc:
+        raise ValueError(f"qfec_framed_layout_mixed: rc={rc} (a length outside [0, 0x3fff], a "
+                         "span outside pay_len, a code index outside the set or overflow)")
+    return bb, offs[0], offs[1], offs[2], tuple(int(t) for t in totals)
+
+
+def arrivals_rx_block_bytes_mixed(codes, code, arr_group, arr_index, pkt_len, ad_len):
+    """arrivals_rx_block_bytes with the k and k + m of each arrival's own group
+    (qfec_arrivals_rx_block_bytes_mixed; host only): code uint8 [G] -> bb int32 [G].  Arrivals
+    tagged to a group without a code are skipped."""
+    pairs, k, m = _codes(codes)
+    code = np.ascontiguousarray(code, dtype=np.uint8)
+    if code.ndim != 1:
+        raise ValueError("code must be one-dimensional")
+    arr_group = np.ascontiguousarray(arr_group, dtype=np.int32).reshape(-1)
+    arr_index = np.ascontiguousarray(arr_index, dtype=np.uint8).reshape(-1)
+    pkt_len = np.ascontiguousarray(pkt_len, dtype=np.int32).reshape(-1)
+    n = pkt_len.size
+    if arr_group.size != n or arr_index.size != n:
+        raise ValueError("arr_group, arr_index and pkt_len must hold one entry per arrival")
+    if isinstance(ad_len, (int, np.integer)):
+        ad_len, a_all = None, int(ad_len)
+    else:
+        ad_len, a_all = np.ascontiguousarray(ad_len, dtype=np.int32).reshape(-1), 0
+        if ad_len.size != n:
+            raise ValueError("ad_len must hold one length per arrival")
+    bb = np.zeros(code.shape[0], np.int32)
+    rc = load().qfec_arrivals_rx_block_bytes_mixed(len(pairs), _vp(k), _vp(m), code.shape[0],
+                                                   _vp(code), n, _vp(arr_group), _vp(arr_index),
+                                                   _vp(pkt_len), _vp(ad_len), a_all, _vp(bb))
+    if rc:
+        raise ValueError(f"qfec_arrivals_rx_block_bytes_mixed: rc={rc} (a bad set, or a code "
+                         "with k + m > 255)")
     return bb
 
 

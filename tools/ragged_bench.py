@@ -51,6 +51,14 @@ same groups, data rows 0 .. r-1 lost:
   unaligned  the same at addresses of every residue mod 16
 The outputs of all four are compared byte for byte first.
 
+--mixed-wire: the mixed-code wire path on the --mixed workload (the six
+presets drawn uniformly, the size mix, two losses per group, an in-order ring), sender and
+receiver, at 1,024 groups and at --groups:
+  mixed   one qfec_frame_encode_seal_groups_batch_mixed / qfec_open_decode_extract_arrivals_mixed
+  sorted  the same groups and arrivals pre-split by code (not timed), one ragged call per code
+and the one-code (32, 4) set against the ragged call on identical input.  Wire packets, pkt_len,
+arr_state, open_len, status, rec_rows and the revived payloads of the routes are compared byte
+for byte first.
 --mixed: the mixed-code batches against the ragged calls, two losses per
 group (data rows 0 and 1):
   mixed   one qfec_encode_batch_mixed / qfec_decode_batch_mixed_recovered call over groups drawn
@@ -63,6 +71,7 @@ are compared byte for byte first.
 
   python tools/ragged_bench.py --out profiles/ragged/ragged_bench.json
   python tools/ragged_bench.py --mixed --out profiles/ragged/mixed_bench.json
+  python tools/ragged_bench.py --mixed-wire --out profiles/ragged/mixed_wire_bench.json
   python tools/ragged_bench.py --ptrs --out profiles/ragged/ptrs_bench.json
   python tools/ragged_bench.py --pp --out profiles/ragged/ragged_pp_bench.json
   python tools/ragged_bench.py --framed --out profiles/ragged/framed_bench.json
@@ -115,6 +124,9 @@ def main():
                     help="the pointer-table batches against the packed ragged calls")
     ap.add_argument("--mixed", action="store_true",
                     help="the mixed-code batches against one ragged call per code")
+    ap.add_argument("--mixed-wire", action="store_true",
+                    help="the mixed-code wire path (framed sender, arrival-order receiver) against "
+                         "one ragged call per code")
     ap.add_argument("--variants", default=None,
                     help="--arrivals: comma-separated subset of slot,arrivals,two_read,shuffled "
                          "to time (for a kernel trace of one route)")
@@ -1006,7 +1018,195 @@ def main():
         results.append(line)
         print(json.dumps(line), flush=True)
 
+    def run_mixed_wire(codes, r, G, label):
+        """--mixed-wire: the mixed framed sender and the mixed arrival-order receiver, one call
+        each, against one ragged call per code on the same groups pre-split by code (not timed);
+        data packets 0 .. r-1 of every group lost, the ring in order."""
+        rng = np.random.default_rng(args.seed + 11)
+        nc, H = len(codes), 16
+        code = rng.integers(0, nc, G).astype(np.uint8)
+        bb = draw_sizes(G, args.seed)
+        ks = np.array([k for k, _ in codes], np.int64)[code]
+        ms = np.array([m for _, m in codes], np.int64)[code]
+        pkt_first, pay_first = fec.mixed_packet_layout(codes, code)
+        npkt, npay = int(pkt_first[-1]), int(pay_first[-1])
+        stride, pay_stride = H + 12 + int(bb.max()), int(bb.max())
+        gpay, gpkt = np.repeat(np.arange(G), ks), np.repeat(np.arange(G), ks + ms)
+        ipkt = np.arange(npkt) - pkt_first[gpkt]
+        lens = (bb[gpay] - 2 - rng.integers(0, 8, npay)).astype(np.int32)
+        fbb, d_off, p_off, r_off, tot = fec.framed_layout_mixed(codes, code, lens)
+        assert np.array_equal(fbb, bb)
+        cs = eng.codeset(codes)
+        kmax, rmax = cs.kmax, cs.rmax
+        cuda = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()          # noqa: E731
+        zeros = lambda shape, dt=torch.uint8: torch.zeros(shape, dtype=dt, device="cuda")  # noqa: E731
+        pay = torch.empty((npay, pay_stride), dtype=torch.uint8, device="cuda")
+        fec.synth_fill(pay, seed=args.seed)
+        hdr = torch.randint(0, 256, (npkt, H), dtype=torch.uint8, device="cuda")
+        lens_d, code_d, bb_d = cuda(lens), cuda(code), cuda(bb)
+        pf_d, qf_d = cuda(pkt_first), cuda(pay_first)
+        d_off_d, p_off_d, r_off_d = cuda(d_off), cuda(p_off), cuda(r_off)
+        data, par = zeros(tot[0]), zeros(tot[1])
+        pkt, plen, est = zeros((npkt, stride)), zeros(npkt, torch.int32), zeros(G, torch.int32)
+
+        def mixed_send():
+            eng.frame_encode_seal_mixed(cs, code_d, bb_d, pf_d, qf_d, data, d_off_d, par, p_off_d,
+                                        hdr, H, pay, lens_d, 1, pkt, plen, status=est)
+
+        mixed_send()
+        kern = {"mixed_send": fec.last_kernels()}
+        torch.cuda.synchronize()
+        assert int(est.abs().max()) == 0 and int(plen.min()) > 0
+        # the in-order ring: every packet but data packets 0 .. r-1 of each group
+        recv = np.flatnonzero(ipkt >= r)
+        n = recv.size
+        recv_d = cuda(recv)
+        ring = dict(pkt=pkt[recv_d].contiguous(), len=plen[recv_d].contiguous(),
+                    grp=cuda(gpkt[recv].astype(np.int32)), idx=cuda(ipkt[recv].astype(np.uint8)))
+
+        def outputs(Gx, kx, rx, slots, nx, tot_x):
+            return dict(blocks=zeros(tot_x[0]), rec=zeros(tot_x[2]), rows=zeros((Gx, kx)),
+                        ol=zeros(slots, torch.int32), at=zeros(slots, torch.int32),
+                        state=zeros(nx, torch.int32), rr=zeros((Gx, rx)), st=zeros(Gx, torch.int32),
+                        rev=zeros((Gx * rx, pay_stride)), rev_len=zeros(Gx * rx, torch.int32),
+                        rev_pn=zeros(Gx * rx))
+
+        o = outputs(G, kmax, rmax, npkt, n, tot)
+
+        def mixed_recv():
+            eng.open_decode_extract_arrivals_mixed(
+                cs, code_d, bb_d, pf_d, ring["pkt"], ring["len"], H, 1, ring["grp"], ring["idx"],
+                o["state"], o["at"], o["blocks"], d_off_d, o["rows"], o["ol"], o["rec"], r_off_d,
+                o["rr"], o["rev"], o["rev_len"], rev_pn_len=o["rev_pn"], status=o["st"])
+
+        mixed_recv()
+        kern["mixed_recv"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        assert int(o["st"].abs().max()) == 0
+        # every lost payload comes back
+        lost = cuda(pay_first[:-1][:, None] + np.arange(r)[None, :])
+        got = o["rev_len"].view(G, rmax)[:, :r]
+        assert torch.equal(got, lens_d[lost])
+        mask = torch.arange(pay_stride, device="cuda")[None, None, :] < got[:, :, None]
+        assert torch.equal(o["rev"].view(G, rmax, pay_stride)[:, :r][mask], pay[lost][mask])
+        del mask
+
+        # the parent's route: groups and arrivals pre-split by code (not timed)
+        buckets = []
+        for c, (k, m) in enumerate(codes):
+            idx = np.flatnonzero(code == c)
+            if not idx.size:
+                continue
+            Gb, per, rm = idx.size, k + m, min(k, m)
+            prow = (pkt_first[idx][:, None] + np.arange(per)[None, :]).ravel()
+            qrow = (pay_first[idx][:, None] + np.arange(k)[None, :]).ravel()
+            bo = fec.ragged_layout(k, m, bb[idx])
+            sel = np.flatnonzero(code[gpkt[recv]] == c)
+            renum = np.zeros(G, np.int32)
+            renum[idx] = np.arange(Gb)
+            sel_d = cuda(sel)
+            B = dict(k=k, m=m, idx=idx, G=Gb, prow=cuda(prow), sel=sel_d, bb=cuda(bb[idx]),
+                     off=[cuda(x) for x in bo[:3]], data=zeros(bo[3][0]), par=zeros(bo[3][1]),
+                     hdr=hdr[cuda(prow)].contiguous(), pay=pay[cuda(qrow)].contiguous(),
+                     lens=cuda(lens[qrow]), pkt=zeros((Gb * per, stride)),
+                     plen=zeros(Gb * per, torch.int32), est=zeros(Gb, torch.int32),
+                     ring=dict(pkt=ring["pkt"][sel_d].contiguous(), len=ring["len"][sel_d].contiguous(),
+                               grp=cuda(renum[gpkt[recv][sel]]), idx=ring["idx"][sel_d].contiguous()),
+                     o=outputs(Gb, k, rm, Gb * per, sel.size, bo[3]))
+            buckets.append(B)
+        nb = len(buckets)
+
+        def sorted_send(ev=None, base=0):
+            for i, B in enumerate(buckets):
+                f = lambda: eng.frame_encode_seal_ragged(                             # noqa: E731
+                    B["k"], B["m"], B["bb"], B["data"], B["off"][0], B["par"], B["off"][1], B["hdr"],
+                    H, B["pay"], B["lens"], 1, B["pkt"], B["plen"], status=B["est"])
+                timed(ev, base + i, f) if ev else f()
+
+        def sorted_recv(ev=None, base=0):
+            for i, B in enumerate(buckets):
+                R, x = B["ring"], B["o"]
+                f = lambda: eng.open_decode_extract_arrivals_ragged(                  # noqa: E731
+                    B["k"], B["m"], B["bb"], R["pkt"], R["len"], H, 1, R["grp"], R["idx"], x["state"],
+                    x["at"], x["blocks"], B["off"][0], x["rows"], x["ol"], x["rec"], B["off"][2],
+                    x["rr"], x["rev"], x["rev_len"], rev_pn_len=x["rev_pn"], status=x["st"])
+                timed(ev, base + i, f) if ev else f()
+
+        # the same bytes from both routes, at the timed size
+        sorted_send()
+        kern["sorted_send"] = fec.last_kernels()
+        sorted_recv()
+        kern["sorted_recv"] = fec.last_kernels()
+        torch.cuda.synchronize()
+        for B in buckets:
+            ix, x, rm = cuda(B["idx"]), B["o"], min(B["k"], B["m"])
+            assert torch.equal(pkt[B["prow"]], B["pkt"]), "wire packets differ between the routes"
+            assert torch.equal(plen[B["prow"]], B["plen"]), "pkt_len differs between the routes"
+            assert torch.equal(o["state"][B["sel"]], x["state"]), "arr_state differs"
+            assert torch.equal(o["ol"][B["prow"]], x["ol"]), "open_len differs"
+            assert torch.equal(o["st"][ix], x["st"]) and torch.equal(o["rr"][ix][:, :rm], x["rr"])
+            assert torch.equal(o["rev_len"].view(G, rmax)[ix][:, :rm].reshape(-1), x["rev_len"])
+            assert torch.equal(o["rev"].view(G, rmax, pay_stride)[ix][:, :rm].reshape(-1, pay_stride),
+                               x["rev"]), "revived payloads differ between the routes"
+
+        ev = DeviceEvents(2 * (2 + 2 * nb))
+        t = {x: [] for x in ("mixed_send", "mixed_recv", "sorted_send", "sorted_recv")}
+        wall = {x: [] for x in t}
+
+        def walled(name, fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            wall[name].append((time.perf_counter() - t0) * 1e3)
+
+        for rep_i in range(args.warmup + args.reps):
+            order = [("mixed_send", lambda: timed(ev, 0, mixed_send)),
+                     ("sorted_send", lambda: sorted_send(ev, 2)),
+                     ("mixed_recv", lambda: timed(ev, 1, mixed_recv)),
+                     ("sorted_recv", lambda: sorted_recv(ev, 2 + nb))]
+            if rep_i % 2:
+                order = [order[1], order[0], order[3], order[2]]
+            for name, fn in order:
+                walled(name, fn)
+            if rep_i < args.warmup:
+                for x in wall:
+                    wall[x].clear()
+                continue
+            t["mixed_send"].append(ev.elapsed_ms(0, 1))
+            t["mixed_recv"].append(ev.elapsed_ms(2, 3))
+            t["sorted_send"].append(sum(ev.elapsed_ms(2 * (2 + i), 2 * (2 + i) + 1)
+                                        for i in range(nb)))
+            t["sorted_recv"].append(sum(ev.elapsed_ms(2 * (2 + nb + i), 2 * (2 + nb + i) + 1)
+                                        for i in range(nb)))
+        ev.close()
+        line = dict(config=label, mode="mixed_wire", codes=[list(c) for c in codes], losses=r,
+                    groups=G, packets=npkt, arrivals=int(n),
+                    groups_per_code=[int((code == c).sum()) for c in range(nc)],
+                    ragged_calls_per_phase=nb, reps=args.reps, kernels=kern)
+        for name, v in t.items():
+            line[name] = dict(kernel_ms_median=round(statistics.median(v), 4),
+                              kernel_ms_min=round(min(v), 4), kernel_ms_max=round(max(v), 4),
+                              wall_ms_median=round(statistics.median(wall[name]), 4),
+                              wall_ms_min=round(min(wall[name]), 4),
+                              wall_ms_max=round(max(wall[name]), 4))
+        for ph in ("send", "recv"):
+            for what in ("kernel", "wall"):
+                line[f"{ph}_{what}_mixed_over_sorted"] = round(
+                    line[f"mixed_{ph}"][f"{what}_ms_median"] /
+                    line[f"sorted_{ph}"][f"{what}_ms_median"], 3)
+        cs.close()
+        results.append(line)
+        print(json.dumps(line), flush=True)
+
     G = args.groups
+    if args.mixed_wire:
+        presets = [(5, 5), (10, 10), (10, 15), (10, 20), (15, 15), (250, 5)]
+        run_mixed_wire(presets, 2, 1024, "(a) six presets, 1024 groups")
+        run_mixed_wire([(32, 4)], 2, 1024, "(b) one code (32,4), 1024 groups")
+        run_mixed_wire(presets, 2, G, f"(c) six presets, {G} groups")
+        run_mixed_wire([(32, 4)], 2, G, f"(d) one code (32,4), {G} groups")
+        args.codes = ""
     if args.mixed:
         presets = [(5, 5), (10, 10), (10, 15), (10, 20), (15, 15), (250, 5)]
         run_mixed(presets, 2, G, f"(a) six presets, {G} groups")

@@ -568,6 +568,154 @@ static void check_arrivals(std::mt19937& rng) {
     }
 }
 
+// ---- the three host helpers of the mixed-code wire path, in arrays of exactly G, G + 1, npay
+// and n entries: empty sets of groups, groups without a code, duplicates, more than k arrivals,
+// tags at the last group, n = 0, and random hostile streams against the sequential rule
+static void check_mixed_wire(std::mt19937& rng) {
+    const int ks[] = {10, 2, 5, 32, 10, 250}, ms[] = {1, 2, 5, 4, 20, 5};
+    const int nc = 6;
+    long long tot[3];
+    // no groups: the tables hold their one entry, nothing else is read or written
+    {
+        std::vector<int> pf(1, 7), qf(1, 7);
+        CHECK(qfec_mixed_packet_layout(nc, ks, ms, 0, nullptr, pf.data(), qf.data()) == 0);
+        CHECK(pf[0] == 0 && qf[0] == 0);
+        CHECK(qfec_mixed_packet_layout(nc, ks, ms, 0, nullptr, nullptr, nullptr) == 0);
+        CHECK(qfec_framed_layout_mixed(nc, ks, ms, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, tot) == 0);
+        CHECK(tot[0] == 0 && tot[1] == 0 && tot[2] == 0);
+        CHECK(qfec_arrivals_rx_block_bytes_mixed(nc, ks, ms, 0, nullptr, 0, nullptr, nullptr, nullptr,
+                                                 nullptr, 0, nullptr) == 0);
+        const int grp[1] = {0}, len[1] = {40};
+        const unsigned char idx[1] = {0};
+        CHECK(qfec_arrivals_rx_block_bytes_mixed(nc, ks, ms, 0, nullptr, 1, grp, idx, len, nullptr, 16,
+                                                 nullptr) == 0);
+        // argument errors
+        const unsigned char c0[1] = {0};
+        int b1[1] = {7};
+        CHECK(qfec_mixed_packet_layout(0, ks, ms, 0, nullptr, nullptr, nullptr) == -2);
+        CHECK(qfec_mixed_packet_layout(nc, ks, ms, -1, nullptr, nullptr, nullptr) == -2);
+        CHECK(qfec_mixed_packet_layout(nc, ks, ms, 1, nullptr, nullptr, nullptr) == -2);
+        CHECK(qfec_framed_layout_mixed(nc, ks, ms, 1, c0, nullptr, 10, nullptr, b1, nullptr, nullptr,
+                                       nullptr, nullptr) == -2);
+        CHECK(qfec_framed_layout_mixed(nc, ks, ms, 1, c0, nullptr, -1, len, b1, nullptr, nullptr,
+                                       nullptr, nullptr) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes_mixed(nc, ks, ms, 1, c0, -1, grp, idx, len, nullptr, 16, b1) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes_mixed(nc, ks, ms, 1, nullptr, 1, grp, idx, len, nullptr, 16, b1) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes_mixed(nc, ks, ms, 1, c0, 1, nullptr, idx, len, nullptr, 16, b1) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes_mixed(nc, ks, ms, 1, c0, 1, grp, idx, len, nullptr, 16, nullptr) == -2);
+        const int kb[1] = {250}, mb[1] = {6};
+        CHECK(qfec_arrivals_rx_block_bytes_mixed(1, kb, mb, 1, c0, 1, grp, idx, len, nullptr, 16, b1) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes_mixed(nc, ks, ms, 1, c0, 0, nullptr, nullptr, nullptr, nullptr,
+                                                 16, b1) == 0);
+        CHECK(b1[0] == 0);
+    }
+    // duplicates, more than k arrivals, a tag at the last group, a group without a code: codes
+    // (2, 2), none, (10, 1)
+    {
+        const unsigned char code[] = {1, 200, 0};
+        //                 dup of (0,0)   late in g0  codeless  last group (k = 10: index 10 is FEC)
+        const int grp[] = {0, 0, 0, 0,    0,          1, 1,     2, 2, 2,   -1, 3};
+        const unsigned char idx[] = {0, 0, 3, 1,  2,  0, 1,     10, 11, 0, 0, 0};
+        const int len[] = {16 + 12 + 10, 16 + 12 + 900, 16 + 12 + 16, 16 + 12 + 500, 16 + 12 + 1000,
+                           16 + 12 + 700, 16 + 12 + 700, 16 + 12 + 24, 2000, 16 + 12 + 30, 2000, 2000};
+        int bb[3] = {7, 7, 7};
+        CHECK(qfec_arrivals_rx_block_bytes_mixed(nc, ks, ms, 3, code, 12, grp, idx, len, nullptr, 16,
+                                                 bb) == 0);
+        CHECK(bb[0] == 16 && bb[1] == 0 && bb[2] == 32);    // g2: FEC 24, index 11 ignored, data 30 + 2
+        int pf[4], qf[4];
+        CHECK(qfec_mixed_packet_layout(nc, ks, ms, 3, code, pf, qf) == 0);
+        CHECK(pf[0] == 0 && pf[1] == 4 && pf[2] == 4 && pf[3] == 15);
+        CHECK(qf[0] == 0 && qf[1] == 2 && qf[2] == 2 && qf[3] == 12);
+        const std::vector<int> lens(12, 100);
+        int fb[3];
+        CHECK(qfec_framed_layout_mixed(nc, ks, ms, 3, code, qf, 12, lens.data(), fb, nullptr, nullptr,
+                                       nullptr, nullptr) == -2);    // the codeless group has no layout
+    }
+    for (int rep = 0; rep < 60; ++rep) {
+        const size_t G = 1 + rng() % 40;
+        std::vector<unsigned char> code(G);
+        for (auto& c : code) c = (unsigned char)(rng() % 8 == 0 ? 6 + rng() % 250 : rng() % nc);
+        std::vector<int> pf(G + 1, -7), qf(G + 1, -7);
+        CHECK(qfec_mixed_packet_layout(nc, ks, ms, (long long)G, code.data(), pf.data(), qf.data()) == 0);
+        long long p = 0, q = 0;
+        for (size_t g = 0; g < G; ++g) {
+            CHECK(pf[g] == p && qf[g] == q);
+            if (code[g] < nc) p += ks[code[g]] + ms[code[g]], q += ks[code[g]];
+        }
+        CHECK(pf[G] == p && qf[G] == q);
+        // framed layout: every group needs a code; lengths in an array of exactly npay entries
+        std::vector<unsigned char> good(code);
+        for (auto& c : good) c = (unsigned char)(c % nc);
+        CHECK(qfec_mixed_packet_layout(nc, ks, ms, (long long)G, good.data(), nullptr, qf.data()) == 0);
+        const size_t npay = (size_t)qf[G];
+        std::vector<int> len(npay), bb(G, -7), want(G);
+        for (auto& l : len) l = (int)(rng() % 8 == 0 ? 0x3fff : rng() % 1400);
+        for (size_t g = 0; g < G; ++g) {
+            int most = 0;
+            for (int i = 0; i < ks[good[g]]; ++i) most = std::max(most, len[(size_t)qf[g] + (size_t)i]);
+            want[g] = (most + 2 + 7) & ~7;
+        }
+        std::vector<long long> d(G), pr(G), r(G), d2(G), p2(G), r2(G);
+        long long tot2[3];
+        for (const int* table : {(const int*)nullptr, (const int*)qf.data()}) {
+            CHECK(qfec_framed_layout_mixed(nc, ks, ms, (long long)G, good.data(), table, (long long)npay,
+                                           len.data(), bb.data(), d.data(), pr.data(), r.data(), tot) == 0);
+            CHECK(bb == want);
+        }
+        CHECK(qfec_mixed_layout(nc, ks, ms, (long long)G, good.data(), bb.data(), d2.data(), p2.data(),
+                                r2.data(), tot2) == 0);
+        CHECK(d == d2 && pr == p2 && r == r2 && tot[0] == tot2[0] && tot[1] == tot2[1] && tot[2] == tot2[2]);
+        // hostile: a length outside the prefix, an array one entry short, a table that leaves it
+        const size_t at = rng() % npay;
+        const int keep = len[at];
+        len[at] = rng() % 2 ? -1 : 0x4000;
+        CHECK(qfec_framed_layout_mixed(nc, ks, ms, (long long)G, good.data(), nullptr, (long long)npay,
+                                       len.data(), bb.data(), nullptr, nullptr, nullptr, nullptr) == -2);
+        len[at] = keep;
+        {
+            std::vector<int> cut(len.begin(), len.end() - 1);
+            CHECK(qfec_framed_layout_mixed(nc, ks, ms, (long long)G, good.data(), nullptr,
+                                           (long long)npay - 1, cut.data(), bb.data(), nullptr, nullptr,
+                                           nullptr, nullptr) == -2);
+            std::vector<int> bad(qf);
+            bad[rng() % G] = rng() % 2 ? -1 : (int)npay;
+            CHECK(qfec_framed_layout_mixed(nc, ks, ms, (long long)G, good.data(), bad.data(),
+                                           (long long)npay, len.data(), bb.data(), nullptr, nullptr,
+                                           nullptr, nullptr) == -2);
+        }
+        // arrivals: hostile tags and lengths against the sequential rule with k per group
+        const size_t n = rng() % 800;
+        std::vector<int> grp(n), wl(n), ad(n), rb(G, 7), rwant(G, 0), held(G, 0);
+        std::vector<unsigned char> idx(n);
+        std::vector<std::vector<bool>> seen(G, std::vector<bool>(256, false));
+        for (size_t a = 0; a < n; ++a) {
+            const unsigned pick = rng() % 16;
+            grp[a] = pick == 0 ? -1 : pick == 1 ? (int)G : pick == 2 ? INT_MIN : pick == 3 ? INT_MAX
+                                                                          : (int)(rng() % G);
+            if (pick == 4) grp[a] = (int)G - 1;
+            idx[a] = (unsigned char)(pick == 6 ? 255 : pick == 5 ? 254 : rng() % 40);
+            ad[a] = pick == 7 ? -3 : (int)(rng() % 20);
+            wl[a] = pick == 8 ? -1 : pick == 9 ? INT_MAX : pick == 10 ? ad[a] + 11
+                                                         : ad[a] + 12 + (int)(rng() % 1400);
+            const long long g = grp[a], pt = (long long)wl[a] - ad[a] - 12;
+            if (g < 0 || g >= (long long)G || code[(size_t)g] >= nc) continue;
+            const int k = ks[code[(size_t)g]], per = k + ms[code[(size_t)g]];
+            if (idx[a] >= per) continue;
+            if (wl[a] < 0 || ad[a] < 0 || pt < 0) continue;
+            if (seen[(size_t)g][idx[a]] || held[(size_t)g] >= k) continue;
+            seen[(size_t)g][idx[a]] = true;
+            ++held[(size_t)g];
+            const long long st = pt + (idx[a] < k ? 2 : 0);
+            rwant[(size_t)g] = std::max(rwant[(size_t)g], (int)std::min<long long>(st, INT_MAX));
+        }
+        CHECK(qfec_arrivals_rx_block_bytes_mixed(nc, ks, ms, (long long)G, code.data(), (long long)n,
+                                                 grp.data(), idx.data(), wl.data(), ad.data(), 0,
+                                                 rb.data()) == 0);
+        CHECK(rb == rwant);
+    }
+}
+
 int main() {
     std::mt19937 rng(20240607);
     const int codes[][2] = {{10, 1}, {3, 2}, {5, 5}, {32, 4}, {10, 20}, {1, 3}, {250, 5}, {10, 10}};
@@ -587,6 +735,7 @@ int main() {
     check_framed(rng);
     check_arrivals(rng);
     check_mixed_layout(rng);
+    check_mixed_wire(rng);
     // errors: a size < 1, bad arguments, overflow of the running offset
     {
         const int bad[3] = {8, 0, 8};
