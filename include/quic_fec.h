@@ -884,6 +884,120 @@ QFEC_API int qfec_open_decode_extract_arrivals_mixed(
     long long rev_stride, int *d_rev_len, unsigned char *d_rev_pn_len, void *stream);
 
 /* ---------------------------------------------------------------------------------
+ * Receiver window: the arrival-order receiver with its state kept between calls.
+ *
+ * qfec_open_decode_extract_arrivals_ragged sets its binding table up again inside every call, so a
+ * group whose packets fall into two ring reads holds "fewer than k" in both.  A socket's ring
+ * does not end at a group boundary: QuicFecGroup keeps a group until its k-th packet comes
+ * (quic_fec_group.cc:167-169, 210-213).  A window is that state on the device: `groups` group
+ * places of one (k, m), fed by any number of pushes, each a ring in arrival order with the tags of
+ * the arrival-order receiver (d_arr_group[a] is the group's place in the window).  A group
+ * delivers its revived payloads in the push that brings its k-th packet; a place is used again
+ * after qfec_rxwin_release.  
+ *
+ * What the window owns, all of it allocated by qfec_rxwin_create (a push allocates nothing): one
+ * hold row of hold_stride bytes per slot (groups*(k+m) rows: every accepted packet keeps a row of
+ * its own, so nothing is packed, placed or copied when a group completes); a state per slot
+ * (empty, held with its plaintext length, seen but late); per group the count of held packets and
+ * a delivered mark; the tables of one push (binding, pre-pass, rows, block and rec pointers, the
+ * effective bb per group); and the context's decode workspace sized for `groups` groups, eager
+ * and graph, so a captured push needs no qfec_reserve.  qfec_rxwin_bytes gives the size of the
+ * window's own allocation (host, no GPU): with S = groups*(k+m), rmax = min(k, m) and r256(x) = x
+ * rounded up to 256,
+ *   r256(S*hold_stride) + 3*r256(4*S) + 4*r256(4*groups) + r256(groups*k) + r256(8*groups*k)
+ *   + r256(8*groups*rmax).
+ * Create limits, -2 with text in qfec_last_error(): those of the ragged calls (k, m >= 1,
+ * k <= 255, groups >= 0); k + m > 255; groups*(k+m) > INT32_MAX; hold_stride below 16 or not a
+ * multiple of 16; a NULL context or out.  An allocation failure returns a code <= -2 with the HIP
+ * text, and nothing is left allocated.  A window belongs to its context and is destroyed before
+ * it; qfec_rxwin_destroy waits for the device.
+ *
+ * Acceptance, defined sequentially over the arrivals of all pushes since the group's last release
+ * (the device result equals it; it is the arrival-order receiver's rule over the concatenation
+ * of the rings):
+ *   1. tag outside [0, groups) or index >= k+m: QFEC_ARR_IGNORED.
+ *   2. the packet fails the framed open's length checks against the d_bb[g] of this push (a data
+ *      plaintext of at most bb-2 bytes, an FEC plaintext of at most bb; none passes where
+ *      bb[g] < 1 or bb[g] > hold_stride) or its tag does not match: QFEC_ARR_REJECTED.  The state
+ *      is untouched.
+ *   3. the slot is not empty, from an earlier push or earlier in this one: QFEC_ARR_DUPLICATE.
+ *   4. the group already holds k: QFEC_ARR_LATE, and the slot becomes seen.
+ *   5. otherwise the arrival is accepted: the slot becomes held, d_arr_state[a] = the plaintext
+ *      length.
+ * Hold rows: a data packet's row is prefix || payload || zeros to hold_stride (prefix = len |
+ * pn_len << 14, little-endian, as the framed calls write it), an FEC packet's row is plaintext ||
+ * zeros to hold_stride.  The first bb bytes of a row are therefore the one-shot call's block for
+ * any bb up to hold_stride: a bb[g] that grows between pushes needs no rewrite.
+ *
+ * Completion: group g completes in the push that accepts its k-th packet, with bb = d_bb[g] of
+ * that push.  Its rows are formed as in the one-shot call (the holes, ascending, take the held
+ * FEC packets, ascending); its blocks are the hold rows, read where they lie by the pointer-table
+ * decode (qfec_decode_batch_ptrs_recovered's kernels); recovered block j goes to d_rec +
+ * d_rec_off[g] + j*bb.  For a completing group d_status[g] (0, or -1 for bb % 8 != 0 with a
+ * recovery block), d_rec_rows, the recovered blocks, d_rev, d_rev_len and d_rev_pn_len are byte for
+ * byte what qfec_open_decode_extract_arrivals_ragged gives over the concatenated rings with the
+ * same bb.  If a held packet's stored size (plaintext + 2 for a data packet) exceeds that push's
+ * bb, which happens only when the caller shrank bb[g], the group completes with status -3 and
+ * nothing is revived.  For every other group of the push: d_status is QFEC_WIN_OPEN (fewer than k
+ * so far) or QFEC_WIN_DELIVERED (completed in an earlier push, not released since), d_rec_rows is
+ * 255, d_rev_len is -1, and no rec or rev byte is written; none of those groups' pointer-table
+ * entries is dereferenced (their effective bb is 0).  The decode's kernels and the fixed-cost
+ * passes run over all `groups` places in every push.
+ * d_rec_off is the ragged calls' array (multiples of 16, as qfec_ragged_layout gives); d_rec_rows
+ * is [groups][rmax], d_rev rows, d_rev_len and d_rev_pn_len are g*rmax + j.  d_arr_state, d_status
+ * and d_rev_pn_len may be NULL.
+ *
+ * qfec_rxwin_release enqueues one kernel: the listed groups (d_groups, int32 [count], a device
+ * array) return to empty: slot states, count and delivered mark.  Entries outside [0, groups) are
+ * skipped and repeats are harmless; d_groups == NULL releases every group; count < 0 is -2.
+ *
+ * Push, call-level -2 before anything is enqueued: a NULL window; n < 0 or n > INT32_MAX; a NULL
+ * d_bb, d_rec, d_rec_off, d_rec_rows, d_rev or d_rev_len; d_rec not 16-byte aligned; pkt_stride < 1
+ * or rev_stride < 0; ad_len_all < 0 without d_ad_len.  n == 0 is valid and the per-arrival arrays
+ * (d_pkt, d_pkt_len, d_arr_group, d_arr_index) may then be NULL.
+ * Streams, graphs: push and release only enqueue; they read no device array back and allocate
+ * nothing.  A captured push replayed over new ring contents carries the state from replay to
+ * replay.  Two calls on one window must be ordered by the caller (one stream, or events); they
+ * run under the context's mutex and in the decode-workspace bracket, like every decode.
+ * Launches of a push: rxwin_init_kernel, rxwin_pre_kernel (not with arr_optimistic = 0),
+ * rxwin_open_kernel, rxwin_assemble_kernel, arrivals_state_kernel (with d_arr_state), the
+ * pointer-table decode's, rxwin_finish_kernel, extract_revived_kernel.
+ * ------------------------------------------------------------------------------- */
+typedef struct qfec_rxwin qfec_rxwin;
+#define QFEC_WIN_OPEN (-3)      /* fewer than k accepted so far (the one-shot's value) */
+#define QFEC_WIN_DELIVERED (-5) /* completed in an earlier push, not released since */
+/* Host helper, no GPU: the bytes of a window's own device allocation (the formula above).  -2 on
+ * the create limits and a NULL bytes. */
+QFEC_API int qfec_rxwin_bytes(int k, int m, long long groups, int hold_stride, long long *bytes);
+QFEC_API int qfec_rxwin_create(qfec_ctx *ctx, int k, int m, long long groups, int hold_stride,
+                               qfec_rxwin **out);
+QFEC_API void qfec_rxwin_destroy(qfec_rxwin *win);
+QFEC_API int qfec_rxwin_release(qfec_rxwin *win, long long count, const int *d_groups,
+                                void *stream);
+/* One ring read: open -> bind against the carried state -> pointer-table decode of the groups
+ * that complete -> extraction. */
+QFEC_API int qfec_rxwin_push(qfec_rxwin *win, const int *d_bb, long long n,
+                             const unsigned char *d_pkt, long long pkt_stride,
+                             const int *d_pkt_len, const int *d_ad_len, int ad_len_all,
+                             const unsigned char *d_pn_len, int pn_len_all,
+                             const int *d_arr_group, const unsigned char *d_arr_index,
+                             int *d_arr_state, unsigned char *d_rec, const long long *d_rec_off,
+                             unsigned char *d_rec_rows, int *d_status, unsigned char *d_rev,
+                             long long rev_stride, int *d_rev_len, unsigned char *d_rev_pn_len,
+                             void *stream);
+/* Host helper, no GPU: the running form of qfec_arrivals_rx_block_bytes, its state in the
+ * caller's hands.  seen [groups][32] (in/out) is a bitset of the indices counted so far (index i
+ * of group g: bit i % 8 of byte g*32 + i / 8); bb [groups] (in/out) the running maximum over the
+ * group's first k distinct indices.  From zeroed state, running it over the pieces of a stream
+ * gives what qfec_arrivals_rx_block_bytes gives over their concatenation; the caller zeroes a
+ * group's 32 bytes and its bb when it releases the group.  -2 as that helper, and a NULL seen. */
+QFEC_API int qfec_arrivals_rx_block_bytes_carry(int k, int m, long long groups, long long n,
+                                                const int *arr_group,
+                                                const unsigned char *arr_index,
+                                                const int *pkt_len, const int *ad_len,
+                                                int ad_len_all, unsigned char *seen, int *bb);
+
+/* ---------------------------------------------------------------------------------
  * Support: the coefficient tables, a seeded synthetic workload, diagnostics.
  * ------------------------------------------------------------------------------- */
 /* Rows 1..m-1 of the Cauchy matrix the reference selects (cauchy_256.cpp:422-480),
@@ -915,7 +1029,10 @@ QFEC_API const char *qfec_last_error(void);
  * open_assemble_kernel<framed>" and "extract_revived_kernel"; the arrivals call names
  * "arrivals_init_kernel", "arrivals_pre_kernel", "open_arrivals_kernel",
  * "arrivals_assemble_kernel" and (with d_arr_state) "arrivals_state_kernel" ahead of the decode's
- * and "extract_revived_kernel"; the mixed-code wire calls name "mixed_wire_plan_kernel" first and
+ * and "extract_revived_kernel"; a window push names "rxwin_init_kernel", "rxwin_pre_kernel",
+ * "rxwin_open_kernel", "rxwin_assemble_kernel" and (with d_arr_state) "arrivals_state_kernel" ahead
+ * of the pointer-table decode's, then "rxwin_finish_kernel" and "extract_revived_kernel"; a
+ * release names "rxwin_release_kernel"; the mixed-code wire calls name "mixed_wire_plan_kernel" first and
  * carry a "<mixed>" suffix on the kernels that read the mixed geometry:
  * "frame_blocks_kernel<mixed>", "null_seal_kernel<mixed>", "arrivals_pre_kernel<mixed>",
  * "open_arrivals_kernel<mixed>", "arrivals_assemble_kernel<mixed>", "arrivals_unowned_kernel",

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "fec_host_plan.h"
 #include "fec_internal.h"
 #include "gf256.h"
 #include "gf_mixed.h"
@@ -1441,6 +1442,119 @@ int qfec_open_decode_extract_arrivals_ragged(
                                         (int32_t*)d_status, st));
         QF_HIP(qfec::launch_extract_revived(k, m, groups, v, d_rec, d_rec_rows,
                                             (const int32_t*)d_status,
+                                            rows_out_of(d_rev, rev_stride, d_rev_len),
+                                            d_rev_pn_len, st));
+        return 0;
+    });
+}
+
+// ---- receiver window: the arrivals call with its state kept between calls (pp_null.hip's rxwin
+// kernels).  bind (init -> pre -> open -> assemble -> state) -> pointer-table decode over the
+// window's own tables (every block is a hold row) -> finish -> extract.  Nothing is read back.
+struct qfec_rxwin {
+    qfec_ctx* ctx = nullptr;
+    qfec::RxWin w{};
+    qfec::DevBuf buf;   // the window's one allocation (RxwinLayout)
+};
+
+int qfec_rxwin_create(qfec_ctx* c, int k, int m, long long groups, int hold_stride,
+                      qfec_rxwin** out) {
+    if (!out) return fail(-2, "null out");
+    *out = nullptr;
+    int rc = ragged_preface(c, k, m, groups);
+    if (rc) return rc;
+    qfec::RxwinLayout L;
+    const char* why = "";
+    if (qfec::rxwin_layout(k, m, groups, hold_stride, &L, &why)) return fail(-2, why);
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    auto win = std::make_unique<qfec_rxwin>();   // frees its allocation on every early return
+    win->ctx = c;
+    if (hipError_t e = win->buf.ensure((size_t)std::max(L.total, 256LL))) {
+        (void)hipGetLastError();   // the launchers return the last error: leave none behind
+        return hip_fail(e, "hipMalloc of the window");
+    }
+    uint8_t* b = (uint8_t*)win->buf.p;
+    win->w = qfec::RxWin{k, m, groups, hold_stride, b + L.hold, (int32_t*)(b + L.slot_state),
+                         (int32_t*)(b + L.held), (int32_t*)(b + L.delivered),
+                         (int32_t*)(b + L.arr_at), (int32_t*)(b + L.pre_at), b + L.rows,
+                         (unsigned long long*)(b + L.blk_ptrs),
+                         (unsigned long long*)(b + L.rec_ptrs), (int32_t*)(b + L.eff),
+                         (int32_t*)(b + L.verdict)};
+    // every slot empty (kSlotEmpty = -1: all-ones bytes), no packet held, nothing delivered
+    QF_HIP(hipMemset(b + L.slot_state, 0xff, (size_t)(L.held - L.slot_state)));
+    QF_HIP(hipMemset(b + L.held, 0, (size_t)(L.arr_at - L.held)));
+    // what a push's decode needs, in both workspaces, so that no push allocates
+    const DecodePlan p = ragged_decode_plan(k, m);
+    for (Workspace* W : {&c->ws, &c->ws_graph})
+        if ((rc = reserve_workspace(*W, p, groups, false))) return rc;
+    if (p.cenc) {
+        const uint8_t* t;
+        if ((rc = get_cenc(c, k, m, &t))) return rc;
+    }
+    QF_HIP(hipDeviceSynchronize());
+    *out = win.release();
+    return 0;
+}
+
+void qfec_rxwin_destroy(qfec_rxwin* win) {
+    if (!win) return;
+    {
+        std::lock_guard<std::mutex> lk(win->ctx->mu);
+        (void)hipSetDevice(win->ctx->device);
+        (void)hipDeviceSynchronize();   // a push or a graph replay may still use the rows
+    }
+    delete win;
+}
+
+int qfec_rxwin_release(qfec_rxwin* win, long long count, const int* d_groups, void* stream) {
+    if (!win) return fail(-2, "null window");
+    if (count < 0) return fail(-2, "count < 0");
+    if (d_groups && count > INT32_MAX / (win->w.k + win->w.m))
+        return fail(-2, "count * (k + m) above INT32_MAX");
+    qfec_ctx* c = win->ctx;
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc = set_device(c);
+    if (rc) return rc;
+    QF_HIP(qfec::launch_rxwin_release(win->w, count, (const int32_t*)d_groups, pick(c, stream)));
+    return 0;
+}
+
+int qfec_rxwin_push(qfec_rxwin* win, const int* d_bb, long long n, const unsigned char* d_pkt,
+                    long long pkt_stride, const int* d_pkt_len, const int* d_ad_len,
+                    int ad_len_all, const unsigned char* d_pn_len, int pn_len_all,
+                    const int* d_arr_group, const unsigned char* d_arr_index, int* d_arr_state,
+                    unsigned char* d_rec, const long long* d_rec_off, unsigned char* d_rec_rows,
+                    int* d_status, unsigned char* d_rev, long long rev_stride, int* d_rev_len,
+                    unsigned char* d_rev_pn_len, void* stream) {
+    if (!win) return fail(-2, "null window");
+    qfec_ctx* c = win->ctx;
+    const qfec::RxWin& w = win->w;
+    int rc;
+    if (any_null({d_bb, d_rec, d_rec_off, d_rec_rows})) return fail(-2, "null buffer");
+    if ((uintptr_t)d_rec & 15) return fail(-2, "ragged base pointers must be 16-byte aligned");
+    if ((rc = open_decode_args(w.k, w.m, true, {}, pkt_stride, d_ad_len, ad_len_all))) return rc;
+    if ((rc = framed_rows_args(d_rev, rev_stride, d_rev_len, "bad rev_stride"))) return rc;
+    if (n < 0) return fail(-2, "n < 0");
+    if (n > INT32_MAX) return fail(-2, "n above INT32_MAX");   // arrival indices are int32
+    // the per-arrival arrays: nothing of them is read when nothing arrived
+    if (n > 0 && any_null({d_pkt, d_pkt_len, d_arr_group, d_arr_index}))
+        return fail(-2, "null buffer");
+    std::lock_guard<std::mutex> lk(c->mu);
+    if ((rc = set_device(c))) return rc;
+    const hipStream_t st = pick(c, stream);
+    return with_workspace(c, st, [&] {
+        QF_HIP(qfec::launch_rxwin_bind(
+            w, (const int32_t*)d_bb, n, rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
+            rows_of(nullptr, 0, d_ad_len, ad_len_all), d_pn_len, pn_len_all,
+            (const int32_t*)d_arr_group, d_arr_index, (int32_t*)d_arr_state, d_rec, d_rec_off,
+            c->tune.arr_optimistic != 0, st));
+        const int r = decode_ptrs_impl(c, w.k, w.m, w.groups, {w.blk_ptrs, w.rec_ptrs, w.eff, 0},
+                                       w.rows, d_rec_rows, (int32_t*)d_status, st);
+        if (r) return r;
+        QF_HIP(qfec::launch_rxwin_finish(w, d_rec_rows, (int32_t*)d_status, st));
+        QF_HIP(qfec::launch_extract_revived(w.k, w.m, w.groups, {w.eff, nullptr, d_rec_off}, d_rec,
+                                            d_rec_rows, (const int32_t*)d_status,
                                             rows_out_of(d_rev, rev_stride, d_rev_len),
                                             d_rev_pn_len, st));
         return 0;

@@ -154,6 +154,81 @@ extern "C" int qfec_arrivals_rx_block_bytes(int k, int m, long long groups, long
     return 0;
 }
 
+// The same with the state in the caller's hands, so that a stream can be fed in pieces: seen
+// [groups][32] is a bitset of the indices counted so far (bit i of a group: byte i / 8, bit
+// i % 8), bb [groups] the running maximum over the group's first k distinct indices.  Both are
+// in/out; a group's entries are zeroed by the caller when it releases the group.  Over the
+// pieces of a stream, from zeroed state, bb ends as qfec_arrivals_rx_block_bytes gives it over
+// their concatenation.
+extern "C" int qfec_arrivals_rx_block_bytes_carry(int k, int m, long long groups, long long n,
+                                                  const int* arr_group,
+                                                  const unsigned char* arr_index,
+                                                  const int* pkt_len, const int* ad_len,
+                                                  int ad_len_all, unsigned char* seen, int* bb) {
+    if (k < 1 || m < 1 || k + m > 255 || groups < 0 || n < 0 || (groups && (!bb || !seen)) ||
+        (n && (!arr_group || !arr_index || !pkt_len)))
+        return -2;
+    const int per = k + m;
+    for (long long a = 0; a < n; ++a) {
+        const long long g = arr_group[a];
+        const int i = arr_index[a];
+        if (g < 0 || g >= groups || i >= per) continue;   // no packet of this window
+        const long long tl = pkt_len[a], al = ad_len ? ad_len[a] : ad_len_all;
+        if (tl < 0 || al < 0 || tl - al < 12) continue;    // no packet
+        unsigned char* sg = seen + g * 32;
+        int held = 0;
+        for (int b = 0; b < 32; ++b) held += __builtin_popcount(sg[b]);
+        if (((sg[i >> 3] >> (i & 7)) & 1) || held >= k) continue;   // duplicate, late
+        sg[i >> 3] = (unsigned char)(sg[i >> 3] | (1u << (i & 7)));
+        const long long size = tl - al - 12 + (i < k ? 2 : 0);
+        bb[g] = (int)std::max<long long>(bb[g], std::min<long long>(size, 0x7fffffffLL));
+    }
+    return 0;
+}
+
+// ---- the receiver window's allocation
+int qfec::rxwin_layout(int k, int m, long long groups, int hold_stride, RxwinLayout* L,
+                       const char** why) {
+    const char* dummy;
+    if (!why) why = &dummy;
+    *why = "";
+    if (k < 1 || m < 1 || groups < 0) return *why = "bad k / m / groups", -2;
+    if (k > 255) return *why = "k > 255 cannot be tagged by an 8-bit row", -2;
+    if (k + m > 255) return *why = "k + m > 255", -2;
+    const long long per = k + m, rmax = std::min(k, m);
+    if (groups > 0x7fffffffLL / per) return *why = "groups * (k + m) above INT32_MAX", -2;
+    if (hold_stride < 16 || hold_stride % 16)
+        return *why = "hold_stride must be a multiple of 16, at least 16", -2;
+    const long long S = groups * per;   // < 2^31, so every product below stays under 2^62
+    long long at = 0;
+    const auto take = [&](long long bytes) {
+        const long long here = at;
+        at += (bytes + 255) & ~255LL;
+        return here;
+    };
+    L->hold = take(S * hold_stride);
+    L->slot_state = take(S * 4);
+    L->held = take(groups * 4);
+    L->delivered = take(groups * 4);
+    L->arr_at = take(S * 4);
+    L->pre_at = take(S * 4);
+    L->rows = take(groups * k);
+    L->blk_ptrs = take(groups * k * 8);
+    L->rec_ptrs = take(groups * rmax * 8);
+    L->eff = take(groups * 4);
+    L->verdict = take(groups * 4);
+    L->total = at;
+    return 0;
+}
+
+extern "C" int qfec_rxwin_bytes(int k, int m, long long groups, int hold_stride,
+                                long long* bytes) {
+    qfec::RxwinLayout L;
+    if (!bytes || qfec::rxwin_layout(k, m, groups, hold_stride, &L, nullptr)) return -2;
+    *bytes = L.total;
+    return 0;
+}
+
 // ---- the packet geometry of a mixed-code batch: with a code per group, packet p no longer
 // belongs to group p / (k + m), so the wire calls take two prefix tables.
 static bool mixed_codes_ok(int ncodes, const int* k, const int* m) {

@@ -118,4 +118,19 @@ long long uniform_chunk(long long groups, size_t per_group, int host_chunk_mb, i
 int ragged_chunks(const StageList& L, const Stage& in, const Stage& out, long long groups,
                   long long target_bytes, Chunks* ch, const char** msg);
 
+// The receiver window's one device allocation (qfec_rxwin_create, include/quic_fec.h): byte
+// offsets of its sections, each rounded up to 256 bytes, in this order.  With S = groups * (k + m)
+// slots and rmax = min(k, m): the hold rows S * hold_stride; the carried state: slot_state int32
+// [S], held int32 [G], delivered int32 [G]; the per-push tables: arr_at and pre_at int32 [S], rows
+// u8 [G][k], blk_ptrs u64 [G * k], rec_ptrs u64 [G * rmax], eff (the effective bb) and verdict
+// int32 [G].  total: their sum, what qfec_rxwin_bytes reports.
+struct RxwinLayout {
+    long long hold, slot_state, held, delivered, arr_at, pre_at, rows, blk_ptrs, rec_ptrs, eff,
+        verdict, total;
+};
+// 0, or -2 with *why (may be null) naming the limit: k, m < 1, k > 255, groups < 0, k + m > 255,
+// groups * (k + m) > INT32_MAX, hold_stride < 16 or not a multiple of 16, a total past 2^62.
+int rxwin_layout(int k, int m, long long groups, int hold_stride, RxwinLayout* L,
+                 const char** why);
+
 }  // namespace qfec

@@ -97,6 +97,33 @@ hipError_t launch_extract_revived(int k, int m, long long groups, RaggedView v, 
                                   const uint8_t* rec_rows, const int32_t* status, RowsOut rev,
                                   uint8_t* rev_pn_len, hipStream_t st);
 
+// The receiver window (include/quic_fec.h, "Receiver window"): the
+// arrival-order open against state that stays on the device between calls.  The sections of the
+// window's allocation (fec_host_plan.h, RxwinLayout) as device pointers.
+struct RxWin {
+    int k, m;
+    long long groups, hold_stride;
+    uint8_t* hold;                            // [groups * (k + m)][hold_stride]
+    int32_t *slot_state, *held, *delivered;   // the carried state
+    int32_t *arr_at, *pre_at;                 // one push's binding and pre-pass tables
+    uint8_t* rows;                            // [groups][k], the decode's rows_in
+    unsigned long long *blk_ptrs, *rec_ptrs;  // [groups * k], [groups * min(k, m)]
+    int32_t *eff, *verdict;                   // [groups]: the effective bb; 0 or the status to set
+};
+// One push up to the decode: init -> pre (optimistic) -> open -> assemble -> state (arr_state).
+// Afterwards w.rows, w.blk_ptrs, w.rec_ptrs and w.eff are the pointer-table decode's arguments:
+// eff[g] = bb[g] for a group that completes in this push, 0 for every other.
+hipError_t launch_rxwin_bind(const RxWin& w, const int32_t* bb, long long n, Rows pkt, Rows ad,
+                             const uint8_t* pn_len, int pn_all, const int32_t* arr_group,
+                             const uint8_t* arr_index, int32_t* arr_state, uint8_t* rec,
+                             const long long* rec_off, bool optimistic, hipStream_t st);
+// After the decode: status (may be null) and rec_rows 255 of the groups that did not complete.
+hipError_t launch_rxwin_finish(const RxWin& w, uint8_t* rec_rows, int32_t* status,
+                               hipStream_t st);
+// list [count] (device, int32) back to empty; list null: every group.
+hipError_t launch_rxwin_release(const RxWin& w, long long count, const int32_t* list,
+                                hipStream_t st);
+
 // After the decode of an open batch: groups with an unfilled slot get status -3 and no
 // recovered rows.
 hipError_t launch_open_status(int k, int rmax, long long groups, const uint8_t* rows,

@@ -49,6 +49,10 @@
 // per-arrival and per-group kernels are one body over a geometry type (UniGeo, MixedGeo); the
 // seal takes MixedRows, whose packets find their group by a search of the table
 // (mixed_group_of); mixed_wire_plan_kernel decides every group once for all of them.
+//
+// Receiver window: the arrival-order receiver with its binding state kept
+// on the device from call to call (rxwin_* kernels): every accepted packet is held in a row of its
+// own, and a group that completes is decoded where it lies through pointer tables.
 #include "fec_kernels.h"
 #include "pp_null.h"
 #include "pp_mixed.h"
@@ -1553,6 +1557,280 @@ __global__ __launch_bounds__(kPPThreads) void arrivals_state_kernel(
         arr_state[a] = kArrDuplicate;
 }
 
+// ------------------------------------------------------------------ receiver window
+// The arrival-order receiver with its state kept on the device between calls (DESIGN.md section
+// 6.7; include/quic_fec.h, "Receiver window").  Every slot p = g * (k + m) + i owns a hold row of
+// hold_stride bytes and a state: kSlotEmpty, kSlotSeen (a first copy that came late), or the
+// plaintext length of the packet it holds.  A push binds its arrivals as the one-shot call does,
+// by a minimum over arrival indices, but against the carried state: rxwin_init_kernel gives a
+// slot that is not empty the value kWinTaken, below every arrival index, so no arrival of the
+// push can win it and all that hit it come out as duplicates.  An accepted packet lies in its own
+// row as prefix || payload || zeros (data) or plaintext || zeros (FEC), so the first bb bytes of
+// the row are the one-shot call's block for any bb up to hold_stride, and a group that completes
+// hands the decode the addresses of its rows: nothing is copied.
+constexpr int32_t kSlotEmpty = -1, kSlotSeen = -2;
+constexpr int32_t kWinTaken = -1;
+constexpr int kWinOpen = -3, kWinDelivered = -5;
+
+// the size the length checks of a push run against: none passes with -1
+__device__ __forceinline__ int win_bb(const int32_t* __restrict__ bbs, long long g,
+                                      long long hold_stride) {
+    const int b = bbs[g];
+    return b < 1 || b > hold_stride ? -1 : b;
+}
+// the longest plaintext slot i takes (FramedSlots::limit)
+__device__ __forceinline__ int win_limit(int bb, bool data) { return data ? bb - 2 : bb; }
+
+// One lane per slot.  pre_at: null without the optimistic write.
+__global__ __launch_bounds__(kPPThreads) void rxwin_init_kernel(
+    long long slots, const int32_t* __restrict__ slot_state, int32_t* arr_at, int32_t* pre_at) {
+    const long long p = (long long)blockIdx.x * kPPThreads + threadIdx.x;
+    if (p >= slots) return;
+    const int32_t v = slot_state[p] == kSlotEmpty ? kArrNone : kWinTaken;
+    arr_at[p] = v;
+    if (pre_at) pre_at[p] = v;
+}
+
+// One lane per arrival, as arrivals_pre_kernel, for data and FEC slots: every packet has a row
+// of its own here, so an FEC packet's first candidate can be written before its tag is known too.
+__global__ __launch_bounds__(kPPThreads) void rxwin_pre_kernel(
+    int k, int m, long long groups, long long hold_stride, const int32_t* __restrict__ bbs,
+    long long n, long long pkt_stride, const int32_t* __restrict__ pkt_len,
+    const int32_t* __restrict__ ad_len, int ad_all, const int32_t* __restrict__ arr_group,
+    const uint8_t* __restrict__ arr_index, int32_t* pre_at) {
+    const long long a = (long long)blockIdx.x * kPPThreads + threadIdx.x;
+    if (a >= n) return;
+    const long long g = arr_group[a];
+    const int i = arr_index[a];
+    if (g < 0 || g >= groups || i >= k + m) return;
+    if (open_len_ok(pkt_len, ad_len, ad_all, a, win_limit(win_bb(bbs, g, hold_stride), i < k),
+                    pkt_stride))
+        atomicMin(pre_at + g * (k + m) + i, (int32_t)a);
+}
+
+// One lane per arrival, 64 per wave: open_arrivals_kernel's body.  The length checks run against
+// the bb[g] of this push; the slot's first candidate by the length checks (pre_at; null: no
+// optimistic write) streams into its hold row with the rest of the row as output length, so the
+// row is zero-padded to hold_stride; a data packet's prefix is written behind it.  A slot that is
+// not empty holds kWinTaken in both tables: it is never written and never won.
+template <class H>
+__global__ __launch_bounds__(64) void rxwin_open_kernel(
+    int k, int m, long long groups, uint8_t* hold, long long hold_stride,
+    const int32_t* __restrict__ bbs, long long n, const uint8_t* __restrict__ pkt,
+    long long pkt_stride, const int32_t* __restrict__ pkt_len, const int32_t* __restrict__ ad_len,
+    int ad_all, const uint8_t* __restrict__ pn_len, int pn_all,
+    const int32_t* __restrict__ arr_group, const uint8_t* __restrict__ arr_index,
+    int32_t* arr_state, int32_t* arr_at, const int32_t* __restrict__ pre_at) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const long long a = (long long)blockIdx.x * 64 + threadIdx.x;
+    bool tagged = false, ok = false, place = false;
+    long long slot = 0;
+    int i = 0, al = 0, cl = 0;
+    if (a < n) {
+        const long long g = arr_group[a];
+        i = arr_index[a];
+        tagged = g >= 0 && g < groups && i < k + m;
+        if (tagged) {
+            slot = g * (k + m) + i;
+            al = len_of(ad_len, ad_all, a);
+            cl = pkt_len[a] - al;
+            ok = open_len_ok(pkt_len, ad_len, ad_all, a,
+                             win_limit(win_bb(bbs, g, hold_stride), i < k), pkt_stride);
+            place = ok && pre_at && pre_at[slot] == (int32_t)a;
+        }
+    }
+    const int lead = i < k ? 2 : 0;
+    const uint8_t* pp = pkt + (ok ? a : 0) * pkt_stride;
+    const uint8_t* c = pp + al;
+    uint8_t* row = hold + slot * hold_stride;
+    H h;
+    h.init();
+    Sink s;
+    if (ok) span<true, false, 1>(h, s, pp, al);
+    tile_stream(h, ok ? c + 12 : nullptr, ok ? cl - 12 : 0, place ? row + lead : nullptr,
+                place ? (int)hold_stride - lead : 0, smem);
+    if (a >= n) return;
+    if (place && lead) {
+        const uint32_t v = (uint32_t)(cl - 12) | ((uint32_t)(pn_len ? pn_len[a] : pn_all) << 14);
+        gst8(row, v);
+        gst8(row + 1, v >> 8);
+    }
+    bool opened = false;
+    if (ok) {
+        uint32_t t0, t1, t2;
+        h.tag(t0, t1, t2);
+        opened = tag_matches(c, t0, t1, t2);
+    }
+    if (opened) atomicMin(arr_at + slot, (int32_t)a);
+    if (arr_state) arr_state[a] = !tagged ? kArrIgnored : opened ? cl - 12 : kArrRejected;
+}
+
+// One wave per group, after the open pass.  The group's candidates of this push are the slots
+// whose arr_at holds an arrival; ranked by arrival index behind the packets the group holds
+// already, the first k - held are accepted (slot state = the plaintext length), the others are
+// late (slot state kSlotSeen, arr_state kArrLate).  An accepted packet that the open pass did not
+// write (pre_at names another arrival, or there is no optimistic write) is placed into its row
+// from the ring.  A group that reaches k completes: rows as arrivals_assemble_kernel forms them
+// over the held slots, block pointer g * k + i = the hold row of the packet in that position, rec
+// pointer g * rmax + j = rec + rec_off[g] + j * bb, eff[g] = bb (this push's bb[g]), verdict 0.
+// Every other group: eff 0 (the decode then dereferences none of its pointers), identity rows (the
+// decode's prep sees a group without a loss) and verdict kWinOpen / kWinDelivered, which
+// rxwin_finish_kernel turns into the group's status after the decode.  A completing group that
+// holds a packet larger than this push's bb: verdict -3, eff 0.
+__global__ __launch_bounds__(kAsmWaves * 64) void rxwin_assemble_kernel(
+    int k, int m, long long groups, uint8_t* hold, long long hold_stride, int32_t* slot_state,
+    int32_t* held, int32_t* delivered, const int32_t* __restrict__ bbs,
+    const uint8_t* __restrict__ pkt, long long pkt_stride, const int32_t* __restrict__ pkt_len,
+    const int32_t* __restrict__ ad_len, int ad_all, const uint8_t* __restrict__ pn_len, int pn_all,
+    int32_t* arr_state, int32_t* arr_at, const int32_t* __restrict__ pre_at, uint8_t* rec,
+    const long long* __restrict__ rec_off, uint8_t* rows, unsigned long long* blk_ptrs,
+    unsigned long long* rec_ptrs, int32_t* eff, int32_t* verdict) {
+    __shared__ int32_t cand[kAsmWaves][256];   // the slot's candidate, then what is to be placed
+    __shared__ uint8_t isheld[kAsmWaves][256], lavail[kAsmWaves][256];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long g = (long long)blockIdx.x * kAsmWaves + w;
+    if (g >= groups) return;   // uniform over the wave; no workgroup barrier below
+    const int per = k + m, rmax = min(k, m);
+    const long long first = g * per;
+    int32_t* at = arr_at + first;
+    int32_t* ss = slot_state + first;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int held0 = __builtin_amdgcn_readfirstlane(held[g]);
+    const int deliv0 = __builtin_amdgcn_readfirstlane(delivered[g]);
+    const int bb = __builtin_amdgcn_readfirstlane(win_bb(bbs, g, hold_stride));
+    for (int s = lane; s < per; s += 64) cand[w][s] = at[s];
+    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes are visible
+    __builtin_amdgcn_wave_barrier();
+    // rank of each candidate among the group's; every lane runs the whole loop
+    int32_t keep[4] = {-1, -1, -1, -1};
+    int32_t st[4] = {kSlotEmpty, kSlotEmpty, kSlotEmpty, kSlotEmpty};
+    int nacc = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (64 * q >= per) break;   // uniform: no slot of the group is left
+        const int s = lane + 64 * q;
+        const int32_t a = s < per ? cand[w][s] : kArrNone;
+        const bool is = a >= 0 && a != kArrNone;
+        int rank = 0;
+        for (int t = 0; t < per; ++t) {
+            const int32_t c = cand[w][t];
+            rank += c >= 0 && c < a ? 1 : 0;
+        }
+        const bool acc = is && held0 + rank < k;
+        if (s < per) st[q] = ss[s];
+        if (acc) {
+            keep[q] = a;
+            st[q] = pkt_len[a] - len_of(ad_len, ad_all, a) - 12;
+            ss[s] = st[q];
+        } else if (is) {
+            st[q] = kSlotSeen;
+            ss[s] = kSlotSeen;
+            if (arr_state) arr_state[a] = kArrLate;
+        }
+        nacc += __popcll(__ballot(acc));
+    }
+    __builtin_amdgcn_wave_barrier();   // every rank is formed before the table changes
+    bool big = false;                   // a held packet that does not fit this push's bb
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int s = lane + 64 * q;
+        if (s < per) {
+            const int32_t a = keep[q];
+            at[s] = a;
+            // what the open pass wrote already is not placed again
+            cand[w][s] = a >= 0 && pre_at && pre_at[first + s] == a ? -1 : a;
+            isheld[w][s] = st[q] >= 0;
+            big |= st[q] >= 0 && st[q] + (s < k ? 2 : 0) > bb;
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+    // the accepted packets the open pass did not write, from the ring into their rows
+    for (int s = 0; s < per; ++s) {
+        const int32_t a = __builtin_amdgcn_readfirstlane(cand[w][s]);   // the same in every lane
+        if (a < 0) continue;
+        const int al = len_of(ad_len, ad_all, a);
+        const int pl = pkt_len[a] - al - 12;
+        const uint32_t pre = (uint32_t)pl | ((uint32_t)(pn_len ? pn_len[a] : pn_all) << 14);
+        wave_place(hold + (first + s) * hold_stride, pkt + a * pkt_stride + al + 12, pl,
+                   (int)hold_stride, s < k ? 2 : 0, pre, lane);
+    }
+    const int newheld = held0 + nacc;
+    const bool completes = held0 < k && newheld == k;
+    const bool toobig = __ballot(big) != 0;
+    if (lane == 0) {
+        held[g] = newheld;
+        if (completes) delivered[g] = 1;
+        eff[g] = completes && !toobig ? bb : 0;
+        verdict[g] = completes ? (toobig ? -3 : 0) : deliv0 ? kWinDelivered : kWinOpen;
+    }
+    if (!completes || toobig) {
+        for (int i = lane; i < k; i += 64) rows[g * k + i] = (uint8_t)i;
+        return;
+    }
+    // rows, as arrivals_assemble_kernel forms them, over the held slots; the blocks are the rows
+    int na = 0;
+    for (int b0 = 0; b0 < m; b0 += 64) {
+        const int j = b0 + lane;
+        const bool v = j < m && isheld[w][k + j];
+        const unsigned long long bal = __ballot(v);
+        if (v) lavail[w][na + __popcll(bal & below)] = (uint8_t)j;
+        na += __popcll(bal);
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);
+    __builtin_amdgcn_wave_barrier();
+    int nh = 0;
+    for (int b0 = 0; b0 < k; b0 += 64) {
+        const int i = b0 + lane;
+        const bool miss = i < k && !isheld[w][i];
+        const unsigned long long bal = __ballot(miss);
+        const int r = nh + __popcll(bal & below);
+        if (i < k) {
+            int row = i;
+            if (miss) row = r < na ? k + lavail[w][r] : 255;
+            rows[g * k + i] = (uint8_t)row;
+            // (a group that holds k has a held FEC packet for every hole: row is never 255)
+            const int from = row == 255 ? i : row;
+            blk_ptrs[g * k + i] = (unsigned long long)(uintptr_t)(hold + (first + from) * hold_stride);
+        }
+        nh += __popcll(bal);
+    }
+    uint8_t* rg = rec + rec_off[g];
+    for (int j = lane; j < rmax; j += 64)
+        rec_ptrs[g * rmax + j] = (unsigned long long)(uintptr_t)(rg + (long long)j * bb);
+}
+
+// One lane per group, after the decode: the decode's prep wrote status 0 and no recovered row
+// for a group that did not complete in this push (identity rows); its status is the verdict, and
+// its rec_rows are 255 whatever path decoded.  rev_len -1 follows from eff 0 in the extraction.
+__global__ __launch_bounds__(kPPThreads) void rxwin_finish_kernel(
+    long long groups, int rmax, const int32_t* __restrict__ verdict, uint8_t* rec_rows,
+    int32_t* status) {
+    const long long g = (long long)blockIdx.x * kPPThreads + threadIdx.x;
+    if (g >= groups) return;
+    const int v = verdict[g];
+    if (v == 0) return;
+    if (status) status[g] = v;
+    for (int j = 0; j < rmax; ++j) rec_rows[g * rmax + j] = 255;
+}
+
+// One lane per slot of the listed groups (list null: of every group): back to empty.
+__global__ __launch_bounds__(kPPThreads) void rxwin_release_kernel(
+    long long groups, int per, long long count, const int32_t* __restrict__ list,
+    int32_t* slot_state, int32_t* held, int32_t* delivered) {
+    const long long q = (long long)blockIdx.x * kPPThreads + threadIdx.x;
+    const long long e = q / per;
+    if (e >= count) return;
+    const int s = (int)(q - e * per);
+    const long long g = list ? (long long)list[e] : e;
+    if (g < 0 || g >= groups) return;
+    slot_state[g * per + s] = kSlotEmpty;
+    if (s == 0) {
+        held[g] = 0;
+        delivered[g] = 0;
+    }
+}
+
 unsigned pp_grid(long long n) {
     return (unsigned)((n + kPPThreads - 1) / kPPThreads);
 }
@@ -1748,6 +2026,70 @@ hipError_t launch_open_status(int k, int rmax, long long groups, const uint8_t* 
     if (!pp_grid_ok(groups)) return hipErrorInvalidValue;
     qlaunch(open_status_kernel<UniRowsK>, dim3(pp_grid(groups)), dim3(kPPThreads), 0, st, groups,
             UniRowsK{k}, rmax, rows, rec_rows, status);
+    return hipGetLastError();
+}
+
+// ---- the receiver window
+hipError_t launch_rxwin_bind(const RxWin& w, const int32_t* bb, long long n, Rows pkt, Rows ad,
+                             const uint8_t* pn_len, int pn_all, const int32_t* arr_group,
+                             const uint8_t* arr_index, int32_t* arr_state, uint8_t* rec,
+                             const long long* rec_off, bool optimistic, hipStream_t st) {
+    const int per = w.k + w.m;
+    const long long slots = w.groups * per;
+    if (per > 255 || n > 0x7fffffffLL || slots > 0x7fffffffLL) return hipErrorInvalidValue;
+    int32_t* pre_at = optimistic && n > 0 ? w.pre_at : nullptr;
+    if (slots > 0) {
+        note_kernel("rxwin_init_kernel");
+        qlaunch(rxwin_init_kernel, dim3(pp_grid(slots)), dim3(kPPThreads), 0, st, slots,
+                (const int32_t*)w.slot_state, w.arr_at, pre_at);
+    }
+    if (n > 0 && slots > 0 && pre_at) {
+        note_kernel("rxwin_pre_kernel");
+        qlaunch(rxwin_pre_kernel, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, w.k, w.m, w.groups,
+                w.hold_stride, bb, n, pkt.stride, pkt.len, ad.len, ad.len_all, arr_group,
+                arr_index, pre_at);
+    }
+    if (n > 0) {
+        note_kernel("rxwin_open_kernel");
+        qlaunch(rxwin_open_kernel<Fnv>, dim3(tile_grid(n)), dim3(64), kTileBytes, st, w.k, w.m,
+                w.groups, w.hold, w.hold_stride, bb, n, pkt.p, pkt.stride, pkt.len, ad.len,
+                ad.len_all, pn_len, pn_all, arr_group, arr_index, arr_state, w.arr_at,
+                slots > 0 ? (const int32_t*)pre_at : nullptr);
+    }
+    if (slots > 0) {
+        note_kernel("rxwin_assemble_kernel");
+        qlaunch(rxwin_assemble_kernel, dim3((unsigned)((w.groups + kAsmWaves - 1) / kAsmWaves)),
+                dim3(kAsmWaves * 64), 0, st, w.k, w.m, w.groups, w.hold, w.hold_stride,
+                w.slot_state, w.held, w.delivered, bb, pkt.p, pkt.stride, pkt.len, ad.len,
+                ad.len_all, pn_len, pn_all, arr_state, w.arr_at, (const int32_t*)pre_at, rec,
+                rec_off, w.rows, w.blk_ptrs, w.rec_ptrs, w.eff, w.verdict);
+    }
+    if (n > 0 && slots > 0 && arr_state) {
+        note_kernel("arrivals_state_kernel");
+        qlaunch(arrivals_state_kernel<UniFirst>, dim3(pp_grid(n)), dim3(kPPThreads), 0, st,
+                UniFirst{per}, n, arr_group, arr_index, (const int32_t*)w.arr_at, arr_state);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_rxwin_finish(const RxWin& w, uint8_t* rec_rows, int32_t* status,
+                               hipStream_t st) {
+    if (w.groups <= 0) return hipSuccess;
+    note_kernel("rxwin_finish_kernel");
+    qlaunch(rxwin_finish_kernel, dim3(pp_grid(w.groups)), dim3(kPPThreads), 0, st, w.groups,
+            std::min(w.k, w.m), (const int32_t*)w.verdict, rec_rows, status);
+    return hipGetLastError();
+}
+
+hipError_t launch_rxwin_release(const RxWin& w, long long count, const int32_t* list,
+                                hipStream_t st) {
+    const int per = w.k + w.m;
+    if (!list) count = w.groups;
+    if (count <= 0 || w.groups <= 0) return hipSuccess;
+    if (count > 0x7fffffffLL / per || !pp_grid_ok(count * per)) return hipErrorInvalidValue;
+    note_kernel("rxwin_release_kernel");
+    qlaunch(rxwin_release_kernel, dim3(pp_grid(count * per)), dim3(kPPThreads), 0, st, w.groups,
+            per, count, list, w.slot_state, w.held, w.delivered);
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@ Device buffers are torch tensors (uint8, contiguous, on a ROCm device): torch is
 used only for memory and streams.
 """
 import ctypes
+import weakref
 
 import numpy as np
 
@@ -264,6 +265,10 @@ class FecEngine:
 
     def close(self):
         if getattr(self, "_h", None):
+            for ref in getattr(self, "_windows", []):   # a window is destroyed before its context
+                win = ref()
+                if win is not None:
+                    win.close()
             self.lib.qfec_ctx_destroy(self._h)
             self._h = None
 
@@ -622,6 +627,11 @@ class FecEngine:
               _ptr(rows), _ptr(open_len), _ptr(rec), _ptr(rec_off), _ptr(rec_rows), _ptr(status),
               _ptr(rev), rev.stride(0), _ptr(rev_len), _ptr(rev_pn_len), _stream(stream, pkt))
 
+    def rxwin(self, k, m, groups, hold_stride):
+        """A receiver window on this engine (include/quic_fec.h, "Receiver window"): `groups`
+        group places of one (k, m) whose state stays on the device from push to push."""
+        return RxWindow(self, k, m, groups, hold_stride)
+
     # mixed-code wire path (include/quic_fec.h, "Mixed-code wire path")
     def frame_encode_seal_mixed(self, cs, code, bb, pkt_first, pay_first, data, data_off, parity,
                                 par_off, hdr, hdr_len, pay, pay_len, pn_len, pkt, pkt_len,
@@ -706,6 +716,86 @@ class FecEngine:
         _call("qfec_decode_batch_host", self, k, m, block_bytes, G, _vp(blocks), _vp(rows),
               _vp(status))
         return blocks, rows, status
+
+
+class RxWindow:
+    """FecEngine.rxwin: the arrival-order receiver with its state kept between calls (qfec_rxwin).
+    push feeds one ring read; a group delivers in the push that brings its k-th packet, with
+    status WIN_OPEN before and WIN_DELIVERED after; release returns places to empty.  The engine
+    must outlive the window."""
+
+    def __init__(self, engine, k, m, groups, hold_stride):
+        self.engine, self.k, self.m = engine, int(k), int(m)
+        self.groups, self.hold_stride = int(groups), int(hold_stride)
+        h = ctypes.c_void_p()
+        rc = engine.lib.qfec_rxwin_create(engine._h, self.k, self.m, self.groups,
+                                          self.hold_stride, ctypes.byref(h))
+        if rc:
+            raise FecError(rc, "qfec_rxwin_create")
+        self._h = h
+        if not hasattr(engine, "_windows"):
+            engine._windows = []
+        engine._windows.append(weakref.ref(self))
+
+    def _call(self, name, *args):
+        rc = getattr(self.engine.lib, name)(self._h, *args)
+        if rc:
+            raise FecError(rc, name)
+
+    def push(self, bb, pkt, pkt_len, ad_len, pn_len, arr_group, arr_index, arr_state, rec,
+             rec_off, rec_rows, rev, rev_len, rev_pn_len=None, status=None, stream=None):
+        """One ring in arrival order: bb int32 [groups] (this push's block size per group); pkt
+        uint8 [n][stride], pkt_len int32 [n], ad_len int32 [n] or an int, pn_len uint8 [n] or an
+        int, arr_group int32 [n] and arr_index uint8 [n] per arrival, as
+        open_decode_extract_arrivals_ragged takes them; arr_state int32 [n] or None.  rec (packed,
+        rec_off int64 [groups]), rec_rows uint8 [groups][rmax], rev uint8 [groups*rmax][stride],
+        rev_len int32 and rev_pn_len uint8 [groups*rmax], status int32 [groups] receive the
+        groups that complete in this push."""
+        G, k, m = self.groups, self.k, self.m
+        _check(bb, "bb", "int32", (G,))
+        _check(rec_off, "rec_off", "int64", (G,))
+        _check(pkt, "pkt", "uint8", (None, None), rows=True)
+        n, rmax = pkt.shape[0], min(k, m)
+        _check(pkt_len, "pkt_len", "int32", (n,), rows=True)
+        _check(ad_len, "ad_len", "int32", (n,), rows=True)
+        _check(pn_len, "pn_len", "uint8", (n,), rows=True)
+        _check(arr_group, "arr_group", "int32", (n,), rows=True)
+        _check(arr_index, "arr_index", "uint8", (n,), rows=True)
+        _check(arr_state, "arr_state", "int32", (n,), rows=True)
+        _check(rev, "rev", "uint8", (G * rmax, None), rows=True)
+        _check(rev_len, "rev_len", "int32", (G * rmax,), rows=True)
+        _check(rev_pn_len, "rev_pn_len", "uint8", (G * rmax,), rows=True)
+        _check(rec_rows, "rec_rows", "uint8", (G, rmax))
+        _check(status, "status", "int32", (G,))
+        a, a_all = _ptr_or_all(ad_len)
+        pn, pn_all = _ptr_or_all(pn_len)
+        self._call("qfec_rxwin_push", _ptr(bb), n, _ptr(pkt) if n else None, pkt.stride(0),
+                   _ptr(pkt_len), a, a_all, pn, pn_all, _ptr(arr_group), _ptr(arr_index),
+                   _ptr(arr_state), _ptr(rec), _ptr(rec_off), _ptr(rec_rows), _ptr(status),
+                   _ptr(rev), rev.stride(0), _ptr(rev_len), _ptr(rev_pn_len), _stream(stream, rec))
+
+    def release(self, groups=None, stream=None):
+        """The listed group places (int32 device tensor [count]) back to empty; None: all."""
+        import torch
+        if groups is None:
+            s = ctypes.c_void_p(int(stream)) if stream is not None else ctypes.c_void_p(
+                torch.cuda.current_stream(self.engine.device).cuda_stream)
+            return self._call("qfec_rxwin_release", 0, None, s)
+        if not isinstance(groups, torch.Tensor):
+            raise TypeError("groups: an int32 device tensor [count], or None for every group")
+        _check(groups, "groups", "int32", (None,))
+        self._call("qfec_rxwin_release", groups.shape[0], _ptr(groups), _stream(stream, groups))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.engine.lib.qfec_rxwin_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def last_kernels():
@@ -909,6 +999,52 @@ def arrivals_rx_block_bytes(k, m, groups, arr_group, arr_index, pkt_len, ad_len)
                                              _vp(pkt_len), _vp(ad_len), a_all, _vp(bb))
     if rc:
         raise ValueError(f"qfec_arrivals_rx_block_bytes: rc={rc} (k={k} m={m} groups={groups})")
+    return bb
+
+
+# RxWindow.push's status of a group that does not complete in the push
+WIN_OPEN, WIN_DELIVERED = -3, -5
+
+
+def rxwin_bytes(k, m, groups, hold_stride):
+    """Bytes of a receiver window's own device allocation (qfec_rxwin_bytes; host only)."""
+    out = ctypes.c_longlong()
+    rc = load().qfec_rxwin_bytes(k, m, groups, hold_stride, ctypes.byref(out))
+    if rc:
+        raise ValueError(f"qfec_rxwin_bytes: rc={rc} (k={k} m={m} groups={groups} "
+                         f"hold_stride={hold_stride})")
+    return out.value
+
+
+def arrivals_rx_block_bytes_carry(k, m, groups, arr_group, arr_index, pkt_len, ad_len, seen, bb):
+    """arrivals_rx_block_bytes fed in pieces (qfec_arrivals_rx_block_bytes_carry; host only):
+    seen uint8 [groups][32] and bb int32 [groups] are C-contiguous numpy arrays updated in place
+    (from zeros: a stream's pieces give what the one-shot helper gives over the whole stream; the
+    caller zeroes a group's row of both when it releases it).  Returns bb."""
+    arr_group = np.ascontiguousarray(arr_group, dtype=np.int32).reshape(-1)
+    arr_index = np.ascontiguousarray(arr_index, dtype=np.uint8).reshape(-1)
+    pkt_len = np.ascontiguousarray(pkt_len, dtype=np.int32).reshape(-1)
+    n = pkt_len.size
+    if arr_group.size != n or arr_index.size != n:
+        raise ValueError("arr_group, arr_index and pkt_len must hold one entry per arrival")
+    if isinstance(ad_len, (int, np.integer)):
+        ad_len, a_all = None, int(ad_len)
+    else:
+        ad_len, a_all = np.ascontiguousarray(ad_len, dtype=np.int32).reshape(-1), 0
+        if ad_len.size != n:
+            raise ValueError("ad_len must hold one length per arrival")
+    for name, arr, dtype, shape in (("seen", seen, np.uint8, (groups, 32)),
+                                    ("bb", bb, np.int32, (groups,))):
+        if not (isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.shape == shape
+                and arr.flags.c_contiguous and arr.flags.writeable):
+            raise ValueError(f"{name}: a writable C-contiguous {np.dtype(dtype).name} array "
+                             f"{shape}")
+    rc = load().qfec_arrivals_rx_block_bytes_carry(k, m, groups, n, _vp(arr_group),
+                                                   _vp(arr_index), _vp(pkt_len), _vp(ad_len),
+                                                   a_all, _vp(seen), _vp(bb))
+    if rc:
+        raise ValueError(f"qfec_arrivals_rx_block_bytes_carry: rc={rc} (k={k} m={m} "
+                         f"groups={groups})")
     return bb
 
 

@@ -8,7 +8,8 @@ Per case: one engine, the options set, then one encode, one recovered-layout dec
 slot-layout in-place decode on zeroed buffers; each prints qfec_last_kernels() and
 qfec_last_grids().  Then, for EXTRA_SHAPES at 11 groups under default options: the ragged
 encode and decode, the grouped seals and the open-decode (uniform and ragged; the opens read
-what the seals wrote) and every host form at host_chunk_mb = 1.  No assertions: the output is
+what the seals wrote), the framed paths, one push into a receiver window and its release, and
+every host form at host_chunk_mb = 1.  No assertions: the output is
 for diffing against another build's.  Under
 `rocprofv3 --kernel-trace --output-format csv -- python3 tools/launch_matrix.py` the trace adds
 the kernel names, grids, workgroup sizes and LDS bytes the device saw; a torch fill before each
@@ -150,6 +151,16 @@ def run_extra(k, m):
         d["open_len"], d["rrec"], d["r_off"], d["rec_rows"], rev, rev_len, status=d["status"]))
     call("f-extract", lambda: eng.extract_revived_ragged(
         k, m, d["bb"], d["rrec"], d["r_off"], d["rec_rows"], d["status"], rev, rev_len))
+    # the receiver window: the framed seal's packets as one in-order ring, then a release
+    win = eng.rxwin(k, m, G, 1360)
+    tags = torch.arange(n, device="cuda")
+    grp, idx = (tags // np_).to(torch.int32), (tags % np_).to(torch.uint8)
+    state = torch.zeros(n, dtype=torch.int32, device="cuda")
+    call("w-push", lambda: win.push(d["bb"], d["pkt"], d["pkt_len"], HDR, 1, grp, idx, state,
+                                    d["rrec"], d["r_off"], d["rec_rows"], rev, rev_len,
+                                    status=d["status"]))
+    call("w-release", lambda: win.release())
+    win.close()
     call("h-encode", lambda: fec.encode_host_into(eng, k, m, bb, h["data"], h["parity"]))
     call("h-decode", lambda: fec.decode_host_into(eng, k, m, bb, h["blocks"], h["rows"], h["status"]))
     call("h-recov", lambda: fec.decode_recovered_host_into(

@@ -59,6 +59,13 @@ receiver, at 1,024 groups and at --groups:
 and the one-code (32, 4) set against the ragged call on identical input.  Wire packets, pkt_len,
 arr_state, open_len, status, rec_rows and the revived payloads of the routes are compared byte
 for byte first.
+--window: the receiver window on the --arrivals workload's in-order ring:
+  one_shot   qfec_open_decode_extract_arrivals_ragged over the whole ring
+  window_P   the ring pushed into a window of --groups places in P = 1, 4 and 16 pieces (the sum
+             of the pushes' times; the release between repetitions is not timed)
+  empty      one push of no arrivals: the fixed cost of a push over all places
+and a window of 4,096 places fed rings of about 16k packets.  arr_state, status, rec_rows, the
+recovered blocks and the revived payloads are compared with the one-shot call's first.
 --mixed: the mixed-code batches against the ragged calls, two losses per
 group (data rows 0 and 1):
   mixed   one qfec_encode_batch_mixed / qfec_decode_batch_mixed_recovered call over groups drawn
@@ -76,6 +83,7 @@ are compared byte for byte first.
   python tools/ragged_bench.py --pp --out profiles/ragged/ragged_pp_bench.json
   python tools/ragged_bench.py --framed --out profiles/ragged/framed_bench.json
   python tools/ragged_bench.py --arrivals --out profiles/ragged/arrivals_bench.json
+  python tools/ragged_bench.py --window --out profiles/ragged/window_bench.json
 """
 import argparse
 import json
@@ -120,6 +128,9 @@ def main():
                     help="the framed protected paths against the unframed ragged ones")
     ap.add_argument("--arrivals", action="store_true",
                     help="the arrival-order receiver against the slot-order framed receiver")
+    ap.add_argument("--window", action="store_true",
+                    help="the receiver window (ring pushed whole, in 4 and in 16 pieces) against "
+                         "the one-shot arrivals call; and a 4,096-group window fed 16k-packet rings")
     ap.add_argument("--ptrs", action="store_true",
                     help="the pointer-table batches against the packed ragged calls")
     ap.add_argument("--mixed", action="store_true",
@@ -723,6 +734,173 @@ def main():
         results.append(line)
         print(json.dumps(line), flush=True)
 
+    def run_window(k, m, r, bb, label, piece_counts, with_empty=True):
+        """--window: the receiver window fed the in-order ring of --arrivals whole and in pieces,
+        against the one-shot arrivals call over the same ring, data packets 0 .. r-1 of every group
+        lost.  A route's time is the sum over its pushes, each between its own pair of timing
+        events; the release that empties the window between repetitions is not timed.  `empty`:
+        one push of no arrivals into the emptied window, the fixed cost of a push."""
+        G, per, rmax, H = len(bb), k + m, min(k, m), 16
+        n = G * per
+        stride = H + 12 + int(bb.max())
+        pay_stride = int(bb.max())
+        hold = (int(bb.max()) + 15) // 16 * 16
+        rng = np.random.default_rng(args.seed + 1)
+        lens = (np.repeat(bb, k) - 2 - rng.integers(0, 8, G * k)).astype(np.int32)
+        fbb, d_off, p_off, r_off, tot = fec.framed_layout(k, m, lens)
+        assert np.array_equal(fbb, bb)
+        pay = torch.empty((G * k, pay_stride), dtype=torch.uint8, device="cuda")
+        fec.synth_fill(pay, seed=args.seed)
+        lens_d = torch.from_numpy(lens).cuda()
+        data = torch.zeros(tot[0], dtype=torch.uint8, device="cuda")
+        par = torch.zeros(tot[1], dtype=torch.uint8, device="cuda")
+        bb_d = torch.from_numpy(bb).cuda()
+        d_off_d, p_off_d, r_off_d = (torch.from_numpy(o).cuda() for o in (d_off, p_off, r_off))
+        hdr = torch.randint(0, 256, (n, H), dtype=torch.uint8, device="cuda")
+        pkt = torch.zeros((n, stride), dtype=torch.uint8, device="cuda")
+        plen = torch.zeros(n, dtype=torch.int32, device="cuda")
+        est = torch.zeros(G, dtype=torch.int32, device="cuda")
+        eng.frame_encode_seal_ragged(k, m, bb_d, data, d_off_d, par, p_off_d, hdr, H, pay, lens_d,
+                                     1, pkt, plen, status=est)
+        torch.cuda.synchronize()
+        assert int(est.abs().max()) == 0
+        del data, par, hdr, pay
+        wl = plen.clone().view(G, per)
+        wl[:, :r] = -1
+        recv = torch.nonzero(wl.view(n) >= 0).view(-1)
+        nr = recv.numel()
+        R = dict(pkt=pkt[recv].contiguous(), len=plen[recv].contiguous(),
+                 grp=(recv // per).to(torch.int32), idx=(recv % per).to(torch.uint8),
+                 state=torch.zeros(nr, dtype=torch.int32, device="cuda"))
+        wire = int(R["len"].to(torch.int64).sum())
+        del pkt
+
+        def outputs():
+            return dict(rec=torch.zeros(tot[2], dtype=torch.uint8, device="cuda"),
+                        rr=torch.zeros((G, rmax), dtype=torch.uint8, device="cuda"),
+                        st=torch.zeros(G, dtype=torch.int32, device="cuda"),
+                        rev=torch.zeros((G * rmax, pay_stride), dtype=torch.uint8, device="cuda"),
+                        rev_len=torch.zeros(G * rmax, dtype=torch.int32, device="cuda"),
+                        rev_pn=torch.zeros(G * rmax, dtype=torch.uint8, device="cuda"))
+
+        one, o = outputs(), outputs()
+        one.update(blocks=torch.zeros(tot[0], dtype=torch.uint8, device="cuda"),
+                   rows=torch.zeros((G, k), dtype=torch.uint8, device="cuda"),
+                   ol=torch.zeros(n, dtype=torch.int32, device="cuda"),
+                   at=torch.zeros(n, dtype=torch.int32, device="cuda"),
+                   state=torch.zeros(nr, dtype=torch.int32, device="cuda"))
+
+        def one_shot():
+            eng.open_decode_extract_arrivals_ragged(
+                k, m, bb_d, R["pkt"], R["len"], H, 1, R["grp"], R["idx"], one["state"], one["at"],
+                one["blocks"], d_off_d, one["rows"], one["ol"], one["rec"], r_off_d, one["rr"],
+                one["rev"], one["rev_len"], rev_pn_len=one["rev_pn"], status=one["st"])
+
+        win = eng.rxwin(k, m, G, hold)
+
+        def push(a, b):
+            win.push(bb_d, R["pkt"][a:b], R["len"][a:b], H, 1, R["grp"][a:b], R["idx"][a:b],
+                     R["state"][a:b], o["rec"], r_off_d, o["rr"], o["rev"], o["rev_len"],
+                     rev_pn_len=o["rev_pn"], status=o["st"])
+
+        def cuts_of(P):
+            return [nr * i // P for i in range(P + 1)]
+
+        one_shot()
+        kern = dict(one_shot=fec.last_kernels())
+        torch.cuda.synchronize()
+        # outputs first: a group's status, rec_rows, rev_len and rev_pn_len are what the push that
+        # completes it wrote (a later push overwrites them with the delivered values, so they are
+        # gathered push by push here); rec and rev bytes are written once
+        for P in piece_counts:
+            for t_ in o.values():
+                t_.zero_()
+            win.release()
+            acc = dict(rr=torch.full_like(o["rr"], 255), rev_len=torch.full_like(o["rev_len"], -1),
+                       rev_pn=torch.zeros_like(o["rev_pn"]),
+                       st=torch.full_like(o["st"], fec.WIN_OPEN))
+            cuts = cuts_of(P)
+            for a, b in zip(cuts[:-1], cuts[1:]):
+                push(a, b)
+                done = (o["st"] != fec.WIN_OPEN) & (o["st"] != fec.WIN_DELIVERED)
+                acc["st"] = torch.where(done, o["st"], acc["st"])
+                acc["rr"] = torch.where(done[:, None], o["rr"], acc["rr"])
+                dq = done.repeat_interleave(rmax)
+                acc["rev_len"] = torch.where(dq, o["rev_len"], acc["rev_len"])
+                acc["rev_pn"] = torch.where(dq, o["rev_pn"], acc["rev_pn"])
+            kern[f"window_{P}"] = fec.last_kernels()
+            torch.cuda.synchronize()
+            assert torch.equal(R["state"], one["state"]), f"arr_state differs, {P} pieces"
+            for name in ("st", "rr", "rev_len"):
+                assert torch.equal(acc[name], one[name]), f"{name} differs, {P} pieces"
+            taken = one["rev_len"] >= 0
+            assert torch.equal(acc["rev_pn"][taken], one["rev_pn"][taken])
+            for name in ("rec", "rev"):
+                assert torch.equal(o[name], one[name]), f"{name} differs, {P} pieces"
+
+        routes = ["one_shot"] + [f"window_{P}" for P in piece_counts] + \
+            (["empty"] if with_empty else [])
+        first = {}
+        pairs = 0
+        for name in routes:
+            first[name] = pairs
+            pairs += int(name.split("_")[1]) if name.startswith("window_") else 1
+        ev = DeviceEvents(2 * pairs)
+
+        def run_route(name):
+            if name == "one_shot":
+                return timed(ev, first[name], one_shot)
+            win.release()
+            if name == "empty":
+                return timed(ev, first[name], lambda: push(0, 0))
+            cuts = cuts_of(int(name.split("_")[1]))
+            for i, (a, b) in enumerate(zip(cuts[:-1], cuts[1:])):
+                timed(ev, first[name] + i, lambda: push(a, b))
+
+        t = {x: [] for x in routes}
+        for rep_i in range(args.warmup + args.reps):
+            for name in (routes if rep_i % 2 == 0 else routes[::-1]):
+                run_route(name)
+            torch.cuda.synchronize()
+            if rep_i >= args.warmup:
+                for name in routes:
+                    cnt = int(name.split("_")[1]) if name.startswith("window_") else 1
+                    t[name].append(sum(ev.elapsed_ms(2 * (first[name] + i), 2 * (first[name] + i) + 1)
+                                       for i in range(cnt)))
+        ev.close()
+        win.close()
+        # bytes moved, from the shapes (T = the bytes of one block per group, S = slots)
+        T, S = int(bb.astype(np.int64).sum()), n
+        after_open = (k + r) * T + 2 * r * T                  # decode in + out, extract in + out
+        per_arrival = 5 * nr + 13 * nr + 8 * nr + 12 * nr     # tags; pre-pass; open; state pass
+        one_tables = 12 * S + 8 * S + 12 * (k - r) * G
+        # one push over all places: init reads the slot states and writes two tables, the assemble
+        # reads three tables and the states and writes one, the group's row tags, effective bb,
+        # verdict and count; the decode's prep and status passes and the finish read them again
+        push_fixed = 12 * S + 20 * S + G * (k + 16) + G * (k + 8 + rmax + 4)
+        completing = G * (8 * k + 8 * rmax)                   # pointer tables, written once
+        one_bytes = wire + per_arrival + one_tables + k * T + after_open
+        line = dict(config=label, mode="window", k=k, m=m, losses=r, groups=G, ring_packets=nr,
+                    hold_stride=hold, window_bytes=fec.rxwin_bytes(k, m, G, hold), reps=args.reps,
+                    kernels=kern,
+                    bytes_moved=dict(one_shot=one_bytes, push_fixed=push_fixed,
+                                     hold_rows_written=k * G * hold))
+        for name in routes:
+            med = statistics.median(t[name])
+            line[name] = dict(kernel_ms_median=round(med, 4), kernel_ms_min=round(min(t[name]), 4),
+                              kernel_ms_max=round(max(t[name]), 4))
+        for P in piece_counts:
+            name = f"window_{P}"
+            line["bytes_moved"][name] = wire + per_arrival + P * push_fixed + completing + \
+                k * G * hold + after_open
+            line[name]["pushes"] = P
+            line[name]["packets_per_push"] = round(nr / P)
+            line[name]["over_one_shot"] = round(line[name]["kernel_ms_median"] /
+                                                line["one_shot"]["kernel_ms_median"], 3)
+            line[name]["byte_ratio"] = round(line["bytes_moved"][name] / one_bytes, 3)
+        results.append(line)
+        print(json.dumps(line), flush=True)
+
     def run_ptrs(k, m, r, bb, label):
         """--ptrs: the packed ragged calls against the pointer form over identity tables and over
         individually placed blocks, data rows 0 .. r-1 of every group lost."""
@@ -1212,6 +1390,15 @@ def main():
         run_mixed(presets, 2, G, f"(a) six presets, {G} groups")
         run_mixed(presets, 2, 1024, "(b) six presets, 1024 groups")
         run_mixed([(32, 4)], 2, G, f"(c) one code (32,4), {G} groups")
+        args.codes = ""
+    if args.window:
+        for k, m, r in (tuple(int(v) for v in c.split(",")) for c in args.codes.split()):
+            run_window(k, m, r, draw_sizes(G, args.seed), f"mixed ({k},{m})", [1, 4, 16])
+        # the shape a connection has: a window of 4,096 places, rings of about 16k packets
+        small = draw_sizes(4096, args.seed)
+        for k, m, r in ((32, 4, 2), (10, 1, 1)):
+            pushes = max(1, round(4096 * (k + m - r) / 16384))
+            run_window(k, m, r, small, f"4096 places, 16k-packet rings ({k},{m})", [1, pushes])
         args.codes = ""
     mixed = draw_sizes(G, args.seed)
     flat = np.full(G, 1352, np.int32)

@@ -568,6 +568,105 @@ static void check_arrivals(std::mt19937& rng) {
     }
 }
 
+// ---- the running form (qfec_arrivals_rx_block_bytes_carry) and the window's size helper
+// (qfec_rxwin_bytes): pieces of hostile random streams in arrays of exactly the piece's entries,
+// state arrays of exactly [G][32] and [G], against the one-shot helper over the whole stream;
+// duplicates and more than k arrivals across pieces, tags at the last group, n = 0, a release
+static void check_arrivals_carry(std::mt19937& rng) {
+    {
+        std::vector<unsigned char> seen(3 * 32, 0);
+        std::vector<int> bb(3, 0);
+        CHECK(qfec_arrivals_rx_block_bytes_carry(5, 5, 3, 0, nullptr, nullptr, nullptr, nullptr, 0,
+                                                 seen.data(), bb.data()) == 0);
+        CHECK(bb == std::vector<int>(3, 0) && seen == std::vector<unsigned char>(96, 0));
+        CHECK(qfec_arrivals_rx_block_bytes_carry(5, 5, 0, 0, nullptr, nullptr, nullptr, nullptr, 0,
+                                                 nullptr, nullptr) == 0);
+        const int grp[1] = {0}, len[1] = {40};
+        const unsigned char idx[1] = {0};
+        CHECK(qfec_arrivals_rx_block_bytes_carry(5, 5, 0, 1, grp, idx, len, nullptr, 16, nullptr, nullptr) == 0);
+        CHECK(qfec_arrivals_rx_block_bytes_carry(5, 5, 1, -1, grp, idx, len, nullptr, 16, seen.data(), bb.data()) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes_carry(250, 6, 1, 1, grp, idx, len, nullptr, 16, seen.data(), bb.data()) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes_carry(5, 5, 1, 1, grp, idx, len, nullptr, 16, nullptr, bb.data()) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes_carry(5, 5, 1, 1, grp, idx, len, nullptr, 16, seen.data(), nullptr) == -2);
+        CHECK(qfec_arrivals_rx_block_bytes_carry(5, 5, 1, 1, nullptr, idx, len, nullptr, 16, seen.data(), bb.data()) == -2);
+    }
+    // k = 2, m = 2, one arrival per call: a duplicate of a packet counted two calls earlier, a
+    // packet late behind k counted ones, a tag at the last group and its last index
+    {
+        const int grp[] = {0, 2, 0, 0, 0, 2, 3};
+        const unsigned char idx[] = {0, 3, 3, 0, 1, 3, 0};
+        const int len[] = {28 + 10, 28 + 24, 28 + 16, 28 + 900, 28 + 1000, 28 + 999, 2000};
+        std::vector<unsigned char> seen(3 * 32, 0);
+        std::vector<int> bb(3, 0);
+        for (int a = 0; a < 7; ++a)
+            CHECK(qfec_arrivals_rx_block_bytes_carry(2, 2, 3, 1, grp + a, idx + a, len + a, nullptr,
+                                                     16, seen.data(), bb.data()) == 0);
+        CHECK(bb[0] == 16 && bb[1] == 0 && bb[2] == 24);
+        CHECK(seen[0] == 0x09 && seen[64] == 0x08 && seen[32] == 0);
+    }
+    for (int rep = 0; rep < 50; ++rep) {
+        const int k = 1 + (int)(rng() % 60), m = 1 + (int)(rng() % 8), per = k + m;
+        const long long G = 1 + (long long)(rng() % 12);
+        const size_t n = rng() % 600;
+        std::vector<int> grp(n), len(n), ad(n);
+        std::vector<unsigned char> idx(n);
+        for (size_t a = 0; a < n; ++a) {
+            const unsigned pick = rng() % 16;
+            grp[a] = pick == 0 ? -1 : pick == 1 ? (int)G : pick == 2 ? INT_MIN : pick == 3 ? INT_MAX
+                                                                          : (int)(rng() % G);
+            if (pick == 4) grp[a] = (int)G - 1;
+            idx[a] = (unsigned char)(pick == 5 ? per : pick == 6 ? 255 : rng() % per);
+            ad[a] = pick == 7 ? -3 : (int)(rng() % 20);
+            len[a] = pick == 8 ? -1 : pick == 9 ? INT_MAX : pick == 10 ? ad[a] + 11
+                                                          : ad[a] + 12 + (int)(rng() % 1400);
+        }
+        std::vector<int> whole((size_t)G, 7);
+        CHECK(qfec_arrivals_rx_block_bytes(k, m, G, (long long)n, grp.data(), idx.data(), len.data(),
+                                           ad.data(), 0, whole.data()) == 0);
+        // the pieces, each in arrays of its own size (an empty one among them)
+        std::vector<unsigned char> seen((size_t)G * 32, 0);
+        std::vector<int> bb((size_t)G, 0);
+        size_t at = 0, released_at = n;
+        const long long rel = (long long)(rng() % G);
+        const bool release = rep % 3 == 0;
+        while (at < n || at == 0) {
+            const size_t take = std::min(n - at, (size_t)(rng() % 97));
+            std::vector<int> pg(grp.begin() + at, grp.begin() + at + take),
+                pl(len.begin() + at, len.begin() + at + take),
+                pa(ad.begin() + at, ad.begin() + at + take);
+            std::vector<unsigned char> pi(idx.begin() + at, idx.begin() + at + take);
+            CHECK(qfec_arrivals_rx_block_bytes_carry(k, m, G, (long long)take, pg.data(), pi.data(),
+                                                     pl.data(), pa.data(), 0, seen.data(),
+                                                     bb.data()) == 0);
+            at += take;
+            if (release && released_at == n && at >= n / 2) {   // one group back to empty
+                std::fill(seen.begin() + rel * 32, seen.begin() + rel * 32 + 32, 0);
+                bb[(size_t)rel] = 0;
+                released_at = at;
+            }
+            if (n == 0) break;
+        }
+        if (release && released_at < n) {
+            std::vector<int> rest((size_t)G, 7);
+            CHECK(qfec_arrivals_rx_block_bytes(k, m, G, (long long)(n - released_at),
+                                               grp.data() + released_at, idx.data() + released_at,
+                                               len.data() + released_at, ad.data() + released_at, 0,
+                                               rest.data()) == 0);
+            whole[(size_t)rel] = rest[(size_t)rel];
+        } else if (release && n > 0) {
+            whole[(size_t)rel] = 0;   // released behind the last arrival
+        }
+        CHECK(bb == whole);
+    }
+    long long bytes = -7;
+    CHECK(qfec_rxwin_bytes(10, 1, 4096, 1360, &bytes) == 0 && bytes > 4096LL * 11 * 1360);
+    CHECK(qfec_rxwin_bytes(2, 2, 0, 16, &bytes) == 0 && bytes == 0);
+    CHECK(qfec_rxwin_bytes(127, 128, 8421504, 2147483632, &bytes) == 0 && bytes > 0);   // the largest
+    CHECK(qfec_rxwin_bytes(127, 128, 8421505, 16, &bytes) == -2);
+    CHECK(qfec_rxwin_bytes(250, 6, 1, 16, &bytes) == -2 && qfec_rxwin_bytes(10, 1, 1, 24, &bytes) == -2);
+    CHECK(qfec_rxwin_bytes(10, 1, 1, 16, nullptr) == -2 && qfec_rxwin_bytes(10, 1, -1, 16, &bytes) == -2);
+}
+
 // ---- the three host helpers of the mixed-code wire path, in arrays of exactly G, G + 1, npay
 // and n entries: empty sets of groups, groups without a code, duplicates, more than k arrivals,
 // tags at the last group, n = 0, and random hostile streams against the sequential rule
@@ -734,6 +833,7 @@ int main() {
     check_plan_errors();
     check_framed(rng);
     check_arrivals(rng);
+    check_arrivals_carry(rng);
     check_mixed_layout(rng);
     check_mixed_wire(rng);
     // errors: a size < 1, bad arguments, overflow of the running offset
