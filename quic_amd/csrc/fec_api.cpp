@@ -1292,6 +1292,22 @@ static int framed_rows_args(const unsigned char* d_row, long long stride, const 
     return 0;
 }
 
+// The per-arrival arguments of the three arrival-order calls and the revived rows they write.
+// required: the call's own arrays that may not be null; n_neg, n_big: the call's messages for
+// n < 0 and for n, or its slots (slots_big), above INT32_MAX: both index int32 tables.
+static int arrivals_args(int k, int m, std::initializer_list<const void*> required,
+                         const Arrivals& ar, RowsOut rev, bool slots_big, const char* n_neg,
+                         const char* n_big) {
+    int rc = open_decode_args(k, m, true, required, ar.pkt.stride, ar.ad.len, ar.ad.len_all);
+    if (rc || (rc = framed_rows_args(rev.p, rev.stride, rev.len, "bad rev_stride"))) return rc;
+    if (ar.n < 0) return fail(-2, n_neg);
+    if (ar.n > INT32_MAX || slots_big) return fail(-2, n_big);
+    // nothing of the per-arrival arrays is read when nothing arrived
+    if (ar.n > 0 && any_null({ar.pkt.p, ar.pkt.len, ar.arr_group, ar.arr_index}))
+        return fail(-2, "null buffer");
+    return 0;
+}
+
 int qfec_frame_blocks_batch_ragged(qfec_ctx* c, int k, long long groups, const int* d_bb,
                                    const unsigned char* d_pay, long long pay_stride,
                                    const int* d_pay_len, const unsigned char* d_pn_len,
@@ -1414,36 +1430,28 @@ int qfec_open_decode_extract_arrivals_ragged(
     long long rev_stride, int* d_rev_len, unsigned char* d_rev_pn_len, void* stream) {
     int rc = ragged_check(c, k, m, groups, d_bb, d_blocks, d_blocks_off, d_rec, d_rec_off);
     if (rc) return rc;
-    if ((rc = open_decode_args(k, m, true, {d_rows, d_open_len, d_rec_rows, d_arr_at}, pkt_stride,
-                               d_ad_len, ad_len_all)))
+    const Arrivals ar{n, {d_pkt, pkt_stride, d_pkt_len, 0}, {nullptr, 0, d_ad_len, ad_len_all},
+                      d_pn_len, pn_len_all, d_arr_group, d_arr_index, d_arr_state};
+    const RowsOut rev = rows_out_of(d_rev, rev_stride, d_rev_len);
+    if ((rc = arrivals_args(k, m, {d_rows, d_open_len, d_rec_rows, d_arr_at}, ar, rev,
+                            groups > INT32_MAX / (k + m), "n < 0",
+                            "n or groups * (k + m) above INT32_MAX")))
         return rc;
-    if ((rc = framed_rows_args(d_rev, rev_stride, d_rev_len, "bad rev_stride"))) return rc;
-    if (n < 0) return fail(-2, "n < 0");
-    // arrival indices and slots live in int32 tables
-    if (n > INT32_MAX || groups > INT32_MAX / (k + m))
-        return fail(-2, "n or groups * (k + m) above INT32_MAX");
-    // the per-arrival arrays: nothing of them is read when nothing arrived
-    if (n > 0 && any_null({d_pkt, d_pkt_len, d_arr_group, d_arr_index}))
-        return fail(-2, "null buffer");
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     const hipStream_t st = pick(c, stream);
     const RaggedView v{(const int32_t*)d_bb, d_blocks_off, d_rec_off};
     return with_workspace(c, st, [&] {
-        QF_HIP(qfec::launch_open_arrivals_framed(
-            k, m, groups, v, n, rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
-            rows_of(nullptr, 0, d_ad_len, ad_len_all), d_pn_len, pn_len_all,
-            (const int32_t*)d_arr_group, d_arr_index, (int32_t*)d_arr_state, (int32_t*)d_arr_at,
-            d_blocks, d_rows, (int32_t*)d_open_len, c->tune.arr_optimistic != 0, st));
+        QF_HIP(qfec::launch_open_arrivals_framed(k, m, groups, v, ar, (int32_t*)d_arr_at, d_blocks,
+                                                 d_rows, (int32_t*)d_open_len,
+                                                 c->tune.arr_optimistic != 0, st));
         const int r = decode_ragged_impl(c, k, m, groups, v, d_blocks, d_rows, d_rec, d_rec_rows,
                                          (int32_t*)d_status, st);
         if (r) return r;
         QF_HIP(qfec::launch_open_status(k, std::min(k, m), groups, d_rows, d_rec_rows,
                                         (int32_t*)d_status, st));
         QF_HIP(qfec::launch_extract_revived(k, m, groups, v, d_rec, d_rec_rows,
-                                            (const int32_t*)d_status,
-                                            rows_out_of(d_rev, rev_stride, d_rev_len),
-                                            d_rev_pn_len, st));
+                                            (const int32_t*)d_status, rev, d_rev_pn_len, st));
         return 0;
     });
 }
@@ -1533,29 +1541,22 @@ int qfec_rxwin_push(qfec_rxwin* win, const int* d_bb, long long n, const unsigne
     int rc;
     if (any_null({d_bb, d_rec, d_rec_off, d_rec_rows})) return fail(-2, "null buffer");
     if ((uintptr_t)d_rec & 15) return fail(-2, "ragged base pointers must be 16-byte aligned");
-    if ((rc = open_decode_args(w.k, w.m, true, {}, pkt_stride, d_ad_len, ad_len_all))) return rc;
-    if ((rc = framed_rows_args(d_rev, rev_stride, d_rev_len, "bad rev_stride"))) return rc;
-    if (n < 0) return fail(-2, "n < 0");
-    if (n > INT32_MAX) return fail(-2, "n above INT32_MAX");   // arrival indices are int32
-    // the per-arrival arrays: nothing of them is read when nothing arrived
-    if (n > 0 && any_null({d_pkt, d_pkt_len, d_arr_group, d_arr_index}))
-        return fail(-2, "null buffer");
+    const Arrivals ar{n, {d_pkt, pkt_stride, d_pkt_len, 0}, {nullptr, 0, d_ad_len, ad_len_all},
+                      d_pn_len, pn_len_all, d_arr_group, d_arr_index, d_arr_state};
+    const RowsOut rev = rows_out_of(d_rev, rev_stride, d_rev_len);
+    if ((rc = arrivals_args(w.k, w.m, {}, ar, rev, false, "n < 0", "n above INT32_MAX"))) return rc;
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
     const hipStream_t st = pick(c, stream);
     return with_workspace(c, st, [&] {
-        QF_HIP(qfec::launch_rxwin_bind(
-            w, (const int32_t*)d_bb, n, rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
-            rows_of(nullptr, 0, d_ad_len, ad_len_all), d_pn_len, pn_len_all,
-            (const int32_t*)d_arr_group, d_arr_index, (int32_t*)d_arr_state, d_rec, d_rec_off,
-            c->tune.arr_optimistic != 0, st));
+        QF_HIP(qfec::launch_rxwin_bind(w, (const int32_t*)d_bb, ar, d_rec, d_rec_off,
+                                       c->tune.arr_optimistic != 0, st));
         const int r = decode_ptrs_impl(c, w.k, w.m, w.groups, {w.blk_ptrs, w.rec_ptrs, w.eff, 0},
                                        w.rows, d_rec_rows, (int32_t*)d_status, st);
         if (r) return r;
         QF_HIP(qfec::launch_rxwin_finish(w, d_rec_rows, (int32_t*)d_status, st));
         QF_HIP(qfec::launch_extract_revived(w.k, w.m, w.groups, {w.eff, nullptr, d_rec_off}, d_rec,
-                                            d_rec_rows, (const int32_t*)d_status,
-                                            rows_out_of(d_rev, rev_stride, d_rev_len),
+                                            d_rec_rows, (const int32_t*)d_status, rev,
                                             d_rev_pn_len, st));
         return 0;
     });
@@ -1632,14 +1633,13 @@ int qfec_open_decode_extract_arrivals_mixed(
                          {d_code, d_bb, d_blocks_off, d_rec_off, d_pkt_first}, d_blocks, d_rec);
     if (rc) return rc;
     if ((rc = mixed_wire_check(cs, npkt, 0))) return rc;
-    if ((rc = open_decode_args(1, 1, true, {d_rows, d_open_len, d_rec_rows, d_arr_at}, pkt_stride,
-                               d_ad_len, ad_len_all)))
+    const Arrivals ar{n, {d_pkt, pkt_stride, d_pkt_len, 0}, {nullptr, 0, d_ad_len, ad_len_all},
+                      d_pn_len, pn_len_all, d_arr_group, d_arr_index, d_arr_state};
+    const RowsOut rev = rows_out_of(d_rev, rev_stride, d_rev_len);
+    const char* n_msg = "n outside [0, INT32_MAX]";
+    if ((rc = arrivals_args(1, 1, {d_rows, d_open_len, d_rec_rows, d_arr_at}, ar, rev, false, n_msg,
+                            n_msg)))
         return rc;
-    if ((rc = framed_rows_args(d_rev, rev_stride, d_rev_len, "bad rev_stride"))) return rc;
-    if (n < 0 || n > INT32_MAX) return fail(-2, "n outside [0, INT32_MAX]");
-    // the per-arrival arrays: nothing of them is read when nothing arrived
-    if (n > 0 && any_null({d_pkt, d_pkt_len, d_arr_group, d_arr_index}))
-        return fail(-2, "null buffer");
     if (groups > 0x7fffffffLL / cs->s.rmax) return fail(-2, "groups * rmax above INT32_MAX");
     std::lock_guard<std::mutex> lk(c->mu);
     if ((rc = set_device(c))) return rc;
@@ -1651,11 +1651,10 @@ int qfec_open_decode_extract_arrivals_mixed(
                           0, nullptr, nullptr};
         mixed_wire_work(W, groups, &w);
         QF_HIP(qfec::launch_mixed_wire_plan(cs->s, groups, w, nullptr, st));
-        QF_HIP(qfec::launch_open_arrivals_mixed(
-            cs->s, groups, w, d_blocks_off, n, rows_of(d_pkt, pkt_stride, d_pkt_len, 0),
-            rows_of(nullptr, 0, d_ad_len, ad_len_all), d_pn_len, pn_len_all,
-            (const int32_t*)d_arr_group, d_arr_index, (int32_t*)d_arr_state, (int32_t*)d_arr_at,
-            d_blocks, d_rows, (int32_t*)d_open_len, c->tune.arr_optimistic != 0, st));
+        QF_HIP(qfec::launch_open_arrivals_mixed(cs->s, groups, w, d_blocks_off, ar,
+                                                (int32_t*)d_arr_at, d_blocks, d_rows,
+                                                (int32_t*)d_open_len,
+                                                c->tune.arr_optimistic != 0, st));
         const int r = decode_mixed_impl(c, cs, groups, {w.ecode, w.eff, d_blocks_off, d_rec_off},
                                         d_blocks, d_rows, d_rec, d_rec_rows, (int32_t*)d_status,
                                         st);
@@ -1663,9 +1662,8 @@ int qfec_open_decode_extract_arrivals_mixed(
         QF_HIP(qfec::launch_open_status_mixed(cs->s, groups, w, d_rows, d_rec_rows,
                                               (int32_t*)d_status, st));
         QF_HIP(qfec::launch_extract_revived_mixed(cs->s, groups, w, d_rec, d_rec_off, d_rec_rows,
-                                                  (const int32_t*)d_status,
-                                                  rows_out_of(d_rev, rev_stride, d_rev_len),
-                                                  d_rev_pn_len, st));
+                                                  (const int32_t*)d_status, rev, d_rev_pn_len,
+                                                  st));
         return 0;
     });
 }

@@ -207,6 +207,19 @@ struct RowsOut {
     long long stride;
     int32_t* len;
 };
+// The packets of one ring read in arrival order: arrival a is pkt row a
+// (pkt.len never null; ad: lengths only), tagged (arr_group[a], arr_index[a]) = (the group's
+// index, packet number - fec_group).  pn_len: u8 per arrival, or null: pn_all for all.
+// arr_state [n] (may be null) is written: what became of each arrival.  n == 0: no array is read.
+struct Arrivals {
+    long long n;
+    Rows pkt, ad;
+    const uint8_t* pn_len;
+    int pn_all;
+    const int32_t* arr_group;
+    const uint8_t* arr_index;
+    int32_t* arr_state;
+};
 
 // Syndrome table (decode prep in syndrome mode, read by gf_dcol's syndrome decode), one per
 // group at coef + g * coef_gstride, k <= 128 and at most 16 parity rows:

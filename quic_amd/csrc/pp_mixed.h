@@ -45,9 +45,7 @@ hipError_t launch_null_seal_mixed(const MixedSet& s, long long groups, MixedWire
 // are ignored and nothing of the group is written; a last pass (arrivals_unowned_kernel) sets
 // arr_at and open_len of every slot below npkt that no kept group owns to -1.
 hipError_t launch_open_arrivals_mixed(const MixedSet& s, long long groups, MixedWire w,
-                                      const long long* blocks_off, long long n, Rows pkt, Rows ad,
-                                      const uint8_t* pn_len, int pn_all, const int32_t* arr_group,
-                                      const uint8_t* arr_index, int32_t* arr_state,
+                                      const long long* blocks_off, const Arrivals& ar,
                                       int32_t* arr_at, uint8_t* blocks, uint8_t* rows,
                                       int32_t* open_len, bool optimistic, hipStream_t st);
 // launch_open_status with the group's own k, rows at g * kmax and rec_rows at g * rmax (the

@@ -68,13 +68,13 @@ hipError_t launch_null_seal_framed(int k, int m, long long groups, RaggedView v,
 hipError_t launch_open_groups_framed(int k, int m, long long groups, RaggedView v, Rows pkt,
                                      Rows ad, const uint8_t* pn_len, int pn_all, uint8_t* blocks,
                                      uint8_t* rows, int32_t* open_len, hipStream_t st);
-// The framed open over n packets in arrival order: arrival a is pkt row a,
-// tagged (arr_group[a], arr_index[a]); pn_len is per arrival.  Per group the first copy of each
-// index that opens is a candidate, the k earliest candidates are accepted, and blocks, rows and
-// open_len [G * (k + m)] come out as launch_open_groups_framed writes them for the accepted
-// packets placed by slot.  arr_at [G * (k + m)]: the arrival accepted for each slot, -1 without
-// one (the call's only table, set up again by every call); arr_state [n] (may be null): the
-// plaintext length of an accepted arrival, -1 rejected, -2 ignored tag, -3 duplicate, -4 late.
+// The framed open over ar.n packets in arrival order (Arrivals, fec_kernels.h; DESIGN.md section
+// 6.5).  Per group the first copy of each index that opens is a candidate, the k earliest
+// candidates are accepted, and blocks, rows and open_len [G * (k + m)] come out as
+// launch_open_groups_framed writes them for the accepted packets placed by slot.  arr_at
+// [G * (k + m)]: the arrival accepted for each slot, -1 without one (the call's only table, set up
+// again by every call); ar.arr_state: the plaintext length of an accepted arrival, -1 rejected, -2
+// ignored tag, -3 duplicate, -4 late.
 // optimistic: a data arrival that is its slot's first candidate by the length checks alone (a
 // pre-pass finds it; its table lives in open_len until the assemble writes open_len) streams its
 // plaintext into the slot during the open pass, so an in-order ring is read once; without it the
@@ -82,10 +82,8 @@ hipError_t launch_open_groups_framed(int k, int m, long long groups, RaggedView 
 // for the bytes of a slot whose row is 255.
 // Five launches (init, pre, open, assemble, state); no pre without optimistic, no state without
 // arr_state.
-hipError_t launch_open_arrivals_framed(int k, int m, long long groups, RaggedView v, long long n,
-                                       Rows pkt, Rows ad, const uint8_t* pn_len, int pn_all,
-                                       const int32_t* arr_group, const uint8_t* arr_index,
-                                       int32_t* arr_state, int32_t* arr_at, uint8_t* blocks,
+hipError_t launch_open_arrivals_framed(int k, int m, long long groups, RaggedView v,
+                                       const Arrivals& ar, int32_t* arr_at, uint8_t* blocks,
                                        uint8_t* rows, int32_t* open_len, bool optimistic,
                                        hipStream_t st);
 // After the decode: recovered block (g, j) at rec + v.out_off[g] + j * bb[g] with
@@ -110,12 +108,12 @@ struct RxWin {
     unsigned long long *blk_ptrs, *rec_ptrs;  // [groups * k], [groups * min(k, m)]
     int32_t *eff, *verdict;                   // [groups]: the effective bb; 0 or the status to set
 };
-// One push up to the decode: init -> pre (optimistic) -> open -> assemble -> state (arr_state).
+// One push up to the decode: launch_open_arrivals_framed's sequence with the window's own init and
+// assemble kernels; its pre and open passes are the one-shot call's kernels over the hold rows,
+// where an FEC packet's first candidate is written optimistically too.
 // Afterwards w.rows, w.blk_ptrs, w.rec_ptrs and w.eff are the pointer-table decode's arguments:
 // eff[g] = bb[g] for a group that completes in this push, 0 for every other.
-hipError_t launch_rxwin_bind(const RxWin& w, const int32_t* bb, long long n, Rows pkt, Rows ad,
-                             const uint8_t* pn_len, int pn_all, const int32_t* arr_group,
-                             const uint8_t* arr_index, int32_t* arr_state, uint8_t* rec,
+hipError_t launch_rxwin_bind(const RxWin& w, const int32_t* bb, const Arrivals& ar, uint8_t* rec,
                              const long long* rec_off, bool optimistic, hipStream_t st);
 // After the decode: status (may be null) and rec_rows 255 of the groups that did not complete.
 hipError_t launch_rxwin_finish(const RxWin& w, uint8_t* rec_rows, int32_t* status,

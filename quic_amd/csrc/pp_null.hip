@@ -51,8 +51,11 @@
 // (mixed_group_of); mixed_wire_plan_kernel decides every group once for all of them.
 //
 // Receiver window: the arrival-order receiver with its binding state kept
-// on the device from call to call (rxwin_* kernels): every accepted packet is held in a row of its
-// own, and a group that completes is decoded where it lies through pointer tables.
+// on the device from call to call: every accepted packet is held in a row of its own, and a group
+// that completes is decoded where it lies through pointer tables.  Its pre and open passes are the
+// arrival-order kernels over one more slot type (WinSlots); the kernels of the carried state are
+// its own (rxwin_*).  Every receiver forms a group's rows by wave_rows, both arrival-order
+// assembles accept by wave_accept, and one host sequence (bind_go) launches both.
 #include "fec_kernels.h"
 #include "pp_null.h"
 #include "pp_mixed.h"
@@ -959,33 +962,69 @@ struct RaggedSlots {
     __device__ __forceinline__ int lead(bool) const { return 0; }
     __device__ __forceinline__ void prefix(uint8_t*, long long, int, int, int, int,
                                            long long) const {}
+    __device__ __forceinline__ int pad(int bb_) const { return bb_; }
+    static constexpr bool kFecPre = false;
 };
-// Framed (QuicFecGroup's stored packets, quic_fec_group.cc:178-183): the ragged slots, but a
-// data packet's plaintext is a payload: it goes two bytes into its slot, behind the prefix
+// the two-byte prefix of a framed data packet's block (little-endian): payload length, pn_len
+__device__ __forceinline__ uint32_t frame_prefix(int len, int pn) {
+    return (uint32_t)len | ((uint32_t)pn << 14);
+}
+// Framed (QuicFecGroup's stored packets, quic_fec_group.cc:178-183) over the slots W: a data
+// packet's plaintext is a payload: it goes two bytes into its slot, behind the prefix
 // len | pn_len << 14 (16 bits, little-endian) that the lane writes itself, so it may be at most
 // bb[g] - 2 bytes long.  An FEC packet's plaintext is a whole block, as in RaggedSlots.
-struct FramedSlots {
-    RaggedSlots r;
-    const uint8_t* pn_len;   // [G * (k + m)], or null: pn_all
+// The arrival-order kernels ask two things more of W.  pad(bb_): the length a slot the open pass
+// writes is zero-padded to.  kFecPre: whether that pass writes FEC slots before the tags are
+// known, too (only where every packet has a slot of its own).
+template <class W>
+struct Framed {
+    W w;
+    const uint8_t* pn_len;   // per packet ([G * (k + m)]) or per arrival; null: pn_all
     int pn_all;
-    __device__ __forceinline__ int size(long long g) const { return r.size(g); }
+    static constexpr bool kFecPre = W::kFecPre;
+    __device__ __forceinline__ int size(long long g) const { return w.size(g); }
     __device__ __forceinline__ uint8_t* slot(uint8_t* blocks, long long g, int k, int s,
                                              int bb_) const {
-        return r.slot(blocks, g, k, s, bb_);
+        return w.slot(blocks, g, k, s, bb_);
     }
+    __device__ __forceinline__ int pad(int bb_) const { return w.pad(bb_); }
     __device__ __forceinline__ int limit(int bb_, bool data) const {
         return data ? bb_ - 2 : bb_;
     }
     __device__ __forceinline__ int lead(bool data) const { return data ? 2 : 0; }
+    // the prefix of a data packet (packet or arrival p) that opened len bytes
+    __device__ __forceinline__ uint32_t prefix_of(int len, long long p) const {
+        return frame_prefix(len, pn_len ? pn_len[p] : pn_all);
+    }
     // data packet i of group g opened len bytes: the prefix in front of them
     __device__ __forceinline__ void prefix(uint8_t* blocks, long long g, int k, int i, int bb_,
                                            int len, long long p) const {
         uint8_t* s = slot(blocks, g, k, i, bb_);
-        const uint32_t v = (uint32_t)len | ((uint32_t)(pn_len ? pn_len[p] : pn_all) << 14);
+        const uint32_t v = prefix_of(len, p);
         gst8(s, v);
         gst8(s + 1, v >> 8);
     }
 };
+typedef Framed<RaggedSlots> FramedSlots;
+// The receiver window's hold rows: slot s of group g is the row of
+// hold_stride bytes at hold + (g * per + s) * hold_stride, whatever this push's bb[g], and it is
+// written to its whole length.  A bb[g] below 1 or above hold_stride gives size -1: no packet
+// passes the length checks then.  g is a group of the window.
+struct HoldRows {
+    const int32_t* bb;
+    long long hold_stride, groups;
+    int per;   // k + m
+    static constexpr bool kFecPre = true;
+    __device__ __forceinline__ int size(long long g) const {
+        const int b = bb[g];
+        return b < 1 || b > hold_stride ? -1 : b;
+    }
+    __device__ __forceinline__ uint8_t* slot(uint8_t* hold, long long g, int, int s, int) const {
+        return hold + (g * per + s) * hold_stride;
+    }
+    __device__ __forceinline__ int pad(int) const { return (int)hold_stride; }
+};
+typedef Framed<HoldRows> WinSlots;
 
 // Receiver, grouped: packet p = g * (k + m) + i, one wave per 64 packets; a data packet's
 // plaintext goes to its block slot, zero-padded to bb, through the wave's LDS tile, and so
@@ -1032,24 +1071,30 @@ __global__ __launch_bounds__(64) void open_group_kernel(
     open_len[p] = tag_matches(c, t0, t1, t2) ? cl - 12 : -1;
 }
 
-// dst[0 .. bb) = src[0 .. pl) zero-padded, by the whole wave
-__device__ void wave_copy_pad(uint8_t* dst, const uint8_t* src, int pl, int bb, int lane) {
+// Block slot dst[0 .. bb) = lead || src[0 .. pl) || zeros, by the whole wave: lead is the two
+// prefix bytes `pre` of a data packet's slot (nlead 2) or nothing (nlead 0).  Dword stores where
+// the slot and bb allow them; the dwords read then hold at least one byte of lead || src, and
+// the bytes in front of src are the packet's own (its tag).
+__device__ void wave_place(uint8_t* dst, const uint8_t* src, int pl, int bb, int nlead,
+                           uint32_t pre, int lane) {
+    const int end = nlead + pl;   // bytes of the slot that are not padding
     if ((((uintptr_t)dst) | (uint32_t)bb) & 3u) {
-        for (int o = lane; o < bb; o += 64) dst[o] = o < pl ? src[o] : 0;
+        for (int o = lane; o < bb; o += 64)
+            dst[o] = o < nlead ? (uint8_t)(pre >> (8 * o)) : o < end ? src[o - nlead] : 0;
         return;
     }
-    const uint32_t sh = (uint32_t)(uintptr_t)src & 3u;
-    const uint32_t* s4 = (const uint32_t*)(src - sh);
-    const uint8_t* send = src + pl;
+    const uint8_t* v0 = src - nlead;   // the slot's byte o is v0[o] for nlead <= o < end
+    const uint32_t sh = (uint32_t)(uintptr_t)v0 & 3u;
+    const uint32_t* s4 = (const uint32_t*)(v0 - sh);
     for (int u = lane; u < (bb >> 2); u += 64) {
         const int o = 4 * u;
         uint32_t v = 0;
-        if (o < pl) {
-            // only dwords holding a plaintext byte are read
+        if (o < end) {
             const uint32_t w0 = s4[u];
-            const uint32_t w1 = (sh && (const uint8_t*)(s4 + u + 1) < send) ? s4[u + 1] : 0u;
+            const uint32_t w1 = (sh && o + 4 - (int)sh < end) ? s4[u + 1] : 0u;
             v = sh ? __builtin_amdgcn_alignbyte(w1, w0, sh) : w0;
-            if (pl - o < 4) v &= (1u << (8 * (pl - o))) - 1u;
+            if (end - o < 4) v &= (1u << (8 * (end - o))) - 1u;
+            if (u == 0 && nlead) v = (v & 0xffff0000u) | (pre & 0xffffu);
         }
         ((uint32_t*)dst)[u] = v;
     }
@@ -1057,10 +1102,49 @@ __device__ void wave_copy_pad(uint8_t* dst, const uint8_t* src, int pl, int bb, 
 
 constexpr int kAsmWaves = 4;
 
-// One wave per group: rows[g][i] = i where data packet i opened; the holes, ascending, take
-// the opened FEC packets, ascending (row k + j); 255 where none is left (the decode then
-// reports the group as malformed, status -3).  The open has already written each FEC packet
-// into the hole the length checks alone give it (fec_pre_slot); a pair the tag checks
+// The rows of one group, by its wave (the rule of every receiver here): rows[i] = i where slot i
+// is present; the holes, ascending, take the present FEC packets, ascending (row k + j); 255
+// where none is left.  present(s): whether slot s of the group holds a packet.  lavail, lhole:
+// this wave's LDS rows; afterwards FEC packet lavail[h] fills hole lhole[h] for h below the
+// count returned (lhole null: not wanted; the caller waits for its LDS writes).  each(i, row):
+// called by the lane that wrote rows[i].
+template <class P, class E>
+__device__ __forceinline__ int wave_rows(int k, int m, int lane, P present, uint8_t* lavail,
+                                         uint8_t* lhole, uint8_t* rows, E each) {
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int na = 0;
+    for (int b0 = 0; b0 < m; b0 += 64) {
+        const int j = b0 + lane;
+        const bool v = j < m && present(k + j);
+        const unsigned long long bal = __ballot(v);
+        if (v) lavail[na + __popcll(bal & below)] = (uint8_t)j;
+        na += __popcll(bal);
+    }
+    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes are visible
+    __builtin_amdgcn_wave_barrier();
+    int nh = 0;
+    for (int b0 = 0; b0 < k; b0 += 64) {
+        const int i = b0 + lane;
+        const bool miss = i < k && !present(i);
+        const unsigned long long bal = __ballot(miss);
+        const int r = nh + __popcll(bal & below);
+        if (i < k) {
+            int row = i;
+            if (miss) {
+                row = r < na ? k + lavail[r] : 255;
+                if (lhole && r < na) lhole[r] = (uint8_t)i;
+            }
+            rows[i] = (uint8_t)row;
+            each(i, row);
+        }
+        nh += __popcll(bal);
+    }
+    return min(nh, na);
+}
+
+// One wave per group: the group's rows (wave_rows) over the packets that opened; with a row 255
+// the decode reports the group as malformed, status -3.  The open has already written each FEC
+// packet into the hole the length checks alone give it (fec_pre_slot); a pair the tag checks
 // changed is copied here.
 template <class S>
 __global__ __launch_bounds__(kAsmWaves * 64) void open_assemble_kernel(
@@ -1076,32 +1160,8 @@ __global__ __launch_bounds__(kAsmWaves * 64) void open_assemble_kernel(
     const int per = k + m;
     const int32_t* ol = open_len + g * per;
     const unsigned long long below = (1ull << lane) - 1ull;
-    int na = 0;
-    for (int b0 = 0; b0 < m; b0 += 64) {
-        const int j = b0 + lane;
-        const bool v = j < m && ol[k + j] >= 0;
-        const unsigned long long bal = __ballot(v);
-        if (v) lavail[w][na + __popcll(bal & below)] = (uint8_t)j;
-        na += __popcll(bal);
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes are visible
-    __builtin_amdgcn_wave_barrier();
-    int nh = 0;
-    for (int b0 = 0; b0 < k; b0 += 64) {
-        const int i = b0 + lane;
-        const bool miss = i < k && ol[i] < 0;
-        const unsigned long long bal = __ballot(miss);
-        const int r = nh + __popcll(bal & below);
-        if (i < k) {
-            int row = i;
-            if (miss) {
-                row = r < na ? k + lavail[w][r] : 255;
-                if (r < na) lhole[w][r] = (uint8_t)i;
-            }
-            rows[g * k + i] = (uint8_t)row;
-        }
-        nh += __popcll(bal);
-    }
+    const int nfill = wave_rows(k, m, lane, [&](int s) { return ol[s] >= 0; }, lavail[w],
+                                lhole[w], rows + g * k, [](int, int) {});
     // the match the open wrote by (fec_pre_slot): ranks of the FEC packets and the holes by
     // the length checks alone
     int npa = 0, nph = 0;
@@ -1123,14 +1183,13 @@ __global__ __launch_bounds__(kAsmWaves * 64) void open_assemble_kernel(
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
-    const int nfill = min(nh, na);
     for (int h = 0; h < nfill; ++h) {
         const int j = lavail[w][h], i = lhole[w][h];
         const int pr = prank[w][j];
         if (pr < nph && phole[w][pr] == i) continue;   // written there by the open
         const long long p = g * per + k + j;
         const uint8_t* src = pkt + p * pkt_stride + len_of(ad_len, ad_all, p) + 12;
-        wave_copy_pad(sl.slot(blocks, g, k, i, bb), src, ol[k + j], bb, lane);
+        wave_place(sl.slot(blocks, g, k, i, bb), src, ol[k + j], bb, 0, 0u, lane);
     }
 }
 
@@ -1305,12 +1364,13 @@ __global__ __launch_bounds__(kPPThreads) void arrivals_init_kernel(long long slo
     if (pre_at) pre_at[p] = kArrNone;
 }
 
-// One lane per arrival: a data arrival with a tag of this batch that passes the length checks
-// takes the minimum of pre_at[g * (k + m) + i] with its own index.  Ge: the groups' geometry
-// (UniGeo, MixedGeo), here and in the kernels below.
-template <class Ge>
+// One lane per arrival: an arrival with a tag of this batch that passes the length checks takes
+// the minimum of pre_at[g * (k + m) + i] with its own index; a data arrival, or (S::kFecPre) any.
+// Ge: the groups' geometry (UniGeo, MixedGeo); S: the framed slots (FramedSlots, WinSlots); here
+// and in the kernels below.
+template <class Ge, class S>
 __global__ __launch_bounds__(kPPThreads) void arrivals_pre_kernel(
-    typename Ge::A0 g0, typename Ge::A1 g1, FramedSlots sl, long long n, long long pkt_stride,
+    typename Ge::A0 g0, typename Ge::A1 g1, S sl, long long n, long long pkt_stride,
     const int32_t* __restrict__ pkt_len, const int32_t* __restrict__ ad_len, int ad_all,
     const int32_t* __restrict__ arr_group, const uint8_t* __restrict__ arr_index,
     int32_t* pre_at) {
@@ -1320,23 +1380,26 @@ __global__ __launch_bounds__(kPPThreads) void arrivals_pre_kernel(
     const long long g = arr_group[a];
     const int i = arr_index[a];
     typename Ge::Lane gl{};
-    if (g < 0 || g >= sl.r.groups || !ge.find(g, &gl) || i >= ge.k(gl)) return;
-    if (open_len_ok(pkt_len, ad_len, ad_all, a, sl.limit(sl.size(g), true), pkt_stride))
+    if (g < 0 || g >= sl.w.groups || !ge.find(g, &gl)) return;
+    if (i >= (S::kFecPre ? ge.per(gl) : ge.k(gl))) return;
+    if (open_len_ok(pkt_len, ad_len, ad_all, a, sl.limit(sl.size(g), i < ge.k(gl)), pkt_stride))
         atomicMin(pre_at + ge.first(gl, g) + i, (int32_t)a);
 }
 
 // One lane per arrival, 64 per wave: the length checks of the framed open against the tagged
-// group's bb (open_len_ok with FramedSlots' limits), AD || plaintext hashed through the wave's
+// group's bb (open_len_ok with the framed limits), AD || plaintext hashed through the wave's
 // tile, and where the tag matches atomicMin(arr_at[g * (k + m) + i], a).  arr_state (may be
 // null) receives the plaintext length of an arrival that opened, kArrRejected or kArrIgnored;
 // the two kernels below turn an opened arrival that is not kept into kArrLate / kArrDuplicate.
-// pre_at (null: no optimistic write): the data arrival that is its slot's first candidate by
-// the length checks writes prefix || plaintext || zeros into the slot, before its tag is known;
-// the assemble overwrites the slot where another packet is accepted for it.
-template <class H, class Ge>
+// pre_at (null: no optimistic write): the arrival that is its slot's first candidate by the
+// length checks (arrivals_pre_kernel) streams into the slot before its tag is known, zeros up to
+// the slot's pad() behind it, and a data packet's prefix in front; the assemble overwrites the
+// slot where another packet is accepted for it.  blocks: what S::slot() takes, the blocks or the
+// window's hold rows.
+template <class H, class Ge, class S>
 __global__ __launch_bounds__(64) void open_arrivals_kernel(
-    typename Ge::A0 g0, typename Ge::A1 g1, FramedSlots sl, long long n,
-    const uint8_t* __restrict__ pkt, long long pkt_stride, const int32_t* __restrict__ pkt_len,
+    typename Ge::A0 g0, typename Ge::A1 g1, S sl, long long n, const uint8_t* __restrict__ pkt,
+    long long pkt_stride, const int32_t* __restrict__ pkt_len,
     const int32_t* __restrict__ ad_len, int ad_all, const int32_t* __restrict__ arr_group,
     const uint8_t* __restrict__ arr_index, int32_t* arr_state, int32_t* arr_at,
     const int32_t* __restrict__ pre_at, uint8_t* blocks) {
@@ -1350,16 +1413,18 @@ __global__ __launch_bounds__(64) void open_arrivals_kernel(
     if (a < n) {
         g = arr_group[a];
         i = arr_index[a];
-        tagged = g >= 0 && g < sl.r.groups && ge.find(g, &gl) && i < ge.per(gl);
+        tagged = g >= 0 && g < sl.w.groups && ge.find(g, &gl) && i < ge.per(gl);
         if (tagged) {
             bb = sl.size(g);
             al = len_of(ad_len, ad_all, a);
             cl = pkt_len[a] - al;
             ok = open_len_ok(pkt_len, ad_len, ad_all, a, sl.limit(bb, i < ge.k(gl)), pkt_stride);
-            place = ok && i < ge.k(gl) && pre_at && pre_at[ge.first(gl, g) + i] == (int32_t)a;
+            place = ok && (S::kFecPre || i < ge.k(gl)) && pre_at &&
+                    pre_at[ge.first(gl, g) + i] == (int32_t)a;
         }
     }
     const int k = ge.k(gl);
+    const int lead = sl.lead(!S::kFecPre || i < k);   // without kFecPre only data is placed
     const uint8_t* pp = pkt + (ok ? a : 0) * pkt_stride;
     const uint8_t* c = pp + al;
     H h;
@@ -1367,9 +1432,10 @@ __global__ __launch_bounds__(64) void open_arrivals_kernel(
     Sink s;
     if (ok) span<true, false, 1>(h, s, pp, al);
     tile_stream(h, ok ? c + 12 : nullptr, ok ? cl - 12 : 0,
-                place ? sl.slot(blocks, g, k, i, bb) + 2 : nullptr, place ? bb - 2 : 0, smem);
+                place ? sl.slot(blocks, g, k, i, bb) + lead : nullptr,
+                place ? sl.pad(bb) - lead : 0, smem);
     if (a >= n) return;
-    if (place) sl.prefix(blocks, g, k, i, bb, cl - 12, a);
+    if (place && lead) sl.prefix(blocks, g, k, i, bb, cl - 12, a);
     bool opened = false;
     if (ok) {
         uint32_t t0, t1, t2;
@@ -1380,42 +1446,35 @@ __global__ __launch_bounds__(64) void open_arrivals_kernel(
     if (arr_state) arr_state[a] = !tagged ? kArrIgnored : opened ? cl - 12 : kArrRejected;
 }
 
-// Block slot dst[0 .. bb) = lead || src[0 .. pl) || zeros, by the whole wave: lead is the two
-// prefix bytes `pre` of a data packet's slot (nlead 2) or nothing (nlead 0).  Dword stores where
-// the slot and bb allow them; the dwords read then hold at least one byte of lead || src, and
-// the bytes in front of src are the packet's own (its tag).
-__device__ void wave_place(uint8_t* dst, const uint8_t* src, int pl, int bb, int nlead,
-                           uint32_t pre, int lane) {
-    const int end = nlead + pl;   // bytes of the slot that are not padding
-    if ((((uintptr_t)dst) | (uint32_t)bb) & 3u) {
-        for (int o = lane; o < bb; o += 64)
-            dst[o] = o < nlead ? (uint8_t)(pre >> (8 * o)) : o < end ? src[o - nlead] : 0;
-        return;
-    }
-    const uint8_t* v0 = src - nlead;   // the slot's byte o is v0[o] for nlead <= o < end
-    const uint32_t sh = (uint32_t)(uintptr_t)v0 & 3u;
-    const uint32_t* s4 = (const uint32_t*)(v0 - sh);
-    for (int u = lane; u < (bb >> 2); u += 64) {
-        const int o = 4 * u;
-        uint32_t v = 0;
-        if (o < end) {
-            const uint32_t w0 = s4[u];
-            const uint32_t w1 = (sh && o + 4 - (int)sh < end) ? s4[u + 1] : 0u;
-            v = sh ? __builtin_amdgcn_alignbyte(w1, w0, sh) : w0;
-            if (end - o < 4) v &= (1u << (8 * (end - o))) - 1u;
-            if (u == 0 && nlead) v = (v & 0xffff0000u) | (pre & 0xffffu);
-        }
-        ((uint32_t*)dst)[u] = v;
+// The acceptance rule (QuicFecGroup takes no packet once it holds k, quic_fec_group.cc:210-213),
+// by the group's wave: cand[s] is slot s's candidate of this call, an arrival index; kArrNone or
+// a negative value where it has none.  Ranked by arrival index behind the held0 packets the group
+// holds already, the candidates below k are accepted.  each(q, s, a, is, acc), called by every
+// lane together for q = 0 .. while 64 q < per: slot s = lane + 64 q has the candidate a (is) and
+// it is accepted (acc).  cand is not written.
+template <class E>
+__device__ __forceinline__ void wave_accept(const int32_t* cand, int per, int k, int held0,
+                                            int lane, E each) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (64 * q >= per) break;   // uniform: no slot of the group is left
+        const int s = lane + 64 * q;
+        const int32_t a = s < per ? cand[s] : kArrNone;
+        // compared as unsigned, a negative entry lies above kArrNone: it is no candidate, and it
+        // is below no candidate
+        const bool is = (uint32_t)a < (uint32_t)kArrNone;
+        int rank = 0;   // every lane runs the whole loop
+        for (int t = 0; t < per; ++t) rank += (uint32_t)cand[t] < (uint32_t)a ? 1 : 0;
+        each(q, s, a, is, is && held0 + rank < k);
     }
 }
 
 // One wave per group, after the open pass: the group's candidates are the slots whose arr_at
-// holds an arrival (the first copy of that index that opened).  Ranked by arrival index, the
-// first k are accepted (QuicFecGroup takes no packet once it holds k, quic_fec_group.cc:
-// 210-213); the others are late: arr_at -1 and, where arr_state is kept, kArrLate.  Then what
-// open_assemble_kernel writes for the accepted packets placed by slot: open_len, rows (the
-// holes, ascending, take the accepted FEC packets, ascending; 255 where none is left), and every
-// accepted packet's plaintext in its slot, a data packet's behind its prefix.  optimistic: on
+// holds an arrival (the first copy of that index that opened).  The first k by arrival index are
+// accepted (wave_accept); the others are late: arr_at -1 and, where arr_state is kept, kArrLate.
+// Then what open_assemble_kernel writes for the accepted packets placed by slot: open_len, rows
+// (wave_rows over the accepted packets), and every accepted packet's plaintext in its slot, a
+// data packet's behind its prefix.  optimistic: on
 // entry open_len holds arrivals_pre_kernel's table, and a data slot whose accepted arrival is
 // the one named there was written by the open pass.
 template <class Ge>
@@ -1430,7 +1489,7 @@ __global__ __launch_bounds__(kAsmWaves * 64) void arrivals_assemble_kernel(
     __shared__ uint8_t inplace[kAsmWaves][256];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long long g = (long long)blockIdx.x * kAsmWaves + w;
-    if (g >= sl.r.groups) return;   // uniform over the wave; no workgroup barrier below
+    if (g >= sl.w.groups) return;   // uniform over the wave; no workgroup barrier below
     typename Ge::Lane gl{};
     if (!ge.find_wave(g, &gl)) return;   // the same: one group per wave
     const int k = ge.k(gl), m = ge.m(gl);
@@ -1438,23 +1497,14 @@ __global__ __launch_bounds__(kAsmWaves * 64) void arrivals_assemble_kernel(
     const int per = ge.per(gl);
     const long long first = ge.first(gl, g);
     int32_t* at = arr_at + first;
-    const unsigned long long below = (1ull << lane) - 1ull;
     for (int s = lane; s < per; s += 64) cand[w][s] = at[s];
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes are visible
     __builtin_amdgcn_wave_barrier();
-    // rank of each candidate among the group's; every lane runs the whole loop
     int32_t keep[4] = {-1, -1, -1, -1};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if (64 * q >= per) break;   // uniform: no slot of the group is left
-        const int s = lane + 64 * q;
-        const int32_t a = s < per ? cand[w][s] : kArrNone;
-        int rank = 0;
-        for (int t = 0; t < per; ++t) rank += cand[w][t] < a ? 1 : 0;
-        const bool is = a != kArrNone;
-        keep[q] = is && rank < k ? a : -1;
-        if (is && rank >= k && arr_state) arr_state[a] = kArrLate;
-    }
+    wave_accept(cand[w], per, k, 0, lane, [&](int q, int, int32_t a, bool is, bool acc) {
+        keep[q] = acc ? a : -1;
+        if (is && !acc && arr_state) arr_state[a] = kArrLate;
+    });
     __builtin_amdgcn_wave_barrier();   // every rank is formed before the table changes
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -1469,33 +1519,8 @@ __global__ __launch_bounds__(kAsmWaves * 64) void arrivals_assemble_kernel(
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
-    // rows, as open_assemble_kernel forms them
-    int na = 0;
-    for (int b0 = 0; b0 < m; b0 += 64) {
-        const int j = b0 + lane;
-        const bool v = j < m && cand[w][k + j] >= 0;
-        const unsigned long long bal = __ballot(v);
-        if (v) lavail[w][na + __popcll(bal & below)] = (uint8_t)j;
-        na += __popcll(bal);
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    int nh = 0;
-    for (int b0 = 0; b0 < k; b0 += 64) {
-        const int i = b0 + lane;
-        const bool miss = i < k && cand[w][i] < 0;
-        const unsigned long long bal = __ballot(miss);
-        const int r = nh + __popcll(bal & below);
-        if (i < k) {
-            int row = i;
-            if (miss) {
-                row = r < na ? k + lavail[w][r] : 255;
-                if (r < na) lhole[w][r] = (uint8_t)i;
-            }
-            rows[ge.rows(g) + i] = (uint8_t)row;
-        }
-        nh += __popcll(bal);
-    }
+    const int nfill = wave_rows(k, m, lane, [&](int s) { return cand[w][s] >= 0; }, lavail[w],
+                                lhole[w], rows + ge.rows(g), [](int, int) {});
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
     // the accepted data packets into their own slots, the accepted FEC packets into the holes
@@ -1504,11 +1529,9 @@ __global__ __launch_bounds__(kAsmWaves * 64) void arrivals_assemble_kernel(
         if (a < 0 || __builtin_amdgcn_readfirstlane((int)inplace[w][i])) continue;
         const int al = len_of(ad_len, ad_all, a);
         const int pl = pkt_len[a] - al - 12;
-        const uint32_t pre = (uint32_t)pl | ((uint32_t)(sl.pn_len ? sl.pn_len[a] : sl.pn_all) << 14);
-        wave_place(sl.slot(blocks, g, k, i, bb), pkt + a * pkt_stride + al + 12, pl, bb, 2, pre,
-                   lane);
+        wave_place(sl.slot(blocks, g, k, i, bb), pkt + a * pkt_stride + al + 12, pl, bb, 2,
+                   sl.prefix_of(pl, a), lane);
     }
-    const int nfill = min(nh, na);
     for (int h = 0; h < nfill; ++h) {
         const int32_t a = __builtin_amdgcn_readfirstlane(cand[w][k + lavail[w][h]]);
         const int al = len_of(ad_len, ad_all, a);
@@ -1572,15 +1595,6 @@ constexpr int32_t kSlotEmpty = -1, kSlotSeen = -2;
 constexpr int32_t kWinTaken = -1;
 constexpr int kWinOpen = -3, kWinDelivered = -5;
 
-// the size the length checks of a push run against: none passes with -1
-__device__ __forceinline__ int win_bb(const int32_t* __restrict__ bbs, long long g,
-                                      long long hold_stride) {
-    const int b = bbs[g];
-    return b < 1 || b > hold_stride ? -1 : b;
-}
-// the longest plaintext slot i takes (FramedSlots::limit)
-__device__ __forceinline__ int win_limit(int bb, bool data) { return data ? bb - 2 : bb; }
-
 // One lane per slot.  pre_at: null without the optimistic write.
 __global__ __launch_bounds__(kPPThreads) void rxwin_init_kernel(
     long long slots, const int32_t* __restrict__ slot_state, int32_t* arr_at, int32_t* pre_at) {
@@ -1591,86 +1605,18 @@ __global__ __launch_bounds__(kPPThreads) void rxwin_init_kernel(
     if (pre_at) pre_at[p] = v;
 }
 
-// One lane per arrival, as arrivals_pre_kernel, for data and FEC slots: every packet has a row
-// of its own here, so an FEC packet's first candidate can be written before its tag is known too.
-__global__ __launch_bounds__(kPPThreads) void rxwin_pre_kernel(
-    int k, int m, long long groups, long long hold_stride, const int32_t* __restrict__ bbs,
-    long long n, long long pkt_stride, const int32_t* __restrict__ pkt_len,
-    const int32_t* __restrict__ ad_len, int ad_all, const int32_t* __restrict__ arr_group,
-    const uint8_t* __restrict__ arr_index, int32_t* pre_at) {
-    const long long a = (long long)blockIdx.x * kPPThreads + threadIdx.x;
-    if (a >= n) return;
-    const long long g = arr_group[a];
-    const int i = arr_index[a];
-    if (g < 0 || g >= groups || i >= k + m) return;
-    if (open_len_ok(pkt_len, ad_len, ad_all, a, win_limit(win_bb(bbs, g, hold_stride), i < k),
-                    pkt_stride))
-        atomicMin(pre_at + g * (k + m) + i, (int32_t)a);
-}
-
-// One lane per arrival, 64 per wave: open_arrivals_kernel's body.  The length checks run against
-// the bb[g] of this push; the slot's first candidate by the length checks (pre_at; null: no
-// optimistic write) streams into its hold row with the rest of the row as output length, so the
-// row is zero-padded to hold_stride; a data packet's prefix is written behind it.  A slot that is
-// not empty holds kWinTaken in both tables: it is never written and never won.
-template <class H>
-__global__ __launch_bounds__(64) void rxwin_open_kernel(
-    int k, int m, long long groups, uint8_t* hold, long long hold_stride,
-    const int32_t* __restrict__ bbs, long long n, const uint8_t* __restrict__ pkt,
-    long long pkt_stride, const int32_t* __restrict__ pkt_len, const int32_t* __restrict__ ad_len,
-    int ad_all, const uint8_t* __restrict__ pn_len, int pn_all,
-    const int32_t* __restrict__ arr_group, const uint8_t* __restrict__ arr_index,
-    int32_t* arr_state, int32_t* arr_at, const int32_t* __restrict__ pre_at) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const long long a = (long long)blockIdx.x * 64 + threadIdx.x;
-    bool tagged = false, ok = false, place = false;
-    long long slot = 0;
-    int i = 0, al = 0, cl = 0;
-    if (a < n) {
-        const long long g = arr_group[a];
-        i = arr_index[a];
-        tagged = g >= 0 && g < groups && i < k + m;
-        if (tagged) {
-            slot = g * (k + m) + i;
-            al = len_of(ad_len, ad_all, a);
-            cl = pkt_len[a] - al;
-            ok = open_len_ok(pkt_len, ad_len, ad_all, a,
-                             win_limit(win_bb(bbs, g, hold_stride), i < k), pkt_stride);
-            place = ok && pre_at && pre_at[slot] == (int32_t)a;
-        }
-    }
-    const int lead = i < k ? 2 : 0;
-    const uint8_t* pp = pkt + (ok ? a : 0) * pkt_stride;
-    const uint8_t* c = pp + al;
-    uint8_t* row = hold + slot * hold_stride;
-    H h;
-    h.init();
-    Sink s;
-    if (ok) span<true, false, 1>(h, s, pp, al);
-    tile_stream(h, ok ? c + 12 : nullptr, ok ? cl - 12 : 0, place ? row + lead : nullptr,
-                place ? (int)hold_stride - lead : 0, smem);
-    if (a >= n) return;
-    if (place && lead) {
-        const uint32_t v = (uint32_t)(cl - 12) | ((uint32_t)(pn_len ? pn_len[a] : pn_all) << 14);
-        gst8(row, v);
-        gst8(row + 1, v >> 8);
-    }
-    bool opened = false;
-    if (ok) {
-        uint32_t t0, t1, t2;
-        h.tag(t0, t1, t2);
-        opened = tag_matches(c, t0, t1, t2);
-    }
-    if (opened) atomicMin(arr_at + slot, (int32_t)a);
-    if (arr_state) arr_state[a] = !tagged ? kArrIgnored : opened ? cl - 12 : kArrRejected;
-}
+// The pre and open passes of a push are arrivals_pre_kernel and open_arrivals_kernel over
+// (UniGeo, WinSlots) with the hold rows as blocks (reported as rxwin_pre_kernel and
+// rxwin_open_kernel): the length checks run against the bb[g] of this push, a first candidate,
+// data or FEC, streams into its hold row, zero-padded to hold_stride, and a slot that is not empty
+// holds kWinTaken in both tables: it is never written and never won.
 
 // One wave per group, after the open pass.  The group's candidates of this push are the slots
 // whose arr_at holds an arrival; ranked by arrival index behind the packets the group holds
-// already, the first k - held are accepted (slot state = the plaintext length), the others are
-// late (slot state kSlotSeen, arr_state kArrLate).  An accepted packet that the open pass did not
-// write (pre_at names another arrival, or there is no optimistic write) is placed into its row
-// from the ring.  A group that reaches k completes: rows as arrivals_assemble_kernel forms them
+// already (wave_accept), the first k - held are accepted (slot state = the plaintext length), the
+// others are late (slot state kSlotSeen, arr_state kArrLate).  An accepted packet that the open
+// pass did not write (pre_at names another arrival, or there is no optimistic write) is placed into
+// its row from the ring.  A group that reaches k completes: rows (wave_rows)
 // over the held slots, block pointer g * k + i = the hold row of the packet in that position, rec
 // pointer g * rmax + j = rec + rec_off[g] + j * bb, eff[g] = bb (this push's bb[g]), verdict 0.
 // Every other group: eff 0 (the decode then dereferences none of its pointers), identity rows (the
@@ -1678,10 +1624,9 @@ __global__ __launch_bounds__(64) void rxwin_open_kernel(
 // rxwin_finish_kernel turns into the group's status after the decode.  A completing group that
 // holds a packet larger than this push's bb: verdict -3, eff 0.
 __global__ __launch_bounds__(kAsmWaves * 64) void rxwin_assemble_kernel(
-    int k, int m, long long groups, uint8_t* hold, long long hold_stride, int32_t* slot_state,
-    int32_t* held, int32_t* delivered, const int32_t* __restrict__ bbs,
-    const uint8_t* __restrict__ pkt, long long pkt_stride, const int32_t* __restrict__ pkt_len,
-    const int32_t* __restrict__ ad_len, int ad_all, const uint8_t* __restrict__ pn_len, int pn_all,
+    int k, int m, WinSlots sl, uint8_t* hold, int32_t* slot_state, int32_t* held,
+    int32_t* delivered, const uint8_t* __restrict__ pkt, long long pkt_stride,
+    const int32_t* __restrict__ pkt_len, const int32_t* __restrict__ ad_len, int ad_all,
     int32_t* arr_state, int32_t* arr_at, const int32_t* __restrict__ pre_at, uint8_t* rec,
     const long long* __restrict__ rec_off, uint8_t* rows, unsigned long long* blk_ptrs,
     unsigned long long* rec_ptrs, int32_t* eff, int32_t* verdict) {
@@ -1689,34 +1634,21 @@ __global__ __launch_bounds__(kAsmWaves * 64) void rxwin_assemble_kernel(
     __shared__ uint8_t isheld[kAsmWaves][256], lavail[kAsmWaves][256];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const long long g = (long long)blockIdx.x * kAsmWaves + w;
-    if (g >= groups) return;   // uniform over the wave; no workgroup barrier below
+    if (g >= sl.w.groups) return;   // uniform over the wave; no workgroup barrier below
     const int per = k + m, rmax = min(k, m);
     const long long first = g * per;
     int32_t* at = arr_at + first;
     int32_t* ss = slot_state + first;
-    const unsigned long long below = (1ull << lane) - 1ull;
     const int held0 = __builtin_amdgcn_readfirstlane(held[g]);
     const int deliv0 = __builtin_amdgcn_readfirstlane(delivered[g]);
-    const int bb = __builtin_amdgcn_readfirstlane(win_bb(bbs, g, hold_stride));
+    const int bb = __builtin_amdgcn_readfirstlane(sl.size(g));
     for (int s = lane; s < per; s += 64) cand[w][s] = at[s];
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's LDS writes are visible
     __builtin_amdgcn_wave_barrier();
-    // rank of each candidate among the group's; every lane runs the whole loop
     int32_t keep[4] = {-1, -1, -1, -1};
     int32_t st[4] = {kSlotEmpty, kSlotEmpty, kSlotEmpty, kSlotEmpty};
     int nacc = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        if (64 * q >= per) break;   // uniform: no slot of the group is left
-        const int s = lane + 64 * q;
-        const int32_t a = s < per ? cand[w][s] : kArrNone;
-        const bool is = a >= 0 && a != kArrNone;
-        int rank = 0;
-        for (int t = 0; t < per; ++t) {
-            const int32_t c = cand[w][t];
-            rank += c >= 0 && c < a ? 1 : 0;
-        }
-        const bool acc = is && held0 + rank < k;
+    wave_accept(cand[w], per, k, held0, lane, [&](int q, int s, int32_t a, bool is, bool acc) {
         if (s < per) st[q] = ss[s];
         if (acc) {
             keep[q] = a;
@@ -1728,7 +1660,7 @@ __global__ __launch_bounds__(kAsmWaves * 64) void rxwin_assemble_kernel(
             if (arr_state) arr_state[a] = kArrLate;
         }
         nacc += __popcll(__ballot(acc));
-    }
+    });
     __builtin_amdgcn_wave_barrier();   // every rank is formed before the table changes
     bool big = false;                   // a held packet that does not fit this push's bb
 #pragma unroll
@@ -1740,7 +1672,7 @@ __global__ __launch_bounds__(kAsmWaves * 64) void rxwin_assemble_kernel(
             // what the open pass wrote already is not placed again
             cand[w][s] = a >= 0 && pre_at && pre_at[first + s] == a ? -1 : a;
             isheld[w][s] = st[q] >= 0;
-            big |= st[q] >= 0 && st[q] + (s < k ? 2 : 0) > bb;
+            big |= st[q] >= 0 && st[q] + sl.lead(s < k) > bb;
         }
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -1751,9 +1683,8 @@ __global__ __launch_bounds__(kAsmWaves * 64) void rxwin_assemble_kernel(
         if (a < 0) continue;
         const int al = len_of(ad_len, ad_all, a);
         const int pl = pkt_len[a] - al - 12;
-        const uint32_t pre = (uint32_t)pl | ((uint32_t)(pn_len ? pn_len[a] : pn_all) << 14);
-        wave_place(hold + (first + s) * hold_stride, pkt + a * pkt_stride + al + 12, pl,
-                   (int)hold_stride, s < k ? 2 : 0, pre, lane);
+        wave_place(sl.slot(hold, g, k, s, bb), pkt + a * pkt_stride + al + 12, pl, sl.pad(bb),
+                   sl.lead(s < k), sl.prefix_of(pl, a), lane);
     }
     const int newheld = held0 + nacc;
     const bool completes = held0 < k && newheld == k;
@@ -1768,33 +1699,13 @@ __global__ __launch_bounds__(kAsmWaves * 64) void rxwin_assemble_kernel(
         for (int i = lane; i < k; i += 64) rows[g * k + i] = (uint8_t)i;
         return;
     }
-    // rows, as arrivals_assemble_kernel forms them, over the held slots; the blocks are the rows
-    int na = 0;
-    for (int b0 = 0; b0 < m; b0 += 64) {
-        const int j = b0 + lane;
-        const bool v = j < m && isheld[w][k + j];
-        const unsigned long long bal = __ballot(v);
-        if (v) lavail[w][na + __popcll(bal & below)] = (uint8_t)j;
-        na += __popcll(bal);
-    }
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    __builtin_amdgcn_wave_barrier();
-    int nh = 0;
-    for (int b0 = 0; b0 < k; b0 += 64) {
-        const int i = b0 + lane;
-        const bool miss = i < k && !isheld[w][i];
-        const unsigned long long bal = __ballot(miss);
-        const int r = nh + __popcll(bal & below);
-        if (i < k) {
-            int row = i;
-            if (miss) row = r < na ? k + lavail[w][r] : 255;
-            rows[g * k + i] = (uint8_t)row;
-            // (a group that holds k has a held FEC packet for every hole: row is never 255)
-            const int from = row == 255 ? i : row;
-            blk_ptrs[g * k + i] = (unsigned long long)(uintptr_t)(hold + (first + from) * hold_stride);
-        }
-        nh += __popcll(bal);
-    }
+    // rows over the held slots; the blocks are the hold rows.  (A group that holds k has a held
+    // FEC packet for every hole: row is never 255.)
+    wave_rows(k, m, lane, [&](int s) { return isheld[w][s] != 0; }, lavail[w], nullptr,
+              rows + g * k, [&](int i, int row) {
+                  blk_ptrs[g * k + i] = (unsigned long long)(uintptr_t)sl.slot(
+                      hold, g, k, row == 255 ? i : row, bb);
+              });
     uint8_t* rg = rec + rec_off[g];
     for (int j = lane; j < rmax; j += 64)
         rec_ptrs[g * rmax + j] = (unsigned long long)(uintptr_t)(rg + (long long)j * bb);
@@ -1947,64 +1858,90 @@ hipError_t launch_open_groups_framed(int k, int m, long long groups, RaggedView 
                    blocks, rows, open_len, st);
 }
 
-// The arrival-order open over the geometry ge (UniGeo, MixedGeo): slots = the length of arr_at
-// and open_len; mixed: the kernels' names carry "<mixed>".
-template <class Ge, class F>
-static hipError_t arrivals_go(bool mixed, typename Ge::A0 g0, typename Ge::A1 g1, F first, long long groups, long long slots,
-                              FramedSlots sl, long long n, Rows pkt, Rows ad,
-                              const int32_t* arr_group, const uint8_t* arr_index,
-                              int32_t* arr_state, int32_t* arr_at, uint8_t* blocks, uint8_t* rows,
-                              int32_t* open_len, bool optimistic, hipStream_t st) {
-    if (n > 0x7fffffffLL || slots > 0x7fffffffLL) return hipErrorInvalidValue;
-    if ((groups + kAsmWaves - 1) / kAsmWaves > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (slots > 0) {
-        note_kernel("arrivals_init_kernel");
-        qlaunch(arrivals_init_kernel, dim3(pp_grid(slots)), dim3(kPPThreads), 0, st, slots, arr_at,
-                optimistic ? open_len : nullptr);
-    }
-    if (n > 0 && slots > 0 && groups > 0 && optimistic) {
-        note_kernel(mixed ? "arrivals_pre_kernel<mixed>" : "arrivals_pre_kernel");
-        qlaunch(arrivals_pre_kernel<Ge>, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, g0, g1, sl, n,
-                pkt.stride, pkt.len, ad.len, ad.len_all, arr_group, arr_index, open_len);
+// The binding sequence of every arrival-order receiver, over the geometry Ge (UniGeo, MixedGeo)
+// and the framed slots S (FramedSlots, WinSlots): init -> pre -> open -> assemble -> unowned ->
+// state.  The pre, open and state kernels are shared and reported under lb's names; init(),
+// where there is a slot, and assemble(workgroups), where a group owns one, launch the caller's
+// own two kernels.  slots: the length of arr_at; pre_at: the pre-pass table (null: no optimistic
+// write); blocks: what S::slot() takes; unowned_len: the open_len of a geometry that leaves slots
+// without a group (null: every slot has one).
+struct ArrLabels {
+    const char *pre, *open, *state;
+};
+template <class Ge, class S, class F, class Init, class Asm>
+static hipError_t bind_go(const ArrLabels& lb, typename Ge::A0 g0, typename Ge::A1 g1, F first,
+                          long long groups, long long slots, S sl, const Arrivals& ar,
+                          int32_t* arr_at, int32_t* pre_at, uint8_t* blocks, int32_t* unowned_len,
+                          Init init, Asm assemble, hipStream_t st) {
+    const long long n = ar.n, wg = (groups + kAsmWaves - 1) / kAsmWaves;
+    if (n > 0x7fffffffLL || slots > 0x7fffffffLL || wg > 0x7fffffffLL) return hipErrorInvalidValue;
+    const bool owned = slots > 0 && groups > 0;
+    if (slots > 0) init();
+    if (n > 0 && owned && pre_at) {
+        note_kernel(lb.pre);
+        qlaunch((arrivals_pre_kernel<Ge, S>), dim3(pp_grid(n)), dim3(kPPThreads), 0, st, g0, g1, sl,
+                n, ar.pkt.stride, ar.pkt.len, ar.ad.len, ar.ad.len_all, ar.arr_group, ar.arr_index,
+                pre_at);
     }
     if (n > 0) {
-        note_kernel(mixed ? "open_arrivals_kernel<mixed>" : "open_arrivals_kernel");
-        qlaunch((open_arrivals_kernel<Fnv, Ge>), dim3(tile_grid(n)), dim3(64), kTileBytes, st, g0,
-                g1, sl, n, pkt.p, pkt.stride, pkt.len, ad.len, ad.len_all, arr_group, arr_index,
-                arr_state, arr_at, slots > 0 && groups > 0 && optimistic ? open_len : nullptr,
-                blocks);
+        note_kernel(lb.open);
+        qlaunch((open_arrivals_kernel<Fnv, Ge, S>), dim3(tile_grid(n)), dim3(64), kTileBytes, st,
+                g0, g1, sl, n, ar.pkt.p, ar.pkt.stride, ar.pkt.len, ar.ad.len, ar.ad.len_all,
+                ar.arr_group, ar.arr_index, ar.arr_state, arr_at,
+                (const int32_t*)(owned ? pre_at : nullptr), blocks);
     }
-    if (slots > 0 && groups > 0) {
-        note_kernel(mixed ? "arrivals_assemble_kernel<mixed>" : "arrivals_assemble_kernel");
-        qlaunch(arrivals_assemble_kernel<Ge>,
-                dim3((unsigned)((groups + kAsmWaves - 1) / kAsmWaves)), dim3(kAsmWaves * 64), 0, st,
-                g0, g1, sl, pkt.p, pkt.stride, pkt.len, ad.len, ad.len_all, arr_state, arr_at, open_len,
-                optimistic, blocks, rows);
-    }
-    if (mixed && slots > 0) {
+    if (owned) assemble((unsigned)wg);
+    if (unowned_len && slots > 0) {
         note_kernel("arrivals_unowned_kernel");
         qlaunch(arrivals_unowned_kernel, dim3(pp_grid(slots)), dim3(kPPThreads), 0, st, slots,
-                arr_at, open_len);
+                arr_at, unowned_len);
     }
-    if (n > 0 && slots > 0 && groups > 0 && arr_state) {
-        note_kernel(mixed ? "arrivals_state_kernel<mixed>" : "arrivals_state_kernel");
+    if (n > 0 && owned && ar.arr_state) {
+        note_kernel(lb.state);
         qlaunch(arrivals_state_kernel<F>, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, first, n,
-                arr_group, arr_index, arr_at, arr_state);
+                ar.arr_group, ar.arr_index, (const int32_t*)arr_at, ar.arr_state);
     }
     return hipGetLastError();
 }
 
-hipError_t launch_open_arrivals_framed(int k, int m, long long groups, RaggedView v, long long n,
-                                       Rows pkt, Rows ad, const uint8_t* pn_len, int pn_all,
-                                       const int32_t* arr_group, const uint8_t* arr_index,
-                                       int32_t* arr_state, int32_t* arr_at, uint8_t* blocks,
+// The one-shot open: the pre-pass table lives in open_len until the assemble writes open_len;
+// mixed: the kernels' names carry "<mixed>".
+template <class Ge, class F>
+static hipError_t arrivals_go(bool mixed, typename Ge::A0 g0, typename Ge::A1 g1, F first,
+                              long long groups, long long slots, FramedSlots sl,
+                              const Arrivals& ar, int32_t* arr_at, uint8_t* blocks, uint8_t* rows,
+                              int32_t* open_len, bool optimistic, hipStream_t st) {
+    static const ArrLabels uni{"arrivals_pre_kernel", "open_arrivals_kernel",
+                               "arrivals_state_kernel"};
+    static const ArrLabels mix{"arrivals_pre_kernel<mixed>", "open_arrivals_kernel<mixed>",
+                               "arrivals_state_kernel<mixed>"};
+    int32_t* pre_at = optimistic ? open_len : nullptr;
+    return bind_go<Ge>(
+        mixed ? mix : uni, g0, g1, first, groups, slots, sl, ar, arr_at, pre_at, blocks,
+        mixed ? open_len : nullptr,
+        [&] {
+            note_kernel("arrivals_init_kernel");
+            qlaunch(arrivals_init_kernel, dim3(pp_grid(slots)), dim3(kPPThreads), 0, st, slots,
+                    arr_at, pre_at);
+        },
+        [&](unsigned wg) {
+            note_kernel(mixed ? "arrivals_assemble_kernel<mixed>" : "arrivals_assemble_kernel");
+            qlaunch(arrivals_assemble_kernel<Ge>, dim3(wg), dim3(kAsmWaves * 64), 0, st, g0, g1,
+                    sl, ar.pkt.p, ar.pkt.stride, ar.pkt.len, ar.ad.len, ar.ad.len_all,
+                    ar.arr_state, arr_at, open_len, optimistic, blocks, rows);
+        },
+        st);
+}
+
+hipError_t launch_open_arrivals_framed(int k, int m, long long groups, RaggedView v,
+                                       const Arrivals& ar, int32_t* arr_at, uint8_t* blocks,
                                        uint8_t* rows, int32_t* open_len, bool optimistic,
                                        hipStream_t st) {
     if (k + m > 255) return hipErrorInvalidValue;
-    return arrivals_go<UniGeo>(false, k, m, UniFirst{k + m}, groups, groups * (k + m),
-                       FramedSlots{RaggedSlots{v.bb, v.in_off, groups}, pn_len, pn_all}, n, pkt,
-                       ad, arr_group, arr_index, arr_state, arr_at, blocks, rows, open_len,
-                       optimistic, st);
+    return arrivals_go<UniGeo>(
+        false, k, m, UniFirst{k + m}, groups, groups * (k + m),
+        FramedSlots{RaggedSlots{v.bb, v.in_off, groups}, ar.pn_len, ar.pn_all}, ar, arr_at, blocks,
+        rows, open_len, optimistic, st);
 }
 
 hipError_t launch_extract_revived(int k, int m, long long groups, RaggedView v, const uint8_t* rec,
@@ -2030,46 +1967,29 @@ hipError_t launch_open_status(int k, int rmax, long long groups, const uint8_t* 
 }
 
 // ---- the receiver window
-hipError_t launch_rxwin_bind(const RxWin& w, const int32_t* bb, long long n, Rows pkt, Rows ad,
-                             const uint8_t* pn_len, int pn_all, const int32_t* arr_group,
-                             const uint8_t* arr_index, int32_t* arr_state, uint8_t* rec,
+hipError_t launch_rxwin_bind(const RxWin& w, const int32_t* bb, const Arrivals& ar, uint8_t* rec,
                              const long long* rec_off, bool optimistic, hipStream_t st) {
+    static const ArrLabels lb{"rxwin_pre_kernel", "rxwin_open_kernel", "arrivals_state_kernel"};
     const int per = w.k + w.m;
     const long long slots = w.groups * per;
-    if (per > 255 || n > 0x7fffffffLL || slots > 0x7fffffffLL) return hipErrorInvalidValue;
-    int32_t* pre_at = optimistic && n > 0 ? w.pre_at : nullptr;
-    if (slots > 0) {
-        note_kernel("rxwin_init_kernel");
-        qlaunch(rxwin_init_kernel, dim3(pp_grid(slots)), dim3(kPPThreads), 0, st, slots,
-                (const int32_t*)w.slot_state, w.arr_at, pre_at);
-    }
-    if (n > 0 && slots > 0 && pre_at) {
-        note_kernel("rxwin_pre_kernel");
-        qlaunch(rxwin_pre_kernel, dim3(pp_grid(n)), dim3(kPPThreads), 0, st, w.k, w.m, w.groups,
-                w.hold_stride, bb, n, pkt.stride, pkt.len, ad.len, ad.len_all, arr_group,
-                arr_index, pre_at);
-    }
-    if (n > 0) {
-        note_kernel("rxwin_open_kernel");
-        qlaunch(rxwin_open_kernel<Fnv>, dim3(tile_grid(n)), dim3(64), kTileBytes, st, w.k, w.m,
-                w.groups, w.hold, w.hold_stride, bb, n, pkt.p, pkt.stride, pkt.len, ad.len,
-                ad.len_all, pn_len, pn_all, arr_group, arr_index, arr_state, w.arr_at,
-                slots > 0 ? (const int32_t*)pre_at : nullptr);
-    }
-    if (slots > 0) {
-        note_kernel("rxwin_assemble_kernel");
-        qlaunch(rxwin_assemble_kernel, dim3((unsigned)((w.groups + kAsmWaves - 1) / kAsmWaves)),
-                dim3(kAsmWaves * 64), 0, st, w.k, w.m, w.groups, w.hold, w.hold_stride,
-                w.slot_state, w.held, w.delivered, bb, pkt.p, pkt.stride, pkt.len, ad.len,
-                ad.len_all, pn_len, pn_all, arr_state, w.arr_at, (const int32_t*)pre_at, rec,
-                rec_off, w.rows, w.blk_ptrs, w.rec_ptrs, w.eff, w.verdict);
-    }
-    if (n > 0 && slots > 0 && arr_state) {
-        note_kernel("arrivals_state_kernel");
-        qlaunch(arrivals_state_kernel<UniFirst>, dim3(pp_grid(n)), dim3(kPPThreads), 0, st,
-                UniFirst{per}, n, arr_group, arr_index, (const int32_t*)w.arr_at, arr_state);
-    }
-    return hipGetLastError();
+    if (per > 255) return hipErrorInvalidValue;
+    int32_t* pre_at = optimistic && ar.n > 0 ? w.pre_at : nullptr;
+    const WinSlots sl{HoldRows{bb, w.hold_stride, w.groups, per}, ar.pn_len, ar.pn_all};
+    return bind_go<UniGeo>(
+        lb, w.k, w.m, UniFirst{per}, w.groups, slots, sl, ar, w.arr_at, pre_at, w.hold, nullptr,
+        [&] {
+            note_kernel("rxwin_init_kernel");
+            qlaunch(rxwin_init_kernel, dim3(pp_grid(slots)), dim3(kPPThreads), 0, st, slots,
+                    (const int32_t*)w.slot_state, w.arr_at, pre_at);
+        },
+        [&](unsigned wg) {
+            note_kernel("rxwin_assemble_kernel");
+            qlaunch(rxwin_assemble_kernel, dim3(wg), dim3(kAsmWaves * 64), 0, st, w.k, w.m, sl,
+                    w.hold, w.slot_state, w.held, w.delivered, ar.pkt.p, ar.pkt.stride, ar.pkt.len,
+                    ar.ad.len, ar.ad.len_all, ar.arr_state, w.arr_at, (const int32_t*)pre_at, rec,
+                    rec_off, w.rows, w.blk_ptrs, w.rec_ptrs, w.eff, w.verdict);
+        },
+        st);
 }
 
 hipError_t launch_rxwin_finish(const RxWin& w, uint8_t* rec_rows, int32_t* status,
@@ -2127,16 +2047,13 @@ hipError_t launch_null_seal_mixed(const MixedSet& s, long long groups, MixedWire
 }
 
 hipError_t launch_open_arrivals_mixed(const MixedSet& s, long long groups, MixedWire w,
-                                      const long long* blocks_off, long long n, Rows pkt, Rows ad,
-                                      const uint8_t* pn_len, int pn_all, const int32_t* arr_group,
-                                      const uint8_t* arr_index, int32_t* arr_state,
+                                      const long long* blocks_off, const Arrivals& ar,
                                       int32_t* arr_at, uint8_t* blocks, uint8_t* rows,
                                       int32_t* open_len, bool optimistic, hipStream_t st) {
-    return arrivals_go<MixedGeo>(true, MixedTabs{s.codes, w.ecode, w.pkt_first}, s.kmax,
-                       MixedFirst{w.pkt_first}, groups, w.npkt,
-                       FramedSlots{RaggedSlots{w.eff, blocks_off, groups}, pn_len, pn_all}, n, pkt,
-                       ad, arr_group, arr_index, arr_state, arr_at, blocks, rows, open_len,
-                       optimistic, st);
+    return arrivals_go<MixedGeo>(
+        true, MixedTabs{s.codes, w.ecode, w.pkt_first}, s.kmax, MixedFirst{w.pkt_first}, groups,
+        w.npkt, FramedSlots{RaggedSlots{w.eff, blocks_off, groups}, ar.pn_len, ar.pn_all}, ar,
+        arr_at, blocks, rows, open_len, optimistic, st);
 }
 
 hipError_t launch_open_status_mixed(const MixedSet& s, long long groups, MixedWire w,
